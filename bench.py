@@ -22,6 +22,12 @@ every rank's output is checked inside the run) -- because one
 window is one chain of 31 dependent alignments: 1024 windows already leave a single MI355X at one wavefront per SIMD,
 and splitting them further only idles SIMDs (the strong-scaling record shows exactly that). RCCL carries the barrier
 and the max / sum reductions of the timing scalars only.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: it fills the batch, makes the cold
+pass and W warm-up steps, times N steps and prints one JSON line (metric, value, unit, ms_per_step, dtype, config, ...).
+Everything else above -- the CPU baselines, the golden check of the last step, `kernel_only`, the in-place extension, the
+roofline's kernel timings, strong scaling, the sub-records of --sub-configs and bench_full_record.json -- runs with --full.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs()), in either mode.
 """
 import argparse
 import hashlib
@@ -818,6 +824,36 @@ def bench_reference_shapes(windows, local_rank, sync, steps):
 
 
 FINAL_LINE_LIMIT = 4096   # bytes: the driver keeps a bounded tail of stdout and parses the LAST line
+DUMP_LIMIT = 64 << 20     # bytes: all files of --dump-outputs together
+
+
+def dump_outputs(out_dir, consensus, coverage, status):
+    """--dump-outputs: what get_consensus() hands a caller after the last timed step, as float32 .npy files with one row per
+    window: consensus (bases as ASCII codes) and coverage, zero-padded to the longest consensus, consensus_length, status, and
+    window (the window index of each row). When all windows would take more than DUMP_LIMIT bytes, a fixed, seeded sample of
+    them is written instead. Returns the names written."""
+    import numpy as np
+    n = len(consensus)
+    rows = np.arange(n)
+    width = max([len(c) for c in consensus] + [1])
+    per_row = 4 * (2 * width + 3)
+    if n * per_row > DUMP_LIMIT:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT // per_row, replace=False))
+        width = max([len(consensus[i]) for i in rows] + [1])
+    cons = np.zeros((len(rows), width), np.float32)
+    cov = np.zeros((len(rows), width), np.float32)
+    for j, i in enumerate(rows):
+        c = np.frombuffer(consensus[i].encode(), np.uint8)
+        cons[j, :len(c)] = c
+        cov[j, :len(coverage[i])] = coverage[i]
+    arrays = {"consensus": cons, "coverage": cov,
+              "consensus_length": np.array([len(consensus[i]) for i in rows], np.float32),
+              "status": np.array([status[i] for i in rows], np.float32),
+              "window": rows.astype(np.float32)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def emit(headline, strong, strong8, sub, record_dir):
@@ -912,8 +948,18 @@ def main():
     ap.add_argument("--long-read-windows", type=int, default=598)
     ap.add_argument("--record-dir", default=os.path.join(ROOT, "gpurun_out"),
                     help="where bench_full_record.json (headline + every sub-record) is written; stdout's last line is the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: CPU baselines, the golden check of the last timed step, the in-place and "
+                         "resident-input variants, the roofline's kernel timings, strong scaling (N > 1), the sub-records of "
+                         "--sub-configs and bench_full_record.json. Without it the run sets up, warms up, times --steps steps and "
+                         "prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (get_consensus(): consensus, coverage, status "
+                         "of every window) to DIR/<name>.npy as float32")
     args = ap.parse_args()
-    subs = set(x for x in args.sub_configs.split(",") if x and x != "none")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    subs = set(x for x in args.sub_configs.split(",") if x and x != "none") if args.full else set()
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -928,7 +974,7 @@ def main():
     first_seed = 1000 # every rank the same batch: the one tests/golden/config3_windows.txt.gz holds the oracle's output for
     windows = [[r.decode() for r in synthetic.generate_window(first_seed + w)] for w in range(args.windows)]
     # the CPU baseline forks one worker per core: before this process makes its first device call
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     cpu = cpu_baseline(windows) if want_cpu else None
     cpu_pairs = {}
     cpu_long = None
@@ -1002,54 +1048,59 @@ def main():
     elapsed = time.perf_counter() - t0
     (elapsed,) = reduce_scalars(dist, torch, [elapsed], "MAX")
     (total_cells,) = reduce_scalars(dist, torch, [float(cells)], "SUM")
-    # the line certifies itself: the consensus of the LAST timed step of every rank against the oracle golden (outside the clock)
-    cons_last, _cov_last, status_last = batch.get_consensus()
-    my_digest = consensus_digest(cons_last)
-    golden = config3_golden_digest()
-    checkable = golden is not None and args.windows == WINDOWS
-    ok_here = 1.0 if (checkable and my_digest == golden and all(int(x) == 0 for x in status_last)) else 0.0
-    (ok_all,) = reduce_scalars(dist, torch, [ok_here], "MIN")
-    equals_golden = (ok_all == 1.0) if checkable else None
+    if args.full or args.dump_outputs:  # what the LAST timed step computed, as a caller receives it (outside the clock)
+        cons_last, cov_last, status_last = batch.get_consensus()
+    if args.dump_outputs and rank == 0:  # (every rank ran the same windows)
+        dump_outputs(args.dump_outputs, cons_last, cov_last, status_last)
 
-    # ---- extension, reported next to the metric and never as the metric: the same step with the library's
-    # get_consensus_in_place (results into the storage of the previous call; cudapoa::Batch has no such entry point) ----
-    batch.generate_poa()
-    batch.get_consensus_native(in_place=True)
-    sync()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
+    if args.full:
+        # the line certifies itself: the consensus of the last timed step of every rank against the oracle golden
+        my_digest = consensus_digest(cons_last)
+        golden = config3_golden_digest()
+        checkable = golden is not None and args.windows == WINDOWS
+        ok_here = 1.0 if (checkable and my_digest == golden and all(int(x) == 0 for x in status_last)) else 0.0
+        (ok_all,) = reduce_scalars(dist, torch, [ok_here], "MIN")
+        equals_golden = (ok_all == 1.0) if checkable else None
+
+        # ---- extension, reported next to the metric and never as the metric: the same step with the library's
+        # get_consensus_in_place (results into the storage of the previous call; cudapoa::Batch has no such entry point) ----
         batch.generate_poa()
         batch.get_consensus_native(in_place=True)
-    sync()
-    in_place = time.perf_counter() - t0
-    (in_place,) = reduce_scalars(dist, torch, [in_place], "MAX")
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            batch.generate_poa()
+            batch.get_consensus_native(in_place=True)
+        sync()
+        in_place = time.perf_counter() - t0
+        (in_place,) = reduce_scalars(dist, torch, [in_place], "MAX")
 
-    # ---- the same kernels on inputs resident in HBM (no H2D) ----
-    batch.relaunch()
-    batch.get_consensus_native()
-    sync()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
+        # ---- the same kernels on inputs resident in HBM (no H2D) ----
         batch.relaunch()
         batch.get_consensus_native()
-    sync()
-    resident = time.perf_counter() - t0
-    (resident,) = reduce_scalars(dist, torch, [resident], "MAX")
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            batch.relaunch()
+            batch.get_consensus_native()
+        sync()
+        resident = time.perf_counter() - t0
+        (resident,) = reduce_scalars(dist, torch, [resident], "MAX")
 
-    # dominant kernel, timed live with HIP events on the batch's own stream (outside the timed regions above)
-    kms, oms = [], []
-    for _ in range(max(3, args.steps)):
-        a, b = batch.relaunch_timed()
-        kms.append(a)
-        oms.append(b)
-    k_ms = sum(kms) / len(kms)
-    o_ms = sum(oms) / len(oms)
+        # dominant kernel, timed live with HIP events on the batch's own stream (outside the timed regions above)
+        kms, oms = [], []
+        for _ in range(max(3, args.steps)):
+            a, b = batch.relaunch_timed()
+            kms.append(a)
+            oms.append(b)
+        k_ms = sum(kms) / len(kms)
+        o_ms = sum(oms) / len(oms)
 
     # ---- strong scaling of the metric config: the SAME windows over the ranks, at 1024 windows (one wavefront per SIMD of ONE
     # device already: splitting them further idles SIMDs) and at 8 x 1024 windows (the size at which an index split can scale:
     # the 1024 golden windows eight times over, so every block of 1024 results is checked against the same golden) ----
     strong = strong8 = None
-    if world > 1:
+    if args.full and world > 1:
         base_windows = [[r.decode() for r in synthetic.generate_window(1000 + w)] for w in range(args.windows)]
 
         def strong_record(copies):
@@ -1121,16 +1172,11 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         gcups = total_cells * args.steps / elapsed / 1e9
-        achieved = cells * BYTES_PER_CELL / (k_ms * 1e-3) / 1e9
-        # HBM bytes per launch from the committed PMC pass of this same workload (rocprofv3 cannot run inside the
-        # timed region; tools/pmc_passes.sh collects FETCH_SIZE / WRITE_SIZE in their own runs)
-        traffic = sub_traffic("headline") if args.windows == WINDOWS else None
         out = {
             "metric": "cudapoa consensus GCUPS, 1024-window short-read batch (static band 256, 32 reads <= 1024 bp)",
             "value": round(gcups, 3), "unit": "GCUPS", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "int16", "data": "synthetic",
-            "equals_oracle_golden": equals_golden, "consensus_sha256": my_digest,
             "windows_per_s": round(world * args.windows * args.steps / elapsed, 1),
             "timed_region": "generate_poa() [H2D from pinned host + graph-build kernel + consensus kernel] + the PUBLIC "
                             "Batch::get_consensus() into three fresh vectors per step [D2H + host un-reversal; the previous step's "
@@ -1140,32 +1186,42 @@ def main():
                                    "backbone 960 bp, <=48 sub/24 ins/24 del, BatchConfig(1024,32,256,static_band), "
                                    "scores 8/-6/-8" % args.windows,
                        "windows_per_gpu": args.windows, "cells_per_gpu": cells, "parallelism": "index-split x%d" % world},
-            "roofline": {"bound": "hbm", "kernel": "poa_window_kernel<int16,int16,static_band>",
-                         "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "stale": pmc_stale(),
-                         "traffic_source": pmc_profile().get("file"),
-                         "algorithmic_bytes_per_launch": cells * BYTES_PER_CELL,
-                         "kernel_ms": round(k_ms, 3), "output_kernel_ms": round(o_ms, 3),
-                         "algorithmic_bytes_per_cell": BYTES_PER_CELL},
-            "roofline_issue": roofline_issue("headline"),
-            "kernel_only": {"what": "relaunch on inputs resident in HBM + get_consensus() (no H2D)",
-                            "ms_per_step": round(resident / args.steps * 1e3, 3),
-                            "gcups": round(total_cells * args.steps / resident / 1e9, 3),
-                            "windows_per_s": round(world * args.windows * args.steps / resident, 1)},
-            "extension_get_consensus_in_place": {
-                "what": "the same step with gw_poa_get_consensus_in_place (result storage of the previous call reused; not part of "
-                        "cudapoa::Batch, not the metric)",
-                "ms_per_step": round(in_place / args.steps * 1e3, 3),
-                "gcups": round(total_cells * args.steps / in_place / 1e9, 3)},
-            "cold_first_pass_ms": round(t_cold * 1e3, 3),
         }
-        if world > 1:
-            out["scaling_note"] = ("weak scaling by construction: every rank runs the same 1024-window batch; the comparable "
-                                   "strong-scaling records are strong_scaling (1024 windows) and strong_scaling_8x (8 x 1024 windows "
-                                   "index-split over the ranks), see the sub-record lines / file")
-        if cpu is not None:  # timed on rank 0 of the 1-GPU run only
-            out["cpu_baseline"] = cpu
-        emit(out, strong, strong8, sub, args.record_dir)
+        if not args.full:  # the plain run: the headline line alone
+            print(json.dumps(out, separators=(",", ":")), flush=True)
+        else:
+            achieved = cells * BYTES_PER_CELL / (k_ms * 1e-3) / 1e9
+            # HBM bytes per launch from the committed PMC pass of this same workload (rocprofv3 cannot run inside the
+            # timed region; tools/pmc_passes.sh collects FETCH_SIZE / WRITE_SIZE in their own runs)
+            traffic = sub_traffic("headline") if args.windows == WINDOWS else None
+            out.update({
+                "equals_oracle_golden": equals_golden, "consensus_sha256": my_digest,
+                "roofline": {"bound": "hbm", "kernel": "poa_window_kernel<int16,int16,static_band>",
+                             "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "stale": pmc_stale(),
+                             "traffic_source": pmc_profile().get("file"),
+                             "algorithmic_bytes_per_launch": cells * BYTES_PER_CELL,
+                             "kernel_ms": round(k_ms, 3), "output_kernel_ms": round(o_ms, 3),
+                             "algorithmic_bytes_per_cell": BYTES_PER_CELL},
+                "roofline_issue": roofline_issue("headline"),
+                "kernel_only": {"what": "relaunch on inputs resident in HBM + get_consensus() (no H2D)",
+                                "ms_per_step": round(resident / args.steps * 1e3, 3),
+                                "gcups": round(total_cells * args.steps / resident / 1e9, 3),
+                                "windows_per_s": round(world * args.windows * args.steps / resident, 1)},
+                "extension_get_consensus_in_place": {
+                    "what": "the same step with gw_poa_get_consensus_in_place (result storage of the previous call reused; not part "
+                            "of cudapoa::Batch, not the metric)",
+                    "ms_per_step": round(in_place / args.steps * 1e3, 3),
+                    "gcups": round(total_cells * args.steps / in_place / 1e9, 3)},
+                "cold_first_pass_ms": round(t_cold * 1e3, 3),
+            })
+            if world > 1:
+                out["scaling_note"] = ("weak scaling by construction: every rank runs the same 1024-window batch; the comparable "
+                                       "strong-scaling records are strong_scaling (1024 windows) and strong_scaling_8x (8 x 1024 "
+                                       "windows index-split over the ranks), see the sub-record lines / file")
+            if cpu is not None:  # timed on rank 0 of the 1-GPU run only
+                out["cpu_baseline"] = cpu
+            emit(out, strong, strong8, sub, args.record_dir)
     if dist is not None:
         dist.destroy_process_group()
 

@@ -119,7 +119,7 @@ def _rank(rank, world, port, q):
     if rank == 1 and os.environ.get("GW_TEST_SPOIL_RANK1"):
         FakeAligner.spoil = (3, "ops")  # (an operation: seen by the edit distances, which the golden holds for every pair)
     import tempfile
-    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--sub-configs", "aligner",
+    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--sub-configs", "aligner",
                 "--record-dir", tempfile.mkdtemp(prefix="gw_bench_")]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):

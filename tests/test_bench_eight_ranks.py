@@ -61,7 +61,7 @@ def _rank(rank, world, port, q):
     torch.cuda.synchronize = lambda *a: None
     import bench
     import tempfile
-    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--sub-configs", "none",
+    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--sub-configs", "none",
                 "--record-dir", tempfile.mkdtemp(prefix="gw_bench_")]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):

@@ -6,7 +6,7 @@ shift
 ARGS=${@:---sub-configs none --steps 20 --warmup 3 --no-cpu-baseline}
 mkdir -p gpurun_out/ab
 run() { # $1 = label
-    python bench.py $ARGS 2>/dev/null | python -c "
+    python bench.py --full $ARGS 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][0])
 print('$1', 'kernel_ms', d['roofline']['kernel_ms'], 'step_ms', d['ms_per_step'], 'gcups', d['value'], 'golden', d['equals_oracle_golden'])"

@@ -8,7 +8,7 @@
 #   tests        pytest -m gpu (PYTEST_ARGS = files, PYTEST_K = a -k expression narrow it)
 #   phases       per-phase cycle breakdown of the metric kernel (tools/profile_phases.py 1024)
 #   bench        the driver's bench line (BENCH_ARGS, default none = the full line with all sub-records)
-#   stats        rocprofv3 --kernel-trace --stats of `bench.py --no-cpu-baseline $STATS_ARGS` -> kernel_stats.csv
+#   stats        rocprofv3 --kernel-trace --stats of `bench.py --full --no-cpu-baseline $STATS_ARGS` -> kernel_stats.csv
 #   pmc          tools/pmc_passes.sh with PASSES (default "insts waits lds fetch write active") and SUBS (default none)
 #   pmcfull      the same passes over the full-band kernel alone (tools/profile_phases.py 1024 full_band) -> pmc_summary_full_band.csv
 #   issue        measure the lone-wavefront issue rate (tools/microbench_fetch.hip) -> microbench_issue.json, which the traffic step
@@ -36,7 +36,7 @@ if has phases; then
     cut -c1-900 $OUT/phase_breakdown.json; echo
 fi
 if has bench; then
-    ( timeout ${BENCH_TIMEOUT:-1500} python bench.py --record-dir $OUT ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err ); echo "bench rc=$?"; tail -3 $OUT/bench.err
+    ( timeout ${BENCH_TIMEOUT:-1500} python bench.py --full --record-dir $OUT ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err ); echo "bench rc=$?"; tail -3 $OUT/bench.err
     python - $OUT/bench.json <<'PY'
 import json, sys
 import os
@@ -60,7 +60,7 @@ if 'band_modes' in s:
 PY
 fi
 if has stats; then
-    (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $REPO/$OUT/stats -- python $REPO/bench.py --no-cpu-baseline ${STATS_ARGS:-} > $REPO/$OUT/bench_under_rocprof.json 2> $REPO/$OUT/stats.log)
+    (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $REPO/$OUT/stats -- python $REPO/bench.py --full --no-cpu-baseline ${STATS_ARGS:-} > $REPO/$OUT/bench_under_rocprof.json 2> $REPO/$OUT/stats.log)
     DB=$(find $OUT/stats -name "*.db" | head -1)
     [ -n "$DB" ] && python tools/rocpd_summary.py "$DB" > $OUT/kernel_stats.csv && head -14 $OUT/kernel_stats.csv | cut -c1-160
     rm -rf $OUT/stats

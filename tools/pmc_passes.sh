@@ -7,7 +7,7 @@ REPO=$(pwd)
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 # SUBS: the sub-records whose kernels should run under the counters as well (aligner, default_aligner, long_reads)
-CMD="python $REPO/bench.py --steps 1 --warmup 0 --no-cpu-baseline --sub-configs ${SUBS:-none}"
+CMD="python $REPO/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --sub-configs ${SUBS:-none}"
 # PMC_CMD: another command to run under the counters instead (e.g. "python $REPO/tools/profile_phases.py 1024 full_band")
 [ -n "${PMC_CMD:-}" ] && CMD="$PMC_CMD"
 PASSES=${PASSES:-all}

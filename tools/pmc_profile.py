@@ -106,7 +106,7 @@ if os.path.exists(issue_json):
 
 out = {"tag": tag, "commit": commit, "kernel_source_sha256": kernel_source_digest(),
        "source": "rocprofv3 --kernel-trace --pmc, one counter group per pass (tools/pmc_passes.sh: insts, waits, lds, fetch, write) over "
-                 "`bench.py --steps 1 --warmup 0 --no-cpu-baseline --sub-configs aligner,default_aligner,long_reads`; FETCH_SIZE x 2 and "
+                 "`bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --sub-configs aligner,default_aligner,long_reads`; FETCH_SIZE x 2 and "
                  "WRITE_SIZE x 0.97 as calibrated in profiles/r03_pmc_traffic.json on microkernels of known size"}
 for key, e in (("headline", entry(lambda k: "poa_window_kernel<short, short, signed char, 1, false, tru" in k and not k.startswith("full_band_session::"))),
                ("full_band", entry(lambda k: k.startswith("full_band_session::") and "poa_window_kernel<short, short, signed char, 0, false, tru" in k, "mean",
