@@ -54,6 +54,7 @@ class PoaBatchConfig(C.Structure):
 
 _gwhip = None
 _host = None
+_extender = None
 
 
 def _load(name):
@@ -100,6 +101,38 @@ def host():
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         _host = L
     return _host
+
+
+def extender():
+    """libcudaextender.so: the cudaextender kernels (include/gwhip_extender.h) and the Extender behind the flat C API
+    (include/gw_extender_capi.h)."""
+    global _extender
+    if _extender is None:
+        host()
+        L = _load("libcudaextender.so")
+        vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+        L.gw_extender_last_error.restype = C.c_char_p
+        L.gw_extender_create.restype = vp
+        L.gw_extender_create.argtypes = [vp, i32, i32, i32, vp, i32, i64, i32]
+        L.gw_extender_extend_host.argtypes = [vp, vp, i32, vp, i32, i32, vp, i64]
+        L.gw_extender_extend_device.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, vp, vp]
+        L.gw_extender_sync.argtypes = [vp]
+        L.gw_extender_result_count.restype = i64
+        L.gw_extender_result_count.argtypes = [vp]
+        L.gw_extender_copy_results.argtypes = [vp, vp, i64]
+        L.gw_extender_reset.restype = None
+        L.gw_extender_reset.argtypes = [vp]
+        L.gw_extender_destroy.restype = None
+        L.gw_extender_destroy.argtypes = [vp]
+        L.gw_extender_set_chunk_size.argtypes = [vp, i32]
+        L.gw_extender_set_instrumentation.argtypes = [vp, i32]
+        L.gw_extender_last_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i64)]
+        L.gw_extender_sort_unique_hook.argtypes = [vp, vp, i32, vp, C.POINTER(i32), vp]
+        L.gwx_workspace_bytes.restype = C.c_size_t
+        L.gwx_workspace_bytes.argtypes = [i32]
+        L.gwx_last_error.restype = C.c_char_p
+        _extender = L
+    return _extender
 
 
 def gwhip_error():

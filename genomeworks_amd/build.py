@@ -2,6 +2,8 @@
 
   genomeworks_amd/lib/libgwhip.so            hand-written HIP kernels + the thin C-ABI (include/gwhip.h)
   genomeworks_amd/lib/libgenomeworks_amd.so  host C++ (Batch / Aligner, allocator, C API include/gw_capi.h)
+  genomeworks_amd/lib/libcudaextender.so     cudaextender: HIP kernels (include/gwhip_extender.h) + Extender
+                                             (cudaextender/extender.hpp, C API include/gw_extender_capi.h)
 
 Called by __graft_entry__.build(); also usable as `python -m genomeworks_amd.build`.
 """
@@ -19,7 +21,11 @@ HIPCC = os.path.join(ROCM, "bin", "hipcc")
 KERNEL_SRCS = ["csrc/gwhip_poa.hip", "csrc/gwhip_poa_part0.hip", "csrc/gwhip_poa_part1.hip", "csrc/gwhip_poa_part2.hip",
                "csrc/gwhip_poa_part3.hip", "csrc/gwhip_poa_part4.hip", "csrc/gwhip_poa_part5.hip", "csrc/gwhip_poa_part6.hip", "csrc/gwhip_poa_part7.hip", "csrc/gwhip_poa_hooks.hip", "csrc/gwhip_myers.hip", "csrc/gwhip_ukkonen.hip"]
 HOST_SRCS = ["host/capi.cpp", "host/cudapoa_batch.cpp", "host/cudapoa_utils.cpp", "host/cudaaligner.cpp", "host/aligner_global.cpp", "host/device_pool.cpp",
-             "host/alignment_impl.cpp", "host/runtime.cpp", "host/logging.cpp", "host/overlap_alignment.cpp", "host/multi_device.cpp"]
+             "host/alignment_impl.cpp", "host/runtime.cpp", "host/logging.cpp", "host/overlap_alignment.cpp", "host/multi_device.cpp",
+             "host/fasta_parser.cpp"]
+# cudaextender lives apart from csrc/ so that kernel_source_digest() (the stamped POA / aligner kernel set) ignores it
+EXTENDER_KERNEL_SRCS = ["extender/gwx_ungapped_xdrop.hip"]
+EXTENDER_HOST_SRCS = ["extender/extender.cpp"]
 
 # no fast-math, no FMA contraction: band placement is IEEE fp32
 KERNEL_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=off",
@@ -135,6 +141,45 @@ def build_host(force=False):
     return target
 
 
+def build_extender(force=False):
+    """libcudaextender.so: the extension kernel + rocPRIM compaction / sort (hipcc, gfx950) and the Extender host
+    classes (g++), linked against libgenomeworks_amd.so for the allocator and logging."""
+    os.makedirs(LIB, exist_ok=True)
+    target = os.path.join(LIB, "libcudaextender.so")
+    inc = ["-I", os.path.join(ROOT, "include")]
+    objs, procs, sigs = [], [], []
+    for s in EXTENDER_KERNEL_SRCS:
+        src = os.path.join(PKG, s)
+        o = os.path.join(LIB, os.path.basename(s) + ".o")
+        sig = _digest([src, os.path.join(ROOT, "include", "gwhip_extender.h")], KERNEL_FLAGS)
+        objs.append(o)
+        sigs.append(sig)
+        if force or _stale(o, sig):
+            cmd = [HIPCC] + KERNEL_FLAGS + inc + ["-c", src, "-o", o]
+            print("[build]", " ".join(cmd), flush=True)
+            procs.append((subprocess.Popen(cmd), o, sig))
+    host_sig = _digest(_deps("extender", (".cpp", ".h", ".hpp")), HOST_FLAGS)
+    for s in EXTENDER_HOST_SRCS:
+        src = os.path.join(PKG, s)
+        o = os.path.join(LIB, os.path.basename(s) + ".o")
+        objs.append(o)
+        sigs.append(host_sig)
+        if force or _stale(o, host_sig):
+            cmd = ["g++"] + HOST_FLAGS + inc + ["-I", os.path.join(ROCM, "include"), "-c", src, "-o", o]
+            print("[build]", " ".join(cmd), flush=True)
+            procs.append((subprocess.Popen(cmd), o, host_sig))
+    for p, o, sig in procs:
+        if p.wait() != 0:
+            raise RuntimeError("building libcudaextender.so failed")
+        _mark(o, sig)
+    link_sig = _digest([], sigs)
+    if force or procs or _stale(target, link_sig):
+        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", target] + objs +
+             ["-L", LIB, "-lgenomeworks_amd", "-Wl,-rpath,$ORIGIN"])
+        _mark(target, link_sig)
+    return target
+
+
 def build_cli(force=False):
     """The command-line tools -> genomeworks_amd/bin/: `cudapoa` (reference: cudapoa/src/main.cpp) and
     `align_overlaps` (the alignment stage of cudamapper, cudamapper/src/main.cu:54-187)."""
@@ -183,6 +228,7 @@ def _run_in(cwd, cmd):
 def build_all(force=False):
     k = build_kernels(force)
     h = build_host(force)
+    build_extender(force)
     build_cli(force)
     build_bindings(force)
     return k, h

@@ -58,6 +58,13 @@ void device_copy_n_async(const Type* src, size_t n, Type* dst, hipMemcpyKind kin
     gpu_assert(hipMemcpyAsync(dst, src, n * sizeof(Type), kind, stream), __FILE__, __LINE__);
 }
 
+/// Copies n elements between any two of host and device memory (direction from the pointers) on `stream`.
+template <typename Type>
+void device_copy_n_async(const Type* src, size_t n, Type* dst, cudaStream_t stream)
+{
+    gpu_assert(hipMemcpyAsync(dst, src, n * sizeof(Type), hipMemcpyDefault, stream), __FILE__, __LINE__);
+}
+
 } // namespace cudautils
 
 #define GW_CU_CHECK_ERR(ans) ::claraparabricks::genomeworks::cudautils::gpu_assert((ans), __FILE__, __LINE__)
