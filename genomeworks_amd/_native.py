@@ -55,6 +55,7 @@ class PoaBatchConfig(C.Structure):
 _gwhip = None
 _host = None
 _extender = None
+_mapper = None
 
 
 def _load(name):
@@ -145,3 +146,36 @@ GWHIP_SYMBOLS = [
     "gwhip_poa_workspace_bytes", "gwhip_poa_bytes_per_window", "gwhip_poa_generate", "gwhip_poa_export_graphs",
     "gwhip_last_error_string", "gwhip_build_arch", "gwhip_abi_version",
 ]
+
+
+def mapper():
+    """libcudamapper.so: the cudamapper kernels (include/gwhip_mapper.h) and the Index / Matcher handles behind the flat
+    C API (include/gw_mapper_capi.h)."""
+    global _mapper
+    if _mapper is None:
+        vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+        L = _load("libcudamapper.so")
+        L.gw_mapper_last_error.restype = C.c_char_p
+        L.gw_mapper_index_create.restype = vp
+        L.gw_mapper_index_create.argtypes = [vp, vp, i32, C.c_uint32, i32, i32, i32, C.c_double, vp]
+        L.gw_mapper_index_destroy.restype = None
+        L.gw_mapper_index_destroy.argtypes = [vp]
+        L.gw_mapper_index_info.argtypes = [vp, vp, vp, vp]
+        L.gw_mapper_index_copy.argtypes = [vp] * 7
+        L.gw_mapper_index_from_arrays.restype = vp
+        L.gw_mapper_index_from_arrays.argtypes = [i64, vp, vp, i64, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.gw_mapper_matcher_create.restype = vp
+        L.gw_mapper_matcher_create.argtypes = [vp, vp, vp]
+        L.gw_mapper_matcher_destroy.restype = None
+        L.gw_mapper_matcher_destroy.argtypes = [vp]
+        L.gw_mapper_matcher_anchor_count.restype = i64
+        L.gw_mapper_matcher_anchor_count.argtypes = [vp]
+        L.gw_mapper_matcher_copy_anchors.argtypes = [vp, vp, i64, vp]
+        L.gw_mapper_get_overlaps.restype = i64
+        L.gw_mapper_get_overlaps.argtypes = [vp, i32, i64, i64, i64, f32, vp, vp, vp]
+        L.gw_mapper_get_overlaps_host.restype = i64
+        L.gw_mapper_get_overlaps_host.argtypes = [vp, i64, i32, i64, i64, i64, f32, vp, vp]
+        L.gw_mapper_map.restype = i64
+        L.gw_mapper_map.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, C.c_double, i64, i64, i64, f32, vp, i64, vp]
+        _mapper = L
+    return _mapper

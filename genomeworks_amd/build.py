@@ -4,6 +4,8 @@
   genomeworks_amd/lib/libgenomeworks_amd.so  host C++ (Batch / Aligner, allocator, C API include/gw_capi.h)
   genomeworks_amd/lib/libcudaextender.so     cudaextender: HIP kernels (include/gwhip_extender.h) + Extender
                                              (cudaextender/extender.hpp, C API include/gw_extender_capi.h)
+  genomeworks_amd/lib/libcudamapper.so       cudamapper: HIP kernels (include/gwhip_mapper.h) + Index / Matcher
+                                             handles (C API include/gw_mapper_capi.h)
 
 Called by __graft_entry__.build(); also usable as `python -m genomeworks_amd.build`.
 """
@@ -26,6 +28,9 @@ HOST_SRCS = ["host/capi.cpp", "host/cudapoa_batch.cpp", "host/cudapoa_utils.cpp"
 # cudaextender lives apart from csrc/ so that kernel_source_digest() (the stamped POA / aligner kernel set) ignores it
 EXTENDER_KERNEL_SRCS = ["extender/gwx_ungapped_xdrop.hip"]
 EXTENDER_HOST_SRCS = ["extender/extender.cpp"]
+# cudamapper likewise
+MAPPER_KERNEL_SRCS = ["mapper/gwm_mapper.hip"]
+MAPPER_HOST_SRCS = ["mapper/mapper.cpp"]
 
 # no fast-math, no FMA contraction: band placement is IEEE fp32
 KERNEL_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=off",
@@ -180,6 +185,44 @@ def build_extender(force=False):
     return target
 
 
+def build_mapper(force=False):
+    """libcudamapper.so: the sketch / index / matcher / overlapper kernels with their rocPRIM scans, selects and sorts
+    (hipcc, gfx950) and the Index / Matcher handles behind the C API (g++)."""
+    os.makedirs(LIB, exist_ok=True)
+    target = os.path.join(LIB, "libcudamapper.so")
+    inc = ["-I", os.path.join(ROOT, "include")]
+    objs, procs, sigs = [], [], []
+    for s in MAPPER_KERNEL_SRCS:
+        src = os.path.join(PKG, s)
+        o = os.path.join(LIB, os.path.basename(s) + ".o")
+        sig = _digest([src, os.path.join(ROOT, "include", "gwhip_mapper.h")], KERNEL_FLAGS)
+        objs.append(o)
+        sigs.append(sig)
+        if force or _stale(o, sig):
+            cmd = [HIPCC] + KERNEL_FLAGS + inc + ["-c", src, "-o", o]
+            print("[build]", " ".join(cmd), flush=True)
+            procs.append((subprocess.Popen(cmd), o, sig))
+    host_sig = _digest(_deps("mapper", (".cpp", ".h", ".hpp")), HOST_FLAGS)
+    for s in MAPPER_HOST_SRCS:
+        src = os.path.join(PKG, s)
+        o = os.path.join(LIB, os.path.basename(s) + ".o")
+        objs.append(o)
+        sigs.append(host_sig)
+        if force or _stale(o, host_sig):
+            cmd = ["g++"] + HOST_FLAGS + inc + ["-I", os.path.join(ROCM, "include"), "-c", src, "-o", o]
+            print("[build]", " ".join(cmd), flush=True)
+            procs.append((subprocess.Popen(cmd), o, host_sig))
+    for p, o, sig in procs:
+        if p.wait() != 0:
+            raise RuntimeError("building libcudamapper.so failed")
+        _mark(o, sig)
+    link_sig = _digest([], sigs)
+    if force or procs or _stale(target, link_sig):
+        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", target] + objs)
+        _mark(target, link_sig)
+    return target
+
+
 def build_cli(force=False):
     """The command-line tools -> genomeworks_amd/bin/: `cudapoa` (reference: cudapoa/src/main.cpp) and
     `align_overlaps` (the alignment stage of cudamapper, cudamapper/src/main.cu:54-187)."""
@@ -229,6 +272,7 @@ def build_all(force=False):
     k = build_kernels(force)
     h = build_host(force)
     build_extender(force)
+    build_mapper(force)
     build_cli(force)
     build_bindings(force)
     return k, h
