@@ -16,6 +16,8 @@
 #include <sstream>
 #include <stdexcept>
 #include <unordered_map>
+#include <utility>
+#include <vector>
 
 namespace claraparabricks
 {
@@ -279,10 +281,24 @@ void print_sam(const std::vector<Overlap>& overlaps, const std::vector<std::stri
             }
             // cudaaligner's 'I' is a base present in the TARGET only and its 'D' one present in the query only
             // (cudaaligner.hpp:47-53), the opposite of SAM's operators, which are named from the reference sequence's side
-            // (RNAME = the target read): swapped here, in the SAM text only (the PAF cg:Z: tag stays cudaaligner's)
+            // (RNAME = the target read): swapped here, in the SAM text only (the PAF cg:Z: tag stays cudaaligner's).
+            // On the reverse strand the aligner walked the forward query against the reverse complement of the target
+            // (run_alignment_batch); against the forward target at POS and the reverse-complemented SEQ both sequences
+            // run backwards, so the same columns come in reverse order: the runs are written from last to first.
             {
+                const std::string& cigar = cigars[i];
+                std::vector<std::pair<size_t, size_t>> runs; // [begin, end) of each <n><op> run
+                for (size_t k = 0, begin = 0; k < cigar.size(); ++k)
+                {
+                    if (cigar[k] < '0' || cigar[k] > '9')
+                    {
+                        runs.emplace_back(begin, k + 1);
+                        begin = k + 1;
+                    }
+                }
+                if (reverse) std::reverse(runs.begin(), runs.end());
                 const size_t at = buffer.size();
-                buffer += cigars[i];
+                for (const auto& run : runs) buffer.append(cigar, run.first, run.second - run.first);
                 for (size_t k = at; k < buffer.size(); ++k)
                     buffer[k] = buffer[k] == 'I' ? 'D' : (buffer[k] == 'D' ? 'I' : buffer[k]);
             }

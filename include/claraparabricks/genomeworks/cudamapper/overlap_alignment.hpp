@@ -3,8 +3,8 @@
 // `align_overlaps()` + `run_alignment_batch()` (cudamapper/src/main.cu:54-187: several alignment engines on host
 // threads share one allocator and one device, each pulling ranges of overlaps, `create_aligner(max_query, max_target,
 // batch_size, global_alignment, allocator, stream, device)` -> add_alignment / align_all / sync_alignments /
-// convert_to_cigar / reset) and `print_paf()` (cudamapper/src/utils.cpp:41-124). The overlap *finder* (index, matcher,
-// chainer) is out of scope: overlaps arrive as PAF records.
+// convert_to_cigar / reset) and `print_paf()` (cudamapper/src/utils.cpp:41-124). Overlaps arrive as PAF records, such as
+// those of the overlap finder in libcudamapper.so (gw_mapper_capi.h).
 #pragma once
 #include <claraparabricks/genomeworks/utils/allocator.hpp>
 
@@ -78,7 +78,9 @@ void print_paf(const std::vector<Overlap>& overlaps, const std::vector<std::stri
 /// @PG line of the tool; one record per overlap with the fields the reference fills: QNAME, FLAG 0 (16 for overlaps on the
 /// reverse strand), RNAME / POS of the TARGET read and start (the reference leaves the target index at 0 and writes the
 /// query start; a SAM consumer needs the position on RNAME), MAPQ 255 as in print_paf, the CIGAR when cigars is not empty
-/// (else *), RNEXT * / PNEXT 0 / TLEN 0, the whole query sequence, QUAL *.
+/// (else *), RNEXT * / PNEXT 0 / TLEN 0, the whole query sequence, QUAL *. The CIGAR has SAM's I / D and soft clips for
+/// the unaligned ends of the read; on the reverse strand SEQ is the reverse complement, the clips swap sides and the runs
+/// come in reverse order (the aligner walked the forward query against the reverse-complemented target).
 void print_sam(const std::vector<Overlap>& overlaps, const std::vector<std::string>& cigars,
                const std::vector<FastaSequence>& queries, const std::vector<FastaSequence>& targets,
                const std::string& program_version, const std::string& command_line, std::FILE* out);

@@ -1,5 +1,6 @@
 # distutils: language = c++
 """cudaaligner bindings: CudaAlignerBatch over cudaaligner::Aligner (API of pygenomeworks' genomeworks.cudaaligner)."""
+cimport cython
 from cython.operator cimport dereference as deref
 from libc.stdint cimport int64_t
 from libcpp.memory cimport shared_ptr, unique_ptr
@@ -58,6 +59,9 @@ class CudaAlignment:
         return "{}\n{}\n{}\n".format(self.format_alignment[0], self.format_alignment[1], self.format_alignment[2])
 
 
+# no_gc_clear: the garbage collector must not drop the stream reference before __dealloc__ has released the
+# batch, or a batch found in a reference cycle would be torn down on a stream that no longer exists
+@cython.no_gc_clear
 cdef class CudaAlignerBatch:
     """A batch of (query, target) pairs aligned globally on one GPU."""
     cdef unique_ptr[cudaaligner.Aligner] aligner

@@ -2,6 +2,7 @@
 """cudapoa bindings: CudaPoaBatch over cudapoa::Batch (API of pygenomeworks' genomeworks.cudapoa)."""
 import networkx as nx
 
+cimport cython
 from cython.operator cimport dereference as deref
 from libc.stdint cimport int8_t, int32_t, int64_t, uint16_t
 from libcpp.memory cimport unique_ptr
@@ -47,6 +48,9 @@ def status_to_str(status):
         raise RuntimeError("Unknown error status : " + str(status))
 
 
+# no_gc_clear: the garbage collector must not drop the stream reference before __dealloc__ has released the
+# batch, or a batch found in a reference cycle would be torn down on a stream that no longer exists
+@cython.no_gc_clear
 cdef class CudaPoaBatch:
     """A batch of POA groups (windows) processed together on one GPU."""
     cdef unique_ptr[cudapoa.Batch] batch
