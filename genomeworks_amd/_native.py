@@ -177,5 +177,19 @@ def mapper():
         L.gw_mapper_get_overlaps_host.argtypes = [vp, i64, i32, i64, i64, i64, f32, vp, vp]
         L.gw_mapper_map.restype = i64
         L.gw_mapper_map.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, C.c_double, i64, i64, i64, f32, vp, i64, vp]
+        u32 = C.c_uint32
+        L.gw_mapper_post_process_overlaps.restype = i64
+        L.gw_mapper_post_process_overlaps.argtypes = [vp, i64, i32, vp, i64, vp, vp]
+        L.gw_mapper_rescue_overlap_ends.argtypes = [vp, i64, vp, vp, i32, vp, vp, i32, u32, u32, i32, f32, vp, vp]
+        L.gw_mapper_group_reads_into_indices.restype = i64
+        L.gw_mapper_group_reads_into_indices.argtypes = [vp, i64, i64, vp, i64]
+        L.gw_mapper_map_batched.restype = vp
+        L.gw_mapper_map_batched.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, C.c_double, i64, i64, i64, f32, i64, i64,
+                                            i32, i32, i32, vp]
+        L.gw_mapper_overlaps_count.restype = i64
+        L.gw_mapper_overlaps_count.argtypes = [vp]
+        L.gw_mapper_overlaps_copy.argtypes = [vp, vp, i64, vp, vp]
+        L.gw_mapper_overlaps_destroy.restype = None
+        L.gw_mapper_overlaps_destroy.argtypes = [vp]
         _mapper = L
     return _mapper

@@ -5,7 +5,8 @@
   genomeworks_amd/lib/libcudaextender.so     cudaextender: HIP kernels (include/gwhip_extender.h) + Extender
                                              (cudaextender/extender.hpp, C API include/gw_extender_capi.h)
   genomeworks_amd/lib/libcudamapper.so       cudamapper: HIP kernels (include/gwhip_mapper.h) + Index / Matcher
-                                             handles (C API include/gw_mapper_capi.h)
+                                             handles and the batched driver (C API include/gw_mapper_capi.h)
+  genomeworks_amd/bin/cudamapper             the cudamapper tool over libcudamapper.so (mapper/cudamapper_main.cpp)
 
 Called by __graft_entry__.build(); also usable as `python -m genomeworks_amd.build`.
 """
@@ -29,7 +30,7 @@ HOST_SRCS = ["host/capi.cpp", "host/cudapoa_batch.cpp", "host/cudapoa_utils.cpp"
 EXTENDER_KERNEL_SRCS = ["extender/gwx_ungapped_xdrop.hip"]
 EXTENDER_HOST_SRCS = ["extender/extender.cpp"]
 # cudamapper likewise
-MAPPER_KERNEL_SRCS = ["mapper/gwm_mapper.hip"]
+MAPPER_KERNEL_SRCS = ["mapper/gwm_mapper.hip", "mapper/gwm_postprocess.hip"]
 MAPPER_HOST_SRCS = ["mapper/mapper.cpp"]
 
 # no fast-math, no FMA contraction: band placement is IEEE fp32
@@ -186,8 +187,9 @@ def build_extender(force=False):
 
 
 def build_mapper(force=False):
-    """libcudamapper.so: the sketch / index / matcher / overlapper kernels with their rocPRIM scans, selects and sorts
-    (hipcc, gfx950) and the Index / Matcher handles behind the C API (g++)."""
+    """libcudamapper.so: the sketch / index / matcher / overlapper / post-processing kernels with their rocPRIM scans,
+    selects and sorts (hipcc, gfx950) and the Index / Matcher handles and the batched driver behind the C API (g++);
+    then bin/cudamapper, which links it and libgenomeworks_amd.so (built before this)."""
     os.makedirs(LIB, exist_ok=True)
     target = os.path.join(LIB, "libcudamapper.so")
     inc = ["-I", os.path.join(ROOT, "include")]
@@ -195,7 +197,7 @@ def build_mapper(force=False):
     for s in MAPPER_KERNEL_SRCS:
         src = os.path.join(PKG, s)
         o = os.path.join(LIB, os.path.basename(s) + ".o")
-        sig = _digest([src, os.path.join(ROOT, "include", "gwhip_mapper.h")], KERNEL_FLAGS)
+        sig = _digest([src, os.path.join(ROOT, "include", "gwhip_mapper.h")] + _local_includes(src), KERNEL_FLAGS)
         objs.append(o)
         sigs.append(sig)
         if force or _stale(o, sig):
@@ -220,6 +222,19 @@ def build_mapper(force=False):
     if force or procs or _stale(target, link_sig):
         _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", target] + objs)
         _mark(target, link_sig)
+    # the cudamapper tool: a thin main over the C API, the FASTA reader and PAF writer of libgenomeworks_amd.so
+    bindir = os.path.join(PKG, "bin")
+    os.makedirs(bindir, exist_ok=True)
+    tool = os.path.join(bindir, "cudamapper")
+    tool_sig = _digest(_deps("host", (".hpp",)), [host_sig, link_sig])
+    if force or _stale(tool, tool_sig):
+        _run(["g++"] + [f for f in HOST_FLAGS if f != "-fPIC"] + inc + ["-I", os.path.join(ROCM, "include"), "-o", tool,
+                                                                      os.path.join(PKG, "mapper", "cudamapper_main.cpp"),
+                                                                      "-L", LIB, "-lcudamapper", "-lgenomeworks_amd", "-lgwhip",
+                                                                      "-L", os.path.join(ROCM, "lib"), "-lamdhip64",
+                                                                      "-Wl,-rpath,$ORIGIN/../lib",
+                                                                      "-Wl,-rpath," + os.path.join(ROCM, "lib")])
+        _mark(tool, tool_sig)
     return target
 
 

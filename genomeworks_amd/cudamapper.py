@@ -5,6 +5,10 @@ gfx950), over the flat C API of include/gw_mapper_capi.h.
     matcher = Matcher(index, index)                                # anchors stay on the device
     overlaps = find_overlaps(matcher, all_to_all=True)             # numpy structured array of OVERLAP records
     overlaps = map_reads(reads)                                    # the same in one call
+    overlaps = post_process_overlaps(overlaps)                     # fuse neighbouring overlaps (the CLI's -D drops)
+    overlaps = rescue_overlap_ends(overlaps, reads, reads)         # extend ends over similar flanks (the CLI's -R)
+    overlaps = map_reads_batched(reads, max_basepairs_per_index=30_000_000)   # what the cudamapper tool runs
+    text = format_paf(overlaps, names, lengths, names, lengths, 15)
 
 Index arrays carry the reference's names (representations, read_ids, positions_in_reads, directions_of_reads,
 unique_representations, first_occurrence_of_representations) and come back as numpy arrays."""
@@ -218,3 +222,108 @@ def map_reads(queries, targets=None, k=15, w=10, filtering_parameter=1e-5, min_r
         m.close()
         q.close()
         t.close()
+
+
+def post_process_overlaps(overlaps, drop_fused_overlaps=False, stream=None, timings=None):
+    """Overlapper::post_process_overlaps: the overlaps (in the order find_overlaps gave them), then one fused record per
+    run of neighbours that fuse; drop_fused_overlaps removes the members of fusing pairs. The rules are in
+    include/gwhip_mapper.h. `timings`, if a dict, receives the device time as timings["fuse"] (ms)."""
+    L = _native.mapper()
+    o = np.ascontiguousarray(overlaps, OVERLAP)
+    out = np.zeros(len(o) + len(o) // 2, OVERLAP)
+    ms = C.c_float(0.0)
+    n = L.gw_mapper_post_process_overlaps(_p(o), len(o), int(bool(drop_fused_overlaps)), _p(out), len(out),
+                                          _stream(stream), C.byref(ms))
+    if n < 0:
+        raise _err(L)
+    if timings is not None:
+        timings["fuse"] = ms.value
+    return out[:n]
+
+
+def rescue_overlap_ends(overlaps, query_reads, target_reads=None, extension=50, required_similarity=0.5,
+                        first_query_read_id=0, first_target_read_id=0, stream=None, timings=None):
+    """Overlapper::rescue_overlap_ends: a copy of `overlaps` with the ends moved over flanks whose 15-mer similarity is
+    at least required_similarity (three rounds of up to `extension` bases, 0 <= extension <= 78). Read id r is
+    query_reads[r - first_query_read_id] / target_reads[r - first_target_read_id]; target_reads None means the query
+    reads. A read id outside its set or an overlap beyond its read raises MapperError."""
+    L = _native.mapper()
+    o = np.ascontiguousarray(overlaps, OVERLAP).copy()
+    qb, qo = pack_reads(query_reads)
+    tb, to = (None, None) if target_reads is None else pack_reads(target_reads)
+    ms = C.c_float(0.0)
+    rc = L.gw_mapper_rescue_overlap_ends(_p(o), len(o), _p(qb), _p(qo), len(query_reads),
+                                         None if tb is None else _p(tb), None if to is None else _p(to),
+                                         0 if target_reads is None else len(target_reads), first_query_read_id,
+                                         first_target_read_id, int(extension), float(required_similarity),
+                                         _stream(stream), C.byref(ms))
+    if rc != 0:
+        raise _err(L)
+    if timings is not None:
+        timings["rescue"] = ms.value
+    return o
+
+
+def group_reads_into_indices(read_lengths, max_basepairs_per_index):
+    """group_reads_into_indices of the reference: [(first_read, number_of_reads)] over consecutive reads whose base
+    count stays <= max_basepairs_per_index (a longer read stands alone). As there, a first read longer than the limit
+    leaves a descriptor of zero reads in front, and no reads give [(0, 0)]."""
+    L = _native.mapper()
+    lengths = np.ascontiguousarray(read_lengths, np.int64)
+    out = np.zeros((len(lengths) + 1, 2), np.uint32)
+    n = L.gw_mapper_group_reads_into_indices(_p(lengths), len(lengths), int(max_basepairs_per_index), _p(out), len(out))
+    if n < 0:
+        raise _err(L)
+    return [(int(a), int(b)) for a, b in out[:n]]
+
+
+def map_reads_batched(queries, targets=None, k=15, w=10, filtering_parameter=1e-5, min_residues=3, min_overlap_len=250,
+                      min_bases_per_residue=1000, min_overlap_fraction=0.8, max_basepairs_per_index=30_000_000,
+                      max_basepairs_per_target_index=None, post_process=True, drop_fused_overlaps=False,
+                      rescue_overlap_ends=False, stream=None, timings=None):
+    """What the cudamapper tool does on one device: queries and targets (None: all against all) grouped into indices
+    of at most max_basepairs_per_index / max_basepairs_per_target_index bases (the CLI's -i / -t, given there in
+    millions), every index pair mapped, its overlaps post-processed (post_process; drop_fused_overlaps is -D) and
+    their ends rescued (-R) on the device, results appended in pair order. Read ids are positions in `queries` /
+    `targets`. `timings`, if a dict, receives the summed device times chain_fuse_filter, fuse and rescue (ms) and the
+    number of index pairs."""
+    L = _native.mapper()
+    qb, qo = pack_reads(queries)
+    tb, to = (None, None) if targets is None else pack_reads(targets)
+    t_limit = max_basepairs_per_index if max_basepairs_per_target_index is None else max_basepairs_per_target_index
+    h = L.gw_mapper_map_batched(_p(qb), _p(qo), len(queries), None if tb is None else _p(tb),
+                                None if to is None else _p(to), 0 if targets is None else len(targets), k, w,
+                                float(filtering_parameter), int(min_residues), int(min_overlap_len),
+                                int(min_bases_per_residue), float(min_overlap_fraction), int(max_basepairs_per_index),
+                                int(t_limit), int(bool(post_process)), int(bool(drop_fused_overlaps)),
+                                int(bool(rescue_overlap_ends)), _stream(stream))
+    if not h:
+        raise _err(L)
+    try:
+        out = np.zeros(int(L.gw_mapper_overlaps_count(h)), OVERLAP)
+        ms, pairs = np.zeros(3, np.float32), C.c_int64(0)
+        L.gw_mapper_overlaps_copy(h, _p(out), len(out), _p(ms), C.byref(pairs))
+    finally:
+        L.gw_mapper_overlaps_destroy(h)
+    if timings is not None:
+        timings.update(chain_fuse_filter=float(ms[0]), fuse=float(ms[1]), rescue=float(ms[2]), index_pairs=pairs.value)
+    return out
+
+
+def format_paf(overlaps, query_names, query_lengths, target_names, target_lengths, kmer_size):
+    """The reference's PAF text (print_paf): per overlap the tab-separated line
+    qname qlen qstart qend strand tname tlen tstart tend num_residues*kmer_size max(|tspan|, |qspan|) 255.
+    Read ids index the name and length lists; positions and the residue product print as the reference's %i does."""
+    def i32(x):
+        x &= 0xFFFFFFFF
+        return x - (1 << 32) if x >= 1 << 31 else x
+    lines = []
+    for o in np.ascontiguousarray(overlaps, OVERLAP):
+        q, t = int(o["query_read_id"]), int(o["target_read_id"])
+        qs, qe = int(o["query_start_position_in_read"]), int(o["query_end_position_in_read"])
+        ts, te = int(o["target_start_position_in_read"]), int(o["target_end_position_in_read"])
+        lines.append("%s\t%d\t%d\t%d\t%c\t%s\t%d\t%d\t%d\t%d\t%d\t255\n" % (
+            query_names[q], query_lengths[q], i32(qs), i32(qe), int(o["relative_strand"]), target_names[t],
+            target_lengths[t], i32(ts), i32(te), i32(int(o["num_residues"]) * kmer_size),
+            max(abs(ts - te), abs(qs - qe))))
+    return "".join(lines)

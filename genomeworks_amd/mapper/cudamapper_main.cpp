@@ -1,0 +1,250 @@
+// cudamapper_main.cpp -- the `cudamapper` command-line tool: a thin main over gw_mapper_map_batched
+// (include/gw_mapper_capi.h), the project's FASTA reader and its PAF writer (cudamapper/overlap_alignment.hpp).
+//
+//   cudamapper [options] query.fasta target.fasta > overlaps.paf
+//
+// Option letters and defaults are those of the reference's cudamapper (application_parameters.cpp) for
+// -k -w -i -t -F -r -l -b -z -R -D -h -v. One device, no index cache; options that ask for anything else are refused
+// with a message instead of being ignored.
+#include "gw_mapper_capi.h"
+
+#include <claraparabricks/genomeworks/cudamapper/overlap_alignment.hpp>
+
+#include <getopt.h>
+
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <exception>
+#include <iostream>
+#include <string>
+#include <vector>
+
+namespace
+{
+
+using namespace claraparabricks::genomeworks::cudamapper;
+
+// gwhip_mapper.h's gwm_overlap, == cudamapper::Overlap of the reference (36 B)
+struct overlap_record
+{
+    uint32_t query_read_id;
+    uint32_t target_read_id;
+    uint32_t query_start_position_in_read;
+    uint32_t target_start_position_in_read;
+    uint32_t query_end_position_in_read;
+    uint32_t target_end_position_in_read;
+    uint8_t relative_strand;
+    uint32_t num_residues;
+    uint8_t overlap_complete;
+};
+static_assert(sizeof(overlap_record) == 36, "overlap layout");
+
+void help(std::FILE* f)
+{
+    std::fputs(
+        "Usage: cudamapper [options ...] <query_sequences> <target_sequences>\n"
+        "     <sequences> FASTA files; the same path twice maps all against all\n"
+        "  -k, --kmer-size              length of kmer to use for minimizers [15] (Max=32)\n"
+        "  -w, --window-size            length of window to use for minimizers [10]\n"
+        "  -i, --index-size             length of batch size used for query in MB [30] (a decimal fraction is accepted)\n"
+        "  -t, --target-index-size      length of batch sized used for target in MB [30]\n"
+        "  -F, --filtering-parameter    remove representations with frequency >= this value; 1.0 disables [1e-5];\n"
+        "                               off by default for less than 0.5 Mbp of input\n"
+        "  -r, --min-residues           minimum number of matching residues in an overlap [3]\n"
+        "  -l, --min-overlap-length     minimum length for an overlap [250]\n"
+        "  -b, --min-bases-per-residue  minimum number of bases in overlap per match [1000]\n"
+        "  -z, --min-overlap-fraction   minimum ratio of overlap length to alignment length [0.8]\n"
+        "  -R, --rescue-overlap-ends    extend the ends of overlaps over similar flanks\n"
+        "  -D, --drop-fused-overlaps    remove overlaps which are joined into larger overlaps\n"
+        "  -v, --version                version information\n"
+        "  -h, --help                   this message\n"
+        "Not in this tool: -a (align this tool's PAF with align_overlaps), -d other than 1, -m, -Q -q -C -c, -S -B,\n"
+        "gzipped input.\n",
+        f);
+}
+
+[[noreturn]] void refuse(const std::string& what)
+{
+    std::cerr << "cudamapper: " << what << std::endl;
+    std::exit(1);
+}
+
+bool is_gzip(const std::string& path)
+{
+    std::FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f)
+        return false;
+    const int a = std::fgetc(f), b = std::fgetc(f);
+    std::fclose(f);
+    return a == 0x1f && b == 0x8b;
+}
+
+struct packed_reads
+{
+    std::string bases;
+    std::vector<int64_t> offsets{0};
+    explicit packed_reads(const std::vector<FastaSequence>& reads)
+    {
+        for (const FastaSequence& r : reads)
+        {
+            bases += r.seq;
+            offsets.push_back(static_cast<int64_t>(bases.size()));
+        }
+    }
+};
+
+} // namespace
+
+int main(int argc, char** argv)
+{
+    int32_t k = 15, w = 10, min_residues = 3, min_overlap_len = 250, min_bases_per_residue = 1000;
+    double index_size = 30, target_index_size = 30, filtering_parameter = 1e-5;
+    float min_overlap_fraction = 0.8f;
+    bool rescue = false, drop = false, custom_filter = false;
+    const struct option options[] = {
+        {"kmer-size", required_argument, 0, 'k'},
+        {"window-size", required_argument, 0, 'w'},
+        {"num-devices", required_argument, 0, 'd'},
+        {"max-cached-memory", required_argument, 0, 'm'},
+        {"index-size", required_argument, 0, 'i'},
+        {"target-index-size", required_argument, 0, 't'},
+        {"filtering-parameter", required_argument, 0, 'F'},
+        {"alignment-engines", required_argument, 0, 'a'},
+        {"min-residues", required_argument, 0, 'r'},
+        {"min-overlap-length", required_argument, 0, 'l'},
+        {"min-bases-per-residue", required_argument, 0, 'b'},
+        {"min-overlap-fraction", required_argument, 0, 'z'},
+        {"rescue-overlap-ends", no_argument, 0, 'R'},
+        {"drop-fused-overlaps", no_argument, 0, 'D'},
+        {"query-indices-in-host-memory", required_argument, 0, 'Q'},
+        {"query-indices-in-device-memory", required_argument, 0, 'q'},
+        {"target-indices-in-host-memory", required_argument, 0, 'C'},
+        {"target-indices-in-device-memory", required_argument, 0, 'c'},
+        {"version", no_argument, 0, 'v'},
+        {"help", no_argument, 0, 'h'},
+        {0, 0, 0, 0},
+    };
+    try
+    {
+        int c = 0;
+        while ((c = getopt_long(argc, argv, "k:w:d:m:i:t:F:a:r:l:b:z:RDQ:q:C:c:BSvh", options, nullptr)) != -1)
+        {
+            switch (c)
+            {
+            case 'k': k = std::stoi(optarg); break;
+            case 'w': w = std::stoi(optarg); break;
+            case 'i': index_size = std::stod(optarg); break;
+            case 't': target_index_size = std::stod(optarg); break;
+            case 'F':
+                filtering_parameter = std::stod(optarg);
+                custom_filter       = true;
+                break;
+            case 'r': min_residues = std::stoi(optarg); break;
+            case 'l': min_overlap_len = std::stoi(optarg); break;
+            case 'b': min_bases_per_residue = std::stoi(optarg); break;
+            case 'z': min_overlap_fraction = std::stof(optarg); break;
+            case 'R': rescue = true; break;
+            case 'D': drop = true; break;
+            case 'd':
+                if (std::stoi(optarg) != 1)
+                    refuse("-d: this tool runs on one device");
+                break;
+            case 'a':
+                refuse("-a is not part of this tool: fused records are appended after alignment in the reference, so "
+                       "its CIGARs and overlaps disagree; run align_overlaps on this tool's PAF instead");
+            case 'm': refuse("-m is not supported: there is no caching allocator to size");
+            case 'Q':
+            case 'q':
+            case 'C':
+            case 'c': refuse(std::string("-") + static_cast<char>(c) + " is not supported: there is no index cache");
+            case 'S':
+            case 'B': refuse("-S / -B are not supported: the output is PAF");
+            case 'v': std::cout << "cudamapper (genomeworks_amd, gfx950)" << std::endl; return 1;
+            case 'h': help(stdout); return 1;
+            default: return 1;
+            }
+        }
+        if (k < 1 || k > 32)
+            refuse("kmer of size " + std::to_string(k) + " is not allowed, maximum k = 32");
+        if (w < 1)
+            refuse("-w / --window-size must be at least 1");
+        if (filtering_parameter > 1.0 || filtering_parameter < 0.0)
+            refuse("-F / --filtering-parameter must be in range [0.0, 1.0]");
+        if (index_size <= 0 || target_index_size <= 0)
+            refuse("-i / -t must be positive");
+        if (argc - optind < 2)
+        {
+            std::cerr << "Invalid inputs. Please refer to the help function." << std::endl;
+            help(stderr);
+            return 1;
+        }
+        const std::string query_path = argv[optind], target_path = argv[optind + 1];
+        const bool all_to_all = query_path == target_path;
+        if (is_gzip(query_path) || is_gzip(target_path))
+            refuse("gzipped input is not supported");
+        if (all_to_all)
+        {
+            target_index_size = index_size;
+            std::cerr << "NOTE - Since query and target files are same, activating all_to_all mode. Query index size "
+                         "used for both files."
+                      << std::endl;
+        }
+        const std::vector<FastaSequence> queries = read_fasta(query_path);
+        const std::vector<FastaSequence> own_targets = all_to_all ? std::vector<FastaSequence>() : read_fasta(target_path);
+        const std::vector<FastaSequence>& targets = all_to_all ? queries : own_targets;
+
+        // the frequency filter is off for less than 0.5 Mbp of input unless -F was given
+        int64_t total = 0, short_reads = 0;
+        for (const std::vector<FastaSequence>* set : {&queries, &own_targets})
+            for (const FastaSequence& r : *set)
+            {
+                total += static_cast<int64_t>(r.seq.size());
+                short_reads += static_cast<int64_t>(r.seq.size()) < static_cast<int64_t>(k) + w - 1 ? 1 : 0;
+            }
+        if (total < 500000 && !custom_filter)
+            filtering_parameter = 1.0;
+        if (short_reads > 0)
+            std::cerr << "WARNING: " << short_reads << " reads are shorter than k + w - 1 = " << (k + w - 1)
+                      << " bases; they are skipped and the read ids behind them in their index shift" << std::endl;
+
+        const packed_reads q(queries);
+        const packed_reads t(own_targets);
+        gw_mapper_overlaps* result = gw_mapper_map_batched(
+            q.bases.data(), q.offsets.data(), static_cast<int32_t>(queries.size()), all_to_all ? nullptr : t.bases.data(),
+            all_to_all ? nullptr : t.offsets.data(), static_cast<int32_t>(own_targets.size()), k, w, filtering_parameter,
+            min_residues, min_overlap_len, min_bases_per_residue, min_overlap_fraction,
+            static_cast<int64_t>(index_size * 1000000.0), static_cast<int64_t>(target_index_size * 1000000.0), 1,
+            drop ? 1 : 0, rescue ? 1 : 0, nullptr);
+        if (!result)
+            refuse(gw_mapper_last_error());
+        std::vector<overlap_record> records(static_cast<size_t>(gw_mapper_overlaps_count(result)));
+        gw_mapper_overlaps_copy(result, records.data(), static_cast<int64_t>(records.size()), nullptr, nullptr);
+        gw_mapper_overlaps_destroy(result);
+
+        std::vector<Overlap> overlaps(records.size());
+        for (size_t i = 0; i < records.size(); ++i)
+        {
+            const overlap_record& r = records[i];
+            if (r.query_read_id >= queries.size() || r.target_read_id >= targets.size())
+                refuse("an overlap names a read outside the input");
+            Overlap& o                       = overlaps[i];
+            o.query_read_id_                 = r.query_read_id;
+            o.target_read_id_                = r.target_read_id;
+            o.query_start_position_in_read_  = r.query_start_position_in_read;
+            o.target_start_position_in_read_ = r.target_start_position_in_read;
+            o.query_end_position_in_read_    = r.query_end_position_in_read;
+            o.target_end_position_in_read_   = r.target_end_position_in_read;
+            o.relative_strand                = static_cast<RelativeStrand>(r.relative_strand);
+            o.num_residues_                  = r.num_residues;
+            o.overlap_complete               = r.overlap_complete != 0;
+        }
+        print_paf(overlaps, {}, queries, targets, k, stdout);
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        std::cerr << "cudamapper: " << e.what() << std::endl;
+        return 1;
+    }
+}

@@ -7,11 +7,7 @@
 // (rocPRIM's own kernels use LDS, and some of them scratch).
 #include "gwhip_mapper.h"
 
-#include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
+#include "gwm_device_utils.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -23,135 +19,6 @@ namespace
 {
 
 thread_local std::string g_error;
-
-void check(hipError_t e, const char* what)
-{
-    if (e != hipSuccess)
-        throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-#define GWM_CHECK(x) check((x), #x)
-
-constexpr int kThreads = 256;
-
-inline unsigned grid_for(int64_t n) { return static_cast<unsigned>((n + kThreads - 1) / kThreads); }
-
-// Owning device allocation.
-template <typename T>
-struct dbuf
-{
-    T* p       = nullptr;
-    int64_t n  = 0;
-    dbuf()     = default;
-    explicit dbuf(int64_t count) { resize(count); }
-    dbuf(const dbuf&) = delete;
-    dbuf& operator=(const dbuf&) = delete;
-    ~dbuf() { reset(); }
-    void resize(int64_t count)
-    {
-        reset();
-        n = count;
-        if (count > 0)
-            GWM_CHECK(hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * static_cast<size_t>(count)));
-    }
-    void reset()
-    {
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    T* release()
-    {
-        T* r = p;
-        p    = nullptr;
-        n    = 0;
-        return r;
-    }
-};
-
-// Scratch for the rocPRIM calls of one stage, grown on demand.
-struct Temp
-{
-    dbuf<char> buf;
-    void* get(size_t bytes)
-    {
-        if (static_cast<int64_t>(bytes) > buf.n)
-            buf.resize(static_cast<int64_t>(std::max<size_t>(bytes, 256)));
-        return buf.p;
-    }
-};
-
-template <typename T>
-T to_host(const T* d, hipStream_t s)
-{
-    T h{};
-    GWM_CHECK(hipMemcpyAsync(&h, d, sizeof(T), hipMemcpyDeviceToHost, s));
-    GWM_CHECK(hipStreamSynchronize(s));
-    return h;
-}
-
-template <typename In, typename Out>
-void inclusive_sum(In in, Out out, int64_t n, Temp& t, hipStream_t s)
-{
-    size_t bytes = 0;
-    GWM_CHECK(rocprim::inclusive_scan(nullptr, bytes, in, out, static_cast<size_t>(n), rocprim::plus<>(), s));
-    GWM_CHECK(rocprim::inclusive_scan(t.get(bytes), bytes, in, out, static_cast<size_t>(n), rocprim::plus<>(), s));
-}
-
-// Indices i in [0, n) with flags[i] != 0, in order, into out; returns their number.
-uint32_t select_indices(const uint32_t* flags, int64_t n, uint32_t* out, uint32_t* d_count, Temp& t, hipStream_t s)
-{
-    rocprim::counting_iterator<uint32_t> idx(0);
-    size_t bytes = 0;
-    GWM_CHECK(rocprim::select(nullptr, bytes, idx, flags, out, d_count, static_cast<size_t>(n), s));
-    GWM_CHECK(rocprim::select(t.get(bytes), bytes, idx, flags, out, d_count, static_cast<size_t>(n), s));
-    return to_host(d_count, s);
-}
-
-// Stable LSD radix sort of (key, index) pairs over key bits [0, bits).
-template <typename K>
-void sort_pairs(K* keys_in, K* keys_out, uint32_t* vals_in, uint32_t* vals_out, int64_t n, unsigned bits, Temp& t,
-                hipStream_t s)
-{
-    size_t bytes = 0;
-    GWM_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, keys_in, keys_out, vals_in, vals_out,
-                                        static_cast<unsigned>(n), 0u, bits, s));
-    GWM_CHECK(rocprim::radix_sort_pairs(t.get(bytes), bytes, keys_in, keys_out, vals_in, vals_out,
-                                        static_cast<unsigned>(n), 0u, bits, s));
-}
-
-unsigned bits_for(uint64_t max_value)
-{
-    unsigned b = 1;
-    while (b < 64 && (max_value >> b) != 0)
-        ++b;
-    return b;
-}
-
-struct Events
-{
-    hipEvent_t e[6] = {};
-    int n           = 0;
-    explicit Events(int count)
-        : n(count)
-    {
-        for (int i = 0; i < n; ++i)
-            GWM_CHECK(hipEventCreate(&e[i]));
-    }
-    ~Events()
-    {
-        for (int i = 0; i < n; ++i)
-            (void)hipEventDestroy(e[i]);
-    }
-    void record(int i, hipStream_t s) { GWM_CHECK(hipEventRecord(e[i], s)); }
-    float ms(int a, int b)
-    {
-        float v = 0.f;
-        GWM_CHECK(hipEventSynchronize(e[b]));
-        GWM_CHECK(hipEventElapsedTime(&v, e[a], e[b]));
-        return v;
-    }
-};
 
 // ------------------------------------------------------------------------------------------------------------------
 // sketch
@@ -588,6 +455,8 @@ void set_empty(gwm_index* out)
 
 } // namespace
 
+void gwm_set_error(const char* text) { g_error = text; }
+
 extern "C" {
 
 const char* gwm_last_error(void) { return g_error.c_str(); }
@@ -881,9 +750,10 @@ int gwm_match(const gwm_index* q, const gwm_index* t, void* stream, gwm_anchors*
     }
 }
 
-int gwm_find_overlaps(const gwm_anchor* anchors, int64_t n, int32_t all_to_all, int64_t min_residues, int64_t min_overlap_len,
-                int64_t min_bases_per_residue, float min_overlap_fraction, void* stream, gwm_overlap* out,
-                int64_t* count, float* chain_fuse_filter_ms)
+static int find_overlaps(const gwm_anchor* anchors, int64_t n, int32_t all_to_all, int64_t min_residues,
+                         int64_t min_overlap_len, int64_t min_bases_per_residue, float min_overlap_fraction,
+                         void* stream, gwm_overlap* out, gwm_overlap** device_out, int64_t* count,
+                         float* chain_fuse_filter_ms)
 {
     *count = 0;
     if (chain_fuse_filter_ms)
@@ -933,8 +803,10 @@ int gwm_find_overlaps(const gwm_anchor* anchors, int64_t n, int32_t all_to_all, 
             GWM_CHECK(rocprim::select(temp.get(bytes), bytes, fused.p, keep.p, kept_overlaps.p, d_count.p,
                                       static_cast<size_t>(n_fused), s));
             n_out = to_host(d_count.p, s);
-            if (n_out > 0)
+            if (n_out > 0 && out)
                 GWM_CHECK(hipMemcpyAsync(out, kept_overlaps.p, sizeof(gwm_overlap) * n_out, hipMemcpyDeviceToHost, s));
+            if (n_out > 0 && device_out)
+                *device_out = kept_overlaps.release();
         }
         ev.record(1, s);
         GWM_CHECK(hipStreamSynchronize(s));
@@ -949,5 +821,24 @@ int gwm_find_overlaps(const gwm_anchor* anchors, int64_t n, int32_t all_to_all, 
         return -1;
     }
 }
+
+int gwm_find_overlaps(const gwm_anchor* anchors, int64_t n, int32_t all_to_all, int64_t min_residues, int64_t min_overlap_len,
+                int64_t min_bases_per_residue, float min_overlap_fraction, void* stream, gwm_overlap* out,
+                int64_t* count, float* chain_fuse_filter_ms)
+{
+    return find_overlaps(anchors, n, all_to_all, min_residues, min_overlap_len, min_bases_per_residue,
+                         min_overlap_fraction, stream, out, nullptr, count, chain_fuse_filter_ms);
+}
+
+int gwm_find_overlaps_device(const gwm_anchor* anchors, int64_t n, int32_t all_to_all, int64_t min_residues,
+                             int64_t min_overlap_len, int64_t min_bases_per_residue, float min_overlap_fraction,
+                             void* stream, gwm_overlap** out, int64_t* count, float* chain_fuse_filter_ms)
+{
+    *out = nullptr;
+    return find_overlaps(anchors, n, all_to_all, min_residues, min_overlap_len, min_bases_per_residue,
+                         min_overlap_fraction, stream, nullptr, out, count, chain_fuse_filter_ms);
+}
+
+void gwm_device_free(void* p) { (void)hipFree(p); }
 
 } // extern "C"

@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
@@ -53,6 +54,92 @@ auto guarded(F&& f, decltype(f()) on_error) -> decltype(f())
     return on_error;
 }
 
+// Owning device copy of a host array.
+template <typename T>
+struct device_array
+{
+    T* p = nullptr;
+    device_array() = default;
+    device_array(const T* host, int64_t n) { upload(host, n); }
+    device_array(const device_array&) = delete;
+    device_array& operator=(const device_array&) = delete;
+    ~device_array() { reset(); }
+    void reset()
+    {
+        if (p)
+            (void)hipFree(p);
+        p = nullptr;
+    }
+    void allocate(int64_t n)
+    {
+        reset();
+        if (n > 0)
+            hip_check(hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * static_cast<size_t>(n)), "hipMalloc");
+    }
+    void upload(const T* host, int64_t n)
+    {
+        allocate(n);
+        if (n > 0)
+            hip_check(hipMemcpy(p, host, sizeof(T) * static_cast<size_t>(n), hipMemcpyHostToDevice), "hipMemcpy H2D");
+    }
+};
+
+// A read set on the device, in the layout gwm_rescue_overlap_ends takes.
+struct device_reads
+{
+    device_array<char> bases;
+    device_array<int64_t> offsets;
+    int32_t n = 0;
+    device_reads(const char* host_bases, const int64_t* host_offsets, int32_t n_reads)
+        : n(n_reads)
+    {
+        if (n_reads < 0)
+            throw std::invalid_argument("negative number of reads");
+        bases.upload(host_bases, std::max<int64_t>(host_offsets[n_reads], 1));
+        offsets.upload(host_offsets, n_reads + 1);
+    }
+};
+
+struct descriptor
+{
+    uint32_t first_read;
+    uint32_t number_of_reads;
+};
+
+// group_reads_into_indices of the reference, its loop as it stands (see gw_mapper_capi.h)
+std::vector<descriptor> group_reads(const int64_t* lengths, int64_t n, int64_t max_basepairs)
+{
+    std::vector<descriptor> out;
+    uint32_t first = 0, count = 0;
+    int64_t bases = 0;
+    for (int64_t i = 0; i < n; ++i)
+    {
+        if (lengths[i] + bases > max_basepairs)
+        {
+            out.push_back({first, count});
+            first = static_cast<uint32_t>(i);
+            count = 1;
+            bases = lengths[i];
+        }
+        else
+        {
+            bases += lengths[i];
+            ++count;
+        }
+    }
+    out.push_back({first, count});
+    return out;
+}
+
+struct device_overlaps
+{
+    gwm_overlap* p = nullptr;
+    device_overlaps() = default;
+    device_overlaps(const device_overlaps&) = delete;
+    device_overlaps& operator=(const device_overlaps&) = delete;
+    ~device_overlaps() { gwm_device_free(p); }
+};
+
 } // namespace
 
 struct gw_mapper_index
@@ -79,6 +166,13 @@ struct gw_mapper_matcher
     ~gw_mapper_matcher() { gwm_anchors_free(&a); }
     gw_mapper_matcher(const gw_mapper_matcher&) = delete;
     gw_mapper_matcher& operator=(const gw_mapper_matcher&) = delete;
+};
+
+struct gw_mapper_overlaps
+{
+    std::vector<gwm_overlap> overlaps;
+    float stage_ms[3]   = {0.f, 0.f, 0.f};
+    int64_t index_pairs = 0;
 };
 
 extern "C" {
@@ -227,5 +321,177 @@ int64_t gw_mapper_map(const char* query_bases, const int64_t* query_offsets, int
         return count;
     }, int64_t(GW_MAPPER_ERROR));
 }
+
+int64_t gw_mapper_post_process_overlaps(const void* overlaps, int64_t n, int32_t drop_fused_overlaps, void* out,
+                                        int64_t capacity, void* stream, float* fuse_ms)
+{
+    return guarded([&] {
+        int64_t count = 0;
+        if (fuse_ms)
+            *fuse_ms = 0.f;
+        if (n <= 0)
+            return count;
+        device_array<gwm_overlap> in(static_cast<const gwm_overlap*>(overlaps), n), result;
+        result.allocate(n + n / 2);
+        throw_on(gwm_post_process_overlaps(in.p, n, drop_fused_overlaps, stream, result.p, &count, fuse_ms));
+        copy_out(static_cast<gwm_overlap*>(out), result.p, count < capacity ? count : capacity);
+        return count;
+    }, int64_t(GW_MAPPER_ERROR));
+}
+
+int gw_mapper_rescue_overlap_ends(void* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                                  int32_t n_queries, const char* target_bases, const int64_t* target_offsets,
+                                  int32_t n_targets, uint32_t first_query_read_id, uint32_t first_target_read_id,
+                                  int32_t extension, float required_similarity, void* stream, float* rescue_ms)
+{
+    return guarded([&] {
+        if (rescue_ms)
+            *rescue_ms = 0.f;
+        if (n <= 0)
+        {
+            // the argument checks still apply
+            throw_on(gwm_rescue_overlap_ends(nullptr, 0, nullptr, nullptr, n_queries, 0, nullptr, nullptr,
+                                             target_bases ? n_targets : n_queries, 0, extension, required_similarity,
+                                             stream, nullptr));
+            return 0;
+        }
+        device_reads q(query_bases, query_offsets, n_queries);
+        std::unique_ptr<device_reads> t;
+        if (target_bases)
+            t.reset(new device_reads(target_bases, target_offsets, n_targets));
+        const device_reads& tr = t ? *t : q;
+        device_array<gwm_overlap> d(static_cast<const gwm_overlap*>(overlaps), n);
+        throw_on(gwm_rescue_overlap_ends(d.p, n, q.bases.p, q.offsets.p, q.n, first_query_read_id, tr.bases.p,
+                                         tr.offsets.p, tr.n, first_target_read_id, extension, required_similarity,
+                                         stream, rescue_ms));
+        copy_out(static_cast<gwm_overlap*>(overlaps), d.p, n);
+        return 0;
+    }, GW_MAPPER_ERROR);
+}
+
+int64_t gw_mapper_group_reads_into_indices(const int64_t* read_lengths, int64_t n_reads, int64_t max_basepairs_per_index,
+                                           uint32_t* out, int64_t capacity)
+{
+    return guarded([&] {
+        if (n_reads < 0)
+            throw std::invalid_argument("gw_mapper_group_reads_into_indices: negative number of reads");
+        const std::vector<descriptor> d = group_reads(read_lengths, n_reads, max_basepairs_per_index);
+        const int64_t count             = static_cast<int64_t>(d.size());
+        for (int64_t i = 0; out && i < count && i < capacity; ++i)
+        {
+            out[2 * i]     = d[i].first_read;
+            out[2 * i + 1] = d[i].number_of_reads;
+        }
+        return count;
+    }, int64_t(GW_MAPPER_ERROR));
+}
+
+gw_mapper_overlaps* gw_mapper_map_batched(const char* query_bases, const int64_t* query_offsets, int32_t n_queries,
+                                          const char* target_bases, const int64_t* target_offsets, int32_t n_targets,
+                                          int32_t kmer_size, int32_t window_size, double filtering_parameter,
+                                          int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                                          float min_overlap_fraction, int64_t max_basepairs_per_query_index,
+                                          int64_t max_basepairs_per_target_index, int32_t post_process,
+                                          int32_t drop_fused_overlaps, int32_t rescue_overlap_ends, void* stream)
+{
+    return guarded([&] {
+        hipStream_t s         = static_cast<hipStream_t>(stream);
+        const bool all_to_all = target_bases == nullptr;
+        if (all_to_all)
+        {
+            target_bases   = query_bases;
+            target_offsets = query_offsets;
+            n_targets      = n_queries;
+        }
+        if (n_queries < 0 || n_targets < 0)
+            throw std::invalid_argument("gw_mapper_map_batched: negative number of reads");
+        auto lengths = [](const int64_t* offsets, int32_t n) {
+            std::vector<int64_t> v(static_cast<size_t>(n));
+            for (int32_t i = 0; i < n; ++i)
+                v[i] = offsets[i + 1] - offsets[i];
+            return v;
+        };
+        const std::vector<int64_t> ql = lengths(query_offsets, n_queries), tl = lengths(target_offsets, n_targets);
+        const std::vector<descriptor> qd = group_reads(ql.data(), n_queries, max_basepairs_per_query_index);
+        const std::vector<descriptor> td = group_reads(tl.data(), n_targets, max_basepairs_per_target_index);
+        std::unique_ptr<device_reads> q_reads, t_reads;
+        if (rescue_overlap_ends)
+        {
+            q_reads.reset(new device_reads(query_bases, query_offsets, n_queries));
+            if (!all_to_all)
+                t_reads.reset(new device_reads(target_bases, target_offsets, n_targets));
+        }
+        std::unique_ptr<gw_mapper_overlaps> result(new gw_mapper_overlaps());
+        for (const descriptor& qx : qd)
+        {
+            if (qx.number_of_reads == 0)
+                continue;
+            // one query index serves the whole row of target indices
+            gw_mapper_index qi(query_bases, query_offsets + qx.first_read, static_cast<int32_t>(qx.number_of_reads),
+                               qx.first_read, kmer_size, window_size, 1, filtering_parameter, s);
+            for (const descriptor& tx : td)
+            {
+                if (tx.number_of_reads == 0 || (all_to_all && tx.first_read < qx.first_read))
+                    continue;
+                const bool same = all_to_all && tx.first_read == qx.first_read && tx.number_of_reads == qx.number_of_reads;
+                std::unique_ptr<gw_mapper_index> ti;
+                if (!same)
+                    ti.reset(new gw_mapper_index(target_bases, target_offsets + tx.first_read,
+                                                 static_cast<int32_t>(tx.number_of_reads), tx.first_read, kmer_size,
+                                                 window_size, 1, filtering_parameter, s));
+                int64_t count = 0;
+                float ms      = 0.f;
+                device_overlaps found;
+                {
+                    gw_mapper_matcher m(qi, same ? qi : *ti, s);
+                    throw_on(gwm_find_overlaps_device(m.a.anchors, m.a.n, all_to_all ? 1 : 0, min_residues,
+                                                      min_overlap_len, min_bases_per_residue, min_overlap_fraction, s,
+                                                      &found.p, &count, &ms));
+                    result->stage_ms[0] += ms;
+                }
+                ++result->index_pairs;
+                if (count == 0)
+                    continue;
+                device_array<gwm_overlap> fused;
+                gwm_overlap* current = found.p;
+                if (post_process)
+                {
+                    fused.allocate(count + count / 2);
+                    throw_on(gwm_post_process_overlaps(found.p, count, drop_fused_overlaps, s, fused.p, &count, &ms));
+                    result->stage_ms[1] += ms;
+                    current = fused.p;
+                }
+                if (rescue_overlap_ends && count > 0)
+                {
+                    const device_reads& tr = t_reads ? *t_reads : *q_reads;
+                    throw_on(gwm_rescue_overlap_ends(current, count, q_reads->bases.p, q_reads->offsets.p, q_reads->n,
+                                                     0, tr.bases.p, tr.offsets.p, tr.n, 0, 50, 0.5f, s, &ms));
+                    result->stage_ms[2] += ms;
+                }
+                const size_t at = result->overlaps.size();
+                result->overlaps.resize(at + static_cast<size_t>(count));
+                copy_out(result->overlaps.data() + at, current, count);
+            }
+        }
+        return result.release();
+    }, static_cast<gw_mapper_overlaps*>(nullptr));
+}
+
+int64_t gw_mapper_overlaps_count(const gw_mapper_overlaps* result) { return static_cast<int64_t>(result->overlaps.size()); }
+
+int gw_mapper_overlaps_copy(const gw_mapper_overlaps* result, void* overlaps, int64_t capacity, float* stage_ms,
+                            int64_t* index_pairs)
+{
+    const int64_t n = std::min<int64_t>(capacity, static_cast<int64_t>(result->overlaps.size()));
+    if (overlaps && n > 0)
+        std::memcpy(overlaps, result->overlaps.data(), sizeof(gwm_overlap) * static_cast<size_t>(n));
+    if (stage_ms)
+        std::memcpy(stage_ms, result->stage_ms, sizeof(result->stage_ms));
+    if (index_pairs)
+        *index_pairs = result->index_pairs;
+    return 0;
+}
+
+void gw_mapper_overlaps_destroy(gw_mapper_overlaps* result) { delete result; }
 
 } // extern "C"

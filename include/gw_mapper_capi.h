@@ -1,7 +1,8 @@
 /*
  * gw_mapper_capi.h -- flat C API of cudamapper (libcudamapper.so), for foreign-function bindings
- * (genomeworks_amd/cudamapper.py): index creation from host reads, the anchor matcher, the triggered overlapper and
- * one call for a whole mapping. Functions returning int give 0 on success; those returning a count give it, or
+ * (genomeworks_amd/cudamapper.py): index creation from host reads, the anchor matcher, the triggered overlapper, one
+ * call for a whole mapping of one index pair, overlap post-processing and end rescue, and the batched driver behind
+ * the cudamapper tool. Functions returning int give 0 on success; those returning a count give it, or
  * GW_MAPPER_ERROR; creators return NULL. On an error the exception text is in gw_mapper_last_error().
  *
  * Reads are passed as one byte array and n_reads + 1 offsets: read i is bases[offsets[i] .. offsets[i+1]).
@@ -75,6 +76,55 @@ int64_t gw_mapper_map(const char* query_bases, const int64_t* query_offsets, int
                       int32_t window_size, double filtering_parameter, int64_t min_residues, int64_t min_overlap_len,
                       int64_t min_bases_per_residue, float min_overlap_fraction, void* overlaps, int64_t capacity,
                       void* stream);
+
+/* ---- what cudamapper does with the overlaps of an index pair before it prints them -------------------------------
+   The rules are spelled out next to gwm_post_process_overlaps / gwm_rescue_overlap_ends in gwhip_mapper.h. */
+
+/* Overlapper::post_process_overlaps over n host overlaps: the originals (without the members of fusing pairs when
+   drop_fused_overlaps is set), then one fused record per run. Returns their number (at most n + n / 2) and writes
+   min(capacity, count) of them to `out`; fuse_ms (device time) may be NULL. */
+int64_t gw_mapper_post_process_overlaps(const void* overlaps, int64_t n, int32_t drop_fused_overlaps, void* out,
+                                        int64_t capacity, void* stream, float* fuse_ms);
+
+/* Overlapper::rescue_overlap_ends over n host overlaps, in place. Query and target reads as everywhere in this
+   header; target_bases NULL means the target set is the query set. Read id r is read r - first_*_read_id of its
+   set. 0 <= extension <= 78. A read id outside its set, or a start or end beyond its read (undefined behaviour or an
+   exception in the reference), is an error: GW_MAPPER_ERROR, and the overlaps are left as they were. */
+int gw_mapper_rescue_overlap_ends(void* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                                  int32_t n_queries, const char* target_bases, const int64_t* target_offsets,
+                                  int32_t n_targets, uint32_t first_query_read_id, uint32_t first_target_read_id,
+                                  int32_t extension, float required_similarity, void* stream, float* rescue_ms);
+
+/* group_reads_into_indices: consecutive reads while the running base count stays <= max_basepairs_per_index; a longer
+   read gets an index of its own. The reference's loop as it stands: when the very first read is longer than the limit
+   a descriptor of zero reads comes first, and no reads at all give the one descriptor {0, 0}. Returns the number of
+   descriptors (at most n_reads + 1) and writes min(capacity, count) pairs (first_read, number_of_reads) to `out`,
+   which may be NULL. */
+int64_t gw_mapper_group_reads_into_indices(const int64_t* read_lengths, int64_t n_reads, int64_t max_basepairs_per_index,
+                                           uint32_t* out, int64_t capacity);
+
+/* The walk of the reference's cudamapper for one device: queries and targets grouped into indices (target_bases NULL:
+   all against all over the query set; queries are grouped by max_basepairs_per_query_index, targets by
+   max_basepairs_per_target_index), index pairs in (query index, target index) order, descriptors of zero reads and,
+   all against all, pairs with target.first_read < query.first_read skipped; per pair index -> match -> overlaps ->
+   post-process (if post_process) -> end rescue with extension 50 and similarity 0.5 (if rescue_overlap_ends), the
+   overlaps staying on the device in between, then appended to the result. Read ids are positions in the query /
+   target set (the id shift behind reads shorter than k + w - 1 applies within an index, as in gwm_index_build).
+   No index cache, no host copies of indices, one device. */
+typedef struct gw_mapper_overlaps gw_mapper_overlaps;
+gw_mapper_overlaps* gw_mapper_map_batched(const char* query_bases, const int64_t* query_offsets, int32_t n_queries,
+                                          const char* target_bases, const int64_t* target_offsets, int32_t n_targets,
+                                          int32_t kmer_size, int32_t window_size, double filtering_parameter,
+                                          int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                                          float min_overlap_fraction, int64_t max_basepairs_per_query_index,
+                                          int64_t max_basepairs_per_target_index, int32_t post_process,
+                                          int32_t drop_fused_overlaps, int32_t rescue_overlap_ends, void* stream);
+int64_t gw_mapper_overlaps_count(const gw_mapper_overlaps* result);
+/* copies min(capacity, count) overlaps; stage_ms[3] (summed device time of chain/fuse/filter, post-processing, end
+   rescue) and index_pairs (pairs walked) may be NULL */
+int gw_mapper_overlaps_copy(const gw_mapper_overlaps* result, void* overlaps, int64_t capacity, float* stage_ms,
+                            int64_t* index_pairs);
+void gw_mapper_overlaps_destroy(gw_mapper_overlaps* result);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 /*
  * gwhip_mapper.h -- kernel-level C-ABI of the cudamapper engine (libcudamapper.so): (k,w)-minimizer sketch, index
- * (stable sort, unique representations, frequency filter), anchor matcher and the triggered overlapper (chain, fuse,
- * filter), all on gfx950.
+ * (stable sort, unique representations, frequency filter), anchor matcher, the triggered overlapper (chain, fuse,
+ * filter) and the post-processing of its overlaps (fusion of neighbours, end rescue), all on gfx950.
  *
  * The object-level API on top of it is gw_mapper_capi.h (flat C) and genomeworks_amd.cudamapper (Python). This header
  * is kept apart from gwhip.h on purpose: the POA / aligner kernel set and its source digest are not affected.
@@ -101,6 +101,46 @@ void gwm_anchors_free(gwm_anchors* anchors);
 int gwm_find_overlaps(const gwm_anchor* anchors, int64_t n, int32_t all_to_all, int64_t min_residues, int64_t min_overlap_len,
                 int64_t min_bases_per_residue, float min_overlap_fraction, void* stream, gwm_overlap* out,
                 int64_t* count, float* chain_fuse_filter_ms);
+
+/* gwm_find_overlaps with the result left on the device: *out is a device array of *count records (NULL when there are
+ * none) that the caller frees with gwm_device_free. */
+int gwm_find_overlaps_device(const gwm_anchor* anchors, int64_t n, int32_t all_to_all, int64_t min_residues,
+                             int64_t min_overlap_len, int64_t min_bases_per_residue, float min_overlap_fraction,
+                             void* stream, gwm_overlap** out, int64_t* count, float* chain_fuse_filter_ms);
+void gwm_device_free(void* device_pointer);
+
+/* Overlapper::post_process_overlaps over device overlaps[0..n), in the order get_overlaps gave them. Two neighbours
+ * fuse when they share strand ('+' or '-') and read pair and (a) both gaps are below 500, or (b) the float ratio of
+ * the smaller gap to the larger exceeds the double 0.8, or (c) both gaps, as float fractions of the summed query /
+ * target lengths, are below the double 0.2. A gap is abs() of the uint32 difference read as int32 (query: start of
+ * the second minus end of the first; target likewise on '+', start of the first minus end of the second on '-'); a
+ * difference of exactly 2^31 is undefined in the reference and stays -2^31 here. Every maximal run of fusing
+ * neighbours gives one record, written after the originals in run order: query start and '+' target start from the
+ * run's first member, query end and '+' target end from its last ('-': target start from the last, target end from
+ * the first), num_residues the sum, every other field from the run's last member -- or from its second to last when
+ * the run reaches the end of the array. With drop_fused_overlaps the originals that belong to a fusing pair are
+ * removed, order kept. `out` is a device array with room for n + n / 2 records and must not alias `overlaps`;
+ * *count is the number written. fuse_ms (device time, HIP events) may be NULL. */
+int gwm_post_process_overlaps(const gwm_overlap* overlaps, int64_t n, int32_t drop_fused_overlaps, void* stream,
+                              gwm_overlap* out, int64_t* count, float* fuse_ms);
+
+/* Overlapper::rescue_overlap_ends over device overlaps[0..n), in place. The reads of the query set and of the target
+ * set are device arrays in the layout gwm_index_build takes (bases, n + 1 offsets); read id r of an overlap is read
+ * r - first_*_read_id of its set. Per overlap, three rounds of: head window = min(query start, target start,
+ * extension) bases before the starts, tail window = min(extension, query length - query end, target length - target
+ * end) bases after the ends; an end moves by its whole window when float(shared) / float(union) of the two windows'
+ * 15-mers (stride 1, multisets; a window shorter than 15 bases, the empty one too, is a single k-mer) is >=
+ * required_similarity. Bytes compare as bytes. A '-' overlap is handled in the coordinates of the reverse-complemented
+ * target (A<->T, C<->G; every other byte stays as it is -- the reference leaves the other upper-case letters alone
+ * and is undefined for the rest; the middle base of an odd-length target is not complemented, as the reference's
+ * in-place swap of len / 2 pairs skips it) and moved back. 0 <= extension <= 78 (one k-mer per lane of a wave64); anything
+ * else is an error. Where the reference is undefined or throws -- a read id outside its set, a start or end beyond
+ * its read -- the call returns -1, says so in gwm_last_error() and leaves the overlaps as they were; the kernel never
+ * reads outside the reads it was given. rescue_ms may be NULL. */
+int gwm_rescue_overlap_ends(gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                            int32_t n_queries, uint32_t first_query_read_id, const char* target_bases,
+                            const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
+                            int32_t extension, float required_similarity, void* stream, float* rescue_ms);
 
 const char* gwm_last_error(void);
 
