@@ -154,6 +154,7 @@ def mapper():
     global _mapper
     if _mapper is None:
         vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+        gwhip()  # libcudamapper.so links it for the aligner behind gwm_align_overlaps
         L = _load("libcudamapper.so")
         L.gw_mapper_last_error.restype = C.c_char_p
         L.gw_mapper_index_create.restype = vp
@@ -191,5 +192,21 @@ def mapper():
         L.gw_mapper_overlaps_copy.argtypes = [vp, vp, i64, vp, vp]
         L.gw_mapper_overlaps_destroy.restype = None
         L.gw_mapper_overlaps_destroy.argtypes = [vp]
+        L.gw_mapper_align_overlaps.restype = vp
+        L.gw_mapper_align_overlaps.argtypes = [vp, i64, vp, vp, i32, u32, vp, vp, i32, u32, i64, vp]
+        L.gw_mapper_cigars_count.restype = i64
+        L.gw_mapper_cigars_count.argtypes = [vp]
+        L.gw_mapper_cigars_text_bytes.restype = i64
+        L.gw_mapper_cigars_text_bytes.argtypes = [vp]
+        L.gw_mapper_cigars_copy.argtypes = [vp, vp, vp, vp, vp]
+        L.gw_mapper_cigars_destroy.restype = None
+        L.gw_mapper_cigars_destroy.argtypes = [vp]
+        L.gw_mapper_map_batched_aligned.restype = vp
+        L.gw_mapper_map_batched_aligned.argtypes = L.gw_mapper_map_batched.argtypes[:-1] + [i32, i64, vp]
+        L.gw_mapper_overlaps_cigar_text_bytes.restype = i64
+        L.gw_mapper_overlaps_cigar_text_bytes.argtypes = [vp]
+        L.gw_mapper_overlaps_copy_cigars.argtypes = [vp, vp, vp, vp, vp]
+        L.gwm_align_bytes_needed.restype = i64
+        L.gwm_align_bytes_needed.argtypes = [i32, i32, i32]
         _mapper = L
     return _mapper

@@ -30,7 +30,7 @@ HOST_SRCS = ["host/capi.cpp", "host/cudapoa_batch.cpp", "host/cudapoa_utils.cpp"
 EXTENDER_KERNEL_SRCS = ["extender/gwx_ungapped_xdrop.hip"]
 EXTENDER_HOST_SRCS = ["extender/extender.cpp"]
 # cudamapper likewise
-MAPPER_KERNEL_SRCS = ["mapper/gwm_mapper.hip", "mapper/gwm_postprocess.hip"]
+MAPPER_KERNEL_SRCS = ["mapper/gwm_mapper.hip", "mapper/gwm_postprocess.hip", "mapper/gwm_align.hip"]
 MAPPER_HOST_SRCS = ["mapper/mapper.cpp"]
 
 # no fast-math, no FMA contraction: band placement is IEEE fp32
@@ -187,8 +187,9 @@ def build_extender(force=False):
 
 
 def build_mapper(force=False):
-    """libcudamapper.so: the sketch / index / matcher / overlapper / post-processing kernels with their rocPRIM scans,
-    selects and sorts (hipcc, gfx950) and the Index / Matcher handles and the batched driver behind the C API (g++);
+    """libcudamapper.so: the sketch / index / matcher / overlapper / post-processing / overlap alignment kernels with
+    their rocPRIM scans, selects and sorts (hipcc, gfx950), linked against libgwhip.so for the aligner, and the Index /
+    Matcher handles and the batched driver behind the C API (g++);
     then bin/cudamapper, which links it and libgenomeworks_amd.so (built before this)."""
     os.makedirs(LIB, exist_ok=True)
     target = os.path.join(LIB, "libcudamapper.so")
@@ -197,7 +198,8 @@ def build_mapper(force=False):
     for s in MAPPER_KERNEL_SRCS:
         src = os.path.join(PKG, s)
         o = os.path.join(LIB, os.path.basename(s) + ".o")
-        sig = _digest([src, os.path.join(ROOT, "include", "gwhip_mapper.h")] + _local_includes(src), KERNEL_FLAGS)
+        sig = _digest([src, os.path.join(ROOT, "include", "gwhip_mapper.h"), os.path.join(ROOT, "include", "gwhip.h")] +
+                      _local_includes(src), KERNEL_FLAGS)
         objs.append(o)
         sigs.append(sig)
         if force or _stale(o, sig):
@@ -220,7 +222,9 @@ def build_mapper(force=False):
         _mark(o, sig)
     link_sig = _digest([], sigs)
     if force or procs or _stale(target, link_sig):
-        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", target] + objs)
+        # gwm_align.hip calls the default aligner of libgwhip.so (built before this)
+        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", target] + objs +
+             ["-L", LIB, "-lgwhip", "-Wl,-rpath,$ORIGIN"])
         _mark(target, link_sig)
     # the cudamapper tool: a thin main over the C API, the FASTA reader and PAF writer of libgenomeworks_amd.so
     bindir = os.path.join(PKG, "bin")

@@ -9,6 +9,9 @@ gfx950), over the flat C API of include/gw_mapper_capi.h.
     overlaps = rescue_overlap_ends(overlaps, reads, reads)         # extend ends over similar flanks (the CLI's -R)
     overlaps = map_reads_batched(reads, max_basepairs_per_index=30_000_000)   # what the cudamapper tool runs
     text = format_paf(overlaps, names, lengths, names, lengths, 15)
+    cigars, edit_distances = align_overlaps(overlaps, reads)       # the default aligner, nothing but text comes back
+    overlaps, cigars = map_reads_batched(reads, align=True)        # the tool's --cigar
+    text = format_paf(overlaps, names, lengths, names, lengths, 15, cigars=cigars)
 
 Index arrays carry the reference's names (representations, read_ids, positions_in_reads, directions_of_reads,
 unique_representations, first_occurrence_of_representations) and come back as numpy arrays."""
@@ -264,6 +267,52 @@ def rescue_overlap_ends(overlaps, query_reads, target_reads=None, extension=50, 
     return o
 
 
+def _split_cigars(text, offsets):
+    t = text.tobytes().decode("ascii")
+    return [t[int(a):int(b)] for a, b in zip(offsets[:-1], offsets[1:])]
+
+
+def align_bytes_needed(query_length, target_length, max_query_length):
+    """Device bytes align_overlaps counts for one overlap with slices of these lengths in a call whose longest query
+    slice is max_query_length: the smallest max_device_bytes it can be aligned with (gwm_align_bytes_needed)."""
+    return int(_native.mapper().gwm_align_bytes_needed(int(query_length), int(target_length), int(max_query_length)))
+
+
+def align_overlaps(overlaps, query_reads, target_reads=None, first_query_read_id=0, first_target_read_id=0,
+                   max_device_bytes=0, stream=None, timings=None):
+    """Global alignment of every overlap over its own slices, on the device from the reads to the CIGAR text: query
+    slice [query start, query end) against target slice [target start, target end), on '-' against that target
+    slice's reverse complement as cudaaligner takes it ("TGAC"[(c >> 1) & 3] for every byte), with the default aligner
+    (Hirschberg + Myers) at max_query_length = the longest query slice of the call. Returns (cigars, edit_distances):
+    the strings of Alignment::convert_to_cigar() in its basic format (M for match and mismatch, I / D as cudaaligner
+    names them) and an int32 array of the columns that are not a match (-1 where the aligner gave no result). Read id
+    r is query_reads[r - first_query_read_id] / target_reads[r - first_target_read_id]; target_reads None means the
+    query reads. Overlaps are aligned in chunks that keep within max_device_bytes (0: half of the free device memory);
+    the result does not depend on it, and an overlap that does not fit alone raises, as do a read id outside its set,
+    start > end and an end beyond its read. `timings`, if a dict, receives gather, align and cigar_text (device ms)."""
+    L = _native.mapper()
+    o = np.ascontiguousarray(overlaps, OVERLAP)
+    qb, qo = pack_reads(query_reads)
+    tb, to = (None, None) if target_reads is None else pack_reads(target_reads)
+    h = L.gw_mapper_align_overlaps(_p(o), len(o), _p(qb), _p(qo), len(query_reads), first_query_read_id,
+                                   None if tb is None else _p(tb), None if to is None else _p(to),
+                                   0 if target_reads is None else len(target_reads), first_target_read_id,
+                                   int(max_device_bytes), _stream(stream))
+    if not h:
+        raise _err(L)
+    try:
+        n = int(L.gw_mapper_cigars_count(h))
+        text = np.zeros(int(L.gw_mapper_cigars_text_bytes(h)), np.uint8)
+        offsets, edits, ms = np.zeros(n + 1, np.int64), np.zeros(n, np.int32), np.zeros(3, np.float32)
+        if L.gw_mapper_cigars_copy(h, _p(text), _p(offsets), _p(edits), _p(ms)) != 0:
+            raise _err(L)
+    finally:
+        L.gw_mapper_cigars_destroy(h)
+    if timings is not None:
+        timings.update(gather=float(ms[0]), align=float(ms[1]), cigar_text=float(ms[2]))
+    return _split_cigars(text, offsets), edits
+
+
 def group_reads_into_indices(read_lengths, max_basepairs_per_index):
     """group_reads_into_indices of the reference: [(first_read, number_of_reads)] over consecutive reads whose base
     count stays <= max_basepairs_per_index (a longer read stands alone). As there, a first read longer than the limit
@@ -280,40 +329,60 @@ def group_reads_into_indices(read_lengths, max_basepairs_per_index):
 def map_reads_batched(queries, targets=None, k=15, w=10, filtering_parameter=1e-5, min_residues=3, min_overlap_len=250,
                       min_bases_per_residue=1000, min_overlap_fraction=0.8, max_basepairs_per_index=30_000_000,
                       max_basepairs_per_target_index=None, post_process=True, drop_fused_overlaps=False,
-                      rescue_overlap_ends=False, stream=None, timings=None):
+                      rescue_overlap_ends=False, stream=None, timings=None, align=False, max_device_bytes=0):
     """What the cudamapper tool does on one device: queries and targets (None: all against all) grouped into indices
     of at most max_basepairs_per_index / max_basepairs_per_target_index bases (the CLI's -i / -t, given there in
     millions), every index pair mapped, its overlaps post-processed (post_process; drop_fused_overlaps is -D) and
     their ends rescued (-R) on the device, results appended in pair order. Read ids are positions in `queries` /
     `targets`. `timings`, if a dict, receives the summed device times chain_fuse_filter, fuse and rescue (ms) and the
-    number of index pairs."""
+    number of index pairs.
+
+    align=True (the tool's --cigar) aligns what is left of every index pair as align_overlaps does, one call per pair,
+    with overlaps and reads staying on the device, and returns (overlaps, cigars), one CIGAR per overlap; timings
+    also gets gather, align, cigar_text and the int32 array edit_distances. A read shorter than k + w - 1 then raises
+    before any device work: the index would skip it and shift the read ids behind it, so the wrong sequences would be
+    aligned. (The reference's -a aligns before fusion appends its records; this aligns the records returned.)"""
     L = _native.mapper()
     qb, qo = pack_reads(queries)
     tb, to = (None, None) if targets is None else pack_reads(targets)
     t_limit = max_basepairs_per_index if max_basepairs_per_target_index is None else max_basepairs_per_target_index
-    h = L.gw_mapper_map_batched(_p(qb), _p(qo), len(queries), None if tb is None else _p(tb),
-                                None if to is None else _p(to), 0 if targets is None else len(targets), k, w,
-                                float(filtering_parameter), int(min_residues), int(min_overlap_len),
-                                int(min_bases_per_residue), float(min_overlap_fraction), int(max_basepairs_per_index),
-                                int(t_limit), int(bool(post_process)), int(bool(drop_fused_overlaps)),
-                                int(bool(rescue_overlap_ends)), _stream(stream))
+    args = (_p(qb), _p(qo), len(queries), None if tb is None else _p(tb), None if to is None else _p(to),
+            0 if targets is None else len(targets), k, w, float(filtering_parameter), int(min_residues),
+            int(min_overlap_len), int(min_bases_per_residue), float(min_overlap_fraction), int(max_basepairs_per_index),
+            int(t_limit), int(bool(post_process)), int(bool(drop_fused_overlaps)), int(bool(rescue_overlap_ends)))
+    if align:
+        h = L.gw_mapper_map_batched_aligned(*args, 1, int(max_device_bytes), _stream(stream))
+    else:
+        h = L.gw_mapper_map_batched(*args, _stream(stream))
     if not h:
         raise _err(L)
     try:
         out = np.zeros(int(L.gw_mapper_overlaps_count(h)), OVERLAP)
         ms, pairs = np.zeros(3, np.float32), C.c_int64(0)
         L.gw_mapper_overlaps_copy(h, _p(out), len(out), _p(ms), C.byref(pairs))
+        if align:
+            text = np.zeros(int(L.gw_mapper_overlaps_cigar_text_bytes(h)), np.uint8)
+            offsets, edits, align_ms = np.zeros(len(out) + 1, np.int64), np.zeros(len(out), np.int32), np.zeros(3, np.float32)
+            if L.gw_mapper_overlaps_copy_cigars(h, _p(text), _p(offsets), _p(edits), _p(align_ms)) != 0:
+                raise _err(L)
     finally:
         L.gw_mapper_overlaps_destroy(h)
     if timings is not None:
         timings.update(chain_fuse_filter=float(ms[0]), fuse=float(ms[1]), rescue=float(ms[2]), index_pairs=pairs.value)
-    return out
+        if align:
+            timings.update(gather=float(align_ms[0]), align=float(align_ms[1]), cigar_text=float(align_ms[2]),
+                           edit_distances=edits)
+    return (out, _split_cigars(text, offsets)) if align else out
 
 
-def format_paf(overlaps, query_names, query_lengths, target_names, target_lengths, kmer_size):
+def format_paf(overlaps, query_names, query_lengths, target_names, target_lengths, kmer_size, cigars=None):
     """The reference's PAF text (print_paf): per overlap the tab-separated line
     qname qlen qstart qend strand tname tlen tstart tend num_residues*kmer_size max(|tspan|, |qspan|) 255.
-    Read ids index the name and length lists; positions and the residue product print as the reference's %i does."""
+    Read ids index the name and length lists; positions and the residue product print as the reference's %i does.
+    With `cigars` (one per overlap) every line continues with a tab and cg:Z:<cigar>, as the tool's --cigar and
+    align_overlaps print it."""
+    if cigars is not None and len(cigars) != len(overlaps):
+        raise ValueError("one CIGAR per overlap")
     def i32(x):
         x &= 0xFFFFFFFF
         return x - (1 << 32) if x >= 1 << 31 else x
@@ -322,8 +391,8 @@ def format_paf(overlaps, query_names, query_lengths, target_names, target_length
         q, t = int(o["query_read_id"]), int(o["target_read_id"])
         qs, qe = int(o["query_start_position_in_read"]), int(o["query_end_position_in_read"])
         ts, te = int(o["target_start_position_in_read"]), int(o["target_end_position_in_read"])
-        lines.append("%s\t%d\t%d\t%d\t%c\t%s\t%d\t%d\t%d\t%d\t%d\t255\n" % (
+        lines.append("%s\t%d\t%d\t%d\t%c\t%s\t%d\t%d\t%d\t%d\t%d\t255%s\n" % (
             query_names[q], query_lengths[q], i32(qs), i32(qe), int(o["relative_strand"]), target_names[t],
             target_lengths[t], i32(ts), i32(te), i32(int(o["num_residues"]) * kmer_size),
-            max(abs(ts - te), abs(qs - qe))))
+            max(abs(ts - te), abs(qs - qe)), "" if cigars is None else "\tcg:Z:" + cigars[len(lines)]))
     return "".join(lines)

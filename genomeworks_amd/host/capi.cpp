@@ -20,6 +20,8 @@
 #include <stdexcept>
 #include <claraparabricks/genomeworks/cudaaligner/aligner.hpp>
 #include <claraparabricks/genomeworks/cudaaligner/alignment.hpp>
+#include <claraparabricks/genomeworks/cudaaligner/cudaaligner.hpp>
+#include <claraparabricks/genomeworks/cudamapper/overlap_alignment.hpp>
 
 namespace gw  = claraparabricks::genomeworks;
 namespace poa = claraparabricks::genomeworks::cudapoa;
@@ -946,5 +948,72 @@ const char* gw_windows_sequence(const gw_windows* w, int32_t window, int32_t seq
     return s.data();
     GW_CATCH(nullptr)
 }
+
+// ---- the alignment stage of cudamapper on the host path (cudamapper/overlap_alignment.hpp) ------------------------
+struct gw_overlap_cigars
+{
+    std::string text;
+    std::vector<int64_t> offsets{0};
+};
+
+gw_overlap_cigars* gw_align_overlaps(const void* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                                     int32_t n_queries, const char* target_bases, const int64_t* target_offsets,
+                                     int32_t n_targets, int32_t num_alignment_engines, int32_t max_alignments_per_batch,
+                                     int64_t max_cached_bytes)
+{
+    GW_TRY
+    namespace cm = claraparabricks::genomeworks::cudamapper;
+    struct record // cudamapper::Overlap as gw_mapper_capi.h passes it (36 B)
+    {
+        uint32_t query_read_id, target_read_id, query_start, target_start, query_end, target_end;
+        uint8_t relative_strand;
+        uint32_t num_residues;
+        uint8_t overlap_complete;
+    };
+    static_assert(sizeof(record) == 36, "overlap layout");
+    if (n < 0 || n_queries < 0 || n_targets < 0) throw std::invalid_argument("gw_align_overlaps: negative count");
+    auto reads = [](const char* bases, const int64_t* offsets, int32_t count) {
+        std::vector<cm::FastaSequence> v(static_cast<size_t>(count));
+        for (int32_t i = 0; i < count; ++i) v[i].seq.assign(bases + offsets[i], bases + offsets[i + 1]);
+        return v;
+    };
+    const std::vector<cm::FastaSequence> queries = reads(query_bases, query_offsets, n_queries);
+    const std::vector<cm::FastaSequence> own     = target_bases ? reads(target_bases, target_offsets, n_targets) : std::vector<cm::FastaSequence>();
+    const record* r = static_cast<const record*>(overlaps);
+    std::vector<cm::Overlap> o(static_cast<size_t>(n));
+    for (int64_t i = 0; i < n; ++i)
+    {
+        o[i].query_read_id_                 = r[i].query_read_id;
+        o[i].target_read_id_                = r[i].target_read_id;
+        o[i].query_start_position_in_read_  = r[i].query_start;
+        o[i].target_start_position_in_read_ = r[i].target_start;
+        o[i].query_end_position_in_read_    = r[i].query_end;
+        o[i].target_end_position_in_read_   = r[i].target_end;
+        o[i].relative_strand                = r[i].relative_strand == '-' ? cm::RelativeStrand::Reverse : cm::RelativeStrand::Forward;
+        o[i].num_residues_                  = r[i].num_residues;
+    }
+    if (claraparabricks::genomeworks::cudaaligner::Init() != claraparabricks::genomeworks::cudaaligner::success)
+        throw std::runtime_error("cudaaligner::Init failed");
+    claraparabricks::genomeworks::DefaultDeviceAllocator allocator =
+        claraparabricks::genomeworks::create_default_device_allocator(static_cast<std::size_t>(max_cached_bytes > 0 ? max_cached_bytes : int64_t(2) << 30));
+    std::vector<std::string> cigars;
+    cm::align_overlaps(allocator, o, queries, target_bases ? own : queries, num_alignment_engines, cigars, max_alignments_per_batch);
+    std::unique_ptr<gw_overlap_cigars> h(new gw_overlap_cigars());
+    for (const std::string& c : cigars)
+    {
+        h->text += c;
+        h->offsets.push_back(static_cast<int64_t>(h->text.size()));
+    }
+    return h.release();
+    GW_CATCH(nullptr)
+}
+int64_t gw_overlap_cigars_count(const gw_overlap_cigars* c) { return static_cast<int64_t>(c->offsets.size()) - 1; }
+int64_t gw_overlap_cigars_text_bytes(const gw_overlap_cigars* c) { return static_cast<int64_t>(c->text.size()); }
+void gw_overlap_cigars_copy(const gw_overlap_cigars* c, char* text, int64_t* offsets)
+{
+    if (text && !c->text.empty()) std::memcpy(text, c->text.data(), c->text.size());
+    if (offsets) std::memcpy(offsets, c->offsets.data(), sizeof(int64_t) * c->offsets.size());
+}
+void gw_overlap_cigars_destroy(gw_overlap_cigars* c) { delete c; }
 
 } // extern "C"

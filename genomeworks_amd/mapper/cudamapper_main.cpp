@@ -5,7 +5,8 @@
 //
 // Option letters and defaults are those of the reference's cudamapper (application_parameters.cpp) for
 // -k -w -i -t -F -r -l -b -z -R -D -h -v. One device, no index cache; options that ask for anything else are refused
-// with a message instead of being ignored.
+// with a message instead of being ignored. --cigar (no letter) aligns the printed records on the device
+// (gw_mapper_map_batched_aligned) and adds the cg:Z: column.
 #include "gw_mapper_capi.h"
 
 #include <claraparabricks/genomeworks/cudamapper/overlap_alignment.hpp>
@@ -57,10 +58,12 @@ void help(std::FILE* f)
         "  -z, --min-overlap-fraction   minimum ratio of overlap length to alignment length [0.8]\n"
         "  -R, --rescue-overlap-ends    extend the ends of overlaps over similar flanks\n"
         "  -D, --drop-fused-overlaps    remove overlaps which are joined into larger overlaps\n"
+        "      --cigar                  align every printed overlap on the device and add its CIGAR as a cg:Z: column\n"
         "  -v, --version                version information\n"
         "  -h, --help                   this message\n"
-        "Not in this tool: -a (align this tool's PAF with align_overlaps), -d other than 1, -m, -Q -q -C -c, -S -B,\n"
-        "gzipped input.\n",
+        "Not in this tool: -a (its letter stays refused: the reference aligns before fusion appends its records, so its\n"
+        "CIGARs and overlaps disagree, while --cigar aligns the final records; align_overlaps still aligns any PAF),\n"
+        "-d other than 1, -m, -Q -q -C -c, -S -B, gzipped input.\n",
         f);
 }
 
@@ -102,6 +105,7 @@ int main(int argc, char** argv)
     double index_size = 30, target_index_size = 30, filtering_parameter = 1e-5;
     float min_overlap_fraction = 0.8f;
     bool rescue = false, drop = false, custom_filter = false;
+    int cigar = 0;
     const struct option options[] = {
         {"kmer-size", required_argument, 0, 'k'},
         {"window-size", required_argument, 0, 'w'},
@@ -117,6 +121,7 @@ int main(int argc, char** argv)
         {"min-overlap-fraction", required_argument, 0, 'z'},
         {"rescue-overlap-ends", no_argument, 0, 'R'},
         {"drop-fused-overlaps", no_argument, 0, 'D'},
+        {"cigar", no_argument, &cigar, 1},
         {"query-indices-in-host-memory", required_argument, 0, 'Q'},
         {"query-indices-in-device-memory", required_argument, 0, 'q'},
         {"target-indices-in-host-memory", required_argument, 0, 'C'},
@@ -146,6 +151,7 @@ int main(int argc, char** argv)
             case 'z': min_overlap_fraction = std::stof(optarg); break;
             case 'R': rescue = true; break;
             case 'D': drop = true; break;
+            case 0: break; // --cigar: the flag is set by getopt_long
             case 'd':
                 if (std::stoi(optarg) != 1)
                     refuse("-d: this tool runs on one device");
@@ -204,22 +210,31 @@ int main(int argc, char** argv)
             }
         if (total < 500000 && !custom_filter)
             filtering_parameter = 1.0;
-        if (short_reads > 0)
+        if (short_reads > 0 && !cigar) // with --cigar the library refuses them, and says why
             std::cerr << "WARNING: " << short_reads << " reads are shorter than k + w - 1 = " << (k + w - 1)
                       << " bases; they are skipped and the read ids behind them in their index shift" << std::endl;
 
         const packed_reads q(queries);
         const packed_reads t(own_targets);
-        gw_mapper_overlaps* result = gw_mapper_map_batched(
+        gw_mapper_overlaps* result = gw_mapper_map_batched_aligned(
             q.bases.data(), q.offsets.data(), static_cast<int32_t>(queries.size()), all_to_all ? nullptr : t.bases.data(),
             all_to_all ? nullptr : t.offsets.data(), static_cast<int32_t>(own_targets.size()), k, w, filtering_parameter,
             min_residues, min_overlap_len, min_bases_per_residue, min_overlap_fraction,
             static_cast<int64_t>(index_size * 1000000.0), static_cast<int64_t>(target_index_size * 1000000.0), 1,
-            drop ? 1 : 0, rescue ? 1 : 0, nullptr);
+            drop ? 1 : 0, rescue ? 1 : 0, cigar, 0, nullptr);
         if (!result)
             refuse(gw_mapper_last_error());
         std::vector<overlap_record> records(static_cast<size_t>(gw_mapper_overlaps_count(result)));
         gw_mapper_overlaps_copy(result, records.data(), static_cast<int64_t>(records.size()), nullptr, nullptr);
+        std::vector<std::string> cigars;
+        if (cigar)
+        {
+            std::string text(static_cast<size_t>(gw_mapper_overlaps_cigar_text_bytes(result)), '\0');
+            std::vector<int64_t> offsets(records.size() + 1, 0);
+            gw_mapper_overlaps_copy_cigars(result, &text[0], offsets.data(), nullptr, nullptr);
+            for (size_t i = 0; i < records.size(); ++i)
+                cigars.push_back(text.substr(static_cast<size_t>(offsets[i]), static_cast<size_t>(offsets[i + 1] - offsets[i])));
+        }
         gw_mapper_overlaps_destroy(result);
 
         std::vector<Overlap> overlaps(records.size());
@@ -239,7 +254,7 @@ int main(int argc, char** argv)
             o.num_residues_                  = r.num_residues;
             o.overlap_complete               = r.overlap_complete != 0;
         }
-        print_paf(overlaps, {}, queries, targets, k, stdout);
+        print_paf(overlaps, cigars, queries, targets, k, stdout);
         return 0;
     }
     catch (const std::exception& e)

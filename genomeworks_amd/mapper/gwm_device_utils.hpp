@@ -1,4 +1,5 @@
-// gwm_device_utils.hpp -- helpers shared by the cudamapper translation units (gwm_mapper.hip, gwm_postprocess.hip):
+// gwm_device_utils.hpp -- helpers shared by the cudamapper translation units (gwm_mapper.hip, gwm_postprocess.hip,
+// gwm_align.hip):
 // checked HIP calls, owning device buffers, the rocPRIM scan / select / sort wrappers and HIP-event stage timers.
 // Everything here has internal linkage; the one shared object is the error text behind gwm_last_error().
 #ifndef GWM_DEVICE_UTILS_HPP
@@ -124,6 +125,15 @@ unsigned bits_for(uint64_t max_value)
         ++b;
     return b;
 }
+
+// A read set on the device: bases[offsets[i] .. offsets[i + 1]) is read first_read_id + i.
+struct ReadSet
+{
+    const uint8_t* bases;
+    const int64_t* offsets;
+    uint32_t n_reads;
+    uint32_t first_read_id;
+};
 
 struct Events
 {

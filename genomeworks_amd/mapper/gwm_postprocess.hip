@@ -122,14 +122,6 @@ __global__ void __launch_bounds__(kThreads) fuse_runs_kernel(const gwm_overlap* 
 // end rescue
 // ------------------------------------------------------------------------------------------------------------------
 
-struct ReadSet
-{
-    const uint8_t* bases;
-    const int64_t* offsets;
-    uint32_t n_reads;
-    uint32_t first_read_id;
-};
-
 // bad[0] |= 1: a read id outside its read set; |= 2: a start or end beyond its read
 __global__ void __launch_bounds__(kThreads) validate_kernel(const gwm_overlap* __restrict__ o, int64_t n, ReadSet q,
                                                             ReadSet t, uint32_t* __restrict__ bad)

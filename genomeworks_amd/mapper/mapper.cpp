@@ -173,6 +173,22 @@ struct gw_mapper_overlaps
     std::vector<gwm_overlap> overlaps;
     float stage_ms[3]   = {0.f, 0.f, 0.f};
     int64_t index_pairs = 0;
+    // with alignment: the CIGAR of overlap i is cigar_text[cigar_offsets[i] .. cigar_offsets[i + 1])
+    bool aligned = false;
+    std::string cigar_text;
+    std::vector<int64_t> cigar_offsets{0};
+    std::vector<int32_t> edit_distances;
+    float align_ms[3] = {0.f, 0.f, 0.f};
+};
+
+// CIGARs of one gwm_align_overlaps call, on the device until they are copied out
+struct gw_mapper_cigars
+{
+    gwm_cigars c{};
+    gw_mapper_cigars() = default;
+    ~gw_mapper_cigars() { gwm_cigars_free(&c); }
+    gw_mapper_cigars(const gw_mapper_cigars&) = delete;
+    gw_mapper_cigars& operator=(const gw_mapper_cigars&) = delete;
 };
 
 extern "C" {
@@ -386,6 +402,55 @@ int64_t gw_mapper_group_reads_into_indices(const int64_t* read_lengths, int64_t 
     }, int64_t(GW_MAPPER_ERROR));
 }
 
+gw_mapper_cigars* gw_mapper_align_overlaps(const void* overlaps, int64_t n, const char* query_bases,
+                                           const int64_t* query_offsets, int32_t n_queries,
+                                           uint32_t first_query_read_id, const char* target_bases,
+                                           const int64_t* target_offsets, int32_t n_targets,
+                                           uint32_t first_target_read_id, int64_t max_device_bytes, void* stream)
+{
+    return guarded([&] {
+        std::unique_ptr<gw_mapper_cigars> h(new gw_mapper_cigars());
+        if (n <= 0)
+        {
+            // the argument checks still apply
+            throw_on(gwm_align_overlaps(nullptr, 0, nullptr, nullptr, n_queries, 0, nullptr, nullptr,
+                                        target_bases ? n_targets : n_queries, 0, max_device_bytes, stream, &h->c));
+            return h.release();
+        }
+        device_reads q(query_bases, query_offsets, n_queries);
+        std::unique_ptr<device_reads> t;
+        if (target_bases)
+            t.reset(new device_reads(target_bases, target_offsets, n_targets));
+        const device_reads& tr = t ? *t : q;
+        device_array<gwm_overlap> d(static_cast<const gwm_overlap*>(overlaps), n);
+        throw_on(gwm_align_overlaps(d.p, n, q.bases.p, q.offsets.p, q.n, first_query_read_id, tr.bases.p, tr.offsets.p,
+                                    tr.n, first_target_read_id, max_device_bytes, stream, &h->c));
+        return h.release();
+    }, static_cast<gw_mapper_cigars*>(nullptr));
+}
+
+int64_t gw_mapper_cigars_count(const gw_mapper_cigars* cigars) { return cigars->c.n; }
+
+int64_t gw_mapper_cigars_text_bytes(const gw_mapper_cigars* cigars) { return cigars->c.text_bytes; }
+
+int gw_mapper_cigars_copy(const gw_mapper_cigars* cigars, char* text, int64_t* offsets, int32_t* edit_distances,
+                          float* stage_ms)
+{
+    return guarded([&] {
+        const gwm_cigars& c = cigars->c;
+        copy_out(text, c.text, c.text_bytes);
+        if (offsets && c.n == 0)
+            offsets[0] = 0;
+        copy_out(offsets, c.cigar_offsets, c.n > 0 ? c.n + 1 : 0);
+        copy_out(edit_distances, c.edit_distances, c.n);
+        if (stage_ms)
+            std::memcpy(stage_ms, c.stage_ms, sizeof(c.stage_ms));
+        return 0;
+    }, GW_MAPPER_ERROR);
+}
+
+void gw_mapper_cigars_destroy(gw_mapper_cigars* cigars) { delete cigars; }
+
 gw_mapper_overlaps* gw_mapper_map_batched(const char* query_bases, const int64_t* query_offsets, int32_t n_queries,
                                           const char* target_bases, const int64_t* target_offsets, int32_t n_targets,
                                           int32_t kmer_size, int32_t window_size, double filtering_parameter,
@@ -393,6 +458,21 @@ gw_mapper_overlaps* gw_mapper_map_batched(const char* query_bases, const int64_t
                                           float min_overlap_fraction, int64_t max_basepairs_per_query_index,
                                           int64_t max_basepairs_per_target_index, int32_t post_process,
                                           int32_t drop_fused_overlaps, int32_t rescue_overlap_ends, void* stream)
+{
+    return gw_mapper_map_batched_aligned(query_bases, query_offsets, n_queries, target_bases, target_offsets, n_targets,
+                                         kmer_size, window_size, filtering_parameter, min_residues, min_overlap_len,
+                                         min_bases_per_residue, min_overlap_fraction, max_basepairs_per_query_index,
+                                         max_basepairs_per_target_index, post_process, drop_fused_overlaps,
+                                         rescue_overlap_ends, 0, 0, stream);
+}
+
+gw_mapper_overlaps* gw_mapper_map_batched_aligned(
+    const char* query_bases, const int64_t* query_offsets, int32_t n_queries, const char* target_bases,
+    const int64_t* target_offsets, int32_t n_targets, int32_t kmer_size, int32_t window_size, double filtering_parameter,
+    int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue, float min_overlap_fraction,
+    int64_t max_basepairs_per_query_index, int64_t max_basepairs_per_target_index, int32_t post_process,
+    int32_t drop_fused_overlaps, int32_t rescue_overlap_ends, int32_t align_overlaps, int64_t max_device_bytes,
+    void* stream)
 {
     return guarded([&] {
         hipStream_t s         = static_cast<hipStream_t>(stream);
@@ -414,14 +494,30 @@ gw_mapper_overlaps* gw_mapper_map_batched(const char* query_bases, const int64_t
         const std::vector<int64_t> ql = lengths(query_offsets, n_queries), tl = lengths(target_offsets, n_targets);
         const std::vector<descriptor> qd = group_reads(ql.data(), n_queries, max_basepairs_per_query_index);
         const std::vector<descriptor> td = group_reads(tl.data(), n_targets, max_basepairs_per_target_index);
+        if (align_overlaps)
+        {
+            // The index numbers its reads by rank among the reads it kept: behind a read it skipped, read ids no
+            // longer name positions in the input, and the alignment would pair the wrong sequences without a sign.
+            const int64_t shortest = static_cast<int64_t>(kmer_size) + window_size - 1;
+            for (const std::vector<int64_t>* set : {&ql, &tl})
+                for (size_t i = 0; i < set->size(); ++i)
+                    if ((*set)[i] < shortest)
+                        throw std::invalid_argument(
+                            "gw_mapper_map_batched_aligned: " + std::string(set == &ql ? "query" : "target") + " read " +
+                            std::to_string(i) + " has " + std::to_string((*set)[i]) + " bases, fewer than k + w - 1 = " +
+                            std::to_string(shortest) + ": the index skips it and numbers the reads behind it by rank, "
+                            "so overlap read ids would no longer name input reads and the alignment would pair the "
+                            "wrong sequences; remove such reads to align");
+        }
         std::unique_ptr<device_reads> q_reads, t_reads;
-        if (rescue_overlap_ends)
+        if (rescue_overlap_ends || align_overlaps)
         {
             q_reads.reset(new device_reads(query_bases, query_offsets, n_queries));
             if (!all_to_all)
                 t_reads.reset(new device_reads(target_bases, target_offsets, n_targets));
         }
         std::unique_ptr<gw_mapper_overlaps> result(new gw_mapper_overlaps());
+        result->aligned = align_overlaps != 0;
         for (const descriptor& qx : qd)
         {
             if (qx.number_of_reads == 0)
@@ -468,6 +564,25 @@ gw_mapper_overlaps* gw_mapper_map_batched(const char* query_bases, const int64_t
                                                      0, tr.bases.p, tr.offsets.p, tr.n, 0, 50, 0.5f, s, &ms));
                     result->stage_ms[2] += ms;
                 }
+                if (align_overlaps && count > 0)
+                {
+                    // what is left of this index pair, where it lies: one aligner capacity per pair
+                    const device_reads& tr = t_reads ? *t_reads : *q_reads;
+                    gw_mapper_cigars cigars;
+                    throw_on(gwm_align_overlaps(current, count, q_reads->bases.p, q_reads->offsets.p, q_reads->n, 0,
+                                                tr.bases.p, tr.offsets.p, tr.n, 0, max_device_bytes, s, &cigars.c));
+                    const size_t text_at = result->cigar_text.size(), n_at = result->edit_distances.size();
+                    result->cigar_text.resize(text_at + static_cast<size_t>(cigars.c.text_bytes));
+                    copy_out(&result->cigar_text[0] + text_at, cigars.c.text, cigars.c.text_bytes);
+                    result->cigar_offsets.resize(n_at + static_cast<size_t>(count) + 1);
+                    copy_out(result->cigar_offsets.data() + n_at, cigars.c.cigar_offsets, count + 1);
+                    for (size_t i = n_at; i < result->cigar_offsets.size(); ++i)
+                        result->cigar_offsets[i] += static_cast<int64_t>(text_at);
+                    result->edit_distances.resize(n_at + static_cast<size_t>(count));
+                    copy_out(result->edit_distances.data() + n_at, cigars.c.edit_distances, count);
+                    for (int k = 0; k < 3; ++k)
+                        result->align_ms[k] += cigars.c.stage_ms[k];
+                }
                 const size_t at = result->overlaps.size();
                 result->overlaps.resize(at + static_cast<size_t>(count));
                 copy_out(result->overlaps.data() + at, current, count);
@@ -489,6 +604,30 @@ int gw_mapper_overlaps_copy(const gw_mapper_overlaps* result, void* overlaps, in
         std::memcpy(stage_ms, result->stage_ms, sizeof(result->stage_ms));
     if (index_pairs)
         *index_pairs = result->index_pairs;
+    return 0;
+}
+
+int64_t gw_mapper_overlaps_cigar_text_bytes(const gw_mapper_overlaps* result)
+{
+    return result->aligned ? static_cast<int64_t>(result->cigar_text.size()) : int64_t(GW_MAPPER_ERROR);
+}
+
+int gw_mapper_overlaps_copy_cigars(const gw_mapper_overlaps* result, char* text, int64_t* offsets,
+                                   int32_t* edit_distances, float* stage_ms)
+{
+    if (!result->aligned)
+    {
+        g_capi_error = "gw_mapper_overlaps_copy_cigars: the overlaps were mapped without alignment";
+        return GW_MAPPER_ERROR;
+    }
+    if (text && !result->cigar_text.empty())
+        std::memcpy(text, result->cigar_text.data(), result->cigar_text.size());
+    if (offsets)
+        std::memcpy(offsets, result->cigar_offsets.data(), sizeof(int64_t) * result->cigar_offsets.size());
+    if (edit_distances && !result->edit_distances.empty())
+        std::memcpy(edit_distances, result->edit_distances.data(), sizeof(int32_t) * result->edit_distances.size());
+    if (stage_ms)
+        std::memcpy(stage_ms, result->align_ms, sizeof(result->align_ms));
     return 0;
 }
 

@@ -231,6 +231,24 @@ int32_t gw_windows_count(const gw_windows* w);
 int32_t gw_windows_num_sequences(const gw_windows* w, int32_t window);
 const char* gw_windows_sequence(const gw_windows* w, int32_t window, int32_t seq, int32_t* length);
 
+/* The alignment stage of cudamapper on the host path: cudamapper::align_overlaps() of cudamapper/overlap_alignment.hpp
+   (slices cut and reverse-complemented on the host, num_alignment_engines host threads with an Aligner each,
+   max_alignments_per_batch <= 0 = the reference's heuristic, one CIGAR string per overlap through
+   Alignment::convert_to_cigar()) over n overlaps in the 36-byte layout of cudamapper::Overlap and reads given as bases +
+   n + 1 offsets; target_bases NULL means the query set. max_cached_bytes <= 0: 2 GiB for the caching allocator.
+   NULL on error (gw_last_error). libcudamapper.so's gw_mapper_align_overlaps returns the same strings without moving
+   bases or alignment states through the host. */
+typedef struct gw_overlap_cigars gw_overlap_cigars;
+gw_overlap_cigars* gw_align_overlaps(const void* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                                     int32_t n_queries, const char* target_bases, const int64_t* target_offsets,
+                                     int32_t n_targets, int32_t num_alignment_engines, int32_t max_alignments_per_batch,
+                                     int64_t max_cached_bytes);
+int64_t gw_overlap_cigars_count(const gw_overlap_cigars* c);
+int64_t gw_overlap_cigars_text_bytes(const gw_overlap_cigars* c);
+/* text: text_bytes bytes, CIGARs back to back; offsets: count + 1 */
+void gw_overlap_cigars_copy(const gw_overlap_cigars* c, char* text, int64_t* offsets);
+void gw_overlap_cigars_destroy(gw_overlap_cigars* c);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,8 @@
 /*
  * gw_mapper_capi.h -- flat C API of cudamapper (libcudamapper.so), for foreign-function bindings
  * (genomeworks_amd/cudamapper.py): index creation from host reads, the anchor matcher, the triggered overlapper, one
- * call for a whole mapping of one index pair, overlap post-processing and end rescue, and the batched driver behind
- * the cudamapper tool. Functions returning int give 0 on success; those returning a count give it, or
+ * call for a whole mapping of one index pair, overlap post-processing, end rescue and alignment of overlaps into
+ * CIGARs, and the batched driver behind the cudamapper tool. Functions returning int give 0 on success; those returning a count give it, or
  * GW_MAPPER_ERROR; creators return NULL. On an error the exception text is in gw_mapper_last_error().
  *
  * Reads are passed as one byte array and n_reads + 1 offsets: read i is bases[offsets[i] .. offsets[i+1]).
@@ -95,6 +95,23 @@ int gw_mapper_rescue_overlap_ends(void* overlaps, int64_t n, const char* query_b
                                   int32_t n_targets, uint32_t first_query_read_id, uint32_t first_target_read_id,
                                   int32_t extension, float required_similarity, void* stream, float* rescue_ms);
 
+/* CIGARs of n host overlaps over host reads (uploaded for the call; target_bases NULL means the target set is the
+   query set): gwm_align_overlaps of gwhip_mapper.h, which states slices, strand, complement, aligner and text format.
+   A read id outside its set, start > end or an end beyond its read is an error (NULL). The CIGARs stay on the device
+   until gw_mapper_cigars_copy: text (text_bytes bytes, back to back), offsets[count + 1], edit_distances[count]
+   (-1: the aligner gave no result), stage_ms[3] (device time of gather, align, CIGAR text); any pointer may be NULL. */
+typedef struct gw_mapper_cigars gw_mapper_cigars;
+gw_mapper_cigars* gw_mapper_align_overlaps(const void* overlaps, int64_t n, const char* query_bases,
+                                           const int64_t* query_offsets, int32_t n_queries,
+                                           uint32_t first_query_read_id, const char* target_bases,
+                                           const int64_t* target_offsets, int32_t n_targets,
+                                           uint32_t first_target_read_id, int64_t max_device_bytes, void* stream);
+int64_t gw_mapper_cigars_count(const gw_mapper_cigars* cigars);
+int64_t gw_mapper_cigars_text_bytes(const gw_mapper_cigars* cigars);
+int gw_mapper_cigars_copy(const gw_mapper_cigars* cigars, char* text, int64_t* offsets, int32_t* edit_distances,
+                          float* stage_ms);
+void gw_mapper_cigars_destroy(gw_mapper_cigars* cigars);
+
 /* group_reads_into_indices: consecutive reads while the running base count stays <= max_basepairs_per_index; a longer
    read gets an index of its own. The reference's loop as it stands: when the very first read is longer than the limit
    a descriptor of zero reads comes first, and no reads at all give the one descriptor {0, 0}. Returns the number of
@@ -119,7 +136,28 @@ gw_mapper_overlaps* gw_mapper_map_batched(const char* query_bases, const int64_t
                                           float min_overlap_fraction, int64_t max_basepairs_per_query_index,
                                           int64_t max_basepairs_per_target_index, int32_t post_process,
                                           int32_t drop_fused_overlaps, int32_t rescue_overlap_ends, void* stream);
+/* gw_mapper_map_batched with one more stage per index pair when align_overlaps is set: what is left of the pair after
+   post-processing and end rescue is aligned where it lies (gwm_align_overlaps of gwhip_mapper.h: the default aligner,
+   max_query_length = the longest query slice of the pair; max_device_bytes as there, 0 = choose), overlaps, reads and
+   alignment states staying on the device; only the CIGAR text comes back. One CIGAR per returned overlap, in the same
+   order. The read sets are uploaded once when end rescue or alignment asks for them. With align_overlaps set, a read
+   shorter than kmer_size + window_size - 1 in either set is an error before any device work: the index skips such a
+   read and numbers the reads behind it by rank, so read ids would no longer name input reads and the wrong sequences
+   would be aligned. With align_overlaps 0 this is gw_mapper_map_batched. */
+gw_mapper_overlaps* gw_mapper_map_batched_aligned(
+    const char* query_bases, const int64_t* query_offsets, int32_t n_queries, const char* target_bases,
+    const int64_t* target_offsets, int32_t n_targets, int32_t kmer_size, int32_t window_size, double filtering_parameter,
+    int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue, float min_overlap_fraction,
+    int64_t max_basepairs_per_query_index, int64_t max_basepairs_per_target_index, int32_t post_process,
+    int32_t drop_fused_overlaps, int32_t rescue_overlap_ends, int32_t align_overlaps, int64_t max_device_bytes,
+    void* stream);
 int64_t gw_mapper_overlaps_count(const gw_mapper_overlaps* result);
+/* bytes of all CIGARs of an aligned result, back to back; GW_MAPPER_ERROR when it was mapped without alignment */
+int64_t gw_mapper_overlaps_cigar_text_bytes(const gw_mapper_overlaps* result);
+/* text (cigar_text_bytes bytes, no separators), offsets[count + 1], edit_distances[count] (-1: no alignment) and
+   stage_ms[3] (summed device time of gather, align, CIGAR text); any pointer may be NULL */
+int gw_mapper_overlaps_copy_cigars(const gw_mapper_overlaps* result, char* text, int64_t* offsets,
+                                   int32_t* edit_distances, float* stage_ms);
 /* copies min(capacity, count) overlaps; stage_ms[3] (summed device time of chain/fuse/filter, post-processing, end
    rescue) and index_pairs (pairs walked) may be NULL */
 int gw_mapper_overlaps_copy(const gw_mapper_overlaps* result, void* overlaps, int64_t capacity, float* stage_ms,

@@ -1,7 +1,8 @@
 /*
  * gwhip_mapper.h -- kernel-level C-ABI of the cudamapper engine (libcudamapper.so): (k,w)-minimizer sketch, index
  * (stable sort, unique representations, frequency filter), anchor matcher, the triggered overlapper (chain, fuse,
- * filter) and the post-processing of its overlaps (fusion of neighbours, end rescue), all on gfx950.
+ * filter), the post-processing of its overlaps (fusion of neighbours, end rescue) and their alignment into CIGARs, all
+ * on gfx950.
  *
  * The object-level API on top of it is gw_mapper_capi.h (flat C) and genomeworks_amd.cudamapper (Python). This header
  * is kept apart from gwhip.h on purpose: the POA / aligner kernel set and its source digest are not affected.
@@ -141,6 +142,47 @@ int gwm_rescue_overlap_ends(gwm_overlap* overlaps, int64_t n, const char* query_
                             int32_t n_queries, uint32_t first_query_read_id, const char* target_bases,
                             const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
                             int32_t extension, float required_similarity, void* stream, float* rescue_ms);
+
+/* The CIGARs of n overlaps. Device arrays, owned by the struct; free them with gwm_cigars_free. */
+typedef struct gwm_cigars
+{
+    int64_t n;               /* overlaps */
+    int64_t text_bytes;      /* cigar_offsets[n] */
+    char* text;              /* device: CIGARs back to back, no separators, no NUL; NULL when text_bytes is 0 */
+    int64_t* cigar_offsets;  /* device [n + 1] */
+    int32_t* edit_distances; /* device [n]: columns that are not a match; -1 where the aligner gave no result */
+    float stage_ms[3];       /* HIP events, summed over the chunks: gather, align, cigar text */
+} gwm_cigars;
+
+/* Global alignment of device overlaps[0..n), each over its own slices, with bases and alignment states staying on the
+ * device. Read sets as for gwm_rescue_overlap_ends. Overlap i aligns Q[query read][query start, query end) against
+ * T[target read][target start, target end) (forward target coordinates); on '-' against the reverse complement of that
+ * target slice, taken with the aligner's table: "TGAC"[(c >> 1) & 3] for every byte, what cudaaligner's
+ * add_alignment(..., reverse_complement_target = true) does -- not the complement of end rescue. The aligner is the
+ * default one (gwhip_hirschberg_myers of gwhip.h, Hirschberg + Myers) with max_query_length = the longest query slice of
+ * the call. CIGAR i is the text of Alignment::convert_to_cigar() in its basic format (match and mismatch both M and
+ * merged, I a base of the target only, D one of the query only, as cudaaligner names them) at
+ * text[cigar_offsets[i] .. cigar_offsets[i + 1]). Where the aligner reports no columns the CIGAR is empty and the edit
+ * distance -1, or 0 when both slices are empty.
+ *
+ * Consecutive overlaps are aligned in chunks: as many as keep gwm_align_bytes_needed's sum for the chunk -- gathered
+ * bases, state slots, the aligner's workspace, the text at its upper bound of two bytes per column, and the small per-
+ * overlap arrays -- within max_device_bytes; 0 means half of the device memory that is free at the call. An overlap
+ * that does not fit alone is an error. The result does not depend on the chunking. The overlap records (36 B each) are
+ * copied to the host to size the chunks; bases and states are not.
+ *
+ * A read id outside its set, start > end, or an end beyond its read return -1 with gwm_last_error() set before anything
+ * is aligned, and leave *out zeroed (as every error does); the kernels never read outside the reads they were given.
+ * n == 0 launches nothing. Synchronous on `stream` when it returns. */
+int gwm_align_overlaps(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                       int32_t n_queries, uint32_t first_query_read_id, const char* target_bases,
+                       const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
+                       int64_t max_device_bytes, void* stream, gwm_cigars* out);
+void gwm_cigars_free(gwm_cigars* cigars);
+/* Device bytes gwm_align_overlaps counts for a chunk that holds one overlap with slices of these lengths, in a call
+ * whose longest query slice is max_query_length: the smallest max_device_bytes that overlap can be aligned with.
+ * Host arithmetic only. */
+int64_t gwm_align_bytes_needed(int32_t query_length, int32_t target_length, int32_t max_query_length);
 
 const char* gwm_last_error(void);
 
