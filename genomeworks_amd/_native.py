@@ -206,6 +206,19 @@ def mapper():
         L.gw_mapper_overlaps_cigar_text_bytes.restype = i64
         L.gw_mapper_overlaps_cigar_text_bytes.argtypes = [vp]
         L.gw_mapper_overlaps_copy_cigars.argtypes = [vp, vp, vp, vp, vp]
+        L.gw_mapper_map_batched_cached.restype = vp
+        L.gw_mapper_map_batched_cached.argtypes = L.gw_mapper_map_batched.argtypes[:-1] + [i32, i64, i32, i32, i32, i32, vp]
+        L.gw_mapper_overlaps_cache_counts.argtypes = [vp, vp, vp, vp]
+        L.gw_mapper_generate_batches_of_indices.restype = i64
+        L.gw_mapper_generate_batches_of_indices.argtypes = [vp, i64, vp, i64, i64, i64, i32, i32, i32, i32, vp, i64]
+        L.gw_mapper_index_host_copy_create.restype = vp
+        L.gw_mapper_index_host_copy_create.argtypes = [vp, vp, vp]
+        L.gw_mapper_index_host_copy_bytes.restype = i64
+        L.gw_mapper_index_host_copy_bytes.argtypes = [vp]
+        L.gw_mapper_index_host_copy_to_device.restype = vp
+        L.gw_mapper_index_host_copy_to_device.argtypes = [vp, vp, vp]
+        L.gw_mapper_index_host_copy_destroy.restype = None
+        L.gw_mapper_index_host_copy_destroy.argtypes = [vp]
         L.gwm_align_bytes_needed.restype = i64
         L.gwm_align_bytes_needed.argtypes = [i32, i32, i32]
         _mapper = L

@@ -30,7 +30,8 @@ HOST_SRCS = ["host/capi.cpp", "host/cudapoa_batch.cpp", "host/cudapoa_utils.cpp"
 EXTENDER_KERNEL_SRCS = ["extender/gwx_ungapped_xdrop.hip"]
 EXTENDER_HOST_SRCS = ["extender/extender.cpp"]
 # cudamapper likewise
-MAPPER_KERNEL_SRCS = ["mapper/gwm_mapper.hip", "mapper/gwm_postprocess.hip", "mapper/gwm_align.hip"]
+MAPPER_KERNEL_SRCS = ["mapper/gwm_mapper.hip", "mapper/gwm_postprocess.hip", "mapper/gwm_align.hip",
+                      "mapper/gwm_index_cache.hip"]
 MAPPER_HOST_SRCS = ["mapper/mapper.cpp"]
 
 # no fast-math, no FMA contraction: band placement is IEEE fp32

@@ -11,6 +11,8 @@ gfx950), over the flat C API of include/gw_mapper_capi.h.
     text = format_paf(overlaps, names, lengths, names, lengths, 15)
     cigars, edit_distances = align_overlaps(overlaps, reads)       # the default aligner, nothing but text comes back
     overlaps, cigars = map_reads_batched(reads, align=True)        # the tool's --cigar
+    overlaps = map_reads_batched(reads, query_indices_in_host_memory=10, query_indices_in_device_memory=5)  # -Q -q
+    copy = index.to_host(); index = copy.to_device()               # packed copy in pinned host memory and back
     text = format_paf(overlaps, names, lengths, names, lengths, 15, cigars=cigars)
 
 Index arrays carry the reference's names (representations, read_ids, positions_in_reads, directions_of_reads,
@@ -129,9 +131,59 @@ class Index:
                                         _p(self.first_occurrence_of_representations)) != 0:
             raise _err(self._L)
 
+    def to_host(self, stream=None):
+        """IndexHostCopy of this index: read ids, positions, one direction bit per element and the unique-representation
+        tables in one pinned host slab (gwm_index_pack). The index stays as it is."""
+        return IndexHostCopy(self, stream)
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.gw_mapper_index_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class IndexHostCopy:
+    """A packed copy of an Index in pinned host memory (the reference's IndexHostCopy): nbytes is
+    8 n + 8 ceil(n / 64) + 12 n_unique plus a constant, against 17 n + 12 n_unique for the arrays themselves, because
+    the representation of every element is filled in again on the device. to_device() gives an Index equal to the
+    packed one in all arrays and attributes. pack_ms is the device time of packing."""
+
+    def __init__(self, index, stream=None):
+        self._L = _native.mapper()
+        self.kmer_size, self.window_size = index.kmer_size, index.window_size
+        ms = C.c_float(0.0)
+        self._h = self._L.gw_mapper_index_host_copy_create(index._h, _stream(stream), C.byref(ms))
+        if not self._h:
+            raise _err(self._L)
+        self.pack_ms = ms.value
+        self.nbytes = int(self._L.gw_mapper_index_host_copy_bytes(self._h))
+
+    def to_device(self, stream=None):
+        """The index again, in one device allocation (gwm_index_unpack); its restore_ms is the device time of the copy
+        and the two kernels."""
+        if not self._h:
+            raise MapperError("the host copy is closed")
+        index = Index.__new__(Index)
+        index._L = self._L
+        index.kmer_size, index.window_size = self.kmer_size, self.window_size
+        ms = C.c_float(0.0)
+        index._h = self._L.gw_mapper_index_host_copy_to_device(self._h, _stream(stream), C.byref(ms))
+        index._fill()
+        index.restore_ms = ms.value
+        return index
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.gw_mapper_index_host_copy_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -326,16 +378,69 @@ def group_reads_into_indices(read_lengths, max_basepairs_per_index):
     return [(int(a), int(b)) for a, b in out[:n]]
 
 
+def generate_batches_of_indices(query_lengths, target_lengths=None, query_indices_in_host_memory=1,
+                                query_indices_in_device_memory=1, target_indices_in_host_memory=None,
+                                target_indices_in_device_memory=None, max_basepairs_per_index=30_000_000,
+                                max_basepairs_per_target_index=None):
+    """generate_batches_of_indices of the reference's index batcher: reads grouped into indices, indices into host
+    batches of query_indices_in_host_memory x target_indices_in_host_memory, every host batch into device batches of
+    the two device counts. target_lengths None means the target set is the query set: upper triangle only. The target
+    counts default to the query's. Returns [(host_batch, [device_batch, ...]), ...] where a batch is
+    (query_indices, target_indices), lists of (first_read, number_of_reads). The same set with different counts or
+    index sizes, a count below 1, or fewer indices in host than in device memory raise MapperError."""
+    L = _native.mapper()
+    ql = np.ascontiguousarray(query_lengths, np.int64)
+    tl = None if target_lengths is None else np.ascontiguousarray(target_lengths, np.int64)
+    C_ = query_indices_in_host_memory if target_indices_in_host_memory is None else target_indices_in_host_memory
+    c_ = query_indices_in_device_memory if target_indices_in_device_memory is None else target_indices_in_device_memory
+    t_limit = max_basepairs_per_index if max_basepairs_per_target_index is None else max_basepairs_per_target_index
+    args = (_p(ql), len(ql), None if tl is None else _p(tl), 0 if tl is None else len(tl), int(max_basepairs_per_index),
+            int(t_limit), int(query_indices_in_host_memory), int(query_indices_in_device_memory), int(C_), int(c_))
+    words = L.gw_mapper_generate_batches_of_indices(*args, None, 0)
+    if words < 0:
+        raise _err(L)
+    flat = np.zeros(words, np.uint32)
+    if L.gw_mapper_generate_batches_of_indices(*args, _p(flat), len(flat)) != words:
+        raise _err(L)
+    flat, at = [int(x) for x in flat], [0]
+
+    def take(n):
+        at[0] += n
+        return flat[at[0] - n:at[0]]
+
+    def batch():
+        nq, nt = take(2)
+        q, t = take(2 * nq), take(2 * nt)
+        return list(zip(q[0::2], q[1::2])), list(zip(t[0::2], t[1::2]))
+
+    out = []
+    for _ in range(take(1)[0]):
+        host = batch()
+        out.append((host, [batch() for _ in range(take(1)[0])]))
+    return out
+
+
 def map_reads_batched(queries, targets=None, k=15, w=10, filtering_parameter=1e-5, min_residues=3, min_overlap_len=250,
                       min_bases_per_residue=1000, min_overlap_fraction=0.8, max_basepairs_per_index=30_000_000,
                       max_basepairs_per_target_index=None, post_process=True, drop_fused_overlaps=False,
-                      rescue_overlap_ends=False, stream=None, timings=None, align=False, max_device_bytes=0):
+                      rescue_overlap_ends=False, stream=None, timings=None, align=False, max_device_bytes=0,
+                      query_indices_in_host_memory=1, query_indices_in_device_memory=1,
+                      target_indices_in_host_memory=None, target_indices_in_device_memory=None):
     """What the cudamapper tool does on one device: queries and targets (None: all against all) grouped into indices
     of at most max_basepairs_per_index / max_basepairs_per_target_index bases (the CLI's -i / -t, given there in
     millions), every index pair mapped, its overlaps post-processed (post_process; drop_fused_overlaps is -D) and
     their ends rescued (-R) on the device, results appended in pair order. Read ids are positions in `queries` /
     `targets`. `timings`, if a dict, receives the summed device times chain_fuse_filter, fuse and rescue (ms) and the
     number of index pairs.
+
+    The four *_indices_in_*_memory keywords are the tool's -Q -q -C -c (the target ones default to the query's): the
+    index pairs are walked in host batches of Q x C indices, each in device batches of q x c
+    (generate_batches_of_indices). The indices of a host batch are built once; those a later device batch needs are
+    kept as packed host copies (Index.to_host) and restored on a second stream while the current device batch is
+    mapped. An index that is still on the device from the previous device batch, or among the host copies of the
+    previous host batch, is not built again. The overlaps are those of 1, 1, 1, 1 in the order of the batches' pairs.
+    Up to 2 x (q + c) indices are on the device at a time. timings also gets index_builds, index_restores and the
+    device times pack and unpack (ms).
 
     align=True (the tool's --cigar) aligns what is left of every index pair as align_overlaps does, one call per pair,
     with overlaps and reads staying on the device, and returns (overlaps, cigars), one CIGAR per overlap; timings
@@ -350,16 +455,18 @@ def map_reads_batched(queries, targets=None, k=15, w=10, filtering_parameter=1e-
             0 if targets is None else len(targets), k, w, float(filtering_parameter), int(min_residues),
             int(min_overlap_len), int(min_bases_per_residue), float(min_overlap_fraction), int(max_basepairs_per_index),
             int(t_limit), int(bool(post_process)), int(bool(drop_fused_overlaps)), int(bool(rescue_overlap_ends)))
-    if align:
-        h = L.gw_mapper_map_batched_aligned(*args, 1, int(max_device_bytes), _stream(stream))
-    else:
-        h = L.gw_mapper_map_batched(*args, _stream(stream))
+    C_ = query_indices_in_host_memory if target_indices_in_host_memory is None else target_indices_in_host_memory
+    c_ = query_indices_in_device_memory if target_indices_in_device_memory is None else target_indices_in_device_memory
+    h = L.gw_mapper_map_batched_cached(*args, int(bool(align)), int(max_device_bytes), int(query_indices_in_host_memory),
+                                       int(query_indices_in_device_memory), int(C_), int(c_), _stream(stream))
     if not h:
         raise _err(L)
     try:
         out = np.zeros(int(L.gw_mapper_overlaps_count(h)), OVERLAP)
         ms, pairs = np.zeros(3, np.float32), C.c_int64(0)
         L.gw_mapper_overlaps_copy(h, _p(out), len(out), _p(ms), C.byref(pairs))
+        builds, restores, cache_ms = C.c_int64(0), C.c_int64(0), np.zeros(2, np.float32)
+        L.gw_mapper_overlaps_cache_counts(h, C.byref(builds), C.byref(restores), _p(cache_ms))
         if align:
             text = np.zeros(int(L.gw_mapper_overlaps_cigar_text_bytes(h)), np.uint8)
             offsets, edits, align_ms = np.zeros(len(out) + 1, np.int64), np.zeros(len(out), np.int32), np.zeros(3, np.float32)
@@ -368,7 +475,9 @@ def map_reads_batched(queries, targets=None, k=15, w=10, filtering_parameter=1e-
     finally:
         L.gw_mapper_overlaps_destroy(h)
     if timings is not None:
-        timings.update(chain_fuse_filter=float(ms[0]), fuse=float(ms[1]), rescue=float(ms[2]), index_pairs=pairs.value)
+        timings.update(chain_fuse_filter=float(ms[0]), fuse=float(ms[1]), rescue=float(ms[2]), index_pairs=pairs.value,
+                       index_builds=builds.value, index_restores=restores.value, pack=float(cache_ms[0]),
+                       unpack=float(cache_ms[1]))
         if align:
             timings.update(gather=float(align_ms[0]), align=float(align_ms[1]), cigar_text=float(align_ms[2]),
                            edit_distances=edits)

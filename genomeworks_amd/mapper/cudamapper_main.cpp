@@ -1,12 +1,14 @@
-// cudamapper_main.cpp -- the `cudamapper` command-line tool: a thin main over gw_mapper_map_batched
+// cudamapper_main.cpp -- the `cudamapper` command-line tool: a thin main over gw_mapper_map_batched_cached
 // (include/gw_mapper_capi.h), the project's FASTA reader and its PAF writer (cudamapper/overlap_alignment.hpp).
 //
 //   cudamapper [options] query.fasta target.fasta > overlaps.paf
 //
 // Option letters and defaults are those of the reference's cudamapper (application_parameters.cpp) for
-// -k -w -i -t -F -r -l -b -z -R -D -h -v. One device, no index cache; options that ask for anything else are refused
-// with a message instead of being ignored. --cigar (no letter) aligns the printed records on the device
-// (gw_mapper_map_batched_aligned) and adds the cg:Z: column.
+// -k -w -i -t -F -r -l -b -z -R -D -Q -q -C -c -h -v. One device; options that ask for anything else are refused
+// with a message instead of being ignored. --cigar (no letter) aligns the printed records on the device and adds the
+// cg:Z: column. -Q -q -C -c size the index cache as in the reference, with its checks and its two notes about -C / -c;
+// a run without any of them walks one index pair at a time (1, 1, 1, 1), which keeps the order of the PAF lines that
+// this tool has always printed. The reference's defaults (10, 5) apply to those not given once one of them is.
 #include "gw_mapper_capi.h"
 
 #include <claraparabricks/genomeworks/cudamapper/overlap_alignment.hpp>
@@ -59,11 +61,17 @@ void help(std::FILE* f)
         "  -R, --rescue-overlap-ends    extend the ends of overlaps over similar flanks\n"
         "  -D, --drop-fused-overlaps    remove overlaps which are joined into larger overlaps\n"
         "      --cigar                  align every printed overlap on the device and add its CIGAR as a cg:Z: column\n"
+        "  -Q, --query-indices-in-host-memory    query indices kept as packed copies in host memory [10]\n"
+        "  -q, --query-indices-in-device-memory  query indices kept in device memory [5]\n"
+        "  -C, --target-indices-in-host-memory   target indices kept in host memory [as -Q]\n"
+        "  -c, --target-indices-in-device-memory target indices kept in device memory [as -q]\n"
+        "                               without any of -Q -q -C -c one index pair is walked at a time (all four 1);\n"
+        "                               the order of the output lines follows the batches\n"
         "  -v, --version                version information\n"
         "  -h, --help                   this message\n"
         "Not in this tool: -a (its letter stays refused: the reference aligns before fusion appends its records, so its\n"
         "CIGARs and overlaps disagree, while --cigar aligns the final records; align_overlaps still aligns any PAF),\n"
-        "-d other than 1, -m, -Q -q -C -c, -S -B, gzipped input.\n",
+        "-d other than 1, -m, -S -B, gzipped input.\n",
         f);
 }
 
@@ -106,6 +114,8 @@ int main(int argc, char** argv)
     float min_overlap_fraction = 0.8f;
     bool rescue = false, drop = false, custom_filter = false;
     int cigar = 0;
+    int32_t query_host = 10, query_device = 5, target_host = 10, target_device = 5;
+    bool query_host_set = false, query_device_set = false, target_host_set = false, target_device_set = false;
     const struct option options[] = {
         {"kmer-size", required_argument, 0, 'k'},
         {"window-size", required_argument, 0, 'w'},
@@ -161,9 +171,21 @@ int main(int argc, char** argv)
                        "its CIGARs and overlaps disagree; run align_overlaps on this tool's PAF instead");
             case 'm': refuse("-m is not supported: there is no caching allocator to size");
             case 'Q':
+                query_host     = std::stoi(optarg);
+                query_host_set = true;
+                break;
             case 'q':
+                query_device     = std::stoi(optarg);
+                query_device_set = true;
+                break;
             case 'C':
-            case 'c': refuse(std::string("-") + static_cast<char>(c) + " is not supported: there is no index cache");
+                target_host     = std::stoi(optarg);
+                target_host_set = true;
+                break;
+            case 'c':
+                target_device     = std::stoi(optarg);
+                target_device_set = true;
+                break;
             case 'S':
             case 'B': refuse("-S / -B are not supported: the output is PAF");
             case 'v': std::cout << "cudamapper (genomeworks_amd, gfx950)" << std::endl; return 1;
@@ -185,10 +207,39 @@ int main(int argc, char** argv)
             help(stderr);
             return 1;
         }
+        if (query_host_set || query_device_set || target_host_set || target_device_set)
+        {
+            if (!target_host_set)
+            {
+                std::cerr << "-C / --target-indices-in-host-memory not set, using -Q / --query-indices-in-host-memory "
+                             "value: "
+                          << query_host << std::endl;
+                target_host = query_host;
+            }
+            if (!target_device_set)
+            {
+                std::cerr << "-c / --target-indices-in-device-memory not set, using -q / "
+                             "--query-indices-in-device-memory value: "
+                          << query_device << std::endl;
+                target_device = query_device;
+            }
+            if (query_host < 1 || query_device < 1 || target_host < 1 || target_device < 1)
+                refuse("-Q / -q / -C / -c must be at least 1");
+            if (target_host < target_device)
+                refuse("-C / --target-indices-in-host-memory  has to be larger or equal than -c / "
+                       "--target-indices-in-device-memory");
+            if (query_host < query_device)
+                refuse("-Q / --query-indices-in-host-memory  has to be larger or equal than -q / "
+                       "--query-indices-in-device-memory");
+        }
+        else
+            query_host = query_device = target_host = target_device = 1;
         const std::string query_path = argv[optind], target_path = argv[optind + 1];
         const bool all_to_all = query_path == target_path;
         if (is_gzip(query_path) || is_gzip(target_path))
             refuse("gzipped input is not supported");
+        if (all_to_all && (query_host != target_host || query_device != target_device))
+            refuse("the same file as query and target needs -C equal to -Q and -c equal to -q");
         if (all_to_all)
         {
             target_index_size = index_size;
@@ -216,12 +267,12 @@ int main(int argc, char** argv)
 
         const packed_reads q(queries);
         const packed_reads t(own_targets);
-        gw_mapper_overlaps* result = gw_mapper_map_batched_aligned(
+        gw_mapper_overlaps* result = gw_mapper_map_batched_cached(
             q.bases.data(), q.offsets.data(), static_cast<int32_t>(queries.size()), all_to_all ? nullptr : t.bases.data(),
             all_to_all ? nullptr : t.offsets.data(), static_cast<int32_t>(own_targets.size()), k, w, filtering_parameter,
             min_residues, min_overlap_len, min_bases_per_residue, min_overlap_fraction,
             static_cast<int64_t>(index_size * 1000000.0), static_cast<int64_t>(target_index_size * 1000000.0), 1,
-            drop ? 1 : 0, rescue ? 1 : 0, cigar, 0, nullptr);
+            drop ? 1 : 0, rescue ? 1 : 0, cigar, 0, query_host, query_device, target_host, target_device, nullptr);
         if (!result)
             refuse(gw_mapper_last_error());
         std::vector<overlap_record> records(static_cast<size_t>(gw_mapper_overlaps_count(result)));

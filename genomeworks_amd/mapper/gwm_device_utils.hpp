@@ -1,5 +1,5 @@
 // gwm_device_utils.hpp -- helpers shared by the cudamapper translation units (gwm_mapper.hip, gwm_postprocess.hip,
-// gwm_align.hip):
+// gwm_align.hip, gwm_index_cache.hip):
 // checked HIP calls, owning device buffers, the rocPRIM scan / select / sort wrappers and HIP-event stage timers.
 // Everything here has internal linkage; the one shared object is the error text behind gwm_last_error().
 #ifndef GWM_DEVICE_UTILS_HPP

@@ -465,6 +465,13 @@ void gwm_index_free(gwm_index* x)
 {
     if (!x)
         return;
+    if (x->device_slab)
+    {
+        // restored by gwm_index_unpack: the arrays lie in this one allocation
+        (void)hipFree(x->device_slab);
+        set_empty(x);
+        return;
+    }
     (void)hipFree(x->representations);
     (void)hipFree(x->read_ids);
     (void)hipFree(x->positions_in_reads);

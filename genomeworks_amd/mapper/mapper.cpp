@@ -6,7 +6,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cstring>
+#include <iterator>
+#include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -131,6 +134,156 @@ std::vector<descriptor> group_reads(const int64_t* lengths, int64_t n, int64_t m
     return out;
 }
 
+bool operator==(const descriptor& a, const descriptor& b)
+{
+    return a.first_read == b.first_read && a.number_of_reads == b.number_of_reads;
+}
+
+// IndexBatch / BatchOfIndices of the reference's index batcher
+struct index_batch
+{
+    std::vector<descriptor> query_indices, target_indices;
+};
+
+struct batch_of_indices
+{
+    index_batch host_batch;
+    std::vector<index_batch> device_batches;
+};
+
+// group_into_batches of the reference: blocks of per_query x per_target indices, query blocks outside; with the same
+// query and target only the upper triangle, the targets starting at the query block's own position
+std::vector<index_batch> group_into_batches(const std::vector<descriptor>& queries, const std::vector<descriptor>& targets,
+                                            int64_t per_query, int64_t per_target, bool same_query_and_target)
+{
+    if (same_query_and_target && per_query != per_target)
+        throw std::invalid_argument("group_into_batches: same query and target, but indices per batch not the same");
+    std::vector<index_batch> batches;
+    const int64_t nq = static_cast<int64_t>(queries.size()), nt = static_cast<int64_t>(targets.size());
+    for (int64_t q = 0; q < nq; q += per_query)
+        for (int64_t t = same_query_and_target ? q : 0; t < nt; t += per_target)
+            batches.push_back({std::vector<descriptor>(queries.begin() + q, queries.begin() + std::min(q + per_query, nq)),
+                               std::vector<descriptor>(targets.begin() + t, targets.begin() + std::min(t + per_target, nt))});
+    return batches;
+}
+
+// generate_batches_of_indices of the reference over descriptors that are already grouped, with the counts checked as
+// its application parameters check them
+std::vector<batch_of_indices> generate_batches(const std::vector<descriptor>& queries,
+                                               const std::vector<descriptor>& targets, int64_t query_host,
+                                               int64_t query_device, int64_t target_host, int64_t target_device,
+                                               bool same_query_and_target)
+{
+    if (query_host < 1 || query_device < 1 || target_host < 1 || target_device < 1)
+        throw std::invalid_argument("generate_batches_of_indices: every number of indices has to be at least 1");
+    if (query_host < query_device)
+        throw std::invalid_argument("generate_batches_of_indices: query indices in host memory has to be larger or "
+                                    "equal than query indices in device memory");
+    if (target_host < target_device)
+        throw std::invalid_argument("generate_batches_of_indices: target indices in host memory has to be larger or "
+                                    "equal than target indices in device memory");
+    if (same_query_and_target)
+    {
+        if (query_host != target_host)
+            throw std::invalid_argument("generate_batches_of_indices: indices_per_host_batch not the same");
+        if (query_device != target_device)
+            throw std::invalid_argument("generate_batches_of_indices: indices_per_device_batch not the same");
+    }
+    std::vector<batch_of_indices> all;
+    for (index_batch& host : group_into_batches(queries, targets, query_host, target_host, same_query_and_target))
+    {
+        // device batches are symmetric only where the host batch's query and target indices are the same
+        const bool same_in_batch = same_query_and_target && host.query_indices == host.target_indices;
+        std::vector<index_batch> device =
+            group_into_batches(host.query_indices, host.target_indices, query_device, target_device, same_in_batch);
+        all.push_back({std::move(host), std::move(device)});
+    }
+    return all;
+}
+
+std::vector<int64_t> read_lengths(const int64_t* offsets, int32_t n)
+{
+    std::vector<int64_t> v(static_cast<size_t>(n));
+    for (int32_t i = 0; i < n; ++i)
+        v[i] = offsets[i + 1] - offsets[i];
+    return v;
+}
+
+// Two HIP events around a piece of work on one stream.
+struct event_span
+{
+    hipEvent_t a = nullptr, b = nullptr;
+    event_span()
+    {
+        hip_check(hipEventCreate(&a), "hipEventCreate");
+        hip_check(hipEventCreate(&b), "hipEventCreate");
+    }
+    event_span(const event_span&) = delete;
+    event_span& operator=(const event_span&) = delete;
+    ~event_span()
+    {
+        (void)hipEventDestroy(a);
+        (void)hipEventDestroy(b);
+    }
+    float ms()
+    {
+        float v = 0.f;
+        hip_check(hipEventSynchronize(b), "hipEventSynchronize");
+        hip_check(hipEventElapsedTime(&v, a, b), "hipEventElapsedTime");
+        return v;
+    }
+};
+
+// The driver's second stream, on which packed indices are restored while the first one maps. settle() puts an event
+// behind what was queued and makes the mapping stream wait for it; the host does not wait. The spans around the
+// restores are kept, and restore_ms() reads them once, at the end of the run.
+struct copy_stream
+{
+    hipStream_t stream = nullptr;
+    hipEvent_t ready   = nullptr;
+    std::vector<std::unique_ptr<event_span>> spans;
+    size_t settled = 0;
+    copy_stream()
+    {
+        hip_check(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "hipStreamCreateWithFlags");
+        if (hipEventCreateWithFlags(&ready, hipEventDisableTiming) != hipSuccess)
+        {
+            (void)hipStreamDestroy(stream);
+            throw std::runtime_error("hipEventCreateWithFlags failed");
+        }
+    }
+    copy_stream(const copy_stream&) = delete;
+    copy_stream& operator=(const copy_stream&) = delete;
+    ~copy_stream()
+    {
+        (void)hipStreamSynchronize(stream);
+        spans.clear();
+        (void)hipEventDestroy(ready);
+        (void)hipStreamDestroy(stream);
+    }
+    void begin_span()
+    {
+        spans.emplace_back(new event_span());
+        hip_check(hipEventRecord(spans.back()->a, stream), "hipEventRecord");
+    }
+    void end_span() { hip_check(hipEventRecord(spans.back()->b, stream), "hipEventRecord"); }
+    void settle(hipStream_t mapping_stream)
+    {
+        if (spans.size() == settled)
+            return;
+        hip_check(hipEventRecord(ready, stream), "hipEventRecord");
+        hip_check(hipStreamWaitEvent(mapping_stream, ready, 0), "hipStreamWaitEvent");
+        settled = spans.size();
+    }
+    float restore_ms()
+    {
+        float total = 0.f;
+        for (const std::unique_ptr<event_span>& span : spans)
+            total += span->ms();
+        return total;
+    }
+};
+
 struct device_overlaps
 {
     gwm_overlap* p = nullptr;
@@ -168,11 +321,26 @@ struct gw_mapper_matcher
     gw_mapper_matcher& operator=(const gw_mapper_matcher&) = delete;
 };
 
+struct gw_mapper_index_host_copy
+{
+    gwm_index_host_copy c{};
+    gw_mapper_index_host_copy(const gw_mapper_index& index, hipStream_t stream)
+    {
+        throw_on(gwm_index_pack(&index.x, stream, &c));
+    }
+    ~gw_mapper_index_host_copy() { gwm_index_host_copy_free(&c); }
+    gw_mapper_index_host_copy(const gw_mapper_index_host_copy&) = delete;
+    gw_mapper_index_host_copy& operator=(const gw_mapper_index_host_copy&) = delete;
+};
+
 struct gw_mapper_overlaps
 {
     std::vector<gwm_overlap> overlaps;
     float stage_ms[3]   = {0.f, 0.f, 0.f};
     int64_t index_pairs = 0;
+    // the index cache: indices built from bases, indices restored from a packed host copy, device time of both ways
+    int64_t index_builds = 0, index_restores = 0;
+    float cache_ms[2]    = {0.f, 0.f}; // pack, unpack
     // with alignment: the CIGAR of overlap i is cigar_text[cigar_offsets[i] .. cigar_offsets[i + 1])
     bool aligned = false;
     std::string cigar_text;
@@ -459,11 +627,11 @@ gw_mapper_overlaps* gw_mapper_map_batched(const char* query_bases, const int64_t
                                           int64_t max_basepairs_per_target_index, int32_t post_process,
                                           int32_t drop_fused_overlaps, int32_t rescue_overlap_ends, void* stream)
 {
-    return gw_mapper_map_batched_aligned(query_bases, query_offsets, n_queries, target_bases, target_offsets, n_targets,
-                                         kmer_size, window_size, filtering_parameter, min_residues, min_overlap_len,
-                                         min_bases_per_residue, min_overlap_fraction, max_basepairs_per_query_index,
-                                         max_basepairs_per_target_index, post_process, drop_fused_overlaps,
-                                         rescue_overlap_ends, 0, 0, stream);
+    return gw_mapper_map_batched_cached(query_bases, query_offsets, n_queries, target_bases, target_offsets, n_targets,
+                                        kmer_size, window_size, filtering_parameter, min_residues, min_overlap_len,
+                                        min_bases_per_residue, min_overlap_fraction, max_basepairs_per_query_index,
+                                        max_basepairs_per_target_index, post_process, drop_fused_overlaps,
+                                        rescue_overlap_ends, 0, 0, 1, 1, 1, 1, stream);
 }
 
 gw_mapper_overlaps* gw_mapper_map_batched_aligned(
@@ -473,6 +641,22 @@ gw_mapper_overlaps* gw_mapper_map_batched_aligned(
     int64_t max_basepairs_per_query_index, int64_t max_basepairs_per_target_index, int32_t post_process,
     int32_t drop_fused_overlaps, int32_t rescue_overlap_ends, int32_t align_overlaps, int64_t max_device_bytes,
     void* stream)
+{
+    return gw_mapper_map_batched_cached(query_bases, query_offsets, n_queries, target_bases, target_offsets, n_targets,
+                                        kmer_size, window_size, filtering_parameter, min_residues, min_overlap_len,
+                                        min_bases_per_residue, min_overlap_fraction, max_basepairs_per_query_index,
+                                        max_basepairs_per_target_index, post_process, drop_fused_overlaps,
+                                        rescue_overlap_ends, align_overlaps, max_device_bytes, 1, 1, 1, 1, stream);
+}
+
+gw_mapper_overlaps* gw_mapper_map_batched_cached(
+    const char* query_bases, const int64_t* query_offsets, int32_t n_queries, const char* target_bases,
+    const int64_t* target_offsets, int32_t n_targets, int32_t kmer_size, int32_t window_size, double filtering_parameter,
+    int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue, float min_overlap_fraction,
+    int64_t max_basepairs_per_query_index, int64_t max_basepairs_per_target_index, int32_t post_process,
+    int32_t drop_fused_overlaps, int32_t rescue_overlap_ends, int32_t align_overlaps, int64_t max_device_bytes,
+    int32_t query_indices_in_host_memory, int32_t query_indices_in_device_memory, int32_t target_indices_in_host_memory,
+    int32_t target_indices_in_device_memory, void* stream)
 {
     return guarded([&] {
         hipStream_t s         = static_cast<hipStream_t>(stream);
@@ -485,15 +669,15 @@ gw_mapper_overlaps* gw_mapper_map_batched_aligned(
         }
         if (n_queries < 0 || n_targets < 0)
             throw std::invalid_argument("gw_mapper_map_batched: negative number of reads");
-        auto lengths = [](const int64_t* offsets, int32_t n) {
-            std::vector<int64_t> v(static_cast<size_t>(n));
-            for (int32_t i = 0; i < n; ++i)
-                v[i] = offsets[i + 1] - offsets[i];
-            return v;
-        };
-        const std::vector<int64_t> ql = lengths(query_offsets, n_queries), tl = lengths(target_offsets, n_targets);
+        const std::vector<int64_t> ql = read_lengths(query_offsets, n_queries), tl = read_lengths(target_offsets, n_targets);
         const std::vector<descriptor> qd = group_reads(ql.data(), n_queries, max_basepairs_per_query_index);
         const std::vector<descriptor> td = group_reads(tl.data(), n_targets, max_basepairs_per_target_index);
+        // The batches are the upper triangle only where query and target indices are the same list. All against all
+        // with two index sizes keeps the whole matrix, and the pair walk below drops the lower triangle as it always did.
+        const bool same_indices = all_to_all && max_basepairs_per_query_index == max_basepairs_per_target_index;
+        const std::vector<batch_of_indices> batches =
+            generate_batches(qd, td, query_indices_in_host_memory, query_indices_in_device_memory,
+                             target_indices_in_host_memory, target_indices_in_device_memory, same_indices);
         if (align_overlaps)
         {
             // The index numbers its reads by rank among the reads it kept: behind a read it skipped, read ids no
@@ -518,79 +702,287 @@ gw_mapper_overlaps* gw_mapper_map_batched_aligned(
         }
         std::unique_ptr<gw_mapper_overlaps> result(new gw_mapper_overlaps());
         result->aligned = align_overlaps != 0;
-        for (const descriptor& qx : qd)
-        {
-            if (qx.number_of_reads == 0)
-                continue;
-            // one query index serves the whole row of target indices
-            gw_mapper_index qi(query_bases, query_offsets + qx.first_read, static_cast<int32_t>(qx.number_of_reads),
-                               qx.first_read, kmer_size, window_size, 1, filtering_parameter, s);
-            for (const descriptor& tx : td)
+
+        // ---- the stages of one index pair, as they always were
+        auto map_pair = [&](const gw_mapper_index& qi, const gw_mapper_index& ti) {
+            int64_t count = 0;
+            float ms      = 0.f;
+            device_overlaps found;
             {
-                if (tx.number_of_reads == 0 || (all_to_all && tx.first_read < qx.first_read))
-                    continue;
-                const bool same = all_to_all && tx.first_read == qx.first_read && tx.number_of_reads == qx.number_of_reads;
-                std::unique_ptr<gw_mapper_index> ti;
-                if (!same)
-                    ti.reset(new gw_mapper_index(target_bases, target_offsets + tx.first_read,
-                                                 static_cast<int32_t>(tx.number_of_reads), tx.first_read, kmer_size,
-                                                 window_size, 1, filtering_parameter, s));
-                int64_t count = 0;
-                float ms      = 0.f;
-                device_overlaps found;
-                {
-                    gw_mapper_matcher m(qi, same ? qi : *ti, s);
-                    throw_on(gwm_find_overlaps_device(m.a.anchors, m.a.n, all_to_all ? 1 : 0, min_residues,
-                                                      min_overlap_len, min_bases_per_residue, min_overlap_fraction, s,
-                                                      &found.p, &count, &ms));
-                    result->stage_ms[0] += ms;
-                }
-                ++result->index_pairs;
-                if (count == 0)
-                    continue;
-                device_array<gwm_overlap> fused;
-                gwm_overlap* current = found.p;
-                if (post_process)
-                {
-                    fused.allocate(count + count / 2);
-                    throw_on(gwm_post_process_overlaps(found.p, count, drop_fused_overlaps, s, fused.p, &count, &ms));
-                    result->stage_ms[1] += ms;
-                    current = fused.p;
-                }
-                if (rescue_overlap_ends && count > 0)
-                {
-                    const device_reads& tr = t_reads ? *t_reads : *q_reads;
-                    throw_on(gwm_rescue_overlap_ends(current, count, q_reads->bases.p, q_reads->offsets.p, q_reads->n,
-                                                     0, tr.bases.p, tr.offsets.p, tr.n, 0, 50, 0.5f, s, &ms));
-                    result->stage_ms[2] += ms;
-                }
-                if (align_overlaps && count > 0)
-                {
-                    // what is left of this index pair, where it lies: one aligner capacity per pair
-                    const device_reads& tr = t_reads ? *t_reads : *q_reads;
-                    gw_mapper_cigars cigars;
-                    throw_on(gwm_align_overlaps(current, count, q_reads->bases.p, q_reads->offsets.p, q_reads->n, 0,
-                                                tr.bases.p, tr.offsets.p, tr.n, 0, max_device_bytes, s, &cigars.c));
-                    const size_t text_at = result->cigar_text.size(), n_at = result->edit_distances.size();
-                    result->cigar_text.resize(text_at + static_cast<size_t>(cigars.c.text_bytes));
-                    copy_out(&result->cigar_text[0] + text_at, cigars.c.text, cigars.c.text_bytes);
-                    result->cigar_offsets.resize(n_at + static_cast<size_t>(count) + 1);
-                    copy_out(result->cigar_offsets.data() + n_at, cigars.c.cigar_offsets, count + 1);
-                    for (size_t i = n_at; i < result->cigar_offsets.size(); ++i)
-                        result->cigar_offsets[i] += static_cast<int64_t>(text_at);
-                    result->edit_distances.resize(n_at + static_cast<size_t>(count));
-                    copy_out(result->edit_distances.data() + n_at, cigars.c.edit_distances, count);
-                    for (int k = 0; k < 3; ++k)
-                        result->align_ms[k] += cigars.c.stage_ms[k];
-                }
-                const size_t at = result->overlaps.size();
-                result->overlaps.resize(at + static_cast<size_t>(count));
-                copy_out(result->overlaps.data() + at, current, count);
+                gw_mapper_matcher m(qi, ti, s);
+                throw_on(gwm_find_overlaps_device(m.a.anchors, m.a.n, all_to_all ? 1 : 0, min_residues, min_overlap_len,
+                                                  min_bases_per_residue, min_overlap_fraction, s, &found.p, &count,
+                                                  &ms));
+                result->stage_ms[0] += ms;
             }
+            ++result->index_pairs;
+            if (count == 0)
+                return;
+            device_array<gwm_overlap> fused;
+            gwm_overlap* current = found.p;
+            if (post_process)
+            {
+                fused.allocate(count + count / 2);
+                throw_on(gwm_post_process_overlaps(found.p, count, drop_fused_overlaps, s, fused.p, &count, &ms));
+                result->stage_ms[1] += ms;
+                current = fused.p;
+            }
+            if (rescue_overlap_ends && count > 0)
+            {
+                const device_reads& tr = t_reads ? *t_reads : *q_reads;
+                throw_on(gwm_rescue_overlap_ends(current, count, q_reads->bases.p, q_reads->offsets.p, q_reads->n, 0,
+                                                 tr.bases.p, tr.offsets.p, tr.n, 0, 50, 0.5f, s, &ms));
+                result->stage_ms[2] += ms;
+            }
+            if (align_overlaps && count > 0)
+            {
+                // what is left of this index pair, where it lies: one aligner capacity per pair
+                const device_reads& tr = t_reads ? *t_reads : *q_reads;
+                gw_mapper_cigars cigars;
+                throw_on(gwm_align_overlaps(current, count, q_reads->bases.p, q_reads->offsets.p, q_reads->n, 0,
+                                            tr.bases.p, tr.offsets.p, tr.n, 0, max_device_bytes, s, &cigars.c));
+                const size_t text_at = result->cigar_text.size(), n_at = result->edit_distances.size();
+                result->cigar_text.resize(text_at + static_cast<size_t>(cigars.c.text_bytes));
+                copy_out(&result->cigar_text[0] + text_at, cigars.c.text, cigars.c.text_bytes);
+                result->cigar_offsets.resize(n_at + static_cast<size_t>(count) + 1);
+                copy_out(result->cigar_offsets.data() + n_at, cigars.c.cigar_offsets, count + 1);
+                for (size_t i = n_at; i < result->cigar_offsets.size(); ++i)
+                    result->cigar_offsets[i] += static_cast<int64_t>(text_at);
+                result->edit_distances.resize(n_at + static_cast<size_t>(count));
+                copy_out(result->edit_distances.data() + n_at, cigars.c.edit_distances, count);
+                for (int k = 0; k < 3; ++k)
+                    result->align_ms[k] += cigars.c.stage_ms[k];
+            }
+            const size_t at = result->overlaps.size();
+            result->overlaps.resize(at + static_cast<size_t>(count));
+            copy_out(result->overlaps.data() + at, current, count);
+        };
+
+        // ---- the index cache. An index is named by its descriptor and, unless the two sets are one, by its kind.
+        using index_key = std::array<uint32_t, 3>;
+        using index_ptr = std::shared_ptr<gw_mapper_index>;
+        using copy_ptr  = std::shared_ptr<gw_mapper_index_host_copy>;
+        auto key_of = [&](uint32_t kind, const descriptor& d) {
+            return index_key{all_to_all ? 0u : kind, d.first_read, d.number_of_reads};
+        };
+        // the indices of a batch that hold reads, each once, queries first
+        auto keys_of = [&](const index_batch& b) {
+            std::vector<std::pair<index_key, descriptor>> keys;
+            for (uint32_t kind = 0; kind < 2; ++kind)
+                for (const descriptor& d : kind == 0 ? b.query_indices : b.target_indices)
+                {
+                    const index_key k = key_of(kind, d);
+                    if (d.number_of_reads > 0 &&
+                        std::none_of(keys.begin(), keys.end(), [&](const auto& e) { return e.first == k; }))
+                        keys.push_back({k, d});
+                }
+            return keys;
+        };
+        copy_stream restores; // the second stream: indices of the next device batch come back while this one is mapped
+        std::map<index_key, index_ptr> on_device; // alive from the previous device batch
+        std::map<index_key, copy_ptr> on_host;    // the host copies of the previous host batch
+        struct drain
+        {
+            copy_stream& c;
+            ~drain() { (void)hipStreamSynchronize(c.stream); } // no copy may outlive the slab it reads
+        } drain_before_the_copies_go{restores};
+        auto build = [&](const index_key& k, const descriptor& d) {
+            const bool target = !all_to_all && k[0] == 1;
+            ++result->index_builds;
+            return std::make_shared<gw_mapper_index>(target ? target_bases : query_bases,
+                                                     (target ? target_offsets : query_offsets) + d.first_read,
+                                                     static_cast<int32_t>(d.number_of_reads), d.first_read, kmer_size,
+                                                     window_size, 1, filtering_parameter, s);
+        };
+        auto restore = [&](const copy_ptr& copy) {
+            index_ptr index = std::make_shared<gw_mapper_index>();
+            restores.begin_span();
+            throw_on(gwm_index_unpack(&copy->c, restores.stream, &index->x));
+            restores.end_span();
+            ++result->index_restores;
+            return index;
+        };
+
+        for (const batch_of_indices& batch : batches)
+        {
+            // 1. the indices of the host batch: those of the first device batch stay on the device, those a later
+            //    device batch asks for get a packed host copy. Before one is built it is looked for among the indices
+            //    still on the device and among the host copies of the previous host batch.
+            std::vector<index_key> first, later;
+            for (size_t b = 0; b < batch.device_batches.size(); ++b)
+                for (const auto& e : keys_of(batch.device_batches[b]))
+                    (b == 0 ? first : later).push_back(e.first);
+            auto in = [](const std::vector<index_key>& v, const index_key& k) {
+                return std::find(v.begin(), v.end(), k) != v.end();
+            };
+            std::map<index_key, index_ptr> current;
+            std::map<index_key, copy_ptr> copies;
+            const auto asked_for = keys_of(batch.host_batch);
+            // what the previous device batch left and this host batch does not ask for goes before anything is built,
+            // so one index per batch never holds more than the two indices of a pair
+            for (auto it = on_device.begin(); it != on_device.end();)
+                it = std::none_of(asked_for.begin(), asked_for.end(), [&](const auto& e) { return e.first == it->first; })
+                         ? on_device.erase(it)
+                         : std::next(it);
+            for (const auto& e : asked_for)
+            {
+                const index_key& k = e.first;
+                const auto alive = on_device.find(k);
+                const auto kept  = on_host.find(k);
+                index_ptr index  = alive != on_device.end() ? alive->second : nullptr;
+                copy_ptr copy    = kept != on_host.end() ? kept->second : nullptr;
+                if (alive != on_device.end())
+                    on_device.erase(alive); // from here on it lives as long as this batch needs it
+                if (!index)
+                {
+                    if (!copy)
+                        index = build(k, e.second);
+                    else if (in(first, k))
+                        index = restore(copy);
+                }
+                if (in(later, k))
+                {
+                    if (!copy)
+                    {
+                        copy = std::make_shared<gw_mapper_index_host_copy>(*index, s);
+                        result->cache_ms[0] += copy->c.pack_ms;
+                    }
+                    copies[k] = copy;
+                }
+                if (in(first, k))
+                    current[k] = index;
+            }
+            restores.settle(s);
+            on_device.clear();
+            // `copies` now holds the previous host batch's copies. A restore queued above may still read one of them,
+            // so they are let go at the end of this host batch, behind a wait for the second stream.
+            on_host.swap(copies);
+
+            // 2. the device batches: while one is mapped, the next one's indices are restored on the second stream
+            for (size_t b = 0; b < batch.device_batches.size(); ++b)
+            {
+                std::map<index_key, index_ptr> next;
+                if (b + 1 < batch.device_batches.size())
+                    for (const auto& e : keys_of(batch.device_batches[b + 1]))
+                    {
+                        const auto here = current.find(e.first);
+                        next[e.first]   = here != current.end() ? here->second : restore(on_host.at(e.first));
+                    }
+                for (const descriptor& qx : batch.device_batches[b].query_indices)
+                    for (const descriptor& tx : batch.device_batches[b].target_indices)
+                    {
+                        if (qx.number_of_reads == 0 || tx.number_of_reads == 0 ||
+                            (all_to_all && tx.first_read < qx.first_read))
+                            continue;
+                        map_pair(*current.at(key_of(0, qx)), *current.at(key_of(1, tx)));
+                    }
+                if (b + 1 < batch.device_batches.size())
+                {
+                    restores.settle(s);
+                    current.swap(next);
+                }
+            }
+            on_device.swap(current);
+            if (!copies.empty()) // the second stream is idle by now; this makes letting the old copies go safe by itself
+                hip_check(hipStreamSynchronize(restores.stream), "hipStreamSynchronize");
         }
+        result->cache_ms[1] = restores.restore_ms();
         return result.release();
     }, static_cast<gw_mapper_overlaps*>(nullptr));
 }
+
+int gw_mapper_overlaps_cache_counts(const gw_mapper_overlaps* result, int64_t* index_builds, int64_t* index_restores,
+                                    float* pack_unpack_ms)
+{
+    if (index_builds)
+        *index_builds = result->index_builds;
+    if (index_restores)
+        *index_restores = result->index_restores;
+    if (pack_unpack_ms)
+        std::memcpy(pack_unpack_ms, result->cache_ms, sizeof(result->cache_ms));
+    return 0;
+}
+
+int64_t gw_mapper_generate_batches_of_indices(const int64_t* query_read_lengths, int64_t n_queries,
+                                              const int64_t* target_read_lengths, int64_t n_targets,
+                                              int64_t query_basepairs_per_index, int64_t target_basepairs_per_index,
+                                              int32_t query_indices_in_host_memory,
+                                              int32_t query_indices_in_device_memory,
+                                              int32_t target_indices_in_host_memory,
+                                              int32_t target_indices_in_device_memory, uint32_t* out, int64_t capacity)
+{
+    return guarded([&] {
+        const bool same = target_read_lengths == nullptr;
+        if (n_queries < 0 || (!same && n_targets < 0))
+            throw std::invalid_argument("gw_mapper_generate_batches_of_indices: negative number of reads");
+        if (same && query_basepairs_per_index != target_basepairs_per_index)
+            throw std::invalid_argument("generate_batches_of_indices: basepairs_per_index not the same");
+        const std::vector<descriptor> qd = group_reads(query_read_lengths, n_queries, query_basepairs_per_index);
+        const std::vector<descriptor> td =
+            same ? qd : group_reads(target_read_lengths, n_targets, target_basepairs_per_index);
+        const std::vector<batch_of_indices> batches =
+            generate_batches(qd, td, query_indices_in_host_memory, query_indices_in_device_memory,
+                             target_indices_in_host_memory, target_indices_in_device_memory, same);
+        std::vector<uint32_t> flat;
+        auto put = [&](const index_batch& b) {
+            flat.push_back(static_cast<uint32_t>(b.query_indices.size()));
+            flat.push_back(static_cast<uint32_t>(b.target_indices.size()));
+            for (const std::vector<descriptor>* v : {&b.query_indices, &b.target_indices})
+                for (const descriptor& d : *v)
+                {
+                    flat.push_back(d.first_read);
+                    flat.push_back(d.number_of_reads);
+                }
+        };
+        flat.push_back(static_cast<uint32_t>(batches.size()));
+        for (const batch_of_indices& b : batches)
+        {
+            put(b.host_batch);
+            flat.push_back(static_cast<uint32_t>(b.device_batches.size()));
+            for (const index_batch& d : b.device_batches)
+                put(d);
+        }
+        const int64_t words = static_cast<int64_t>(flat.size());
+        if (out && words <= capacity)
+            std::memcpy(out, flat.data(), sizeof(uint32_t) * flat.size());
+        return words;
+    }, int64_t(GW_MAPPER_ERROR));
+}
+
+gw_mapper_index_host_copy* gw_mapper_index_host_copy_create(const gw_mapper_index* index, void* stream, float* pack_ms)
+{
+    return guarded([&] {
+        std::unique_ptr<gw_mapper_index_host_copy> h(
+            new gw_mapper_index_host_copy(*index, static_cast<hipStream_t>(stream)));
+        if (pack_ms)
+            *pack_ms = h->c.pack_ms;
+        return h.release();
+    }, static_cast<gw_mapper_index_host_copy*>(nullptr));
+}
+
+int64_t gw_mapper_index_host_copy_bytes(const gw_mapper_index_host_copy* copy)
+{
+    return gwm_index_host_copy_bytes(&copy->c);
+}
+
+gw_mapper_index* gw_mapper_index_host_copy_to_device(const gw_mapper_index_host_copy* copy, void* stream,
+                                                     float* restore_ms)
+{
+    return guarded([&] {
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        std::unique_ptr<gw_mapper_index> h(new gw_mapper_index());
+        event_span span;
+        hip_check(hipEventRecord(span.a, s), "hipEventRecord");
+        throw_on(gwm_index_unpack(&copy->c, s, &h->x));
+        hip_check(hipEventRecord(span.b, s), "hipEventRecord");
+        const float ms = span.ms(); // waits: the index is ready when this returns
+        if (restore_ms)
+            *restore_ms = ms;
+        return h.release();
+    }, static_cast<gw_mapper_index*>(nullptr));
+}
+
+void gw_mapper_index_host_copy_destroy(gw_mapper_index_host_copy* copy) { delete copy; }
 
 int64_t gw_mapper_overlaps_count(const gw_mapper_overlaps* result) { return static_cast<int64_t>(result->overlaps.size()); }
 

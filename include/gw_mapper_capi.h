@@ -2,8 +2,9 @@
  * gw_mapper_capi.h -- flat C API of cudamapper (libcudamapper.so), for foreign-function bindings
  * (genomeworks_amd/cudamapper.py): index creation from host reads, the anchor matcher, the triggered overlapper, one
  * call for a whole mapping of one index pair, overlap post-processing, end rescue and alignment of overlaps into
- * CIGARs, and the batched driver behind the cudamapper tool. Functions returning int give 0 on success; those returning a count give it, or
- * GW_MAPPER_ERROR; creators return NULL. On an error the exception text is in gw_mapper_last_error().
+ * CIGARs, packed host copies of indices, the index batcher and the cached batched driver behind the cudamapper tool.
+ * Functions returning int give 0 on success; those returning a count give it, or GW_MAPPER_ERROR; creators return NULL.
+ * On an error the exception text is in gw_mapper_last_error().
  *
  * Reads are passed as one byte array and n_reads + 1 offsets: read i is bases[offsets[i] .. offsets[i+1]).
  * Anchors use the layout of cudamapper::Anchor (4 x uint32, 16 B), overlaps that of cudamapper::Overlap (36 B).
@@ -127,7 +128,7 @@ int64_t gw_mapper_group_reads_into_indices(const int64_t* read_lengths, int64_t 
    post-process (if post_process) -> end rescue with extension 50 and similarity 0.5 (if rescue_overlap_ends), the
    overlaps staying on the device in between, then appended to the result. Read ids are positions in the query /
    target set (the id shift behind reads shorter than k + w - 1 applies within an index, as in gwm_index_build).
-   No index cache, no host copies of indices, one device. */
+   One device. This is gw_mapper_map_batched_cached with one index per batch on every level. */
 typedef struct gw_mapper_overlaps gw_mapper_overlaps;
 gw_mapper_overlaps* gw_mapper_map_batched(const char* query_bases, const int64_t* query_offsets, int32_t n_queries,
                                           const char* target_bases, const int64_t* target_offsets, int32_t n_targets,
@@ -151,6 +152,68 @@ gw_mapper_overlaps* gw_mapper_map_batched_aligned(
     int64_t max_basepairs_per_query_index, int64_t max_basepairs_per_target_index, int32_t post_process,
     int32_t drop_fused_overlaps, int32_t rescue_overlap_ends, int32_t align_overlaps, int64_t max_device_bytes,
     void* stream);
+
+/* ---- the index cache ----------------------------------------------------------------------------------------------
+   generate_batches_of_indices of the reference's index batcher over read lengths: reads are grouped into indices
+   (gw_mapper_group_reads_into_indices), indices into host batches of query_indices_in_host_memory x
+   target_indices_in_host_memory (query blocks outside, target blocks inside), every host batch the same way into device
+   batches of query_indices_in_device_memory x target_indices_in_device_memory. target_read_lengths NULL means the
+   target set is the query set: only the upper triangle of blocks is formed (targets start at the query block's own
+   position), and a host batch is split symmetrically only when its query and target lists are equal. Errors
+   (GW_MAPPER_ERROR, nothing written): the same set with different host counts, device counts or index sizes; any count
+   below 1; fewer indices in host memory than in device memory.
+   Returns the number of uint32 words of the flat result and writes it when `out` is not NULL and capacity suffices:
+   n_host_batches, then per host batch a batch record, n_device_batches and that many batch records; a batch record is
+   n_query_indices, n_target_indices, then (first_read, number_of_reads) of every query index and of every target
+   index. */
+int64_t gw_mapper_generate_batches_of_indices(const int64_t* query_read_lengths, int64_t n_queries,
+                                              const int64_t* target_read_lengths, int64_t n_targets,
+                                              int64_t query_basepairs_per_index, int64_t target_basepairs_per_index,
+                                              int32_t query_indices_in_host_memory,
+                                              int32_t query_indices_in_device_memory,
+                                              int32_t target_indices_in_host_memory,
+                                              int32_t target_indices_in_device_memory, uint32_t* out, int64_t capacity);
+
+/* IndexHostCopy: a packed copy of an index in pinned host memory (gwm_index_pack of gwhip_mapper.h: read ids,
+   positions, one direction bit per element and the unique-representation tables). _create is synchronous on `stream`;
+   _to_device (gwm_index_unpack, then a wait) returns an index equal to the packed one in all arrays and attributes.
+   pack_ms / restore_ms (device time, HIP events) may be NULL. */
+typedef struct gw_mapper_index_host_copy gw_mapper_index_host_copy;
+gw_mapper_index_host_copy* gw_mapper_index_host_copy_create(const gw_mapper_index* index, void* stream, float* pack_ms);
+int64_t gw_mapper_index_host_copy_bytes(const gw_mapper_index_host_copy* copy);
+gw_mapper_index* gw_mapper_index_host_copy_to_device(const gw_mapper_index_host_copy* copy, void* stream,
+                                                     float* restore_ms);
+void gw_mapper_index_host_copy_destroy(gw_mapper_index_host_copy* copy);
+
+/* gw_mapper_map_batched_aligned through the index cache (the reference's -Q -q -C -c). The index pairs are walked
+   host batch by host batch (gw_mapper_generate_batches_of_indices; all against all with one index size is the same
+   set). Per host batch: its indices are generated, those of the first device batch stay on the device and those a
+   later device batch asks for get a packed host copy (none when there is one device batch); then the device batches
+   are walked, and while one is mapped on `stream` the indices of the next are restored from their host copies on a
+   second stream, with an event between the two. Within a device batch pairs go query-major, with the skips of
+   gw_mapper_map_batched; per pair the stages are the same. Records and their order do not depend on the four counts
+   beyond the order of the pairs; at 1, 1, 1, 1 that is the order of gw_mapper_map_batched_aligned.
+   Reuse: before an index is built it is looked for (1) among the indices still on the device from the previous device
+   batch, (2) among the host copies of the previous host batch -- of the same kind (query / target), or of either kind
+   all against all. Only an index found in neither is built.
+   Device footprint: the indices of two device batches, 2 x (query_indices_in_device_memory +
+   target_indices_in_device_memory); while a host batch's indices are generated, what the previous device batch left
+   and the new host batch asks for (the rest is freed first), the first device batch, and one index built only to be
+   packed. At 1, 1, 1, 1 never more than the two indices of a pair. Host: the packed copies of one host batch, and
+   those of the previous one until the current host batch ends. An allocation failure is an error; no pair is skipped.
+   Errors as for gw_mapper_generate_batches_of_indices. */
+gw_mapper_overlaps* gw_mapper_map_batched_cached(
+    const char* query_bases, const int64_t* query_offsets, int32_t n_queries, const char* target_bases,
+    const int64_t* target_offsets, int32_t n_targets, int32_t kmer_size, int32_t window_size, double filtering_parameter,
+    int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue, float min_overlap_fraction,
+    int64_t max_basepairs_per_query_index, int64_t max_basepairs_per_target_index, int32_t post_process,
+    int32_t drop_fused_overlaps, int32_t rescue_overlap_ends, int32_t align_overlaps, int64_t max_device_bytes,
+    int32_t query_indices_in_host_memory, int32_t query_indices_in_device_memory, int32_t target_indices_in_host_memory,
+    int32_t target_indices_in_device_memory, void* stream);
+/* indices built from bases, indices restored from a host copy, and pack_unpack_ms[2]: summed device time of packing
+   and of restoring (HIP events); any pointer may be NULL */
+int gw_mapper_overlaps_cache_counts(const gw_mapper_overlaps* result, int64_t* index_builds, int64_t* index_restores,
+                                    float* pack_unpack_ms);
 int64_t gw_mapper_overlaps_count(const gw_mapper_overlaps* result);
 /* bytes of all CIGARs of an aligned result, back to back; GW_MAPPER_ERROR when it was mapped without alignment */
 int64_t gw_mapper_overlaps_cigar_text_bytes(const gw_mapper_overlaps* result);

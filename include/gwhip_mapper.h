@@ -63,6 +63,9 @@ typedef struct gwm_index
     uint32_t number_of_basepairs_in_longest_read;
     /* device time (ms, HIP events) of the stages: sketch, sort, unique, filter */
     float stage_ms[4];
+    /* NULL for an index that was built: its six arrays are six allocations. An index restored by gwm_index_unpack
+     * lives in this one allocation and its array pointers point into it. gwm_index_free frees either kind. */
+    void* device_slab;
 } gwm_index;
 
 /* Builds the index of n_reads host reads: bases[offsets[i] .. offsets[i+1]) is read first_read_id + i. Reads shorter
@@ -72,6 +75,37 @@ typedef struct gwm_index
 int gwm_index_build(const char* bases, const int64_t* offsets, int32_t n_reads, uint32_t first_read_id, int32_t k,
                     int32_t w, int32_t hash_representations, double filtering_parameter, void* stream, gwm_index* out);
 void gwm_index_free(gwm_index* index);
+
+/* A packed copy of an index in pinned host memory (hipHostMalloc), made so that bringing the index back costs as few
+ * bytes over the host link as possible. The slab is: a 64 B header (n, n_unique, n_first_occurrence, first_read_id,
+ * number_of_reads, number_of_basepairs_in_longest_read), read_ids[n], positions_in_reads[n], one direction bit per
+ * element (bit i % 64 of 64-bit word i / 64, zero beyond n), unique_representations[n_unique] and
+ * first_occurrence_of_representations[n_first_occurrence], each section starting at a multiple of 16 B. That is
+ * 8 n + 8 ceil(n / 64) + 12 n_unique + O(1) bytes against 17 n + 12 n_unique for the six arrays: the 8 B
+ * representation of every element is left out, because it is the unique representation of the section of
+ * first_occurrence the element lies in, and is filled in on the device again. */
+typedef struct gwm_index_host_copy
+{
+    void* slab;    /* pinned host memory, `bytes` long; NULL after gwm_index_host_copy_free */
+    int64_t bytes;
+    float pack_ms; /* device time of gwm_index_pack: bitmap kernel and the copies (HIP events) */
+} gwm_index_host_copy;
+
+/* Packs a device index into a new host copy; the index is not changed. A kernel turns the direction bytes into the
+ * bitmap (one 64-bit ballot per wave64), then the arrays are copied to the slab with asynchronous copies on `stream`.
+ * Synchronous on `stream` when it returns: the slab is complete. Packing never changes a value: a direction byte
+ * other than 0 or 1 is an error (-1, no copy is left behind). The empty index packs into a header alone. */
+int gwm_index_pack(const gwm_index* index, void* stream, gwm_index_host_copy* out);
+/* Restores the index of a host copy into one device allocation: one asynchronous copy of the slab on `stream`, a
+ * kernel that gives element i the representation of its section (upper-bound search of i in first_occurrence, so empty
+ * sections are skipped; an element outside every section gets 0, as gwm_index_from_arrays leaves it) and a kernel that
+ * turns the bitmap back into direction bytes. The result equals the packed index in all six arrays and all attributes
+ * (stage_ms is zero: nothing was built); the empty index comes back with no arrays. Asynchronous: the work is queued
+ * on `stream` when this returns, so the copy must outlive it and the index may be used on `stream`, or on another
+ * stream behind an event recorded on `stream`. */
+int gwm_index_unpack(const gwm_index_host_copy* copy, void* stream, gwm_index* out);
+void gwm_index_host_copy_free(gwm_index_host_copy* copy);
+int64_t gwm_index_host_copy_bytes(const gwm_index_host_copy* copy);
 
 /* All anchors of query x target, sorted by (query read, target read, query position, target position). */
 typedef struct gwm_anchors
