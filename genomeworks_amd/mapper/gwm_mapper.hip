@@ -98,7 +98,8 @@ __global__ void __launch_bounds__(kThreads) kmer_kernel(const uint8_t* __restric
 
 // Window j of a read with nk k-mers covers k-mers [max(0, j-w+1), min(nk-1, j)], j in [0, nk+w-1): the w-1 front-end
 // windows, the nk-w+1 central ones and the w-1 back-end ones. Its minimizer is the LAST k-mer of smallest
-// representation. A window emits its minimizer when j == 0 or the previous window's minimizer sits elsewhere.
+// representation. A window emits its minimizer when j == 0 or the previous window's minimizer sits elsewhere -- with the
+// one exception of central_step() below.
 __device__ inline uint32_t window_min(const uint64_t* rep, int64_t j, int64_t nk, int64_t w)
 {
     const int64_t lo = j - w + 1 > 0 ? j - w + 1 : 0;
@@ -117,6 +118,17 @@ __device__ inline uint32_t window_min(const uint64_t* rep, int64_t j, int64_t nk
     return static_cast<uint32_t>(at);
 }
 
+// The reference walks the central windows of a read in steps of 514 - k - w windows (64 threads x 8 bases, held in 16
+// bits) and hands the last window's position from step to step through a carry stored by thread `step % 64 - 1`. When
+// the step is a multiple of 64 (k + w = 2 mod 64, e.g. k 15 w 51) no thread stores it: the carry keeps its first value,
+// the position of the last front-end minimizer (0 when w == 1), and the first window of every later step is compared
+// with that instead of with its left neighbour. Such a window sits at a position >= step, the carry at <= w - 2, so it
+// always emits as long as w - 2 < step (gwm_index_build refuses the rest).
+__device__ inline uint32_t central_step(uint32_t k, uint32_t w)
+{
+    return static_cast<uint16_t>(static_cast<uint16_t>(512u - (k - 1)) - (w - 1));
+}
+
 __global__ void __launch_bounds__(kThreads) window_kernel(const uint64_t* __restrict__ rep,
                                                           const int64_t* __restrict__ base_offsets,
                                                           const int64_t* __restrict__ window_offsets, uint32_t n_reads,
@@ -132,7 +144,12 @@ __global__ void __launch_bounds__(kThreads) window_kernel(const uint64_t* __rest
     const uint64_t* q = rep + base_offsets[r];
     const uint32_t at = window_min(q, j, nk, w);
     min_pos[x]        = at;
-    emit[x]           = (j == 0 || window_min(q, j - 1, nk, w) != at) ? 1u : 0u;
+    const uint32_t step = central_step(k, w);
+    const int64_t c     = j - (w - 1); // central window number
+    if (step % 64 == 0 && c > 0 && c < nk - w + 1 && c % step == 0)
+        emit[x] = at != (w > 1 ? window_min(q, w - 2, nk, w) : 0u) ? 1u : 0u;
+    else
+        emit[x] = (j == 0 || window_min(q, j - 1, nk, w) != at) ? 1u : 0u;
 }
 
 // Emitted windows -> (representation, global index) keys for the stable sort, and the rest of the element.
@@ -489,6 +506,11 @@ int gwm_index_build(const char* bases, const int64_t* offsets, int32_t n_reads, 
     {
         if (k < 1 || k > 32 || w < 1 || n_reads < 0)
             throw std::invalid_argument("gwm_index_build: need 1 <= k <= 32, w >= 1, n_reads >= 0");
+        {
+            const uint32_t step = static_cast<uint16_t>(static_cast<uint16_t>(512 - (k - 1)) - (w - 1));
+            if (step % 64 == 0 && static_cast<int64_t>(w) - 2 >= static_cast<int64_t>(step))
+                throw std::invalid_argument("gwm_index_build: k + w = 2 (mod 64) needs w - 2 < 514 - k - w");
+        }
         hipStream_t s = static_cast<hipStream_t>(stream);
         out->first_read_id = first_read_id;
         // reads of at least k + w - 1 bases, in order

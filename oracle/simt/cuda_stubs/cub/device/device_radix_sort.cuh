@@ -42,5 +42,14 @@ struct DeviceRadixSort
         values.selector ^= 1;
         return cudaSuccess;
     }
+    /// the same from (keys_in, values_in) into (keys_out, values_out)
+    template <typename K, typename V>
+    static cudaError_t SortPairs(void* temp, size_t& temp_bytes, const K* keys_in, K* keys_out, const V* values_in, V* values_out, int n,
+                                 int begin_bit = 0, int end_bit = sizeof(K) * 8, cudaStream_t stream = nullptr)
+    {
+        DoubleBuffer<K> keys(const_cast<K*>(keys_in), keys_out);
+        DoubleBuffer<V> values(const_cast<V*>(values_in), values_out);
+        return SortPairs(temp, temp_bytes, keys, values, n, begin_bit, end_bit, stream);
+    }
 };
 } // namespace cub

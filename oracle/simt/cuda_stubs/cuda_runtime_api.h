@@ -67,6 +67,9 @@ inline cudaError_t cudaHostAlloc(void** p, size_t bytes, unsigned) { return cuda
 template <typename T>
 inline cudaError_t cudaHostAlloc(T** p, size_t bytes, unsigned f) { return cudaMalloc(reinterpret_cast<void**>(p), bytes); }
 constexpr unsigned cudaHostAllocDefault = 0;
+constexpr unsigned cudaHostRegisterDefault = 0;
+inline cudaError_t cudaHostRegister(void*, size_t, unsigned) { return cudaSuccess; }
+inline cudaError_t cudaHostUnregister(void*) { return cudaSuccess; }
 inline cudaError_t cudaFreeHost(void* p) { std::free(p); return cudaSuccess; }
 inline cudaError_t cudaMemcpy(void* dst, const void* src, size_t n, cudaMemcpyKind) { std::memcpy(dst, src, n); return cudaSuccess; }
 inline cudaError_t cudaMemcpyAsync(void* dst, const void* src, size_t n, cudaMemcpyKind, cudaStream_t = nullptr) { std::memcpy(dst, src, n); return cudaSuccess; }

@@ -1,0 +1,3 @@
+// thrust/transform_scan.h -- TEST INFRASTRUCTURE (oracle/simt): see simt_algorithms.h
+#pragma once
+#include "simt_algorithms.h"

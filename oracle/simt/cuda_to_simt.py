@@ -1,6 +1,7 @@
 """TEST INFRASTRUCTURE (oracle/simt): two rewrites of a reference source, nothing else is touched.
-1. The CUDA kernel-launch syntax, so that g++ can parse it:
-    kernel<T...> <<<grid, block, shmem, stream>>>(args);   ->   simt::launch(grid, block, [&]() { kernel<T...>(args); });
+1. The CUDA kernel-launch syntax and the declaration of dynamic shared memory, so that g++ can parse them:
+    kernel<T...> <<<grid, block, shmem, stream>>>(args);   ->   simt::launch_shared(grid, block, shmem, [&]() { kernel<T...>(args); });
+    extern __shared__ T name[];                            ->   T* name = simt::dynamic_shared<T>();
 2. With --converge (every one-lane section of the file: the cudapoa sources) or --converge-lines=<file>:<lines> (the named sections:
    hirschberg_myers_gpu.cu, whose other one-lane sections sit inside divergent code, where a full-warp meeting point would be
    wrong). Reconvergence points around one-lane sections:
@@ -54,6 +55,11 @@ def rewrite(text):
         m = text.find("<<<", pos)
         if m < 0:
             break
+        if "//" in text[text.rfind("\n", 0, m) + 1:m]:  # a comment's arrows (overlapper_triggered.cu: `// <<<<<<<<<<`)
+            end_of_line = text.find("\n", m)
+            out.append(text[pos:end_of_line])
+            pos = end_of_line
+            continue
         close = text.index(">>>", m)
         cfg = text[m + 3:close]
         paren = text.index("(", close)
@@ -63,12 +69,17 @@ def rewrite(text):
         callee = text[start:m].rstrip()
         parts = [p.strip() for p in re.split(r",(?![^()]*\))", cfg)]
         out.append(text[pos:start])
-        out.append("simt::launch(%s, %s, [&]() { %s%s; })" % (parts[0], parts[1], callee, text[paren:end + 1]))
+        if len(parts) >= 3:  # the dynamic shared memory of the launch
+            out.append("simt::launch_shared(%s, %s, %s, [&]() { %s%s; })" % (parts[0], parts[1], parts[2], callee, text[paren:end + 1]))
+        else:
+            out.append("simt::launch(%s, %s, [&]() { %s%s; })" % (parts[0], parts[1], callee, text[paren:end + 1]))
         pos = end + 1
     out.append(text[pos:])
-    return "".join(out)
+    return EXTERN_SHARED.sub(r"\1* \2 = simt::dynamic_shared<\1>();", "".join(out))
 
 
+# `extern __shared__ T name[];` -> `T* name = simt::dynamic_shared<T>();` (the block's buffer of the launch's third argument)
+EXTERN_SHARED = re.compile(r"\bextern\s+__shared__\s+([\w:]+)\s+(\w+)\s*\[\s*\]\s*;")
 ONE_LANE = re.compile(r"\bif\s*\(\s*(lane_idx|threadIdx\.x)\s*==\s*0\s*\)")
 
 

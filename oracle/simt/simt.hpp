@@ -3,7 +3,7 @@
 // threads of a block are fibers (ucontext) that the scheduler runs round robin on one OS thread; a warp is 32 consecutive
 // fibers; the warp-level primitives (__shfl_sync, __shfl_up_sync, __shfl_down_sync, __any_sync, __all_sync, __ballot_sync,
 // __syncwarp) and __syncthreads are rendezvous points among the fibers that have not left the kernel. A kernel launch
-// (`k<<<grid, block, shmem, stream>>>(args)`, rewritten by oracle/simt/cuda_to_simt.py into simt::launch(grid, block, [&] { k(args); }))
+// (`k<<<grid, block, shmem, stream>>>(args)`, rewritten by oracle/simt/cuda_to_simt.py into simt::launch_shared(grid, block, shmem, [&] { k(args); }))
 // runs its blocks one after the other and returns when the last thread has finished: every launch is synchronous.
 // Nothing of the product links or includes this: it exists so that tests can compare oracle/poa_oracle.c (and through it the
 // HIP kernels) with the reference's own kernels on arbitrary inputs.
@@ -19,6 +19,7 @@
 #include <cstring>
 #include <functional>
 #include <map>
+#include <memory>
 #include <type_traits>
 #include <vector>
 
@@ -63,7 +64,7 @@ constexpr size_t kStackBytes = size_t(1) << 20;
 struct Fiber
 {
     ucontext_t ctx;
-    std::vector<char> stack;
+    char* stack = nullptr; // one of stack_pool()'s
     bool done = false;
     unsigned tid = 0;
 };
@@ -87,6 +88,24 @@ struct Block
     uint64_t progress = 0; // (deadlock detection: rounds completed + fibers finished)
 };
 inline Block* g_block = nullptr;
+
+// the fibers' stacks are kept from block to block (a kernel of 350 blocks x 256 threads would otherwise zero 90 GB of fresh stacks)
+inline char* pooled_stack(size_t i)
+{
+    static std::vector<std::unique_ptr<char[]>> pool;
+    while (pool.size() <= i) pool.emplace_back(new char[kStackBytes]());
+    return pool[i].get();
+}
+
+// dynamic shared memory (`extern __shared__ T name[];`, rewritten by cuda_to_simt.py into `T* name = simt::dynamic_shared<T>();`): one
+// buffer of the launch's third argument per block, filled like fresh device memory (zero, or the byte of SIMT_MALLOC_FILL)
+inline std::vector<unsigned char> g_dynamic_shared;
+inline size_t g_dynamic_shared_bytes = 0;
+template <typename T>
+inline T* dynamic_shared()
+{
+    return reinterpret_cast<T*>(g_dynamic_shared.data());
+}
 
 inline void yield()
 {
@@ -178,14 +197,18 @@ inline void run_block(unsigned threads, const std::function<void()>& body)
     b.slot.assign(threads, 0);
     b.body  = &body;
     g_block = &b;
+    {
+        static const int fill = [] { const char* e = std::getenv("SIMT_MALLOC_FILL"); return e ? std::atoi(e) : 0; }();
+        g_dynamic_shared.assign(g_dynamic_shared_bytes + 16, static_cast<unsigned char>(fill)); // (+16: never a null pointer)
+    }
     for (unsigned t = 0; t < threads; ++t)
     {
         Fiber& f = b.fibers[t];
         f.tid    = t;
-        f.stack.resize(kStackBytes);
+        f.stack  = pooled_stack(t);
         getcontext(&f.ctx);
-        f.ctx.uc_stack.ss_sp   = f.stack.data();
-        f.ctx.uc_stack.ss_size = f.stack.size();
+        f.ctx.uc_stack.ss_sp   = f.stack;
+        f.ctx.uc_stack.ss_size = kStackBytes;
         f.ctx.uc_link          = &b.scheduler;
         makecontext(&f.ctx, reinterpret_cast<void (*)()>(+[]() {
                         Block& blk = *g_block;
@@ -237,9 +260,10 @@ inline void run_block(unsigned threads, const std::function<void()>& body)
 
 /// k<<<grid, block, shared memory, stream>>>(args): blocks one after the other, synchronous
 template <typename Body>
-inline void launch(dim3 grid, dim3 block, Body body)
+inline void launch(dim3 grid, dim3 block, Body body, size_t shared_bytes = 0)
 {
     const std::function<void()> fn = body;
+    g_dynamic_shared_bytes         = shared_bytes;
     gridDim  = grid;
     blockDim = block;
     static const bool trace = std::getenv("SIMT_TRACE") != nullptr;
@@ -252,15 +276,11 @@ inline void launch(dim3 grid, dim3 block, Body body)
                 run_block(block.x * block.y * block.z, fn);
             }
 }
-template <typename Body, typename A>
-inline void launch(dim3 grid, dim3 block, A, Body body)
+/// the same with the launch's third argument: every block gets that many bytes of dynamic shared memory
+template <typename Body>
+inline void launch_shared(dim3 grid, dim3 block, size_t shared_bytes, Body body)
 {
-    launch(grid, block, body);
-}
-template <typename Body, typename A, typename B>
-inline void launch(dim3 grid, dim3 block, A, B, Body body)
-{
-    launch(grid, block, body);
+    launch(grid, block, body, shared_bytes);
 }
 } // namespace simt
 

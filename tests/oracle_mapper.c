@@ -43,9 +43,13 @@ static uint64_t place(uint32_t code, uint32_t shift)
 static const uint8_t kComplement[8] = {0, 4, 0, 7, 1, 0, 0, 3};
 
 /* Sketch: capacity of the outputs is sum over kept reads of (len - k + w). Returns the number of elements, in read
- * and position order. A read shorter than k + w - 1 is skipped and the reads after it take its id. */
+ * and position order. A read shorter than k + w - 1 is skipped and the reads after it take its id. Needs k + w <= 513.
+ * direction_mode 0: dir_out is the strand of the minimizer (0 forward, 1 reverse) -- what the GPU path gives;
+ * 1: the byte the reference gives, which for some elements of reads of more than one central step is a byte of a window
+ * position (see below); 2: 1 for exactly those elements, else 0. */
 int64_t om_sketch(const char* bases, const int64_t* offsets, int32_t n_reads, uint32_t first_read_id, int32_t k,
-                  int32_t w, int32_t hash, uint64_t* rep_out, uint32_t* rid_out, uint32_t* pos_out, uint8_t* dir_out)
+                  int32_t w, int32_t hash, int32_t direction_mode, uint64_t* rep_out, uint32_t* rid_out,
+                  uint32_t* pos_out, uint8_t* dir_out)
 {
     int64_t n       = 0;
     uint32_t rank   = 0;
@@ -55,6 +59,7 @@ int64_t om_sketch(const char* bases, const int64_t* offsets, int32_t n_reads, ui
             longest = offsets[r + 1] - offsets[r];
     uint64_t* rep = (uint64_t*)malloc(sizeof(uint64_t) * (size_t)(longest + 1));
     uint8_t* dir  = (uint8_t*)malloc((size_t)(longest + 1));
+    int64_t* at_of = (int64_t*)malloc(sizeof(int64_t) * (size_t)(longest + w + 1));
     for (int32_t r = 0; r < n_reads; ++r)
     {
         const unsigned char* s = (const unsigned char*)bases + offsets[r];
@@ -80,9 +85,9 @@ int64_t om_sketch(const char* bases, const int64_t* offsets, int32_t n_reads, ui
             rep[p] = f <= rv ? f : rv;
             dir[p] = f <= rv ? 0 : 1;
         }
-        /* window j covers k-mers [max(0, j-w+1), min(nk-1, j)]; the last smallest wins; emit on a new position */
-        int64_t last = -1;
-        for (int64_t j = 0; j < nk + w - 1; ++j)
+        /* window j covers k-mers [max(0, j-w+1), min(nk-1, j)]; the last smallest wins */
+        const int64_t nw = nk + w - 1, wir = nk - w + 1; /* all windows; the central ones are j in [w-1, w-1+wir) */
+        for (int64_t j = 0; j < nw; ++j)
         {
             const int64_t lo = j - w + 1 > 0 ? j - w + 1 : 0;
             const int64_t hi = j < nk - 1 ? j : nk - 1;
@@ -90,20 +95,61 @@ int64_t om_sketch(const char* bases, const int64_t* offsets, int32_t n_reads, ui
             for (int64_t i = lo + 1; i <= hi; ++i)
                 if (rep[i] <= rep[at])
                     at = i;
-            if (at != last)
+            at_of[j] = at;
+        }
+        /* A window emits its minimizer when it sits elsewhere than its left neighbour's. The reference walks the central
+         * windows in steps of s = 514 - k - w (64 threads x 8 bases) and hands the last window's position from step to step
+         * through a carry that the thread `s % 64 - 1` stores: when s is a multiple of 64 (k + w = 2 mod 64) no thread does, the
+         * carry keeps its first value -- the position of the last front-end element, 0 when w == 1 -- and the first window of
+         * every later step is compared with that. The first back-end window is compared with the last element written. */
+        const int64_t step = (int64_t)(uint16_t)((uint16_t)(512 - (k - 1)) - (w - 1));
+        int64_t carry = 0, written = -1;
+        for (int64_t j = 0; j < nw; ++j)
+        {
+            const int64_t c  = j - (w - 1); /* central window number */
+            const int64_t at = at_of[j];
+            int central      = c >= 0 && c < wir;
+            int64_t left;
+            if (j == 0)
+                left = -1;
+            else if (central && c % step == 0)
+                left = c == 0 ? written : carry;
+            else if (c == wir)
+                left = written;
+            else
+                left = at_of[j - 1];
+            if (c == 0)
+                carry = written < 0 ? 0 : written;
+            if (at != left)
             {
+                uint8_t d = dir[at];
+                /* the directions of a central step live in an array of `step` bytes, rounded up to 8, that the reference indexes
+                 * by k-mer, up to step + w - 2: the bytes behind it are those of the step's window positions (uint32, little
+                 * endian), written after the directions and before they are read */
+                const int64_t room = (step + 7) / 8 * 8;
+                const int aliased  = central && at - c / step * step >= room;
+                if (aliased && direction_mode == 1)
+                {
+                    const int64_t b = at - c / step * step - room;
+                    d               = (uint8_t)((uint32_t)at_of[w - 1 + c / step * step + b / 4] >> (8 * (b % 4)));
+                }
+                if (direction_mode == 2)
+                    d = (uint8_t)aliased;
                 rep_out[n] = rep[at];
                 rid_out[n] = first_read_id + rank;
                 pos_out[n] = (uint32_t)at;
-                dir_out[n] = dir[at];
+                dir_out[n] = d;
                 ++n;
-                last = at;
+                written = at;
             }
+            if (central && c % step == step - 1 && c + 1 < wir && step % 64 != 0)
+                carry = at;
         }
         ++rank;
     }
     free(rep);
     free(dir);
+    free(at_of);
     return n;
 }
 

@@ -41,7 +41,7 @@ def lib():
             os.replace(tmp, path)
         L = C.CDLL(path)
         L.om_sketch.restype = i64
-        L.om_sketch.argtypes = [vp, vp, i32, C.c_uint32, i32, i32, i32, vp, vp, vp, vp]
+        L.om_sketch.argtypes = [vp, vp, i32, C.c_uint32, i32, i32, i32, i32, vp, vp, vp, vp]
         L.om_index.restype = None
         L.om_index.argtypes = [i64, vp, vp, vp, vp, C.c_double, vp, vp, C.POINTER(i64), C.POINTER(i64)]
         L.om_count_anchors.restype = i64
@@ -66,20 +66,27 @@ def pack_reads(reads):
     return np.frombuffer(b"".join(bs) or b"\0", np.uint8).copy(), offsets
 
 
-def sketch(reads, k, w, hash_representations=True, first_read_id=0):
-    """Minimizers in read / position order: dict of representations, read_ids, positions_in_reads, directions."""
+TRUE_DIRECTIONS, REFERENCE_DIRECTIONS, ALIASED_DIRECTIONS = 0, 1, 2
+
+
+def sketch(reads, k, w, hash_representations=True, first_read_id=0, direction_mode=TRUE_DIRECTIONS):
+    """Minimizers in read / position order: dict of representations, read_ids, positions_in_reads, directions.
+    direction_mode: TRUE_DIRECTIONS (0 forward, 1 reverse: what the GPU path gives), REFERENCE_DIRECTIONS (the bytes
+    the reference gives: a byte of a window position where its direction array is overrun, oracle_mapper.c), or
+    ALIASED_DIRECTIONS (1 for exactly those elements)."""
     bases, offsets = pack_reads(reads)
     cap = int(sum(max(0, int(offsets[i + 1] - offsets[i]) - k + w) for i in range(len(reads)))) + 1
     rep, rid, pos, d = np.zeros(cap, np.uint64), np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint8)
     n = lib().om_sketch(_p(bases), _p(offsets), len(reads), first_read_id, k, w, int(bool(hash_representations)),
-                        _p(rep), _p(rid), _p(pos), _p(d))
+                        direction_mode, _p(rep), _p(rid), _p(pos), _p(d))
     return dict(representations=rep[:n], read_ids=rid[:n], positions_in_reads=pos[:n], directions=d[:n])
 
 
-def index(reads, k, w, hash_representations=True, filtering_parameter=1.0, first_read_id=0):
+def index(reads, k, w, hash_representations=True, filtering_parameter=1.0, first_read_id=0,
+          direction_mode=TRUE_DIRECTIONS):
     """The index arrays of the reads, with the reference's names, plus number_of_reads / smallest_read_id /
     largest_read_id / number_of_basepairs_in_longest_read."""
-    s = sketch(reads, k, w, hash_representations, first_read_id)
+    s = sketch(reads, k, w, hash_representations, first_read_id, direction_mode)
     n = len(s["representations"])
     rep, rid = s["representations"].copy(), s["read_ids"].copy()
     pos, d = s["positions_in_reads"].copy(), s["directions"].copy()
