@@ -32,7 +32,7 @@ EXTENDER_HOST_SRCS = ["extender/extender.cpp"]
 # cudamapper likewise
 MAPPER_KERNEL_SRCS = ["mapper/gwm_mapper.hip", "mapper/gwm_postprocess.hip", "mapper/gwm_align.hip",
                       "mapper/gwm_index_cache.hip"]
-MAPPER_HOST_SRCS = ["mapper/mapper.cpp"]
+MAPPER_HOST_SRCS = ["mapper/mapper.cpp", "mapper/gwm_driver.cpp", "mapper/gwm_index_batcher.cpp"]
 
 # no fast-math, no FMA contraction: band placement is IEEE fp32
 KERNEL_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=off",
@@ -108,29 +108,40 @@ def _local_includes(src):
     return sorted(seen)
 
 
-def build_kernels(force=False):
+INCLUDE = ["-I", os.path.join(ROOT, "include")]
+HIPCC_OBJECT = [HIPCC] + KERNEL_FLAGS + INCLUDE
+GXX_OBJECT = ["g++"] + HOST_FLAGS + INCLUDE + ["-I", os.path.join(ROCM, "include")]
+
+
+def _build_library(name, jobs, link_args, force):
+    """lib/<name> from `jobs`, a list of (compiler command without source and output, source, signature): every source
+    is compiled to lib/<its name>.o, in parallel, when its stamped signature is not the job's (or on `force`), and the
+    objects are linked when one was compiled or their signatures are not the ones the library was linked from."""
     os.makedirs(LIB, exist_ok=True)
-    target = os.path.join(LIB, "libgwhip.so")
-    srcs = [os.path.join(PKG, s) for s in KERNEL_SRCS if os.path.exists(os.path.join(PKG, s))]
-    objs, procs, sigs = [], [], []
-    for s in srcs:
-        o = os.path.join(LIB, os.path.basename(s) + ".o")
+    target = os.path.join(LIB, name)
+    objs, procs = [], []
+    for compiler, src, sig in jobs:
+        o = os.path.join(LIB, os.path.basename(src) + ".o")
         objs.append(o)
-        sig = _digest([s] + _local_includes(s), KERNEL_FLAGS)
-        sigs.append(sig)
         if force or _stale(o, sig):
-            cmd = [HIPCC] + KERNEL_FLAGS + ["-I", os.path.join(ROOT, "include"), "-c", s, "-o", o]
+            cmd = compiler + ["-c", src, "-o", o]
             print("[build]", " ".join(cmd), flush=True)
             procs.append((subprocess.Popen(cmd), o, sig))
     for p, o, sig in procs:
         if p.wait() != 0:
-            raise RuntimeError("hipcc failed")
+            raise RuntimeError("building %s failed" % name)
         _mark(o, sig)
-    link_sig = _digest([], sigs)
+    link_sig = _digest([], [sig for compiler, src, sig in jobs])
     if force or procs or _stale(target, link_sig):
-        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", target] + objs)
+        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", target] + objs + link_args)
         _mark(target, link_sig)
-    return target
+    return target, link_sig
+
+
+def build_kernels(force=False):
+    srcs = [os.path.join(PKG, s) for s in KERNEL_SRCS if os.path.exists(os.path.join(PKG, s))]
+    return _build_library("libgwhip.so", [(HIPCC_OBJECT, s, _digest([s] + _local_includes(s), KERNEL_FLAGS))
+                                          for s in srcs], [], force)[0]
 
 
 def build_host(force=False):
@@ -151,114 +162,52 @@ def build_host(force=False):
 def build_extender(force=False):
     """libcudaextender.so: the extension kernel + rocPRIM compaction / sort (hipcc, gfx950) and the Extender host
     classes (g++), linked against libgenomeworks_amd.so for the allocator and logging."""
-    os.makedirs(LIB, exist_ok=True)
-    target = os.path.join(LIB, "libcudaextender.so")
-    inc = ["-I", os.path.join(ROOT, "include")]
-    objs, procs, sigs = [], [], []
-    for s in EXTENDER_KERNEL_SRCS:
-        src = os.path.join(PKG, s)
-        o = os.path.join(LIB, os.path.basename(s) + ".o")
-        sig = _digest([src, os.path.join(ROOT, "include", "gwhip_extender.h")], KERNEL_FLAGS)
-        objs.append(o)
-        sigs.append(sig)
-        if force or _stale(o, sig):
-            cmd = [HIPCC] + KERNEL_FLAGS + inc + ["-c", src, "-o", o]
-            print("[build]", " ".join(cmd), flush=True)
-            procs.append((subprocess.Popen(cmd), o, sig))
+    header = os.path.join(ROOT, "include", "gwhip_extender.h")
     host_sig = _digest(_deps("extender", (".cpp", ".h", ".hpp")), HOST_FLAGS)
-    for s in EXTENDER_HOST_SRCS:
-        src = os.path.join(PKG, s)
-        o = os.path.join(LIB, os.path.basename(s) + ".o")
-        objs.append(o)
-        sigs.append(host_sig)
-        if force or _stale(o, host_sig):
-            cmd = ["g++"] + HOST_FLAGS + inc + ["-I", os.path.join(ROCM, "include"), "-c", src, "-o", o]
-            print("[build]", " ".join(cmd), flush=True)
-            procs.append((subprocess.Popen(cmd), o, host_sig))
-    for p, o, sig in procs:
-        if p.wait() != 0:
-            raise RuntimeError("building libcudaextender.so failed")
-        _mark(o, sig)
-    link_sig = _digest([], sigs)
-    if force or procs or _stale(target, link_sig):
-        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", target] + objs +
-             ["-L", LIB, "-lgenomeworks_amd", "-Wl,-rpath,$ORIGIN"])
-        _mark(target, link_sig)
-    return target
+    jobs = [(HIPCC_OBJECT, src, _digest([src, header], KERNEL_FLAGS))
+            for src in (os.path.join(PKG, s) for s in EXTENDER_KERNEL_SRCS)]
+    jobs += [(GXX_OBJECT, os.path.join(PKG, s), host_sig) for s in EXTENDER_HOST_SRCS]
+    return _build_library("libcudaextender.so", jobs, ["-L", LIB, "-lgenomeworks_amd", "-Wl,-rpath,$ORIGIN"], force)[0]
 
 
 def build_mapper(force=False):
     """libcudamapper.so: the sketch / index / matcher / overlapper / post-processing / overlap alignment kernels with
     their rocPRIM scans, selects and sorts (hipcc, gfx950), linked against libgwhip.so for the aligner, and the Index /
-    Matcher handles and the batched driver behind the C API (g++);
+    Matcher handles, the index batcher and the batched driver behind the C API (g++);
     then bin/cudamapper, which links it and libgenomeworks_amd.so (built before this)."""
-    os.makedirs(LIB, exist_ok=True)
-    target = os.path.join(LIB, "libcudamapper.so")
-    inc = ["-I", os.path.join(ROOT, "include")]
-    objs, procs, sigs = [], [], []
-    for s in MAPPER_KERNEL_SRCS:
-        src = os.path.join(PKG, s)
-        o = os.path.join(LIB, os.path.basename(s) + ".o")
-        sig = _digest([src, os.path.join(ROOT, "include", "gwhip_mapper.h"), os.path.join(ROOT, "include", "gwhip.h")] +
-                      _local_includes(src), KERNEL_FLAGS)
-        objs.append(o)
-        sigs.append(sig)
-        if force or _stale(o, sig):
-            cmd = [HIPCC] + KERNEL_FLAGS + inc + ["-c", src, "-o", o]
-            print("[build]", " ".join(cmd), flush=True)
-            procs.append((subprocess.Popen(cmd), o, sig))
+    headers = [os.path.join(ROOT, "include", "gwhip_mapper.h"), os.path.join(ROOT, "include", "gwhip.h")]
     host_sig = _digest(_deps("mapper", (".cpp", ".h", ".hpp")), HOST_FLAGS)
-    for s in MAPPER_HOST_SRCS:
-        src = os.path.join(PKG, s)
-        o = os.path.join(LIB, os.path.basename(s) + ".o")
-        objs.append(o)
-        sigs.append(host_sig)
-        if force or _stale(o, host_sig):
-            cmd = ["g++"] + HOST_FLAGS + inc + ["-I", os.path.join(ROCM, "include"), "-c", src, "-o", o]
-            print("[build]", " ".join(cmd), flush=True)
-            procs.append((subprocess.Popen(cmd), o, host_sig))
-    for p, o, sig in procs:
-        if p.wait() != 0:
-            raise RuntimeError("building libcudamapper.so failed")
-        _mark(o, sig)
-    link_sig = _digest([], sigs)
-    if force or procs or _stale(target, link_sig):
-        # gwm_align.hip calls the default aligner of libgwhip.so (built before this)
-        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", target] + objs +
-             ["-L", LIB, "-lgwhip", "-Wl,-rpath,$ORIGIN"])
-        _mark(target, link_sig)
+    jobs = [(HIPCC_OBJECT, src, _digest([src] + headers + _local_includes(src), KERNEL_FLAGS))
+            for src in (os.path.join(PKG, s) for s in MAPPER_KERNEL_SRCS)]
+    jobs += [(GXX_OBJECT, os.path.join(PKG, s), host_sig) for s in MAPPER_HOST_SRCS]
+    # gwm_align.hip calls the default aligner of libgwhip.so (built before this)
+    target, link_sig = _build_library("libcudamapper.so", jobs, ["-L", LIB, "-lgwhip", "-Wl,-rpath,$ORIGIN"], force)
     # the cudamapper tool: a thin main over the C API, the FASTA reader and PAF writer of libgenomeworks_amd.so
-    bindir = os.path.join(PKG, "bin")
-    os.makedirs(bindir, exist_ok=True)
-    tool = os.path.join(bindir, "cudamapper")
-    tool_sig = _digest(_deps("host", (".hpp",)), [host_sig, link_sig])
-    if force or _stale(tool, tool_sig):
-        _run(["g++"] + [f for f in HOST_FLAGS if f != "-fPIC"] + inc + ["-I", os.path.join(ROCM, "include"), "-o", tool,
-                                                                      os.path.join(PKG, "mapper", "cudamapper_main.cpp"),
-                                                                      "-L", LIB, "-lcudamapper", "-lgenomeworks_amd", "-lgwhip",
-                                                                      "-L", os.path.join(ROCM, "lib"), "-lamdhip64",
-                                                                      "-Wl,-rpath,$ORIGIN/../lib",
-                                                                      "-Wl,-rpath," + os.path.join(ROCM, "lib")])
-        _mark(tool, tool_sig)
+    _build_tool("cudamapper", os.path.join(PKG, "mapper", "cudamapper_main.cpp"), ["-lcudamapper"],
+                _digest(_deps("host", (".hpp",)), [host_sig, link_sig]), force)
+    return target
+
+
+def _build_tool(name, src, more_libs, sig, force):
+    """bin/<name> from one main source, linked against `more_libs` of lib/, libgenomeworks_amd.so, libgwhip.so and the
+    HIP runtime, when its stamped signature is not `sig` (or on `force`)."""
+    os.makedirs(os.path.join(PKG, "bin"), exist_ok=True)
+    target = os.path.join(PKG, "bin", name)
+    if force or _stale(target, sig):
+        _run(["g++"] + [f for f in HOST_FLAGS if f != "-fPIC"] + INCLUDE +
+             ["-I", os.path.join(ROCM, "include"), "-o", target, src, "-L", LIB] + more_libs +
+             ["-lgenomeworks_amd", "-lgwhip", "-L", os.path.join(ROCM, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN/../lib",
+              "-Wl,-rpath," + os.path.join(ROCM, "lib")])
+        _mark(target, sig)
     return target
 
 
 def build_cli(force=False):
     """The command-line tools -> genomeworks_amd/bin/: `cudapoa` (reference: cudapoa/src/main.cpp) and
     `align_overlaps` (the alignment stage of cudamapper, cudamapper/src/main.cu:54-187)."""
-    bindir = os.path.join(PKG, "bin")
-    os.makedirs(bindir, exist_ok=True)
     sig = _digest(_deps("host", (".cpp", ".h", ".hpp")), HOST_FLAGS)
-    target = None
     for tool, main_src in (("align_overlaps", "align_overlaps_main.cpp"), ("cudapoa", "cudapoa_main.cpp")):
-        target = os.path.join(bindir, tool)
-        src = os.path.join(PKG, "host", main_src)
-        if force or _stale(target, sig):
-            cmd = ["g++"] + [f for f in HOST_FLAGS if f != "-fPIC"] + ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROCM, "include"),
-                              "-o", target, src, "-L", LIB, "-lgenomeworks_amd", "-lgwhip", "-L", os.path.join(ROCM, "lib"),
-                              "-lamdhip64", "-Wl,-rpath,$ORIGIN/../lib", "-Wl,-rpath," + os.path.join(ROCM, "lib")]
-            _run(cmd)
-            _mark(target, sig)
+        target = _build_tool(tool, os.path.join(PKG, "host", main_src), [], sig, force)
     return target
 
 

@@ -72,9 +72,39 @@ def pack_reads(reads):
     return np.frombuffer(b"".join(bs) or b"\0", np.uint8).copy(), offsets
 
 
-class Index:
+def _read_set_args(query_reads, target_reads):
+    """(bases, offsets, number of reads) of the queries and of the targets as the C API takes them; no target set,
+    which there means the query set, is (None, None, 0)"""
+    qb, qo = pack_reads(query_reads)
+    if target_reads is None:
+        return (_p(qb), _p(qo), len(query_reads)), (None, None, 0)
+    tb, to = pack_reads(target_reads)
+    return (_p(qb), _p(qo), len(query_reads)), (_p(tb), _p(to), len(target_reads))
+
+
+class _Handle:
+    """What Index, IndexHostCopy and Matcher share: self._h, a handle of the C API (self._L), is destroyed once, by the
+    entry point their _destroy names: on close(), at the end of a `with` block or when the object is collected."""
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._L, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class Index(_Handle):
     """Index::create_index_async + wait_to_be_ready over `reads`, whose ids are first_read_id, first_read_id + 1, ...
     (reads shorter than k + w - 1 are skipped and, as in the reference, the reads after them take their ids)."""
+    _destroy = "gw_mapper_index_destroy"
 
     def __init__(self, reads, k=15, w=10, hash_representations=True, filtering_parameter=1.0, first_read_id=0,
                  stream=None):
@@ -136,26 +166,13 @@ class Index:
         tables in one pinned host slab (gwm_index_pack). The index stays as it is."""
         return IndexHostCopy(self, stream)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.gw_mapper_index_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        self.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class IndexHostCopy:
+class IndexHostCopy(_Handle):
     """A packed copy of an Index in pinned host memory (the reference's IndexHostCopy): nbytes is
     8 n + 8 ceil(n / 64) + 12 n_unique plus a constant, against 17 n + 12 n_unique for the arrays themselves, because
     the representation of every element is filled in again on the device. to_device() gives an Index equal to the
     packed one in all arrays and attributes. pack_ms is the device time of packing."""
+    _destroy = "gw_mapper_index_host_copy_destroy"
 
     def __init__(self, index, stream=None):
         self._L = _native.mapper()
@@ -181,25 +198,12 @@ class IndexHostCopy:
         index.restore_ms = ms.value
         return index
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.gw_mapper_index_host_copy_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        self.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class Matcher:
+class Matcher(_Handle):
     """Matcher::create_matcher(query_index, target_index): anchors sorted by (query read, target read, query position,
     target position), kept on the device for find_overlaps; anchors() copies them out. stage_ms holds the device time
     of the match and anchor-sort stages, and of chain/fuse/filter once find_overlaps ran on it."""
+    _destroy = "gw_mapper_matcher_destroy"
 
     def __init__(self, query_index, target_index, stream=None):
         self._L = _native.mapper()
@@ -223,22 +227,11 @@ class Matcher:
             self._anchors = out
         return self._anchors
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.gw_mapper_matcher_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
 
 def find_anchors(query_index, target_index, stream=None):
     """All anchors between two indices, as an ANCHOR array."""
-    m = Matcher(query_index, target_index, stream)
-    try:
+    with Matcher(query_index, target_index, stream) as m:
         return m.anchors()
-    finally:
-        m.close()
 
 
 def find_overlaps(anchors, all_to_all=True, min_residues=3, min_overlap_len=250, min_bases_per_residue=1000,
@@ -267,16 +260,11 @@ def map_reads(queries, targets=None, k=15, w=10, filtering_parameter=1e-5, min_r
     """Overlaps of `queries` against `targets`, or all against all (self-mappings dropped) when targets is None, with
     hashed representations as in the reference's cudamapper. One index per read set: batching into several indices
     (the CLI's -i / -t) is the caller's."""
-    q = Index(queries, k, w, True, filtering_parameter, stream=stream)
-    t = q if targets is None else Index(targets, k, w, True, filtering_parameter, stream=stream)
-    m = Matcher(q, t, stream)
-    try:
+    with Index(queries, k, w, True, filtering_parameter, stream=stream) as q, \
+            (q if targets is None else Index(targets, k, w, True, filtering_parameter, stream=stream)) as t, \
+            Matcher(q, t, stream) as m:
         return find_overlaps(m, targets is None, min_residues, min_overlap_len, min_bases_per_residue,
                              min_overlap_fraction, stream)
-    finally:
-        m.close()
-        q.close()
-        t.close()
 
 
 def post_process_overlaps(overlaps, drop_fused_overlaps=False, stream=None, timings=None):
@@ -304,14 +292,10 @@ def rescue_overlap_ends(overlaps, query_reads, target_reads=None, extension=50, 
     reads. A read id outside its set or an overlap beyond its read raises MapperError."""
     L = _native.mapper()
     o = np.ascontiguousarray(overlaps, OVERLAP).copy()
-    qb, qo = pack_reads(query_reads)
-    tb, to = (None, None) if target_reads is None else pack_reads(target_reads)
+    q, t = _read_set_args(query_reads, target_reads)
     ms = C.c_float(0.0)
-    rc = L.gw_mapper_rescue_overlap_ends(_p(o), len(o), _p(qb), _p(qo), len(query_reads),
-                                         None if tb is None else _p(tb), None if to is None else _p(to),
-                                         0 if target_reads is None else len(target_reads), first_query_read_id,
-                                         first_target_read_id, int(extension), float(required_similarity),
-                                         _stream(stream), C.byref(ms))
+    rc = L.gw_mapper_rescue_overlap_ends(_p(o), len(o), *q, *t, first_query_read_id, first_target_read_id,
+                                         int(extension), float(required_similarity), _stream(stream), C.byref(ms))
     if rc != 0:
         raise _err(L)
     if timings is not None:
@@ -344,11 +328,8 @@ def align_overlaps(overlaps, query_reads, target_reads=None, first_query_read_id
     start > end and an end beyond its read. `timings`, if a dict, receives gather, align and cigar_text (device ms)."""
     L = _native.mapper()
     o = np.ascontiguousarray(overlaps, OVERLAP)
-    qb, qo = pack_reads(query_reads)
-    tb, to = (None, None) if target_reads is None else pack_reads(target_reads)
-    h = L.gw_mapper_align_overlaps(_p(o), len(o), _p(qb), _p(qo), len(query_reads), first_query_read_id,
-                                   None if tb is None else _p(tb), None if to is None else _p(to),
-                                   0 if target_reads is None else len(target_reads), first_target_read_id,
+    q, t = _read_set_args(query_reads, target_reads)
+    h = L.gw_mapper_align_overlaps(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id,
                                    int(max_device_bytes), _stream(stream))
     if not h:
         raise _err(L)
@@ -448,13 +429,11 @@ def map_reads_batched(queries, targets=None, k=15, w=10, filtering_parameter=1e-
     before any device work: the index would skip it and shift the read ids behind it, so the wrong sequences would be
     aligned. (The reference's -a aligns before fusion appends its records; this aligns the records returned.)"""
     L = _native.mapper()
-    qb, qo = pack_reads(queries)
-    tb, to = (None, None) if targets is None else pack_reads(targets)
+    q, t = _read_set_args(queries, targets)
     t_limit = max_basepairs_per_index if max_basepairs_per_target_index is None else max_basepairs_per_target_index
-    args = (_p(qb), _p(qo), len(queries), None if tb is None else _p(tb), None if to is None else _p(to),
-            0 if targets is None else len(targets), k, w, float(filtering_parameter), int(min_residues),
-            int(min_overlap_len), int(min_bases_per_residue), float(min_overlap_fraction), int(max_basepairs_per_index),
-            int(t_limit), int(bool(post_process)), int(bool(drop_fused_overlaps)), int(bool(rescue_overlap_ends)))
+    args = (*q, *t, k, w, float(filtering_parameter), int(min_residues), int(min_overlap_len),
+            int(min_bases_per_residue), float(min_overlap_fraction), int(max_basepairs_per_index), int(t_limit),
+            int(bool(post_process)), int(bool(drop_fused_overlaps)), int(bool(rescue_overlap_ends)))
     C_ = query_indices_in_host_memory if target_indices_in_host_memory is None else target_indices_in_host_memory
     c_ = query_indices_in_device_memory if target_indices_in_device_memory is None else target_indices_in_device_memory
     h = L.gw_mapper_map_batched_cached(*args, int(bool(align)), int(max_device_bytes), int(query_indices_in_host_memory),

@@ -1,20 +1,18 @@
 // gwm_device_utils.hpp -- helpers shared by the cudamapper translation units (gwm_mapper.hip, gwm_postprocess.hip,
-// gwm_align.hip, gwm_index_cache.hip):
-// checked HIP calls, owning device buffers, the rocPRIM scan / select / sort wrappers and HIP-event stage timers.
+// gwm_align.hip, gwm_index_cache.hip): what gwm_host_utils.hpp holds (checked HIP calls, owning device buffers,
+// HIP-event stage timers, the device read set) and, on top of it, the rocPRIM scan / select / sort wrappers.
 // Everything here has internal linkage; the one shared object is the error text behind gwm_last_error().
 #ifndef GWM_DEVICE_UTILS_HPP
 #define GWM_DEVICE_UTILS_HPP
 
-#include <hip/hip_runtime.h>
+#include "gwm_host_utils.hpp"
+
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
 #include <algorithm>
-#include <cstdint>
-#include <stdexcept>
-#include <string>
 
 // sets the text gwm_last_error() returns on the calling thread (defined in gwm_mapper.hip)
 void gwm_set_error(const char* text);
@@ -22,50 +20,9 @@ void gwm_set_error(const char* text);
 namespace
 {
 
-void check(hipError_t e, const char* what)
-{
-    if (e != hipSuccess)
-        throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-#define GWM_CHECK(x) check((x), #x)
-
 constexpr int kThreads = 256;
 
 inline unsigned grid_for(int64_t n) { return static_cast<unsigned>((n + kThreads - 1) / kThreads); }
-
-// Owning device allocation.
-template <typename T>
-struct dbuf
-{
-    T* p       = nullptr;
-    int64_t n  = 0;
-    dbuf()     = default;
-    explicit dbuf(int64_t count) { resize(count); }
-    dbuf(const dbuf&) = delete;
-    dbuf& operator=(const dbuf&) = delete;
-    ~dbuf() { reset(); }
-    void resize(int64_t count)
-    {
-        reset();
-        n = count;
-        if (count > 0)
-            GWM_CHECK(hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * static_cast<size_t>(count)));
-    }
-    void reset()
-    {
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    T* release()
-    {
-        T* r = p;
-        p    = nullptr;
-        n    = 0;
-        return r;
-    }
-};
 
 // Scratch for the rocPRIM calls of one stage, grown on demand.
 struct Temp
@@ -125,40 +82,6 @@ unsigned bits_for(uint64_t max_value)
         ++b;
     return b;
 }
-
-// A read set on the device: bases[offsets[i] .. offsets[i + 1]) is read first_read_id + i.
-struct ReadSet
-{
-    const uint8_t* bases;
-    const int64_t* offsets;
-    uint32_t n_reads;
-    uint32_t first_read_id;
-};
-
-struct Events
-{
-    hipEvent_t e[6] = {};
-    int n           = 0;
-    explicit Events(int count)
-        : n(count)
-    {
-        for (int i = 0; i < n; ++i)
-            GWM_CHECK(hipEventCreate(&e[i]));
-    }
-    ~Events()
-    {
-        for (int i = 0; i < n; ++i)
-            (void)hipEventDestroy(e[i]);
-    }
-    void record(int i, hipStream_t s) { GWM_CHECK(hipEventRecord(e[i], s)); }
-    float ms(int a, int b)
-    {
-        float v = 0.f;
-        GWM_CHECK(hipEventSynchronize(e[b]));
-        GWM_CHECK(hipEventElapsedTime(&v, e[a], e[b]));
-        return v;
-    }
-};
 
 } // namespace
 

@@ -12,10 +12,16 @@ Acceptance (written into the record as booleans, and the exit status): the cache
 by more than the larger of the two spreads; this tree at 1, 1, 1, 1 is not slower than the baseline beyond that spread;
 the overlaps agree; every restore is faster than its build.
 
+With --like-for-like the baseline library has the cached driver too and the question is whether this tree's driver
+costs what the baseline's does: both are called through gw_mapper_map_batched_cached, at 1, 1, 1, 1 and at 10, 5, 10, 5,
+the four runs alternating. Accepted when at each setting this tree's median is not above the baseline's by more than
+the larger of the two spreads, the overlaps are equal and the builds / restores are equal. The per-index table is
+left out of that record.
+
 Not measured: other k / w settings, host memory pressure at large -Q, more than one device.
 
     python tools/bench_mapper_cache.py --baseline-lib path/to/parent/libcudamapper.so [--index-mbp 15] [--repeats 5]
-                                       [--out profiles/mapper_cache.json]
+                                       [--like-for-like] [--out profiles/mapper_cache.json]
 """
 import argparse
 import ctypes as C
@@ -49,6 +55,10 @@ def load_baseline(path):
     L.gw_mapper_last_error.restype = C.c_char_p
     L.gw_mapper_map_batched.restype = vp
     L.gw_mapper_map_batched.argtypes = MAP_ARGS + [vp]
+    if hasattr(L, "gw_mapper_map_batched_cached"):  # a baseline from before the index cache has neither
+        L.gw_mapper_map_batched_cached.restype = vp
+        L.gw_mapper_map_batched_cached.argtypes = MAP_ARGS + [i32, i64, i32, i32, i32, i32, vp]
+        L.gw_mapper_overlaps_cache_counts.argtypes = [vp, vp, vp, vp]
     L.gw_mapper_overlaps_count.restype = i64
     L.gw_mapper_overlaps_count.argtypes = [vp]
     L.gw_mapper_overlaps_copy.argtypes = [vp, vp, i64, vp, vp]
@@ -145,6 +155,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--genome-mbp", type=float, default=5.0)
     ap.add_argument("--coverage", type=float, default=30.0)
+    ap.add_argument("--like-for-like", action="store_true",
+                    help="call the baseline through gw_mapper_map_batched_cached at the same counts as this tree")
     ap.add_argument("--out")
     args = ap.parse_args()
     if args.repeats < 5:
@@ -163,6 +175,9 @@ def main():
     bases, offsets = cudamapper.pack_reads(reads)
     runner = Runner(hip, bases, offsets, len(reads), index_bases)
     runs = (("baseline", baseline, None), ("cached", tree, CACHED), ("one_pair_at_a_time", tree, (1, 1, 1, 1)))
+    if args.like_for_like:
+        runs = (("baseline_one_pair_at_a_time", baseline, (1, 1, 1, 1)), ("one_pair_at_a_time", tree, (1, 1, 1, 1)),
+                ("baseline_cached", baseline, CACHED), ("cached", tree, CACHED))
 
     results, infos, walls = {}, {}, {name: [] for name, L, counts in runs}
     for name, L, counts in runs:  # warm-up: code objects, pinned and device allocations
@@ -175,11 +190,15 @@ def main():
     record = {"metric": "cudamapper batched driver, all-vs-all, wall seconds per run", "device": "gpu0", "k": K, "w": W,
               "F": F, "genome_mbp": args.genome_mbp, "coverage": args.coverage, "reads": len(reads),
               "bases": int(offsets[-1]), "index_mbp": args.index_mbp, "indices": len(groups),
-              "repeats": args.repeats, "generation_s": round(generation, 1), "cached_setting": list(CACHED)}
+              "repeats": args.repeats, "generation_s": round(generation, 1), "cached_setting": list(CACHED),
+              "like_for_like": args.like_for_like}
     for name, L, counts in runs:
         w = walls[name]
         record[name] = dict(infos[name], wall_s=[round(x, 4) for x in w], median_s=round(statistics.median(w), 4),
                             spread_s=round(max(w) - min(w), 4), overlaps=len(results[name]))
+    if args.like_for_like:
+        return finish(record, like_for_like_checks(record, results), ["the --cigar path (covered by the tests only)"],
+                      args.out)
     spread = max(record["baseline"]["spread_s"], record["cached"]["spread_s"])
     spread_ones = max(record["baseline"]["spread_s"], record["one_pair_at_a_time"]["spread_s"])
     rows = per_index(baseline, reads, groups)
@@ -197,12 +216,28 @@ def main():
         "every_round_trip_equal": all(r["round_trip_equal"] for r in rows),
     }
     record["speedup_cached_over_baseline"] = round(record["baseline"]["median_s"] / record["cached"]["median_s"], 3)
+    return finish(record, checks, [], args.out)
+
+
+def like_for_like_checks(record, results):
+    checks = {}
+    for name in ("one_pair_at_a_time", "cached"):
+        tree, base = record[name], record["baseline_" + name]
+        checks[name + "_not_slower_beyond_spread"] = \
+            tree["median_s"] - base["median_s"] <= max(tree["spread_s"], base["spread_s"])
+        checks[name + "_overlaps_equal"] = bool(np.array_equal(results[name], results["baseline_" + name]))
+        checks[name + "_builds_and_restores_equal"] = all(tree[k] == base[k] for k in ("index_builds", "index_restores"))
+    return checks
+
+
+def finish(record, checks, also_not_measured, out):
     record["checks"] = checks
-    record["not_measured"] = ["other k / w settings", "host memory pressure at large -Q", "more than one device"]
+    record["not_measured"] = ["other k / w settings", "host memory pressure at large -Q",
+                              "more than one device"] + also_not_measured
     line = json.dumps(record)
     print(line)
-    if args.out:
-        with open(args.out, "w") as f:
+    if out:
+        with open(out, "w") as f:
             f.write(line + "\n")
     return 0 if all(checks.values()) else 1
 
