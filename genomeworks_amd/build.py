@@ -1,6 +1,8 @@
 """In-tree build of the native libraries (hipcc for gfx950, no GPU needed).
 
   genomeworks_amd/lib/libgwhip.so            hand-written HIP kernels + the thin C-ABI (include/gwhip.h)
+  genomeworks_amd/lib/libgwsemiglobal.so     cudaaligner's infix / prefix types: the ends scan and the slice gather
+                                             (include/gwhip_semiglobal.h), linked against libgwhip.so
   genomeworks_amd/lib/libgenomeworks_amd.so  host C++ (Batch / Aligner, allocator, C API include/gw_capi.h)
   genomeworks_amd/lib/libcudaextender.so     cudaextender: HIP kernels (include/gwhip_extender.h) + Extender
                                              (cudaextender/extender.hpp, C API include/gw_extender_capi.h)
@@ -24,11 +26,13 @@ HIPCC = os.path.join(ROCM, "bin", "hipcc")
 KERNEL_SRCS = ["csrc/gwhip_poa.hip", "csrc/gwhip_poa_part0.hip", "csrc/gwhip_poa_part1.hip", "csrc/gwhip_poa_part2.hip",
                "csrc/gwhip_poa_part3.hip", "csrc/gwhip_poa_part4.hip", "csrc/gwhip_poa_part5.hip", "csrc/gwhip_poa_part6.hip", "csrc/gwhip_poa_part7.hip", "csrc/gwhip_poa_hooks.hip", "csrc/gwhip_myers.hip", "csrc/gwhip_ukkonen.hip"]
 HOST_SRCS = ["host/capi.cpp", "host/cudapoa_batch.cpp", "host/cudapoa_utils.cpp", "host/cudaaligner.cpp", "host/aligner_global.cpp", "host/device_pool.cpp",
-             "host/alignment_impl.cpp", "host/runtime.cpp", "host/logging.cpp", "host/overlap_alignment.cpp", "host/multi_device.cpp",
+             "host/aligner_semiglobal.cpp", "host/alignment_impl.cpp", "host/runtime.cpp", "host/logging.cpp", "host/overlap_alignment.cpp", "host/multi_device.cpp",
              "host/fasta_parser.cpp"]
 # cudaextender lives apart from csrc/ so that kernel_source_digest() (the stamped POA / aligner kernel set) ignores it
 EXTENDER_KERNEL_SRCS = ["extender/gwx_ungapped_xdrop.hip"]
 EXTENDER_HOST_SRCS = ["extender/extender.cpp"]
+# the infix / prefix alignment types of cudaaligner likewise (the host class is in host/)
+SEMIGLOBAL_KERNEL_SRCS = ["semiglobal/gws_ends.hip"]
 # cudamapper likewise
 MAPPER_KERNEL_SRCS = ["mapper/gwm_mapper.hip", "mapper/gwm_postprocess.hip", "mapper/gwm_align.hip",
                       "mapper/gwm_index_cache.hip"]
@@ -148,15 +152,30 @@ def build_host(force=False):
     os.makedirs(LIB, exist_ok=True)
     target = os.path.join(LIB, "libgenomeworks_amd.so")
     srcs = [os.path.join(PKG, s) for s in HOST_SRCS if os.path.exists(os.path.join(PKG, s))]
-    sig = _digest(_deps("host", (".cpp", ".h", ".hpp")), HOST_FLAGS)
+    # the host library links libgwhip.so and libgwsemiglobal.so. Called alone in a fresh tree, this builds the first;
+    # the second is brought up to date every time (one small translation unit, incremental), and a relink follows it
+    if not os.path.exists(os.path.join(LIB, "libgwhip.so")):
+        build_kernels()
+    with open(build_semiglobal() + ".stamp") as f:
+        semiglobal_sig = f.read().strip()
+    sig = _digest(_deps("host", (".cpp", ".h", ".hpp")), [HOST_FLAGS, semiglobal_sig])
     if force or _stale(target, sig):
         cmd = ["g++"] + HOST_FLAGS + ["-shared", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROCM, "include"),
                                      "-o", target] + srcs + [
-            "-L", LIB, "-lgwhip", "-L", os.path.join(ROCM, "lib"), "-lamdhip64",
+            "-L", LIB, "-lgwsemiglobal", "-lgwhip", "-L", os.path.join(ROCM, "lib"), "-lamdhip64",
             "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(ROCM, "lib")]
         _run(cmd)
         _mark(target, sig)
     return target
+
+
+def build_semiglobal(force=False):
+    """libgwsemiglobal.so: the ends scan and the slice gather of the infix / prefix alignment types (hipcc, gfx950),
+    linked against libgwhip.so, whose default aligner takes the gathered slices (built before this)."""
+    header = os.path.join(ROOT, "include", "gwhip_semiglobal.h")
+    jobs = [(HIPCC_OBJECT, src, _digest([src, header], KERNEL_FLAGS))
+            for src in (os.path.join(PKG, s) for s in SEMIGLOBAL_KERNEL_SRCS)]
+    return _build_library("libgwsemiglobal.so", jobs, ["-L", LIB, "-lgwhip", "-Wl,-rpath,$ORIGIN"], force)[0]
 
 
 def build_extender(force=False):
@@ -196,7 +215,7 @@ def _build_tool(name, src, more_libs, sig, force):
     if force or _stale(target, sig):
         _run(["g++"] + [f for f in HOST_FLAGS if f != "-fPIC"] + INCLUDE +
              ["-I", os.path.join(ROCM, "include"), "-o", target, src, "-L", LIB] + more_libs +
-             ["-lgenomeworks_amd", "-lgwhip", "-L", os.path.join(ROCM, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN/../lib",
+             ["-lgenomeworks_amd", "-lgwsemiglobal", "-lgwhip", "-L", os.path.join(ROCM, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN/../lib",
               "-Wl,-rpath," + os.path.join(ROCM, "lib")])
         _mark(target, sig)
     return target
@@ -239,6 +258,7 @@ def _run_in(cwd, cmd):
 
 def build_all(force=False):
     k = build_kernels(force)
+    build_semiglobal(force)
     h = build_host(force)
     build_extender(force)
     build_mapper(force)

@@ -1,7 +1,9 @@
 """Python mirror of pygenomeworks' genomeworks.cudaaligner (cudaaligner.pyx) over the object-level C API.
 
 CudaAlignerBatch keeps the reference's constructor (the default, fixed-stride factory); `max_bandwidth=` selects the
-banded Myers aligner (create_aligner(global_alignment, max_bandwidth, ...)), which is what the benchmarks use."""
+banded Myers aligner (create_aligner(global_alignment, max_bandwidth, ...)), which is what the benchmarks use.
+`alignment_type="infix"` / `"prefix"` (not in pygenomeworks) place the whole query on the best slice / the best prefix of
+its target: CudaAlignment.target_begin / .target_end name the slice that the states, the CIGARs and the distance describe."""
 import ctypes as C
 
 import numpy as np
@@ -16,6 +18,9 @@ exceeded_max_alignments = 2
 exceeded_max_length = 3
 exceeded_max_alignment_difference = 4
 generic_error = 5
+
+# cudaaligner::AlignmentType (cudaaligner.hpp); the reference has global_alignment and unset only
+_ALIGNMENT_TYPES = {"global": 0, "infix": 2, "prefix": 3}
 
 _STATUS = {0: "success", 1: "uninitialized", 2: "exceeded_max_alignments", 3: "exceeded_max_length",
            4: "exceeded_max_alignment_difference", 5: "generic_error"}
@@ -35,6 +40,10 @@ def _bind(L):
     L.gw_aligner_create_banded.argtypes = [i32, vp, i32, C.c_int64]
     L.gw_aligner_create.restype = vp
     L.gw_aligner_create.argtypes = [i32, i32, i32, vp, i32, C.c_int64]
+    L.gw_aligner_create_typed.restype = vp
+    L.gw_aligner_create_typed.argtypes = [i32, i32, i32, i32, vp, i32, C.c_int64]
+    L.gw_alignment_target_range.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
+    L.gw_aligner_stage_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.gw_aligner_create_algorithm.restype = vp
     L.gw_aligner_create_algorithm.argtypes = [C.c_char_p, i32, i32, i32, vp, i32, C.c_int64]
     L.gw_aligner_destroy.argtypes = [vp]
@@ -60,7 +69,8 @@ def _bind(L):
 class CudaAlignment:
     """One alignment result (pygenomeworks CudaAlignment): query, target, cigar, status, alignment states."""
 
-    def __init__(self, query, target, cigar, cigar_extended, status, is_optimal, edit_distance, states):
+    def __init__(self, query, target, cigar, cigar_extended, status, is_optimal, edit_distance, states,
+                 target_begin=0, target_end=None):
         self.query = query
         self.target = target
         self.cigar = cigar
@@ -69,10 +79,13 @@ class CudaAlignment:
         self.is_optimal = is_optimal
         self.edit_distance = edit_distance
         self.alignment = states
+        # the slice of the target that the alignment covers: all of it unless the batch is "infix" or "prefix"
+        self.target_begin = target_begin
+        self.target_end = len(target) if target_end is None else target_end
 
     def format_alignment(self):
-        """(query line, pairing line, target line) like Alignment::format_alignment."""
-        q, p, t, qi, ti = [], [], [], 0, 0
+        """(query line, pairing line, target line) like Alignment::format_alignment, over target[target_begin:target_end]."""
+        q, p, t, qi, ti = [], [], [], 0, self.target_begin
         for s in self.alignment:
             if s in (0, 1):
                 q.append(self.query[qi]); t.append(self.target[ti]); p.append("|" if s == 0 else "x"); qi += 1; ti += 1
@@ -92,13 +105,20 @@ class CudaAlignerBatch:
         """algorithm (not in pygenomeworks): one of the reference's non-public aligner classes that its C++ tests and
         benchmarks construct directly -- "hirschberg_myers" (the default), "ukkonen", "myers"."""
         self._L = _bind(_native.host())
-        if alignment_type != "global":
-            raise RuntimeError("Unknown alignment_type provided. Must be global.")
+        if alignment_type not in _ALIGNMENT_TYPES:
+            raise RuntimeError("Unknown alignment_type provided. Must be global, infix or prefix.")
+        if alignment_type != "global" and (max_bandwidth is not None or algorithm is not None):
+            raise RuntimeError("alignment_type %r has one aligner: max_bandwidth and algorithm select global aligners" % alignment_type)
+        self.alignment_type = alignment_type
         if stream is not None and not isinstance(stream, CudaStream):
             raise RuntimeError("Type for stream option must be CudaStream")
         self.stream = stream
         st = stream.stream if stream is not None else None
-        if max_bandwidth is not None:
+        if alignment_type != "global":
+            self._h = self._L.gw_aligner_create_typed(_ALIGNMENT_TYPES[alignment_type], int(max_query_length),
+                                                      int(max_target_length), int(max_alignments), st, device_id,
+                                                      int(max_device_memory_allocator_caching_size))
+        elif max_bandwidth is not None:
             self._h = self._L.gw_aligner_create_banded(int(max_bandwidth), st, device_id,
                                                        int(max_device_memory_allocator_caching_size))
         elif algorithm is not None:
@@ -155,6 +175,13 @@ class CudaAlignerBatch:
         if self._L.gw_aligner_device_alignments(self._h, C.byref(n), C.byref(total)) < 0:
             raise RuntimeError(self._L.gw_last_error().decode())
         return n.value, total.value
+
+    def stage_ms(self):
+        """Measurement aid for "infix" / "prefix" batches: (ends scan ms, gather + traceback ms) of the last align_all()."""
+        ends, tb = C.c_float(0), C.c_float(0)
+        if self._L.gw_aligner_stage_ms(self._h, C.byref(ends), C.byref(tb)) != 0:
+            raise RuntimeError(self._L.gw_last_error().decode())
+        return ends.value, tb.value
 
     def band_cells(self):
         v = C.c_uint64(0)
@@ -220,9 +247,12 @@ class CudaAlignerBatch:
             q, t = self._pairs[i] if i < len(self._pairs) else ("", "")
             st, opt, ed = (self._L.gw_alignment_status(self._h, i), self._L.gw_alignment_is_optimal(self._h, i),
                            self._L.gw_alignment_edit_distance(self._h, i))
-            if ns < 0 or st < 0 or opt < 0 or ed < 0:  # the C ABI reports a bad index / a thrown accessor as -1 + error string
+            tb, te, rng = C.c_int32(0), C.c_int32(len(t)), 0
+            if self.alignment_type != "global":  # a global alignment covers its whole target
+                rng = self._L.gw_alignment_target_range(self._h, i, C.byref(tb), C.byref(te))
+            if ns < 0 or st < 0 or opt < 0 or ed < 0 or rng < 0:  # the C ABI reports a bad index / a thrown accessor as -1 + error string
                 raise RuntimeError("alignment %d: %s" % (i, self._L.gw_last_error().decode()))
-            out.append(CudaAlignment(q, t, cigar, cigar_x, st, bool(opt), ed, [int(x) for x in states[:ns]]))
+            out.append(CudaAlignment(q, t, cigar, cigar_x, st, bool(opt), ed, [int(x) for x in states[:ns]], tb.value, te.value))
         return out
 
     def reset(self):

@@ -124,6 +124,9 @@ int32_t AlignmentImpl::get_edit_distance() const
 
 FormattedAlignment AlignmentImpl::format_alignment(int32_t maximal_line_length) const
 {
+    if (target_end_ >= 0) // the slice an infix / prefix alignment covers
+        return format_states(query_, target_.substr(static_cast<size_t>(target_begin_), static_cast<size_t>(target_end_ - target_begin_)), alignment_,
+                             maximal_line_length);
     return format_states(query_, target_, alignment_, maximal_line_length);
 }
 

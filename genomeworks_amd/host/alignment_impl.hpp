@@ -31,7 +31,15 @@ public:
     const std::vector<int32_t>& get_runlengths() const override { return runlength_; }
     int32_t get_edit_distance() const override;
     FormattedAlignment format_alignment(int32_t maximal_line_length = 80) const override;
+    int32_t get_target_begin() const override { return target_begin_; }
+    int32_t get_target_end() const override { return target_end_ < 0 ? static_cast<int32_t>(target_.size()) : target_end_; }
 
+    /// infix / prefix alignments: the slice of the target that the states describe
+    void set_target_range(int32_t begin, int32_t end)
+    {
+        target_begin_ = begin;
+        target_end_   = end;
+    }
     void set_alignment_type(AlignmentType type) { type_ = type; }
     void set_status(StatusType status) { status_ = status; }
     /// per-position form
@@ -62,6 +70,8 @@ private:
     std::vector<int8_t> action_;
     std::vector<int32_t> runlength_;
     bool is_optimal_ = false;
+    int32_t target_begin_ = 0;
+    int32_t target_end_   = -1; ///< -1: the whole target
 };
 
 /// Results of one sync_alignments() of the banded aligner, kept the way they left the device: the sequences of the
@@ -120,6 +130,12 @@ public:
     const std::string& get_target_sequence() const override;
     std::string convert_to_cigar(CigarFormat format = CigarFormat::basic) const override;
     AlignmentType get_alignment_type() const override { return AlignmentType::global_alignment; }
+    /// the target's length from the offsets: no string is materialised for it
+    int32_t get_target_end() const override
+    {
+        const int64_t* st = block_->seq_starts + 2 * static_cast<size_t>(index_);
+        return static_cast<int32_t>(st[2] - st[1]);
+    }
     bool is_optimal() const override { return has_result() && (block_->metadata[index_] >> 31) != 0; }
     StatusType get_status() const override { return has_result() ? StatusType::success : StatusType::uninitialized; }
     const std::vector<AlignmentState>& get_alignment() const override;

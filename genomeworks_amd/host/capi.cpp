@@ -14,6 +14,7 @@
 #include "poa_batch_impl.hpp"
 #include "aligner_impl.hpp"
 #include "aligner_global.hpp"
+#include "aligner_semiglobal.hpp"
 #include "alignment_impl.hpp"
 #include <claraparabricks/genomeworks/cudapoa/multi_device.hpp>
 #include <claraparabricks/genomeworks/utils/cudautils.hpp>
@@ -400,6 +401,22 @@ gw_aligner* gw_aligner_create(int32_t max_query_length, int32_t max_target_lengt
     GW_CATCH(nullptr)
 }
 
+gw_aligner* gw_aligner_create_typed(int32_t alignment_type, int32_t max_query_length, int32_t max_target_length, int32_t max_alignments,
+                                    void* stream, int32_t device_id, int64_t max_device_memory)
+{
+    GW_TRY
+    if (alignment_type != aln::AlignmentType::global_alignment && alignment_type != aln::AlignmentType::infix_alignment &&
+        alignment_type != aln::AlignmentType::prefix_alignment)
+        throw std::invalid_argument("gw_aligner_create_typed: alignment_type " + std::to_string(alignment_type) +
+                                    " is none of global_alignment (0), infix_alignment (2), prefix_alignment (3)");
+    auto h     = std::make_unique<gw_aligner>();
+    h->aligner = aln::create_aligner(max_query_length, max_target_length, max_alignments, static_cast<aln::AlignmentType>(alignment_type),
+                                     static_cast<cudaStream_t>(stream), device_id, max_device_memory);
+    h->impl    = dynamic_cast<aln::BandedAligner*>(h->aligner.get());
+    return h.release();
+    GW_CATCH(nullptr)
+}
+
 gw_aligner* gw_aligner_create_algorithm(const char* algorithm, int32_t max_query_length, int32_t max_target_length,
                                         int32_t max_alignments, void* stream, int32_t device_id, int64_t max_device_memory)
 {
@@ -479,6 +496,36 @@ int32_t gw_alignment_is_optimal(gw_aligner* a, int32_t i)
 {
     GW_TRY
     return a->aligner->get_alignments().at(static_cast<size_t>(i))->is_optimal() ? 1 : 0;
+    GW_CATCH(-1)
+}
+int32_t gw_alignment_type(gw_aligner* a, int32_t i)
+{
+    GW_TRY
+    return static_cast<int32_t>(a->aligner->get_alignments().at(static_cast<size_t>(i))->get_alignment_type());
+    GW_CATCH(-1)
+}
+int gw_alignment_target_range(gw_aligner* a, int32_t i, int32_t* begin, int32_t* end)
+{
+    GW_TRY
+    const auto& al = *a->aligner->get_alignments().at(static_cast<size_t>(i));
+    if (begin) *begin = al.get_target_begin();
+    if (end) *end = al.get_target_end();
+    return 0;
+    GW_CATCH(-1)
+}
+int gw_aligner_stage_ms(gw_aligner* a, float* ends_ms, float* traceback_ms)
+{
+    GW_TRY
+    auto* semiglobal = dynamic_cast<aln::AlignerSemiglobal*>(a->aligner.get());
+    float ends = 0.f, traceback = 0.f;
+    if (semiglobal == nullptr || !semiglobal->last_stage_ms(&ends, &traceback))
+    {
+        gwhost::set_last_error(semiglobal ? "gw_aligner_stage_ms: no align_all() to report" : "gw_aligner_stage_ms: not an infix / prefix aligner");
+        return -1;
+    }
+    if (ends_ms) *ends_ms = ends;
+    if (traceback_ms) *traceback_ms = traceback;
+    return 0;
     GW_CATCH(-1)
 }
 int32_t gw_alignment_edit_distance(gw_aligner* a, int32_t i)
@@ -619,7 +666,11 @@ int gw_aligner_copy_device_alignments(gw_aligner* a, int8_t* cigar_operations, i
 int gw_aligner_relaunch(gw_aligner* a)
 {
     GW_TRY
-    if (!a->impl) return -1;
+    if (!a->impl)
+    {
+        gwhost::set_last_error("gw_aligner_relaunch: this aligner class keeps no relaunchable batch (the banded aligner does)");
+        return -1;
+    }
     a->impl->relaunch_resident();
     return 0;
     GW_CATCH(-1)
@@ -649,7 +700,11 @@ int gw_aligner_relaunch_timed(gw_aligner* a, float* kernels_ms)
 int gw_aligner_band_cells(gw_aligner* a, uint64_t* cells)
 {
     GW_TRY
-    if (!a->impl) return -1;
+    if (!a->impl)
+    {
+        gwhost::set_last_error("gw_aligner_band_cells: this aligner class counts no band cells (the banded aligner does)");
+        return -1;
+    }
     *cells = a->impl->total_band_cells();
     return 0;
     GW_CATCH(-1)

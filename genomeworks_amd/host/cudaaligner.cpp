@@ -30,6 +30,7 @@
 #include "chunk_order.hpp"
 #include "host_common.hpp"
 #include "aligner_global.hpp"
+#include "aligner_semiglobal.hpp"
 #include "alignment_impl.hpp"
 
 namespace claraparabricks
@@ -727,10 +728,13 @@ std::unique_ptr<Aligner> create_aligner(int32_t max_query_length, int32_t max_ta
                                         AlignmentType type, DefaultDeviceAllocator allocator, cudaStream_t stream,
                                         int32_t device_id)
 {
-    if (type != AlignmentType::global_alignment) throw std::runtime_error("Aligner for specified type not implemented yet.");
+    if (type != AlignmentType::global_alignment && type != AlignmentType::infix_alignment && type != AlignmentType::prefix_alignment)
+        throw std::runtime_error("Aligner for specified type not implemented yet.");
     throw_on_negative(max_query_length, "max_query_length must be non-negative.");
     throw_on_negative(max_target_length, "max_target_length must be non-negative.");
     throw_on_negative(max_alignments, "max_alignments must be non-negative.");
+    if (type != AlignmentType::global_alignment) // the ends scan in front of the default aligner (aligner_semiglobal.hpp)
+        return std::make_unique<AlignerSemiglobal>(type, max_query_length, max_target_length, max_alignments, allocator, stream, device_id);
     // the reference's default: Hirschberg + Myers (aligner.cpp:39-43)
     return std::make_unique<HirschbergAligner>(max_query_length, max_target_length, max_alignments, allocator, stream, device_id);
 }

@@ -47,6 +47,11 @@ public:
     virtual const std::vector<int32_t>& get_runlengths() const                      = 0;
     virtual int32_t get_edit_distance() const                                       = 0;
     virtual FormattedAlignment format_alignment(int32_t maximal_line_length = 80) const = 0;
+    /// (not in the reference) the slice [begin, end) of the target sequence that the alignment covers: the whole target
+    /// for global_alignment; for infix_alignment / prefix_alignment the slice the query was placed on, which the
+    /// states, the CIGAR and format_alignment() describe
+    virtual int32_t get_target_begin() const { return 0; }
+    virtual int32_t get_target_end() const { return static_cast<int32_t>(get_target_sequence().size()); }
 };
 
 } // namespace cudaaligner

@@ -23,7 +23,11 @@ enum StatusType
 enum AlignmentType
 {
     global_alignment = 0,
-    unset
+    unset,
+    /// (not in the reference) the whole query against the best-matching slice T[target_begin:target_end] of the target
+    infix_alignment,
+    /// (not in the reference) the whole query against the best-matching prefix T[0:target_end] of the target
+    prefix_alignment
 };
 
 /// One position of an alignment.

@@ -173,6 +173,14 @@ gw_aligner* gw_aligner_create(int32_t max_query_length, int32_t max_target_lengt
    its tests and benchmarks construct directly: algorithm = "default" | "hirschberg_myers" | "ukkonen" | "myers". */
 gw_aligner* gw_aligner_create_algorithm(const char* algorithm, int32_t max_query_length, int32_t max_target_length,
                                         int32_t max_alignments, void* stream, int32_t device_id, int64_t max_device_memory);
+/* create_aligner(max_query_length, max_target_length, max_alignments, type, ...) for any AlignmentType (cudaaligner.hpp):
+   0 global_alignment (what gw_aligner_create builds), 2 infix_alignment, 3 prefix_alignment -- the whole query against the
+   best slice T[begin:end] / the best prefix T[0:end] of its target; the states, CIGAR and edit distance describe that slice,
+   which gw_alignment_target_range reports. An aligner of these two types has no device-resident results: gw_aligner_get_runs
+   works; gw_aligner_device_alignments returns 1; gw_aligner_relaunch, _relaunch_timed and _band_cells return -1 with
+   gw_last_error() saying so. NULL on error. */
+gw_aligner* gw_aligner_create_typed(int32_t alignment_type, int32_t max_query_length, int32_t max_target_length,
+                                    int32_t max_alignments, void* stream, int32_t device_id, int64_t max_device_memory);
 void gw_aligner_destroy(gw_aligner* a);
 int gw_aligner_add_alignment(gw_aligner* a, const char* query, int32_t query_length, const char* target,
                              int32_t target_length, int reverse_complement_query, int reverse_complement_target);
@@ -184,6 +192,12 @@ int gw_aligner_reset(gw_aligner* a);
 int32_t gw_alignment_status(gw_aligner* a, int32_t i);
 int32_t gw_alignment_is_optimal(gw_aligner* a, int32_t i);
 int32_t gw_alignment_edit_distance(gw_aligner* a, int32_t i);
+int32_t gw_alignment_type(gw_aligner* a, int32_t i); /* Alignment::get_alignment_type() */
+/* Alignment::get_target_begin() / get_target_end(): 0 and the target's length for a global alignment. 0, or -1 on error. */
+int gw_alignment_target_range(gw_aligner* a, int32_t i, int32_t* begin, int32_t* end);
+/* infix / prefix aligners, measurement aid: HIP-event times (ms) of the last align_all() -- the ends scan, and the gather of
+   the slices with the traceback by the default global aligner. -1 for other aligners or before an align_all(). */
+int gw_aligner_stage_ms(gw_aligner* a, float* ends_ms, float* traceback_ms);
 const char* gw_alignment_cigar(gw_aligner* a, int32_t i, int32_t extended, int32_t* length);
 int32_t gw_alignment_states(gw_aligner* a, int32_t i, int8_t* out, int32_t cap);
 /* All alignments of the last sync_alignments() at once, as run-length CIGARs in forward order: offsets[n + 1] index
