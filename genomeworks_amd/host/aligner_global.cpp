@@ -1,8 +1,6 @@
 // aligner_global.cpp -- host side of the fixed-limit global aligners (see aligner_global.hpp).
 // The sequences are packed back to back (q0 t0 q1 t1 ...) instead of the reference's fixed 2 * max_length stride;
 // limits, statuses and the host-side reversal of the kernels' back-to-front paths follow aligner_global.cpp.
-#include <cstring>
-#include <exception>
 #include <thread>
 #include "aligner_global.hpp"
 
@@ -25,9 +23,10 @@ namespace genomeworks
 namespace cudaaligner
 {
 
-AlignerGlobal::AlignerGlobal(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments,
+FixedLimitAligner::FixedLimitAligner(AlignmentType type, int32_t max_query_length, int32_t max_target_length, int32_t max_alignments,
                                      DefaultDeviceAllocator allocator, cudaStream_t stream, int32_t device_id)
-    : max_query_length_(throw_on_negative(max_query_length, "max_query_length must be non-negative."))
+    : type_(type)
+    , max_query_length_(throw_on_negative(max_query_length, "max_query_length must be non-negative."))
     , max_target_length_(throw_on_negative(max_target_length, "max_target_length must be non-negative."))
     , max_alignments_(throw_on_negative(max_alignments, "max_alignments must be non-negative."))
     , allocator_(allocator)
@@ -38,24 +37,14 @@ AlignerGlobal::AlignerGlobal(int32_t max_query_length, int32_t max_target_length
     seq_starts_h_.assign(1, 0);
 }
 
-AlignerGlobal::~AlignerGlobal()
+void FixedLimitAligner::drain_and_free_device()
 {
     scoped_device_switch dev(device_id_);
     (void)hipStreamSynchronize(stream_);
     free_device();
 }
 
-void AlignerGlobal::free_device()
-{
-    if (device_block_)
-    {
-        allocator_.deallocate(device_block_, device_block_bytes_);
-        device_block_       = nullptr;
-        device_block_bytes_ = 0;
-    }
-}
-
-StatusType AlignerGlobal::add_alignment(const char* query, int32_t query_length, const char* target, int32_t target_length,
+StatusType FixedLimitAligner::add_alignment(const char* query, int32_t query_length, const char* target, int32_t target_length,
                                             bool reverse_complement_query, bool reverse_complement_target)
 {
     if (query_length < 0 || target_length < 0)
@@ -80,10 +69,53 @@ StatusType AlignerGlobal::add_alignment(const char* query, int32_t query_length,
     // the reference (aligner_global.cpp:100-109): a caller may hold the vector from before the sync -- its Python
     // binding does (cudaaligner.pyx:243-247)
     auto alignment = std::make_shared<AlignmentImpl>(seq_h_.data() + begin, query_length, seq_h_.data() + begin + query_length, target_length);
-    alignment->set_alignment_type(AlignmentType::global_alignment);
+    alignment->set_alignment_type(type_);
     alignments_.push_back(std::move(alignment));
     launched_ = false;
     return StatusType::success;
+}
+
+void FixedLimitAligner::reset()
+{
+    drain_and_free_device();
+    alignments_.clear();
+    seq_h_.clear();
+    seq_starts_h_.assign(1, 0);
+    launched_ = false;
+}
+
+int launch_hirschberg_myers(const char* sequences_d, const int64_t* sequence_starts_d, int32_t n, int32_t max_query_length,
+                            int8_t* results_d, int32_t* result_lengths_d, void* workspace_d, size_t workspace_size,
+                            cudaStream_t stream)
+{
+    gwhip_hirschberg_args a{};
+    a.n_alignments     = n;
+    a.sequences        = sequences_d;
+    a.sequence_starts  = sequence_starts_d;
+    a.max_query_length = max_query_length;
+    a.results          = results_d;
+    a.result_lengths   = result_lengths_d;
+    a.workspace        = workspace_d;
+    a.workspace_bytes  = workspace_size;
+    return gwhip_hirschberg_myers(&a, stream);
+}
+
+AlignerGlobal::AlignerGlobal(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments,
+                             DefaultDeviceAllocator allocator, cudaStream_t stream, int32_t device_id)
+    : FixedLimitAligner(AlignmentType::global_alignment, max_query_length, max_target_length, max_alignments, allocator, stream, device_id)
+{
+}
+
+AlignerGlobal::~AlignerGlobal() { drain_and_free_device(); }
+
+void AlignerGlobal::free_device()
+{
+    if (device_block_)
+    {
+        allocator_.deallocate(device_block_, device_block_bytes_);
+        device_block_       = nullptr;
+        device_block_bytes_ = 0;
+    }
 }
 
 StatusType AlignerGlobal::align_all()
@@ -92,32 +124,24 @@ StatusType AlignerGlobal::align_all()
     if (n == 0) return StatusType::success;
     scoped_device_switch dev(device_id_);
     const int64_t total = seq_starts_h_.back();
-    const size_t ws_bytes = workspace_bytes(n, seq_starts_h_.data());
-    size_t off = 0;
-    auto take  = [&](size_t b) { size_t o = off; off += (b + 255) / 256 * 256; return o; };
-    const size_t o_seq = take(static_cast<size_t>(total) + 16), o_starts = take((2 * static_cast<size_t>(n) + 1) * 8);
-    const size_t o_res = take(static_cast<size_t>(total) + 16), o_len = take(static_cast<size_t>(n) * 4), o_ws = take(ws_bytes);
+    ws_bytes_           = workspace_bytes(n, seq_starts_h_.data());
+    gwhost::BlockLayout layout;
+    const auto seq     = layout.take<char>(static_cast<size_t>(total) + 16);
+    const auto starts  = layout.take<int64_t>(2 * static_cast<size_t>(n) + 1);
+    const auto results = layout.take<int8_t>(static_cast<size_t>(total) + 16);
+    const auto lengths = layout.take<int32_t>(static_cast<size_t>(n));
+    const auto ws      = layout.take<char>(ws_bytes_);
     free_device();
-    device_block_bytes_ = off;
+    device_block_bytes_ = layout.bytes;
     device_block_       = allocator_.allocate(device_block_bytes_, {stream_});
-    char* d_seq         = device_block_ + o_seq;
-    int64_t* d_starts   = reinterpret_cast<int64_t*>(device_block_ + o_starts);
-    d_results_          = reinterpret_cast<int8_t*>(device_block_ + o_res);
-    d_result_lengths_   = reinterpret_cast<int32_t*>(device_block_ + o_len);
-    GW_CU_CHECK_ERR(hipMemcpyAsync(d_seq, seq_h_.data(), static_cast<size_t>(total), hipMemcpyHostToDevice, stream_));
-    GW_CU_CHECK_ERR(hipMemcpyAsync(d_starts, seq_starts_h_.data(), seq_starts_h_.size() * 8, hipMemcpyHostToDevice, stream_));
-    d_seq_    = d_seq;
-    d_starts_ = d_starts;
-    d_ws_     = device_block_ + o_ws;
-    ws_bytes_ = ws_bytes;
-    const int rc = run_alignment(n, d_seq, d_starts, seq_starts_h_.data(), d_results_, d_result_lengths_, device_block_ + o_ws, ws_bytes);
-    if (rc != 0)
-    {
-        char buf[512];
-        gwhip_last_error_string(buf, sizeof(buf));
-        GW_LOG_ERROR(buf);
-        GW_CU_CHECK_ERR(static_cast<hipError_t>(rc));
-    }
+    d_seq_              = seq.in(device_block_);
+    d_starts_           = starts.in(device_block_);
+    d_results_          = results.in(device_block_);
+    d_result_lengths_   = lengths.in(device_block_);
+    d_ws_               = ws.in(device_block_);
+    GW_CU_CHECK_ERR(hipMemcpyAsync(d_seq_, seq_h_.data(), static_cast<size_t>(total), hipMemcpyHostToDevice, stream_));
+    GW_CU_CHECK_ERR(hipMemcpyAsync(d_starts_, seq_starts_h_.data(), seq_starts_h_.size() * 8, hipMemcpyHostToDevice, stream_));
+    check_gwhip(run_alignment(n, d_seq_, d_starts_, seq_starts_h_.data(), d_results_, d_result_lengths_, d_ws_, ws_bytes_));
     results_h_.resize(static_cast<size_t>(total) + 16);
     result_lengths_h_.resize(static_cast<size_t>(n));
     GW_CU_CHECK_ERR(hipMemcpyAsync(results_h_.data(), d_results_, static_cast<size_t>(total), hipMemcpyDeviceToHost, stream_));
@@ -133,7 +157,7 @@ StatusType AlignerGlobal::sync_alignments()
     const size_t n = static_cast<size_t>(num_alignments());
     if (!launched_ || n == 0) return StatusType::success;
     // the device writes every path back to front; one reversed copy per alignment, handed over without a second one.
-    // Big batches are split over a few host threads (the alignments are independent objects).
+    // Big batches are split over a few threads of the host pool (the alignments are independent objects).
     auto fill_range = [&](size_t first, size_t last) {
         for (size_t i = first; i < last; ++i)
         {
@@ -142,68 +166,17 @@ StatusType AlignerGlobal::sync_alignments()
             AlignmentImpl* alignment = dynamic_cast<AlignmentImpl*>(alignments_[i].get());
             const int32_t len        = result_lengths_h_[i];
             const size_t count       = static_cast<size_t>(std::abs(len));
-            const int8_t* r_begin    = results_h_.data() + seq_starts_h_[2 * i];
-            std::vector<AlignmentState> states(count);
-            static_assert(sizeof(AlignmentState) == 1, "the device writes one byte per state");
-            {
-                // reversed copy, eight states at a time (one byte-swapped 64-bit word), the tail byte by byte
-                uint8_t* dst       = reinterpret_cast<uint8_t*>(states.data());
-                const uint8_t* src = reinterpret_cast<const uint8_t*>(r_begin);
-                size_t k           = 0;
-                for (; k + 8 <= count; k += 8)
-                {
-                    uint64_t v;
-                    std::memcpy(&v, src + count - 8 - k, 8);
-                    v = __builtin_bswap64(v);
-                    std::memcpy(dst + k, &v, 8);
-                }
-                for (; k < count; ++k) dst[k] = src[count - 1 - k];
-            }
             if (count != 0 || (qlen == 0 && tlen == 0))
             {
-                alignment->set_alignment(std::move(states), len >= 0);
+                alignment->set_alignment(reversed_states(results_h_.data() + seq_starts_h_[2 * i], count), len >= 0);
                 alignment->set_status(StatusType::success);
             }
         }
     };
     const size_t total     = static_cast<size_t>(seq_starts_h_.back());
     const size_t n_threads = (n >= 256 && total >= (size_t(1) << 20)) ? std::min<size_t>(8, std::max(1u, std::thread::hardware_concurrency())) : 1;
-    if (n_threads <= 1)
-        fill_range(0, n);
-    else
-    {
-        const size_t chunk = (n + n_threads - 1) / n_threads;
-        std::vector<std::thread> workers;
-        std::vector<std::exception_ptr> errors(n_threads);
-        {
-            // joins whatever was started on every exit path (a throwing emplace_back or the caller's own range included);
-            // a worker's exception is carried back to the caller instead of ending the process
-            struct JoinAll
-            {
-                std::vector<std::thread>& threads;
-                ~JoinAll()
-                {
-                    for (std::thread& t : threads)
-                        if (t.joinable()) t.join();
-                }
-            } join_on_exit{workers};
-            workers.reserve(n_threads);
-            for (size_t t = 1; t < n_threads; ++t)
-                workers.emplace_back([&, t] {
-                    try
-                    {
-                        fill_range(std::min(n, t * chunk), std::min(n, (t + 1) * chunk));
-                    }
-                    catch (...)
-                    {
-                        errors[t] = std::current_exception();
-                    }
-                });
-            fill_range(0, std::min(n, chunk));
-        }
-        for (const std::exception_ptr& e : errors)
-            if (e) std::rethrow_exception(e);
-    }
+    const size_t share     = (n + n_threads - 1) / n_threads;
+    gwhost::parallel_tasks(n_threads, n_threads, [&](size_t t) { fill_range(std::min(n, t * share), std::min(n, (t + 1) * share)); });
     return StatusType::success;
 }
 
@@ -231,24 +204,6 @@ float AlignerGlobal::relaunch_resident_timed()
     return rc == 0 ? ms : -1.f;
 }
 
-DeviceAlignmentsPtrs AlignerGlobal::get_alignments_device() const
-{
-    // the packed run-length form of DeviceAlignmentsPtrs is only produced by the banded aligner; as in the reference
-    // (aligner_global.hpp:54-64, "TODO implement for other aligners") the others hand back null pointers
-    return DeviceAlignmentsPtrs{};
-}
-
-void AlignerGlobal::reset()
-{
-    scoped_device_switch dev(device_id_);
-    (void)hipStreamSynchronize(stream_);
-    alignments_.clear();
-    seq_h_.clear();
-    seq_starts_h_.assign(1, 0);
-    launched_ = false;
-    free_device();
-}
-
 // ---- Hirschberg + Myers (the default) ----------------------------------------------------------------------------
 size_t AlignerGlobalHirschbergMyers::workspace_bytes(int32_t n, const int64_t* sequence_starts) const
 {
@@ -259,16 +214,8 @@ int AlignerGlobalHirschbergMyers::run_alignment(int32_t n, const char* sequences
                                                 const int64_t*, int8_t* results_d, int32_t* result_lengths_d,
                                                 void* workspace_d, size_t workspace_size)
 {
-    gwhip_hirschberg_args a{};
-    a.n_alignments     = n;
-    a.sequences        = sequences_d;
-    a.sequence_starts  = sequence_starts_d;
-    a.max_query_length = get_max_query_length();
-    a.results          = results_d;
-    a.result_lengths   = result_lengths_d;
-    a.workspace        = workspace_d;
-    a.workspace_bytes  = workspace_size;
-    return gwhip_hirschberg_myers(&a, get_stream());
+    return launch_hirschberg_myers(sequences_d, sequence_starts_d, n, get_max_query_length(), results_d, result_lengths_d, workspace_d,
+                                   workspace_size, get_stream());
 }
 
 // ---- Ukkonen ----------------------------------------------------------------------------------------------------

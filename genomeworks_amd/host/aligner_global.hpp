@@ -1,7 +1,7 @@
 // aligner_global.hpp -- the fixed-limit global aligners (reference: cudaaligner/src/aligner_global.hpp and its three
-// subclasses). AlignerGlobal holds what they share -- limits, statuses, packing, the device block, the host-side
-// reversal of the kernels' back-to-front paths (aligner_global.cpp:48-190) -- and each algorithm supplies its
-// workspace size and its launch through the C-ABI of libgwhip:
+// subclasses). FixedLimitAligner holds the limits, statuses and packing (shared with AlignerSemiglobal), AlignerGlobal
+// the device block and the host-side reversal of the kernels' back-to-front paths (aligner_global.cpp:48-190), and
+// each algorithm supplies its workspace size and its launch through the C-ABI of libgwhip:
 //   AlignerGlobalHirschbergMyers  the default of create_aligner(max_query, max_target, max_alignments, ...)
 //                                 (aligner_global_hirschberg_myers.cpp)             -> gwhip_hirschberg_myers
 //   AlignerGlobalUkkonen          band parameter p = 100, int16 scores (aligner_global_ukkonen.cpp) -> gwhip_ukkonen
@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "aligner_impl.hpp"
+#include "host_common.hpp"
 
 namespace claraparabricks
 {
@@ -23,7 +24,61 @@ namespace genomeworks
 namespace cudaaligner
 {
 
-class AlignerGlobal : public Aligner
+/// What the aligners with fixed limits share (AlignerGlobal and its subclasses, AlignerSemiglobal): the limits and the
+/// statuses of add_alignment(), the pinned staging arrays q0 t0 q1 t1 ... and their offsets, the Alignment objects that
+/// exist from add time, and the life cycle around a batch in flight.
+class FixedLimitAligner : public Aligner
+{
+public:
+    StatusType add_alignment(const char* query, int32_t query_length, const char* target, int32_t target_length,
+                             bool reverse_complement_query = false, bool reverse_complement_target = false) override;
+    const std::vector<std::shared_ptr<Alignment>>& get_alignments() const override { return alignments_; }
+    /// the packed run-length form of DeviceAlignmentsPtrs is only produced by the banded aligner; as in the reference
+    /// (aligner_global.hpp:54-64, "TODO implement for other aligners") the others hand back null pointers
+    DeviceAlignmentsPtrs get_alignments_device() const override { return DeviceAlignmentsPtrs{}; }
+    void reset() override;
+    void free_temporary_device_buffers() override {}
+    int32_t num_alignments() const override { return static_cast<int32_t>(alignments_.size()); }
+    cudaStream_t get_stream() const override { return stream_; }
+    int32_t get_device() const override { return device_id_; }
+    DefaultDeviceAllocator get_device_allocator() const override { return allocator_; }
+
+    int32_t get_max_query_length() const { return max_query_length_; }
+    int32_t get_max_target_length() const { return max_target_length_; }
+
+protected:
+    FixedLimitAligner(AlignmentType type, int32_t max_query_length, int32_t max_target_length, int32_t max_alignments,
+                      DefaultDeviceAllocator allocator, cudaStream_t stream, int32_t device_id);
+    virtual void free_device() = 0; ///< the batch's device blocks go back to the allocator
+    void drain_and_free_device();   ///< waits for the stream first: reset() and the subclasses' destructors
+
+    AlignmentType type_; ///< of every Alignment this aligner hands out
+    int32_t max_query_length_, max_target_length_, max_alignments_;
+    DefaultDeviceAllocator allocator_;
+    cudaStream_t stream_;
+    int32_t device_id_;
+    // staging arrays in pinned memory (process-wide cache of pinned buffers): the copies of align_all() are true async DMA
+    PinnedVector<char> seq_h_;
+    PinnedVector<int64_t> seq_starts_h_;
+    std::vector<std::shared_ptr<Alignment>> alignments_;
+    bool launched_ = false;
+};
+
+/// gwhip_hirschberg_myers (the default global aligner) on n pairs laid out as q0 t0 q1 t1 ...; 0 or a hipError_t
+int launch_hirschberg_myers(const char* sequences_d, const int64_t* sequence_starts_d, int32_t n, int32_t max_query_length,
+                            int8_t* results_d, int32_t* result_lengths_d, void* workspace_d, size_t workspace_size,
+                            cudaStream_t stream);
+
+/// the device writes every path back to front, one byte per state: the forward copy
+inline std::vector<AlignmentState> reversed_states(const int8_t* back_to_front, size_t count)
+{
+    static_assert(sizeof(AlignmentState) == 1, "the device writes one byte per state");
+    std::vector<AlignmentState> states(count);
+    gwhost::reverse_bytes(states.data(), back_to_front, count);
+    return states;
+}
+
+class AlignerGlobal : public FixedLimitAligner
 {
 public:
     AlignerGlobal(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments,
@@ -32,23 +87,10 @@ public:
 
     StatusType align_all() override;
     StatusType sync_alignments() override;
-    StatusType add_alignment(const char* query, int32_t query_length, const char* target, int32_t target_length,
-                             bool reverse_complement_query = false, bool reverse_complement_target = false) override;
-    const std::vector<std::shared_ptr<Alignment>>& get_alignments() const override { return alignments_; }
-    DeviceAlignmentsPtrs get_alignments_device() const override;
-    void reset() override;
-    void free_temporary_device_buffers() override {}
-    int32_t num_alignments() const override { return static_cast<int32_t>(alignments_.size()); }
-    cudaStream_t get_stream() const override { return stream_; }
-    int32_t get_device() const override { return device_id_; }
-    DefaultDeviceAllocator get_device_allocator() const override { return allocator_; }
 
     /// measurement aid: the kernels of the last align_all() once more on the inputs still resident in HBM, timed with HIP
     /// events on the aligner's stream; < 0 when nothing is resident
     float relaunch_resident_timed();
-
-    int32_t get_max_query_length() const { return max_query_length_; }
-    int32_t get_max_target_length() const { return max_target_length_; }
 
 protected:
     /// device bytes the algorithm needs for the queued pairs (sequence_starts: host, [2n+1])
@@ -59,16 +101,8 @@ protected:
                               void* workspace_d, size_t workspace_size) = 0;
 
 private:
-    void free_device();
+    void free_device() override;
 
-    int32_t max_query_length_, max_target_length_, max_alignments_;
-    DefaultDeviceAllocator allocator_;
-    cudaStream_t stream_;
-    int32_t device_id_;
-    // staging arrays in pinned memory (process-wide cache of pinned buffers): the copies of align_all() are true async DMA
-    PinnedVector<char> seq_h_;
-    PinnedVector<int64_t> seq_starts_h_;
-    std::vector<std::shared_ptr<Alignment>> alignments_;
     PinnedVector<int8_t> results_h_;
     PinnedVector<int32_t> result_lengths_h_;
     char* device_block_        = nullptr;
@@ -79,7 +113,6 @@ private:
     size_t ws_bytes_           = 0;
     int8_t* d_results_         = nullptr;
     int32_t* d_result_lengths_ = nullptr;
-    bool launched_             = false;
 };
 
 class AlignerGlobalHirschbergMyers : public AlignerGlobal

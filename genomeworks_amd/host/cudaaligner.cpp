@@ -49,14 +49,14 @@ StatusType Init()
 namespace
 {
 constexpr int32_t kWordSize = 32;
-size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
 using gwhost::pack_bases;
 using gwhost::query_code;
 using gwhost::target_code;
+using gwhost::up256;
 // GW_ALIGNER_TRACE=1: host-side timeline of align_all() / sync_alignments() on stderr (debugging aid)
 struct Tracer
 {
-    bool on = std::getenv("GW_ALIGNER_TRACE") != nullptr;
+    bool on;
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     void mark(const char* what)
     {
@@ -67,6 +67,25 @@ struct Tracer
     }
 };
 } // namespace
+
+void check_gwhip(int rc)
+{
+    if (rc == 0) return;
+    char buf[512];
+    gwhip_last_error_string(buf, sizeof(buf));
+    GW_LOG_ERROR(buf);
+    GW_CU_CHECK_ERR(static_cast<hipError_t>(rc));
+}
+
+BandedAligner::Switches BandedAligner::Switches::read()
+{
+    Switches s;
+    if (const char* e = std::getenv("GW_ALIGNER_CHUNKS")) s.chunks = std::max(1, std::atoi(e));
+    s.raw_upload = std::getenv("GW_ALIGNER_RAW_UPLOAD") != nullptr;
+    if (const char* e = std::getenv("GW_ALIGNER_MIRROR_RUNS")) s.mirror_runs = std::max<int64_t>(1, std::atoll(e));
+    s.trace = std::getenv("GW_ALIGNER_TRACE") != nullptr;
+    return s;
+}
 
 BandedAligner::BandedAligner(int64_t max_device_memory, int32_t max_bandwidth, DefaultDeviceAllocator allocator,
                              cudaStream_t stream, int32_t device_id, bool expand_results, int32_t max_query_length,
@@ -88,21 +107,14 @@ BandedAligner::BandedAligner(int64_t max_device_memory, int32_t max_bandwidth, D
 BandedAligner::~BandedAligner()
 {
     scoped_device_switch dev(device_id_);
-    (void)hipStreamSynchronize(stream_);
-    if (upload_stream_ != nullptr)
-    {
-        (void)hipStreamSynchronize(static_cast<hipStream_t>(upload_stream_));
-        (void)hipStreamDestroy(static_cast<hipStream_t>(upload_stream_));
-    }
-    if (side_stream_ != nullptr)
-    {
-        (void)hipStreamSynchronize(static_cast<hipStream_t>(side_stream_));
-        (void)hipStreamDestroy(static_cast<hipStream_t>(side_stream_));
-    }
-    for (void* e : upload_events_) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
+    drain_streams();
+    if (upload_stream_ != nullptr) (void)hipStreamDestroy(upload_stream_);
+    if (side_stream_ != nullptr) (void)hipStreamDestroy(side_stream_);
+    if (begin_ != nullptr) (void)hipEventDestroy(begin_);
+    if (side_joined_ != nullptr) (void)hipEventDestroy(side_joined_);
+    for (hipEvent_t e : uploaded_) (void)hipEventDestroy(e);
+    for (hipEvent_t e : sized_) (void)hipEventDestroy(e);
     free_device();
-    if (head_ != nullptr) pinned_release(head_, head_cap_);
-    if (mirror_ != nullptr) pinned_release(mirror_, mirror_cap_);
 }
 
 void BandedAligner::reset_max_bandwidth(int32_t max_bandwidth)
@@ -144,9 +156,7 @@ void BandedAligner::reset_data()
 void BandedAligner::reset()
 {
     scoped_device_switch dev(device_id_);
-    (void)hipStreamSynchronize(stream_);
-    if (upload_stream_ != nullptr) (void)hipStreamSynchronize(static_cast<hipStream_t>(upload_stream_));
-    if (side_stream_ != nullptr) (void)hipStreamSynchronize(static_cast<hipStream_t>(side_stream_));
+    drain_streams();
     uploads_in_flight_ = false;
     reset_data();
     free_device();
@@ -162,8 +172,8 @@ void BandedAligner::drain_streams()
 {
     // the aligner's stream has waited for the other two by the end of align_all(); after a call that threw in between it has not
     (void)hipStreamSynchronize(stream_);
-    if (upload_stream_ != nullptr) (void)hipStreamSynchronize(static_cast<hipStream_t>(upload_stream_));
-    if (side_stream_ != nullptr) (void)hipStreamSynchronize(static_cast<hipStream_t>(side_stream_));
+    if (upload_stream_ != nullptr) (void)hipStreamSynchronize(upload_stream_);
+    if (side_stream_ != nullptr) (void)hipStreamSynchronize(side_stream_);
 }
 
 StatusType BandedAligner::add_alignment(const char* query, int32_t query_length, const char* target, int32_t target_length,
@@ -253,18 +263,23 @@ StatusType BandedAligner::align_all()
     if (n == 0) return StatusType::success;
     scoped_device_switch dev(device_id_);
     const int64_t total_len = seq_starts_h_.back();
-    Tracer trace;
+    switches_               = Switches::read();
+    Tracer trace{switches_.trace};
     // Inputs and outputs first: the sequences (the bulk of the upload: 300 MB for a million 150-bp pairs), their offsets and the
     // band widths do not depend on the processing order, so their copies are under way while the host sorts the batch and
     // sizes the workspace below (aligner_global_myers_banded.cpp:364-371 uploads after sorting; the result is the same).
-    size_t off       = 0;
-    auto take        = [&](size_t b) { size_t o = off; off += up256(b); return o; };
-    const size_t o_seq = take(static_cast<size_t>(total_len) + 16), o_starts = take((2 * static_cast<size_t>(n) + 1) * 8);
-    const size_t o_bw = take(static_cast<size_t>(n) * 4), o_order = take(static_cast<size_t>(n) * 4);
-    const size_t o_res = take(static_cast<size_t>(total_len) + 16), o_cnt = take((static_cast<size_t>(total_len) + 16) * 4);
-    const size_t o_rs = take((static_cast<size_t>(n) + 1) * 4), o_meta = take(static_cast<size_t>(n) * 4);
-    const size_t o_cells = take(static_cast<size_t>(n) * 8);
-    const size_t o_packed = take(static_cast<size_t>(total_len) / 2 + 64);
+    const size_t un = static_cast<size_t>(n), bases = static_cast<size_t>(total_len);
+    gwhost::BlockLayout layout;
+    const auto seq           = layout.take<char>(bases + 16);
+    const auto starts        = layout.take<int64_t>(2 * un + 1);
+    const auto bw            = layout.take<int32_t>(un);
+    const auto order_slot    = layout.take<int32_t>(un);
+    const auto results       = layout.take<int8_t>(bases + 16);
+    const auto counts        = layout.take<int32_t>(bases + 16);
+    const auto result_starts = layout.take<int32_t>(un + 1);
+    const auto metadata      = layout.take<uint32_t>(un);
+    const auto cells         = layout.take<uint64_t>(un);
+    const auto packed        = layout.take<uint8_t>(bases / 2 + 64);
     // a previous align_all() without a sync in between may still be uploading from / computing on what this replaces
     if (uploads_in_flight_)
     {
@@ -273,27 +288,27 @@ StatusType BandedAligner::align_all()
     }
     // from here until launch() the object describes NO finished run: if an allocation below throws, a later
     // sync_alignments() must not read the previous run's offsets against the fresh, never-written result block
-    launched_ = false;
-    n_head_   = 0;
+    launched_   = false;
+    head_.pairs = 0;
     free_device();
-    device_block_bytes_ = off;
+    device_block_bytes_ = layout.bytes;
     device_block_       = allocator_.allocate(device_block_bytes_, {stream_});
-    d_seq_              = device_block_ + o_seq;
-    d_starts_           = reinterpret_cast<int64_t*>(device_block_ + o_starts);
-    d_bw_               = reinterpret_cast<int32_t*>(device_block_ + o_bw);
-    d_order_            = reinterpret_cast<int32_t*>(device_block_ + o_order);
-    d_results_          = reinterpret_cast<int8_t*>(device_block_ + o_res);
-    d_result_counts_    = reinterpret_cast<int32_t*>(device_block_ + o_cnt);
-    d_result_starts_    = reinterpret_cast<int32_t*>(device_block_ + o_rs);
-    d_metadata_         = reinterpret_cast<uint32_t*>(device_block_ + o_meta);
-    d_cells_            = reinterpret_cast<uint64_t*>(device_block_ + o_cells);
-    d_packed_           = reinterpret_cast<uint8_t*>(device_block_ + o_packed);
+    d_seq_              = seq.in(device_block_);
+    d_starts_           = starts.in(device_block_);
+    d_bw_               = bw.in(device_block_);
+    d_order_            = order_slot.in(device_block_);
+    d_results_          = results.in(device_block_);
+    d_result_counts_    = counts.in(device_block_);
+    d_result_starts_    = result_starts.in(device_block_);
+    d_metadata_         = metadata.in(device_block_);
+    d_cells_            = cells.in(device_block_);
+    d_packed_           = packed.in(device_block_);
 
     // Chunks of consecutive pairs for large batches (a million short reads: the upload is 2 / 3 of the call): the upload of
     // chunk k + 1 runs on a stream of its own under the kernels of chunk k. The pairs' results do not depend on how the
     // batch is cut (scheduling order and workspace are per chunk, the packed runs are appended in input order).
     int32_t n_chunks = (n >= 131072 && total_len >= (int64_t(32) << 20)) ? 6 : 1; // (2 .. 24 measured: profiles/r05_d_aligner_chunk_sweep.txt)
-    if (const char* e = std::getenv("GW_ALIGNER_CHUNKS")) n_chunks = std::max(1, std::min(std::atoi(e), std::max(1, n / 64)));
+    if (switches_.chunks > 0) n_chunks = std::min(switches_.chunks, std::max(1, n / 64));
     chunks_.resize(static_cast<size_t>(n_chunks));
     for (int32_t k = 0; k < n_chunks; ++k)
     {
@@ -304,49 +319,27 @@ StatusType BandedAligner::align_all()
         c.span         = seq_starts_h_[2 * static_cast<size_t>(c.hi)] - c.first_offset;
     }
     launched_total_length_ = total_len;
-    raw_upload_            = std::getenv("GW_ALIGNER_RAW_UPLOAD") != nullptr;
     // a chunked batch's runs also arrive in a pinned mirror as the chunks finish (gwhip_myers_args::results_host): sized for 16 runs
     // per pair or one per 16 bases; sync_alignments() copies for itself when a batch has more
     if (n_chunks > 1)
     {
-        int64_t want     = std::min<int64_t>(total_len, std::max<int64_t>(16 * static_cast<int64_t>(n), total_len / 16));
-        const char* runs = std::getenv("GW_ALIGNER_MIRROR_RUNS"); // tests: a capacity the batch exceeds
-        if (runs != nullptr) want = std::max<int64_t>(1, std::min<int64_t>(std::atoll(runs), total_len));
-        if (mirror_ == nullptr || mirror_runs_ < want || runs != nullptr)
-        {
-            if (mirror_ != nullptr) pinned_release(mirror_, mirror_cap_);
-            mirror_      = nullptr;
-            mirror_runs_ = 0;
-            mirror_      = pinned_acquire(static_cast<size_t>((want + 63) & ~int64_t(63)) + static_cast<size_t>(want) * 4 + 64, &mirror_cap_);
-            mirror_runs_ = want;
-        }
-    }
-    hipStream_t up = stream_;
-    if (n_chunks > 1)
-    {
-        if (upload_stream_ == nullptr)
-        {
-            hipStream_t s = nullptr;
-            GW_CU_CHECK_ERR(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-            upload_stream_ = s;
-        }
-        if (side_stream_ == nullptr)
-        {
-            hipStream_t s = nullptr;
-            GW_CU_CHECK_ERR(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-            side_stream_ = s;
-        }
-        while (upload_events_.size() < 2 * static_cast<size_t>(n_chunks) + 2)
-        {
+        int64_t want = std::min<int64_t>(total_len, std::max<int64_t>(16 * static_cast<int64_t>(n), total_len / 16));
+        if (switches_.mirror_runs > 0) want = std::max<int64_t>(1, std::min(switches_.mirror_runs, total_len));
+        if (mirror_.data == nullptr || mirror_.runs < want || switches_.mirror_runs > 0) mirror_.acquire_runs(want);
+        if (upload_stream_ == nullptr) GW_CU_CHECK_ERR(hipStreamCreateWithFlags(&upload_stream_, hipStreamNonBlocking));
+        if (side_stream_ == nullptr) GW_CU_CHECK_ERR(hipStreamCreateWithFlags(&side_stream_, hipStreamNonBlocking));
+        auto new_event = [] {
             hipEvent_t e = nullptr;
             GW_CU_CHECK_ERR(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            upload_events_.push_back(e);
-        }
-        up = static_cast<hipStream_t>(upload_stream_);
+            return e;
+        };
+        if (begin_ == nullptr) begin_ = new_event();
+        if (side_joined_ == nullptr) side_joined_ = new_event();
+        while (uploaded_.size() < static_cast<size_t>(n_chunks)) uploaded_.push_back(new_event());
+        while (sized_.size() < static_cast<size_t>(n_chunks)) sized_.push_back(new_event());
         // the fresh block may be memory that earlier work on the aligner's stream still uses: the uploads start behind it
-        hipEvent_t begin = static_cast<hipEvent_t>(upload_events_[static_cast<size_t>(n_chunks)]);
-        GW_CU_CHECK_ERR(hipEventRecord(begin, stream_));
-        GW_CU_CHECK_ERR(hipStreamWaitEvent(up, begin, 0));
+        GW_CU_CHECK_ERR(hipEventRecord(begin_, stream_));
+        GW_CU_CHECK_ERR(hipStreamWaitEvent(upload_stream_, begin_, 0));
     }
     PinnedVector<int32_t> order;
     order.resize(static_cast<size_t>(n));
@@ -389,10 +382,10 @@ StatusType BandedAligner::align_all()
 void BandedAligner::enqueue_inputs(size_t k)
 {
     Chunk& c         = chunks_[k];
-    hipStream_t up   = chunks_.size() > 1 ? static_cast<hipStream_t>(upload_stream_) : stream_;
+    hipStream_t up   = chunks_.size() > 1 ? upload_stream_ : stream_;
     const int64_t b0 = seq_starts_h_[2 * static_cast<size_t>(c.lo)], b1 = seq_starts_h_[2 * static_cast<size_t>(c.hi)];
     const size_t m   = static_cast<size_t>(c.hi - c.lo);
-    if (b1 > b0 && raw_upload_)
+    if (b1 > b0 && switches_.raw_upload)
         GW_CU_CHECK_ERR(hipMemcpyAsync(d_seq_ + b0, seq_h_.data() + b0, static_cast<size_t>(b1 - b0), hipMemcpyHostToDevice, up));
     else if (b1 > b0)
     {
@@ -403,11 +396,25 @@ void BandedAligner::enqueue_inputs(size_t k)
     GW_CU_CHECK_ERR(hipMemcpyAsync(d_starts_ + 2 * static_cast<size_t>(c.lo), seq_starts_h_.data() + 2 * static_cast<size_t>(c.lo), (2 * m + 1) * 8,
                                    hipMemcpyHostToDevice, up));
     GW_CU_CHECK_ERR(hipMemcpyAsync(d_bw_ + c.lo, max_bandwidths_h_.data() + c.lo, m * 4, hipMemcpyHostToDevice, up));
-    if (chunks_.size() > 1)
+    if (chunks_.size() > 1) GW_CU_CHECK_ERR(hipEventRecord(uploaded_[k], up));
+}
+
+void BandedAligner::queue_chunk(size_t k, const int32_t* order, bool allocate, hipStream_t s, int32_t phases)
+{
+    Chunk& c = chunks_[k];
+    if (order != nullptr)
     {
-        c.uploaded = upload_events_[k];
-        GW_CU_CHECK_ERR(hipEventRecord(static_cast<hipEvent_t>(c.uploaded), up));
+        // (the copy reads the caller's vector, whose storage order_h_ takes over at the end of align_all())
+        GW_CU_CHECK_ERR(hipMemcpyAsync(d_order_ + c.lo, order + c.lo, static_cast<size_t>(c.hi - c.lo) * 4, hipMemcpyHostToDevice, s));
+        // the chunk's bases from two per byte to characters
+        if (!switches_.raw_upload && c.span != 0) check_gwhip(gwhip_unpack_bases(d_packed_, d_seq_, c.first_offset, c.first_offset + c.span, s));
     }
+    if (allocate)
+    {
+        c.block_bytes = up256(c.workspace_bytes);
+        c.workspace   = allocator_.allocate(c.block_bytes, {stream_});
+    }
+    launch_chunk(c, phases);
 }
 
 void BandedAligner::run_chunks(const int32_t* order, bool allocate)
@@ -415,63 +422,35 @@ void BandedAligner::run_chunks(const int32_t* order, bool allocate)
     // A chunked batch keeps three streams busy: the uploads; the alignment kernels, back to back on the aligner's stream; and on
     // the side stream what surrounds them (gwhip_myers_args::side_stream, ::phases) -- the processing order going up and the
     // workspace sizing of chunk k + 1 (queued ahead of) the run-offset scan and compaction of chunk k and its offsets' way to
-    // the host. Events: upload_events_[k] = chunk k's inputs are up, [n + 2 + k] = its workspace is sized.
+    // the host.
     const size_t n_chunks = chunks_.size();
-    prepare_head();
-    // the chunk's bases from two per byte to characters (gwhip_unpack_bases), on the stream that has waited for its upload
-    auto unpack_chunk = [&](const Chunk& c, hipStream_t s) {
-        if (raw_upload_ || c.span == 0) return;
-        const int rc = gwhip_unpack_bases(d_packed_, d_seq_, c.first_offset, c.first_offset + c.span, s);
-        if (rc != 0) GW_CU_CHECK_ERR(static_cast<hipError_t>(rc));
-    };
+    head_.prepare(chunks_.empty() ? 0 : chunks_.back().hi);
     if (n_chunks <= 1)
     {
-        for (Chunk& c : chunks_)
+        for (size_t k = 0; k < n_chunks; ++k)
         {
-            if (order != nullptr)
-            {
-                GW_CU_CHECK_ERR(hipMemcpyAsync(d_order_ + c.lo, order + c.lo, static_cast<size_t>(c.hi - c.lo) * 4, hipMemcpyHostToDevice, stream_));
-                unpack_chunk(c, stream_);
-            }
-            if (allocate)
-            {
-                c.block_bytes = up256(c.workspace_bytes);
-                c.workspace   = allocator_.allocate(c.block_bytes, {stream_});
-            }
-            launch_chunk(c);
-            fetch_head_slice(c, stream_);
+            queue_chunk(k, order, allocate, stream_, 0);
+            fetch_head_slice(chunks_[k], stream_);
         }
         return;
     }
-    hipStream_t side = static_cast<hipStream_t>(side_stream_);
-    auto size_chunk  = [&](size_t k) {
-        Chunk& c = chunks_[k];
-        if (c.uploaded != nullptr && order != nullptr) GW_CU_CHECK_ERR(hipStreamWaitEvent(side, static_cast<hipEvent_t>(c.uploaded), 0));
-        // (the copy reads the caller's vector, whose storage order_h_ takes over at the end of align_all())
-        if (order != nullptr)
-        {
-            GW_CU_CHECK_ERR(hipMemcpyAsync(d_order_ + c.lo, order + c.lo, static_cast<size_t>(c.hi - c.lo) * 4, hipMemcpyHostToDevice, side));
-            unpack_chunk(c, side);
-        }
-        if (allocate)
-        {
-            c.block_bytes = up256(c.workspace_bytes);
-            c.workspace   = allocator_.allocate(c.block_bytes, {stream_});
-        }
-        launch_chunk(c, GWHIP_MYERS_SIZING);
-        GW_CU_CHECK_ERR(hipEventRecord(static_cast<hipEvent_t>(upload_events_[n_chunks + 2 + k]), side));
+    auto size_chunk = [&](size_t k) {
+        if (order != nullptr) GW_CU_CHECK_ERR(hipStreamWaitEvent(side_stream_, uploaded_[k], 0));
+        queue_chunk(k, order, allocate, side_stream_, GWHIP_MYERS_SIZING);
+        GW_CU_CHECK_ERR(hipEventRecord(sized_[k], side_stream_));
     };
     size_chunk(0);
     for (size_t k = 0; k < n_chunks; ++k)
     {
         if (k + 1 < n_chunks) size_chunk(k + 1);
         if (order != nullptr && k + 2 < n_chunks) enqueue_inputs(k + 2);
-        Chunk& c = chunks_[k];
-        if (c.uploaded != nullptr && order != nullptr) GW_CU_CHECK_ERR(hipStreamWaitEvent(stream_, static_cast<hipEvent_t>(c.uploaded), 0));
-        GW_CU_CHECK_ERR(hipStreamWaitEvent(stream_, static_cast<hipEvent_t>(upload_events_[n_chunks + 2 + k]), 0));
-        launch_chunk(c, GWHIP_MYERS_ALIGN);
+        if (order != nullptr) GW_CU_CHECK_ERR(hipStreamWaitEvent(stream_, uploaded_[k], 0));
+        GW_CU_CHECK_ERR(hipStreamWaitEvent(stream_, sized_[k], 0));
+        launch_chunk(chunks_[k], GWHIP_MYERS_ALIGN);
     }
-    join_side_stream();
+    // stream_ continues after everything queued on the side stream
+    GW_CU_CHECK_ERR(hipEventRecord(side_joined_, side_stream_));
+    GW_CU_CHECK_ERR(hipStreamWaitEvent(stream_, side_joined_, 0));
 }
 
 void BandedAligner::launch_chunk(const Chunk& c, int32_t phases)
@@ -495,41 +474,33 @@ void BandedAligner::launch_chunk(const Chunk& c, int32_t phases)
     a.result_starts_base    = c.lo > 0 ? d_result_starts_ + lo : nullptr; // written by the chunk before this one
     a.scheduling_index      = d_order_ + lo;
     a.band_cells            = d_cells_ + lo;
-    a.side_stream           = chunks_.size() > 1 ? side_stream_ : nullptr;
+    a.side_stream           = chunks_.size() > 1 ? side_stream_ : nullptr; // (a void* in the C ABI)
     a.phases                = phases;
     if (chunks_.size() > 1)
     {
         // the chunk's offsets and metadata reach the pinned head by a kernel of the call (no copies queued behind the uploads)
-        a.result_starts_host   = reinterpret_cast<int32_t*>(head_) + lo;
-        a.result_metadata_host = reinterpret_cast<uint32_t*>(head_) + static_cast<size_t>(n_head_) + 1 + lo;
+        a.result_starts_host   = head_.offsets() + lo;
+        a.result_metadata_host = head_.metadata() + lo;
     }
-    if (chunks_.size() > 1 && mirror_ != nullptr)
+    if (chunks_.size() > 1 && mirror_.data != nullptr)
     {
-        a.results_host          = reinterpret_cast<int8_t*>(mirror_);
-        a.result_counts_host    = reinterpret_cast<int32_t*>(mirror_ + static_cast<size_t>((mirror_runs_ + 63) & ~int64_t(63)));
-        a.results_host_capacity = mirror_runs_;
+        a.results_host          = mirror_.ops();
+        a.result_counts_host    = mirror_.counts();
+        a.results_host_capacity = mirror_.runs;
     }
     // hints for the LDS-cached kernel variant: longest query and widest band of this batch
     a.max_query_length   = longest_query_;
     a.max_bandwidth_hint = widest_band_;
-    const int rc         = gwhip_myers_banded(&a, stream_);
-    if (rc != 0)
-    {
-        char buf[512];
-        gwhip_last_error_string(buf, sizeof(buf));
-        GW_LOG_ERROR(buf);
-        GW_CU_CHECK_ERR(static_cast<hipError_t>(rc));
-    }
+    check_gwhip(gwhip_myers_banded(&a, stream_));
 }
 
-void BandedAligner::launch(void* event_before, void* event_after)
+void BandedAligner::launch(hipEvent_t event_before, hipEvent_t event_after)
 {
-    if (event_before != nullptr) GW_CU_CHECK_ERR(hipEventRecord(static_cast<hipEvent_t>(event_before), stream_));
+    if (event_before != nullptr) GW_CU_CHECK_ERR(hipEventRecord(event_before, stream_));
     if (chunks_.size() > 1) // the side stream's work of this round starts behind what the aligner's stream holds
     {
-        hipEvent_t begin = static_cast<hipEvent_t>(upload_events_[chunks_.size()]);
-        GW_CU_CHECK_ERR(hipEventRecord(begin, stream_));
-        GW_CU_CHECK_ERR(hipStreamWaitEvent(static_cast<hipStream_t>(side_stream_), begin, 0));
+        GW_CU_CHECK_ERR(hipEventRecord(begin_, stream_));
+        GW_CU_CHECK_ERR(hipStreamWaitEvent(side_stream_, begin_, 0));
     }
     try
     {
@@ -543,38 +514,18 @@ void BandedAligner::launch(void* event_before, void* event_after)
         launched_ = false;
         throw;
     }
-    if (event_after != nullptr) GW_CU_CHECK_ERR(hipEventRecord(static_cast<hipEvent_t>(event_after), stream_));
+    if (event_after != nullptr) GW_CU_CHECK_ERR(hipEventRecord(event_after, stream_));
 }
 
-void BandedAligner::join_side_stream()
-{
-    if (chunks_.size() <= 1) return;
-    hipEvent_t done = static_cast<hipEvent_t>(upload_events_[chunks_.size() + 1]);
-    GW_CU_CHECK_ERR(hipEventRecord(done, static_cast<hipStream_t>(side_stream_)));
-    GW_CU_CHECK_ERR(hipStreamWaitEvent(stream_, done, 0));
-}
-
-void BandedAligner::prepare_head()
+void BandedAligner::fetch_head_slice(const Chunk& c, hipStream_t s)
 {
     // result offsets and metadata follow the kernels to the host (pinned), as the reference's align_all() does with its
     // result_starts (aligner_global_myers_banded.cpp:372-374): sync_alignments() and get_alignments_device() read
     // them after the stream has drained
-    const size_t un = chunks_.empty() ? 0 : static_cast<size_t>(chunks_.back().hi);
-    if (head_ == nullptr || head_cap_ < (2 * un + 1) * 4) // (sync_alignments() hands the buffer to the views' block)
-    {
-        if (head_ != nullptr) pinned_release(head_, head_cap_);
-        head_ = pinned_acquire((2 * un + 1) * 4, &head_cap_);
-    }
-    n_head_ = static_cast<int32_t>(un);
-}
-
-void BandedAligner::fetch_head_slice(const Chunk& c, void* stream)
-{
-    const size_t un = static_cast<size_t>(n_head_), lo = static_cast<size_t>(c.lo), m = static_cast<size_t>(c.hi - c.lo);
-    hipStream_t s   = static_cast<hipStream_t>(stream);
+    const size_t lo = static_cast<size_t>(c.lo), m = static_cast<size_t>(c.hi - c.lo);
     // entry hi of the offsets is the number of runs up to the chunk's end (the batch's total for the last chunk)
-    GW_CU_CHECK_ERR(hipMemcpyAsync(head_ + lo * 4, d_result_starts_ + lo, (m + 1) * 4, hipMemcpyDeviceToHost, s));
-    GW_CU_CHECK_ERR(hipMemcpyAsync(head_ + (un + 1 + lo) * 4, d_metadata_ + lo, m * 4, hipMemcpyDeviceToHost, s));
+    GW_CU_CHECK_ERR(hipMemcpyAsync(head_.offsets() + lo, d_result_starts_ + lo, (m + 1) * 4, hipMemcpyDeviceToHost, s));
+    GW_CU_CHECK_ERR(hipMemcpyAsync(head_.metadata() + lo, d_metadata_ + lo, m * 4, hipMemcpyDeviceToHost, s));
 }
 
 void BandedAligner::relaunch_resident()
@@ -627,8 +578,8 @@ StatusType BandedAligner::sync_alignments()
     auto block            = std::make_shared<PackedAlignmentBlock>();
     block->expand_states  = expand_results_;
     const size_t un       = static_cast<size_t>(n);
-    if (!launched_ || n_head_ != n || head_ == nullptr) throw std::runtime_error("sync_alignments() called before align_all()");
-    Tracer trace;
+    if (!launched_ || head_.pairs != n || head_.data == nullptr) throw std::runtime_error("sync_alignments() called before align_all()");
+    Tracer trace{switches_.trace};
     // From here on the batch's pinned arrays belong to the block while copies from / into them may be in flight: any exception
     // below (bad_alloc, a HIP error) must first drain the stream -- the block's destructor hands the pinned buffers back to the
     // process-wide cache -- and leave the aligner in its empty, consistent state.
@@ -638,12 +589,9 @@ StatusType BandedAligner::sync_alignments()
         block->sequences         = block->sequences_buffer;
         block->seq_starts_buffer = reinterpret_cast<char*>(seq_starts_h_.detach(&block->seq_starts_bytes));
         block->seq_starts        = reinterpret_cast<const int64_t*>(block->seq_starts_buffer);
-        block->head_buffer       = head_;
-        block->head_bytes        = head_cap_;
-        block->run_starts        = reinterpret_cast<const int32_t*>(head_);
-        block->metadata          = reinterpret_cast<const uint32_t*>(head_) + un + 1; // the kernels write metadata[i] = i | flags
-        head_                    = nullptr;
-        head_cap_                = 0;
+        block->run_starts        = head_.offsets();
+        block->metadata          = head_.metadata(); // the kernels write metadata[i] = i | flags
+        block->head_buffer       = head_.detach(&block->head_bytes);
         block->allocate_views(un);
         alignments_.resize(un);
         trace.mark("sync: view storage");
@@ -669,29 +617,22 @@ StatusType BandedAligner::sync_alignments()
         uploads_in_flight_ = false;
         trace.mark("sync: stream drained (H2D + kernels)");
         const size_t total = static_cast<size_t>(block->run_starts[un]);
-        if (chunks_.size() > 1 && mirror_ != nullptr && static_cast<int64_t>(total) <= mirror_runs_)
+        // the chunks' kernels have put the runs into the mirror already, if it holds them all; else into a buffer of the same
+        // layout by copies here. Either way the block takes the buffer over
+        const bool mirrored = chunks_.size() > 1 && mirror_.data != nullptr && static_cast<int64_t>(total) <= mirror_.runs;
+        RunsMirror copied;
+        if (!mirrored) copied.acquire_runs(static_cast<int64_t>(total));
+        RunsMirror& runs = mirrored ? mirror_ : copied;
+        int8_t* ops      = runs.ops();
+        int32_t* counts  = runs.counts();
+        block->ops       = ops;
+        block->counts    = counts;
+        block->pinned    = runs.detach(&block->pinned_bytes);
+        if (!mirrored && total > 0)
         {
-            // the chunks' kernels have put the runs there already: the block takes the buffer over
-            block->pinned       = mirror_;
-            block->pinned_bytes = mirror_cap_;
-            block->ops          = reinterpret_cast<const int8_t*>(mirror_);
-            block->counts       = reinterpret_cast<const int32_t*>(mirror_ + static_cast<size_t>((mirror_runs_ + 63) & ~int64_t(63)));
-            mirror_             = nullptr;
-            mirror_cap_         = 0;
-            mirror_runs_        = 0;
-        }
-        else
-        {
-            const size_t counts_at = (total + 63) & ~size_t(63);
-            block->pinned          = pinned_acquire(counts_at + total * 4 + 64, &block->pinned_bytes);
-            block->ops             = reinterpret_cast<const int8_t*>(block->pinned);
-            block->counts          = reinterpret_cast<const int32_t*>(block->pinned + counts_at);
-            if (total > 0)
-            {
-                GW_CU_CHECK_ERR(hipMemcpyAsync(block->pinned, d_results_, total, hipMemcpyDeviceToHost, stream_));
-                GW_CU_CHECK_ERR(hipMemcpyAsync(block->pinned + counts_at, d_result_counts_, total * 4, hipMemcpyDeviceToHost, stream_));
-                GW_CU_CHECK_ERR(hipStreamSynchronize(stream_));
-            }
+            GW_CU_CHECK_ERR(hipMemcpyAsync(ops, d_results_, total, hipMemcpyDeviceToHost, stream_));
+            GW_CU_CHECK_ERR(hipMemcpyAsync(counts, d_result_counts_, total * 4, hipMemcpyDeviceToHost, stream_));
+            GW_CU_CHECK_ERR(hipStreamSynchronize(stream_));
         }
         trace.mark("sync: runs on the host");
         total_length_h_ = static_cast<int64_t>(total);
@@ -718,7 +659,7 @@ DeviceAlignmentsPtrs BandedAligner::get_alignments_device() const
     r.cigar_offsets    = d_result_starts_;
     r.metadata         = d_metadata_;
     // after align_all() + a stream synchronisation the offsets are on the host; after sync_alignments() the total is kept
-    r.total_length     = (launched_ && head_ != nullptr) ? reinterpret_cast<const int32_t*>(head_)[static_cast<size_t>(n_head_)] : total_length_h_;
+    r.total_length     = (launched_ && head_.data != nullptr) ? head_.offsets()[head_.pairs] : total_length_h_;
     r.n_alignments     = launched_ ? num_alignments() : n_last_;
     return r;
 }

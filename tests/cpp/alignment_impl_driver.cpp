@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "alignment_impl.hpp"
+#include "host_common.hpp"
 
 using namespace claraparabricks::genomeworks::cudaaligner;
 
@@ -38,6 +39,20 @@ int main()
         a.set_status(StatusType::success);
         a.set_alignment_type(AlignmentType::global_alignment);
         std::cout << "after_set\t" << static_cast<int>(a.get_status()) << '\t' << static_cast<int>(a.get_alignment_type()) << '\n';
+    }
+    {
+        // gwhost::reverse_bytes (the un-reversal of the kernels' back-to-front paths: a byte-swapped word per eight states, then
+        // the tail) against a plain reverse loop, for lengths around the word size
+        std::string bad;
+        for (size_t n : {0, 1, 7, 8, 9, 15, 16, 17, 1000})
+        {
+            std::vector<uint8_t> src(n + 2, 0xee), got(n + 2, 0xdd), want(n + 2, 0xdd);
+            for (size_t i = 0; i < n; ++i) src[1 + i] = static_cast<uint8_t>((i * 37 + 11) % 251);
+            for (size_t i = 0; i < n; ++i) want[1 + i] = src[1 + n - 1 - i];
+            gwhost::reverse_bytes(got.data() + 1, src.data() + 1, n); // (the guard bytes around the range stay)
+            if (got != want) bad += std::to_string(n) + ",";
+        }
+        std::cout << "reverse_bytes\t" << (bad.empty() ? "ok" : bad) << '\n';
     }
     std::string line;
     while (std::getline(std::cin, line))

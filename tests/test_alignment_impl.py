@@ -38,7 +38,7 @@ def test_reference_vectors(driver):
     rows = run(driver, cases)
     assert rows[0] == ["initial", "1", "1"]      # StatusType::uninitialized, AlignmentType::unset
     assert rows[1] == ["after_set", "0", "0"]    # success, global_alignment
-    rows = rows[2:]
+    rows = rows[3:]
     per_case = 4  # AlignmentImpl, PackedAlignment(runs), runs, PackedAlignment(states)
     assert len(rows) == per_case * len(cases)
     for k, c in enumerate(cases):
@@ -59,12 +59,48 @@ def test_reference_vectors(driver):
 
 def test_line_wrapped_output_and_empty_alignment(driver):
     rows = run(driver, [dict(query="ACGTA", target="ACTA", alignment=[0, 0, 3, 0, 0], is_optimal=True),
-                        dict(query="", target="", alignment=[], is_optimal=True)])[2:]
+                        dict(query="", target="", alignment=[], is_optimal=True)])[3:]
     impl = rows[0]
     # operator<< with linebreak_after = 3: query / pairing / target in blocks of three columns
     assert impl[13] == "ACG/|| /AC-/TA/||/TA//"
     empty = rows[4]
     assert empty[0] == "AlignmentImpl" and empty[7] == "" and empty[8] == "" and empty[9] == "0"
+
+
+def test_reversed_states_helper_equals_a_plain_reverse_loop(driver):
+    """gwhost::reverse_bytes (host_common.hpp), which turns the kernels' back-to-front paths around for AlignerGlobal and
+    AlignerSemiglobal: lengths 0, 1, 7, 8, 9, 15, 16, 17 and 1000 against a plain loop, guard bytes around the range."""
+    assert run(driver, [])[2] == ["reverse_bytes", "ok"]
+
+
+def test_banded_pipeline_submits_the_recorded_calls(tmp_path):
+    """The banded aligner's three-stream pipeline replayed on the CPU (tests/cpp/banded_pipeline_replay_driver.cpp: recording
+    stand-ins for the HIP runtime and the kernels' entry points, defined in the executable so that they take precedence over
+    the libraries'): create_aligner, 640 x add_alignment, align_all, relaunch, sync_alignments and a second batch with another
+    chunk count on the same object, for one chunk, five chunks, and seven chunks with a mirror of three runs. Every HIP call --
+    stream by role, copy sizes and offsets, events by role and chunk -- equals tests/golden/banded_pipeline_calls*.txt, recorded
+    from the commit before the host classes' streams, events and pinned buffers were restructured."""
+    from genomeworks_amd import build
+    build.build_host()
+    exe = str(tmp_path / "banded_pipeline_replay_driver")
+    lib = os.path.join(ROOT, "genomeworks_amd", "lib")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(ROOT, "include"),
+                    "-I", os.path.join(ROOT, "genomeworks_amd", "host"), "-I", os.path.join(ROCM, "include"), "-o", exe,
+                    os.path.join(ROOT, "tests", "cpp", "banded_pipeline_replay_driver.cpp"), "-rdynamic", "-L", lib,
+                    "-lgenomeworks_amd", "-lgwhip", "-L", os.path.join(ROCM, "lib"), "-lamdhip64", "-Wl,-rpath," + lib,
+                    "-Wl,-rpath," + os.path.join(ROCM, "lib"), "-pthread"], check=True)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("GW_ALIGNER_")}
+    # (the second run: the second chunk's workspace does not fit, align_all() drains its streams and throws, and the same object
+    # is reset and takes a whole batch)
+    for args, golden in (([], "banded_pipeline_calls.txt"), (["--fail-alloc"], "banded_pipeline_calls_alloc_failure.txt")):
+        out = subprocess.run([exe] + args, capture_output=True, text=True, timeout=120, env=env)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr
+        with open(os.path.join(ROOT, "tests", "golden", golden)) as f:
+            want = f.read().split("\n")
+        got = out.stdout.split("\n")
+        first = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
+        assert got == want, "%s: first difference at line %d:\n  got  %r\n  want %r" % (
+            golden, first + 1, got[first] if first < len(got) else None, want[first] if first < len(want) else None)
 
 
 def test_worker_pool_runs_every_task_once(tmp_path):

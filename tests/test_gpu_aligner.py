@@ -1,4 +1,5 @@
 """GPU parity tests of the banded Myers aligner (through the C-ABI) vs the CPU oracle and the known answers."""
+import functools
 import random
 
 import pytest
@@ -113,11 +114,10 @@ def test_bases_outside_acgt_and_odd_offsets_equal_the_oracle():
         assert [(r.query, r.target) for r in res[:50]] == pairs[:50]
 
 
-def test_chunked_batch_runs_reach_the_host_through_the_mirror_or_the_copy(monkeypatch):
-    """A chunked batch's runs are written to a pinned mirror by the chunks' kernels (gwhip_myers_args::results_host);
-    sync_alignments() copies for itself when the batch has more runs than the mirror holds. Both ways, and one chunk, give the
-    same alignments as the oracle: pairs with a run per base (every other base substituted) next to identical pairs, so that
-    the capacity cut falls inside a chunk, and a batch that fits."""
+@functools.lru_cache(maxsize=None)
+def _run_heavy_pairs():
+    """640 pairs with a run per base (every other base substituted) next to identical and lightly mutated ones, and what the
+    oracle says about them at max_bandwidth 512: (pairs, oracle results)."""
     rng = random.Random(99)
     swap = {"A": "C", "C": "G", "G": "T", "T": "A"}
     pairs = []
@@ -131,7 +131,15 @@ def test_chunked_batch_runs_reach_the_host_through_the_mirror_or_the_copy(monkey
         else:
             t = _mutate(rng, q, 3) or "A"
         pairs.append((q, t))
-    ref = [A.align(q, t, 512) for q, t in pairs]
+    return tuple(pairs), tuple(A.align(q, t, 512) for q, t in pairs)
+
+
+def test_chunked_batch_runs_reach_the_host_through_the_mirror_or_the_copy(monkeypatch):
+    """A chunked batch's runs are written to a pinned mirror by the chunks' kernels (gwhip_myers_args::results_host);
+    sync_alignments() copies for itself when the batch has more runs than the mirror holds. Both ways, and one chunk, give the
+    same alignments as the oracle: pairs with a run per base (every other base substituted) next to identical pairs, so that
+    the capacity cut falls inside a chunk, and a batch that fits."""
+    pairs, ref = _run_heavy_pairs()
     want = [(e["status"], e["cigar_extended"], e["optimal"], e["edit_distance"]) for e in ref]
     assert sum(len(e["runs"]) for e in ref) > 16 * len(pairs)  # more than the default capacity of a small batch
     for chunks, mirror_runs in (("1", None), ("5", None), ("5", "1000"), ("5", "10000000"), ("7", "3")):
@@ -142,6 +150,38 @@ def test_chunked_batch_runs_reach_the_host_through_the_mirror_or_the_copy(monkey
             monkeypatch.setenv("GW_ALIGNER_MIRROR_RUNS", mirror_runs)
         got = [(r.status, r.cigar_extended, r.is_optimal, r.edit_distance) for r in run(pairs, max_bandwidth=512)]
         assert got == want, (chunks, mirror_runs)
+
+
+def test_one_aligner_object_relaunches_a_chunked_batch_and_takes_a_second_batch(monkeypatch):
+    """One CudaAlignerBatch across batches: a five-chunk batch is aligned and relaunched on its resident inputs, its
+    device-resident form agrees with the host's in pairs and total runs, and its alignments equal the oracle; then, after
+    reset(), the same object aligns the first 300 pairs with other switches (seven chunks asked for, a mirror of three runs: the
+    copy path). The object's streams and events outlive the first batch, its event pool has to cover the new chunk count, and
+    the pinned head and mirror that sync_alignments() handed to the first batch's views are acquired afresh."""
+    from genomeworks_amd import cudaaligner
+    pairs, ref = _run_heavy_pairs()
+    want = [(e["status"], e["cigar_extended"], e["optimal"], e["edit_distance"]) for e in ref]
+    monkeypatch.setenv("GW_ALIGNER_CHUNKS", "5")
+    monkeypatch.delenv("GW_ALIGNER_MIRROR_RUNS", raising=False)
+    al = cudaaligner.CudaAlignerBatch(max_bandwidth=512, max_device_memory_allocator_caching_size=4 << 30)
+    for q, t in pairs:
+        assert al.add_alignment(q, t) == 0
+    al.align_all()
+    al.relaunch()
+    device = al.get_alignments_device()
+    res = al.get_alignments()
+    assert device["n_alignments"] == len(res) == len(pairs)
+    # (the oracle's runs are the device's runs, cut where the kernels cut them; the alignments below are the oracle's too)
+    assert device["total_length"] == sum(len(e["runs"]) for e in ref)
+    assert [(r.status, r.cigar_extended, r.is_optimal, r.edit_distance) for r in res] == want
+
+    monkeypatch.setenv("GW_ALIGNER_CHUNKS", "7")
+    monkeypatch.setenv("GW_ALIGNER_MIRROR_RUNS", "3")
+    al.reset()
+    for q, t in pairs[:300]:
+        assert al.add_alignment(q, t) == 0
+    al.align_all()
+    assert [(r.status, r.cigar_extended, r.is_optimal, r.edit_distance) for r in al.get_alignments()] == want[:300]
 
 
 def test_group_kernel_equals_one_lane_kernel(monkeypatch):
