@@ -62,16 +62,29 @@ struct gw_aligner
         return ret;                                                                                                    \
     }
 
-static void fill(gw_poa_batch_config* out, const poa::BatchConfig& c)
+static gw_poa_batch_config to_c(const poa::BatchConfig& c)
 {
-    out->max_sequence_size         = c.max_sequence_size;
-    out->max_consensus_size        = c.max_consensus_size;
-    out->max_nodes_per_graph       = c.max_nodes_per_graph;
-    out->matrix_sequence_dimension = c.matrix_sequence_dimension;
-    out->alignment_band_width      = c.alignment_band_width;
-    out->max_sequences_per_poa     = c.max_sequences_per_poa;
-    out->band_mode                 = static_cast<int32_t>(c.band_mode);
-    out->max_banded_pred_distance  = c.max_banded_pred_distance;
+    return gw_poa_batch_config{c.max_sequence_size,    c.max_consensus_size,    c.max_nodes_per_graph,             c.matrix_sequence_dimension,
+                               c.alignment_band_width, c.max_sequences_per_poa, static_cast<int32_t>(c.band_mode), c.max_banded_pred_distance};
+}
+
+// (the fields were validated when the config was built: rebuilt through the explicit ctor)
+static poa::BatchConfig from_c(const gw_poa_batch_config* cfg)
+{
+    return poa::BatchConfig(cfg->max_sequence_size, cfg->max_consensus_size, cfg->max_nodes_per_graph, cfg->alignment_band_width,
+                            cfg->max_sequences_per_poa, cfg->matrix_sequence_dimension, static_cast<poa::BandMode>(cfg->band_mode),
+                            cfg->max_banded_pred_distance);
+}
+
+// windows from the flat arrays of the C API: reads_per_window[w] reads each, seqs / lengths over all reads in window order
+static std::vector<std::vector<std::string>> unpack_windows(int32_t n_windows, const int32_t* reads_per_window, const char* const* seqs,
+                                                            const int32_t* lengths)
+{
+    std::vector<std::vector<std::string>> windows(static_cast<size_t>(n_windows));
+    size_t at = 0;
+    for (int32_t w = 0; w < n_windows; ++w)
+        for (int32_t r = 0; r < reads_per_window[w]; ++r, ++at) windows[static_cast<size_t>(w)].emplace_back(seqs[at], static_cast<size_t>(lengths[at]));
+    return windows;
 }
 
 extern "C" {
@@ -83,7 +96,7 @@ int gw_poa_batch_config_default(gw_poa_batch_config* out, int32_t max_seq_sz, in
     GW_TRY
     poa::BatchConfig c(max_seq_sz, max_seq_per_poa, band_width, static_cast<poa::BandMode>(band_mode),
                        adaptive_storage_factor, graph_length_factor, max_pred_dist);
-    fill(out, c);
+    *out = to_c(c);
     return 0;
     GW_CATCH(-1)
 }
@@ -95,7 +108,7 @@ int gw_poa_batch_config_full(gw_poa_batch_config* out, int32_t max_seq_sz, int32
     GW_TRY
     poa::BatchConfig c(max_seq_sz, max_consensus_sz, max_nodes_per_poa, band_width, max_seq_per_poa, matrix_seq_dim,
                        static_cast<poa::BandMode>(band_mode), max_pred_distance);
-    fill(out, c);
+    *out = to_c(c);
     return 0;
     GW_CATCH(-1)
 }
@@ -105,12 +118,8 @@ gw_poa_batch* gw_poa_create_batch(int32_t device_id, void* stream, int64_t max_m
                                   int16_t match_score)
 {
     GW_TRY
-    // the fields were validated when the config was built; rebuild through the explicit ctor
-    poa::BatchConfig c(cfg->max_sequence_size, cfg->max_consensus_size, cfg->max_nodes_per_graph,
-                       cfg->alignment_band_width, cfg->max_sequences_per_poa, cfg->matrix_sequence_dimension,
-                       static_cast<poa::BandMode>(cfg->band_mode), cfg->max_banded_pred_distance);
     auto h   = std::make_unique<gw_poa_batch>();
-    h->batch = poa::create_batch(device_id, static_cast<cudaStream_t>(stream), max_mem, output_mask, c, gap_score,
+    h->batch = poa::create_batch(device_id, static_cast<cudaStream_t>(stream), max_mem, output_mask, from_c(cfg), gap_score,
                                  mismatch_score, match_score);
     h->impl  = dynamic_cast<poa::PoaBatch*>(h->batch.get());
     return h.release();
@@ -724,13 +733,8 @@ gw_poa_multi* gw_poa_multi_device_run(int32_t n_windows, const int32_t* reads_pe
                                       int16_t gap_score, int16_t mismatch_score, int16_t match_score)
 {
     GW_TRY
-    std::vector<std::vector<std::string>> windows(static_cast<size_t>(n_windows));
-    size_t at = 0;
-    for (int32_t w = 0; w < n_windows; ++w)
-        for (int32_t r = 0; r < reads_per_window[w]; ++r, ++at) windows[static_cast<size_t>(w)].emplace_back(seqs[at], static_cast<size_t>(lengths[at]));
-    const poa::BatchConfig c(cfg->max_sequence_size, cfg->max_consensus_size, cfg->max_nodes_per_graph, cfg->alignment_band_width,
-                             cfg->max_sequences_per_poa, cfg->matrix_sequence_dimension, static_cast<poa::BandMode>(cfg->band_mode),
-                             cfg->max_banded_pred_distance);
+    const std::vector<std::vector<std::string>> windows = unpack_windows(n_windows, reads_per_window, seqs, lengths);
+    const poa::BatchConfig c = from_c(cfg);
     poa::MultiDeviceConfig mc;
     mc.devices.assign(devices, devices + n_devices);
     mc.batches_per_device = batches_per_device;
@@ -818,17 +822,7 @@ int gw_poa_size_plan_class(gw_poa_size_plan* p, int32_t k, gw_poa_batch_config* 
 {
     GW_TRY
     const poa::BatchConfig& c = p->plan.configs.at(static_cast<size_t>(k));
-    if (cfg)
-    {
-        cfg->max_sequence_size         = c.max_sequence_size;
-        cfg->max_consensus_size        = c.max_consensus_size;
-        cfg->max_nodes_per_graph       = c.max_nodes_per_graph;
-        cfg->matrix_sequence_dimension = c.matrix_sequence_dimension;
-        cfg->alignment_band_width      = c.alignment_band_width;
-        cfg->max_sequences_per_poa     = c.max_sequences_per_poa;
-        cfg->band_mode                 = static_cast<int32_t>(c.band_mode);
-        cfg->max_banded_pred_distance  = c.max_banded_pred_distance;
-    }
+    if (cfg) *cfg = to_c(c);
     if (bytes_per_window) *bytes_per_window = p->plan.bytes_per_window.at(static_cast<size_t>(k));
     if (n_windows) *n_windows = static_cast<int32_t>(p->plan.groups.at(static_cast<size_t>(k)).size());
     return 0;
@@ -873,10 +867,7 @@ gw_poa_multi* gw_poa_size_classes_run(int32_t n_windows, const int32_t* reads_pe
                                       int16_t mismatch_score, int16_t match_score, double* compute_seconds)
 {
     GW_TRY
-    std::vector<std::vector<std::string>> windows(static_cast<size_t>(n_windows));
-    size_t at = 0;
-    for (int32_t w = 0; w < n_windows; ++w)
-        for (int32_t r = 0; r < reads_per_window[w]; ++r, ++at) windows[static_cast<size_t>(w)].emplace_back(seqs[at], static_cast<size_t>(lengths[at]));
+    const std::vector<std::vector<std::string>> windows = unpack_windows(n_windows, reads_per_window, seqs, lengths);
     auto h = std::make_unique<gw_poa_multi>();
     poa::process_windows_size_classes(h->out, windows, plan->plan, device, memory_budget, output_mask, gap_score, mismatch_score, match_score,
                                       compute_seconds);
@@ -899,10 +890,7 @@ static int emit_plan(const std::vector<poa::BatchConfig>& shapes, const std::vec
     int32_t pos = 0;
     for (size_t b = 0; b < shapes.size(); b++)
     {
-        const poa::BatchConfig& c = shapes[b];
-        batch_cfgs[b] = gw_poa_batch_config{c.max_sequence_size, c.max_consensus_size, c.max_nodes_per_graph,
-                                            c.matrix_sequence_dimension, c.alignment_band_width, c.max_sequences_per_poa,
-                                            static_cast<int32_t>(c.band_mode), c.max_banded_pred_distance};
+        batch_cfgs[b]       = to_c(shapes[b]);
         groups_per_batch[b] = static_cast<int32_t>(groups[b].size());
         for (int32_t id : groups[b])
         {
@@ -954,9 +942,7 @@ int32_t gw_poa_estimate_max_poas(const gw_poa_batch_config* cfg, int32_t msa_fla
                                  int32_t mismatch_score, int32_t gap_score, int32_t match_score)
 {
     GW_TRY
-    const poa::BatchConfig c(cfg->max_sequence_size, cfg->max_consensus_size, cfg->max_nodes_per_graph,
-                                 cfg->alignment_band_width, cfg->max_sequences_per_poa, cfg->matrix_sequence_dimension,
-                                 static_cast<poa::BandMode>(cfg->band_mode), cfg->max_banded_pred_distance);
+    const poa::BatchConfig c = from_c(cfg);
     return poa::estimate_max_poas(c, msa_flag != 0, gpu_memory_usage_quota, mismatch_score, gap_score, match_score);
     GW_CATCH(-1)
 }
@@ -965,9 +951,7 @@ int64_t gw_poa_window_device_bytes(const gw_poa_batch_config* cfg, int32_t msa_f
                                    int32_t match_score)
 {
     GW_TRY
-    const poa::BatchConfig c(cfg->max_sequence_size, cfg->max_consensus_size, cfg->max_nodes_per_graph,
-                             cfg->alignment_band_width, cfg->max_sequences_per_poa, cfg->matrix_sequence_dimension,
-                             static_cast<poa::BandMode>(cfg->band_mode), cfg->max_banded_pred_distance);
+    const poa::BatchConfig c = from_c(cfg);
     const gwhip_poa_config dc = poa::make_device_config(c, static_cast<int8_t>(msa_flag ? poa::OutputType::msa : poa::OutputType::consensus),
                                                         gap_score, mismatch_score, match_score);
     int64_t per_poa = 0, per_matrix = 0;

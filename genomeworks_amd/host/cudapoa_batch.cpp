@@ -26,6 +26,7 @@
 #include "../../include/gwhip.h"
 #include "alignment_impl.hpp" // pinned_acquire / pinned_release (the process-wide cache of pinned buffers, runtime.cpp)
 #include "host_common.hpp"
+#include "owned_hip.hpp"
 #include "poa_batch_impl.hpp"
 
 namespace claraparabricks
@@ -42,6 +43,11 @@ constexpr int32_t kMinBandWidth   = 128; // CUDAPOA_MIN_BAND_WIDTH (API constant
 constexpr int32_t kRightPadding   = 8;   // CUDAPOA_BANDED_MATRIX_RIGHT_PADDING
 constexpr uint8_t kKernelError    = 0xFF;
 std::atomic<int32_t> g_batch_ids{0};     // one process-wide atomic counter (the reference has six racy ones)
+
+std::runtime_error requires_at_least(int64_t bytes)
+{
+    return std::runtime_error("Requires at least " + std::to_string(bytes) + " bytes of device memory per CUDAPOA batch to process correctly.");
+}
 } // namespace
 
 StatusType Init()
@@ -200,66 +206,32 @@ PoaBatch::PoaBatch(int32_t device_id, cudaStream_t stream, DefaultDeviceAllocato
     gwhip_poa_bytes_per_window(&cfg_, &per_poa, &per_matrix);
     const int64_t avail_mem = std::min(get_size_of_largest_free_memory_block(allocator_), max_mem);
     const int64_t minimum   = per_poa + per_matrix;
-    if (avail_mem < minimum)
-    {
-        std::string msg = std::string("Requires at least ").append(std::to_string(minimum)).append(
-            " bytes of device memory per CUDAPOA batch to process correctly.");
-        throw std::runtime_error(msg);
-    }
-    // ---- carve the device block: [sequences | weights | lengths | windows | consensus | coverage | msa | cells | workspace]
+    if (avail_mem < minimum) throw requires_at_least(minimum);
     int64_t guess = std::min<int64_t>(avail_mem / (per_poa + per_matrix), INT32_MAX);
     // window_details.seq_starts and the host write offset are int32 (as in the reference, cudapoa_batch.cuh:456-537): a
     // 288 GB device could otherwise hold more input bases than they can index
     const int64_t per_poa_input = std::max<int64_t>(1, static_cast<int64_t>(max_sequences_per_poa_) *
                                                            cudautils::align<int32_t, 4>(batch_size_.max_sequence_size));
-    guess = std::min<int64_t>(guess, (static_cast<int64_t>(INT32_MAX) - 8192) / per_poa_input);
-    size_t o[10];
+    guess     = std::min<int64_t>(guess, (static_cast<int64_t>(INT32_MAX) - 8192) / per_poa_input);
     max_poas_ = static_cast<int32_t>(std::max<int64_t>(guess, 1));
-    while (max_poas_ > 1 && static_cast<int64_t>(plan(max_poas_, o)) > avail_mem) max_poas_--;
-    device_block_bytes_ = plan(max_poas_, o);
-    if (static_cast<int64_t>(device_block_bytes_) > avail_mem)
-    {
-        std::string msg = std::string("Requires at least ").append(std::to_string(device_block_bytes_)).append(
-            " bytes of device memory per CUDAPOA batch to process correctly.");
-        throw std::runtime_error(msg);
-    }
+    while (max_poas_ > 1 && static_cast<int64_t>(plan(max_poas_).block.bytes) > avail_mem) max_poas_--;
+    layout_ = plan(max_poas_);
+    if (static_cast<int64_t>(layout_.block.bytes) > avail_mem) throw requires_at_least(static_cast<int64_t>(layout_.block.bytes));
     score_buffer_bytes_ = static_cast<size_t>(per_matrix) * static_cast<size_t>(max_poas_);
     workspace_bytes_    = gwhip_poa_workspace_bytes(&cfg_, max_poas_, 0);
-    const size_t o_seq = o[0], o_w = o[1], o_len = o[2], o_wd = o[3], o_cons = o[4], o_cov = o[5], o_msa = o[6], o_cells = o[7], o_ws = o[8];
-    const size_t seq_bytes = o_w - o_seq, len_bytes = o_wd - o_len, wd_bytes = o_cons - o_wd, cons_bytes = o_cov - o_cons;
-    const size_t cov_bytes = o_msa - o_cov, msa_bytes = o_cells - o_msa, cell_bytes = o_ws - o_cells;
-    device_block_ = allocator_.allocate(device_block_bytes_, {stream_});
-    d_sequences_  = reinterpret_cast<uint8_t*>(device_block_ + o_seq);
-    d_weights_    = reinterpret_cast<int8_t*>(device_block_ + o_w);
-    d_seq_lens_   = reinterpret_cast<int32_t*>(device_block_ + o_len);
-    d_windows_    = reinterpret_cast<gwhip_window_details*>(device_block_ + o_wd);
-    d_consensus_  = reinterpret_cast<uint8_t*>(device_block_ + o_cons);
-    d_coverage_   = reinterpret_cast<uint16_t*>(device_block_ + o_cov);
-    d_msa_        = msa_bytes ? reinterpret_cast<uint8_t*>(device_block_ + o_msa) : nullptr;
-    d_cells_      = reinterpret_cast<uint64_t*>(device_block_ + o_cells);
-    d_work_counters_ = reinterpret_cast<uint32_t*>(device_block_ + o_ws - 256);
-    d_workspace_  = device_block_ + o_ws;
-    input_capacity_ = seq_bytes - 4096;
+    device_block_       = allocator_.allocate(layout_.block.bytes, {stream_});
+    d_                  = layout_.in(device_block_);
+    input_capacity_     = layout_.sequence_bytes - 4096;
     // the kernels read up to 2 KiB past a read (never consumed): keep that slack zero
-    GW_CU_CHECK_ERR(hipMemsetAsync(d_sequences_, 0, seq_bytes, stream_));
-    GW_CU_CHECK_ERR(hipMemsetAsync(d_weights_, 0, seq_bytes, stream_));
-    GW_CU_CHECK_ERR(hipMemsetAsync(d_work_counters_, 0, 256, stream_)); // (a launch leaves them at zero again)
+    GW_CU_CHECK_ERR(hipMemsetAsync(d_.sequences, 0, layout_.sequence_bytes, stream_));
+    GW_CU_CHECK_ERR(hipMemsetAsync(d_.weights, 0, layout_.sequence_bytes, stream_));
+    GW_CU_CHECK_ERR(hipMemsetAsync(d_.work_counters, 0, 256, stream_)); // (a launch leaves them at zero again)
 
-    // ---- pinned staging block ----
-    host_block_bytes_ = seq_bytes * 2 + len_bytes + wd_bytes + cons_bytes + cov_bytes + msa_bytes + cell_bytes;
-    // from the process-wide cache of pinned buffers (runtime.cpp): pinning and unpinning 1.2 GB took 200 and 100 ms of every
-    // construction and destruction of a BatchConfig(1024, 200) batch with 32 GB of device memory
-    host_block_ = cudaaligner::pinned_acquire(host_block_bytes_, &host_block_capacity_);
-    size_t h          = 0;
-    auto htake        = [&](size_t b) { size_t o = h; h += b; return o; };
-    h_sequences_      = reinterpret_cast<uint8_t*>(host_block_ + htake(seq_bytes));
-    h_weights_        = reinterpret_cast<int8_t*>(host_block_ + htake(seq_bytes));
-    h_seq_lens_       = reinterpret_cast<int32_t*>(host_block_ + htake(len_bytes));
-    h_windows_        = reinterpret_cast<gwhip_window_details*>(host_block_ + htake(wd_bytes));
-    h_consensus_      = reinterpret_cast<uint8_t*>(host_block_ + htake(cons_bytes));
-    h_coverage_       = reinterpret_cast<uint16_t*>(host_block_ + htake(cov_bytes));
-    h_msa_            = msa_bytes ? reinterpret_cast<uint8_t*>(host_block_ + htake(msa_bytes)) : nullptr;
-    h_cells_          = reinterpret_cast<uint64_t*>(host_block_ + htake(cell_bytes));
+    // the pinned staging block: the device block without the workspace, from the process-wide cache of pinned buffers
+    // (runtime.cpp): pinning and unpinning 1.2 GB took 200 and 100 ms of every construction and destruction of a
+    // BatchConfig(1024, 200) batch with 32 GB of device memory
+    host_block_ = cudaaligner::pinned_acquire(layout_.workspace.offset, &host_block_capacity_);
+    h_          = layout_.in(host_block_);
     // (the staging arrays are not cleared: an upload covers exactly the bytes add_seq_to_poa() wrote, padding included, and
     // the read-ahead slack is zeroed on the device -- clearing 2 x 600 MB of pinned memory was most of the construction time of
     // a BatchConfig(1024, 200) batch with tens of GB of device memory)
@@ -276,7 +248,7 @@ PoaBatch::~PoaBatch()
     (void)hipStreamSynchronize(stream_);
     live_batches(device_id_).fetch_sub(1);
     if (host_block_ != nullptr) cudaaligner::pinned_release(host_block_, host_block_capacity_);
-    if (device_block_ != nullptr) allocator_.deallocate(device_block_, device_block_bytes_);
+    if (device_block_ != nullptr) allocator_.deallocate(device_block_, layout_.block.bytes);
 }
 
 void PoaBatch::debug_message(const std::string& message)
@@ -285,25 +257,27 @@ void PoaBatch::debug_message(const std::string& message)
     GW_LOG_DEBUG(msg.c_str());
 }
 
-// Byte plan of the device block for n windows; fills the 9 section offsets, returns the total.
-size_t PoaBatch::plan(int32_t n_poas, size_t* o) const
+// The device block of a batch of n windows.
+PoaBlockLayout PoaBatch::plan(int32_t n_poas) const
 {
-    auto up          = [](size_t v) { return (v + 255) & ~size_t(255); };
-    const size_t n   = static_cast<size_t>(n_poas);
+    const size_t n     = static_cast<size_t>(n_poas);
+    const size_t reads = n * static_cast<size_t>(max_sequences_per_poa_);
+    const size_t rows  = n * static_cast<size_t>(batch_size_.max_consensus_size);
+    PoaBlockLayout l;
     // every read is padded to a multiple of 4 bytes (add_seq_to_poa)
-    const size_t seq = up(n * max_sequences_per_poa_ * static_cast<size_t>(cudautils::align<int32_t, 4>(batch_size_.max_sequence_size)) + 4096);
-    size_t off       = 0;
-    auto take        = [&](size_t b) { size_t at = off; off += b; return at; };
-    o[0] = take(seq);
-    o[1] = take(seq);
-    o[2] = take(up(n * max_sequences_per_poa_ * sizeof(int32_t)));
-    o[3] = take(up(n * sizeof(gwhip_window_details)));
-    o[4] = take(up(n * batch_size_.max_consensus_size));
-    o[5] = take(up(n * batch_size_.max_consensus_size * sizeof(uint16_t)));
-    o[6] = take((output_mask_ & OutputType::msa) ? up(n * max_sequences_per_poa_ * batch_size_.max_consensus_size) : 0);
-    o[7] = take(up(n * sizeof(uint64_t)) + 256); // + the two work counters of a persistent launch (gwhip_poa_args::work_counters)
-    o[8] = take(up(gwhip_poa_workspace_bytes(&cfg_, n_poas, 0)));
-    return off;
+    l.sequences      = l.block.take<uint8_t>(reads * static_cast<size_t>(cudautils::align<int32_t, 4>(batch_size_.max_sequence_size)) + 4096);
+    l.sequence_bytes = l.block.bytes;
+    l.weights        = l.block.take<int8_t>(l.sequence_bytes);
+    l.lengths        = l.block.take<int32_t>(reads);
+    l.windows        = l.block.take<gwhip_window_details>(n);
+    l.consensus      = l.block.take<uint8_t>(rows);
+    l.coverage       = l.block.take<uint16_t>(rows);
+    l.has_msa        = (output_mask_ & OutputType::msa) != 0;
+    l.msa            = l.block.take<uint8_t>(l.has_msa ? rows * static_cast<size_t>(max_sequences_per_poa_) : 0);
+    l.cells          = l.block.take<uint64_t>(n);
+    l.work_counters  = l.block.take<uint32_t>(64); // the two work counters of a persistent launch (gwhip_poa_args::work_counters)
+    l.workspace      = l.block.take<char>(gwhip_poa_workspace_bytes(&cfg_, n_poas, 0));
+    return l;
 }
 
 void PoaBatch::reset()
@@ -351,7 +325,7 @@ StatusType PoaBatch::add_poa()
     wd.seq_starts            = num_nucleotides_copied_;
     wd.scores_width          = 0;
     wd.scores_offset         = next_scores_offset_;
-    h_windows_[poa_count_]   = wd;
+    h_.windows[poa_count_]   = wd;
     poa_count_++;
     return StatusType::success;
 }
@@ -370,7 +344,7 @@ StatusType PoaBatch::add_seq_to_poa(const char* seq, const int8_t* weights, int3
         }
         if (all_zero) return StatusType::zero_weighted_poa_sequence;
     }
-    gwhip_window_details* wd = &h_windows_[poa_count_ - 1];
+    gwhip_window_details* wd = &h_.windows[poa_count_ - 1];
     const int32_t scores_width = cudautils::align<int32_t, 4>(seq_len + 1 + kCellsPerThread);
     if (scores_width > wd->scores_width)
     {
@@ -379,22 +353,22 @@ StatusType PoaBatch::add_seq_to_poa(const char* seq, const int8_t* weights, int3
     }
     if (static_cast<int32_t>(wd->num_seqs) >= max_sequences_per_poa_) return StatusType::exceeded_maximum_sequences_per_poa;
     wd->num_seqs++;
-    std::memcpy(&h_sequences_[num_nucleotides_copied_], seq, static_cast<size_t>(seq_len));
+    std::memcpy(&h_.sequences[num_nucleotides_copied_], seq, static_cast<size_t>(seq_len));
     if (weights == nullptr)
-        std::memset(&h_weights_[num_nucleotides_copied_], 1, static_cast<size_t>(seq_len));
+        std::memset(&h_.weights[num_nucleotides_copied_], 1, static_cast<size_t>(seq_len));
     else
     {
-        std::memcpy(&h_weights_[num_nucleotides_copied_], weights, static_cast<size_t>(seq_len));
+        std::memcpy(&h_.weights[num_nucleotides_copied_], weights, static_cast<size_t>(seq_len));
         unit_weights_only_ = false;
     }
     // padding to the 4-byte boundary: the reference leaves stale bytes there; we zero them (never consumed)
     const int32_t padded = cudautils::align<int32_t, 4>(seq_len);
     for (int32_t i = seq_len; i < padded; i++)
     {
-        h_sequences_[num_nucleotides_copied_ + i] = 0;
-        h_weights_[num_nucleotides_copied_ + i]   = 0;
+        h_.sequences[num_nucleotides_copied_ + i] = 0;
+        h_.weights[num_nucleotides_copied_ + i]   = 0;
     }
-    h_seq_lens_[global_sequence_idx_] = seq_len;
+    h_.lengths[global_sequence_idx_] = seq_len;
     num_nucleotides_copied_ += padded;
     global_sequence_idx_++;
     return StatusType::success;
@@ -441,34 +415,40 @@ gwhip_poa_args PoaBatch::kernel_args() const
     gwhip_poa_args a{};
     a.cfg              = cfg_;
     a.total_windows    = poa_count_;
-    a.sequences        = d_sequences_;
-    a.base_weights     = d_weights_;
-    a.sequence_lengths = d_seq_lens_;
-    a.window_details   = d_windows_;
-    a.consensus        = d_consensus_;
-    a.coverage         = d_coverage_;
-    a.msa              = d_msa_;
-    a.workspace        = d_workspace_;
+    a.sequences        = d_.sequences;
+    a.base_weights     = d_.weights;
+    a.sequence_lengths = d_.lengths;
+    a.window_details   = d_.windows;
+    a.consensus        = d_.consensus;
+    a.coverage         = d_.coverage;
+    a.msa              = d_.msa;
+    a.workspace        = layout_.workspace.in(device_block_);
     a.workspace_bytes  = workspace_bytes_;
-    a.cells            = d_cells_;
-    a.work_counters    = d_work_counters_;
+    a.cells            = d_.cells;
+    a.work_counters    = d_.work_counters;
     a.shared_device    = live_batches(device_id_).load(std::memory_order_relaxed) > 1 ? 1 : 0;
     return a;
 }
 
 void PoaBatch::upload_inputs()
 {
-    GW_CU_CHECK_ERR(hipMemcpyAsync(d_sequences_, h_sequences_, static_cast<size_t>(num_nucleotides_copied_), hipMemcpyHostToDevice, stream_));
+    GW_CU_CHECK_ERR(hipMemcpyAsync(d_.sequences, h_.sequences, static_cast<size_t>(num_nucleotides_copied_), hipMemcpyHostToDevice, stream_));
     // a batch whose reads all came without base weights (the common case, and the benchmark's) needs no weight upload:
     // every consumed byte is 1 (padding bytes are never read), so the device array is filled in place
     if (unit_weights_only_)
-        GW_CU_CHECK_ERR(hipMemsetAsync(d_weights_, 1, static_cast<size_t>(num_nucleotides_copied_), stream_));
+        GW_CU_CHECK_ERR(hipMemsetAsync(d_.weights, 1, static_cast<size_t>(num_nucleotides_copied_), stream_));
     else
-        GW_CU_CHECK_ERR(hipMemcpyAsync(d_weights_, h_weights_, static_cast<size_t>(num_nucleotides_copied_), hipMemcpyHostToDevice, stream_));
+        GW_CU_CHECK_ERR(hipMemcpyAsync(d_.weights, h_.weights, static_cast<size_t>(num_nucleotides_copied_), hipMemcpyHostToDevice, stream_));
     // zero the 2 KiB read-ahead slack behind the last read (it may hold an older batch's bases)
-    GW_CU_CHECK_ERR(hipMemsetAsync(d_sequences_ + num_nucleotides_copied_, 0, 2048, stream_));
-    GW_CU_CHECK_ERR(hipMemcpyAsync(d_windows_, h_windows_, static_cast<size_t>(poa_count_) * sizeof(gwhip_window_details), hipMemcpyHostToDevice, stream_));
-    GW_CU_CHECK_ERR(hipMemcpyAsync(d_seq_lens_, h_seq_lens_, static_cast<size_t>(global_sequence_idx_) * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+    GW_CU_CHECK_ERR(hipMemsetAsync(d_.sequences + num_nucleotides_copied_, 0, 2048, stream_));
+    GW_CU_CHECK_ERR(hipMemcpyAsync(d_.windows, h_.windows, static_cast<size_t>(poa_count_) * sizeof(gwhip_window_details), hipMemcpyHostToDevice, stream_));
+    restore_lengths();
+}
+
+// sequence_lengths[first read of each window] is overwritten with the node count by a launch
+void PoaBatch::restore_lengths()
+{
+    GW_CU_CHECK_ERR(hipMemcpyAsync(d_.lengths, h_.lengths, static_cast<size_t>(global_sequence_idx_) * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
 }
 
 void PoaBatch::launch(void* event_after_graph_build, uint64_t* phase_cycles)
@@ -507,8 +487,7 @@ void PoaBatch::relaunch_resident()
 {
     scoped_device_switch dev(device_id_);
     if (poa_count_ == 0) return;
-    // sequence_lengths[first read of each window] was overwritten with the node count: restore lengths only
-    GW_CU_CHECK_ERR(hipMemcpyAsync(d_seq_lens_, h_seq_lens_, static_cast<size_t>(global_sequence_idx_) * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+    restore_lengths();
     launch();
 }
 
@@ -516,20 +495,15 @@ void PoaBatch::relaunch_resident_timed(float* graph_build_ms, float* output_ms)
 {
     scoped_device_switch dev(device_id_);
     if (poa_count_ == 0) return;
-    hipEvent_t e0, e1, e2;
-    GW_CU_CHECK_ERR(hipEventCreate(&e0));
-    GW_CU_CHECK_ERR(hipEventCreate(&e1));
-    GW_CU_CHECK_ERR(hipEventCreate(&e2));
-    GW_CU_CHECK_ERR(hipMemcpyAsync(d_seq_lens_, h_seq_lens_, static_cast<size_t>(global_sequence_idx_) * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+    gwhost::OwnedEvents events;
+    const hipEvent_t e0 = events.create(hipEventDefault), e1 = events.create(hipEventDefault), e2 = events.create(hipEventDefault);
+    restore_lengths();
     GW_CU_CHECK_ERR(hipEventRecord(e0, stream_));
     launch(e1);
     GW_CU_CHECK_ERR(hipEventRecord(e2, stream_));
     GW_CU_CHECK_ERR(hipEventSynchronize(e2));
     GW_CU_CHECK_ERR(hipEventElapsedTime(graph_build_ms, e0, e1));
     GW_CU_CHECK_ERR(hipEventElapsedTime(output_ms, e1, e2));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipEventDestroy(e2);
 }
 
 void PoaBatch::profile_phases(double out[6])
@@ -550,51 +524,34 @@ void PoaBatch::profile_phases_per_window(std::vector<uint64_t>& ticks)
     if (n == 0) return;
     uint64_t* d = nullptr;
     GW_CU_CHECK_ERR(hipMalloc(reinterpret_cast<void**>(&d), n * sizeof(uint64_t)));
-    GW_CU_CHECK_ERR(hipMemcpyAsync(d_seq_lens_, h_seq_lens_, static_cast<size_t>(global_sequence_idx_) * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+    restore_lengths();
     launch(nullptr, d);
     GW_CU_CHECK_ERR(hipMemcpyAsync(ticks.data(), d, n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream_));
     GW_CU_CHECK_ERR(hipStreamSynchronize(stream_));
     GW_CU_CHECK_ERR(hipFree(d));
 }
 
-void PoaBatch::log_kernel_error(StatusType error_type, std::vector<StatusType>& output_status)
+void PoaBatch::log_kernel_error(StatusType error_type)
 {
     std::string message, hint;
     decode_error(error_type, message, hint);
     message += " in batch " + std::to_string(bid_) + "\n" + hint;
     GW_LOG_WARN(message.c_str());
-    output_status.emplace_back(error_type);
 }
 
-namespace
+void PoaBatch::log_failed_windows(const StatusType* status, size_t count)
 {
-// dst[0 .. n) = src[n-1 .. 0]: the kernels write consensus and coverage back to front, as the reference's do
-// (cudapoa_generate_consensus.cuh:245-283). Eight bytes / four counters per step through a 64-bit word.
-void reversed_copy_u8(char* dst, const char* src, size_t n)
-{
-    size_t i = 0;
-    for (; i + 8 <= n; i += 8)
-    {
-        uint64_t v;
-        std::memcpy(&v, src + n - i - 8, 8);
-        v = __builtin_bswap64(v);
-        std::memcpy(dst + i, &v, 8);
-    }
-    for (; i < n; i++) dst[i] = src[n - 1 - i];
+    for (size_t poa = 0; poa < count; poa++)
+        if (status[poa] != StatusType::success) log_kernel_error(status[poa]);
 }
-void reversed_copy_u16(uint16_t* dst, const uint16_t* src, size_t n)
+
+// The kernels write consensus and coverage back to front, as the reference's do (cudapoa_generate_consensus.cuh:245-283),
+// and mark a failed window with 0xFF and its status code at the start of its consensus row.
+StatusType PoaBatch::window_status(size_t poa) const
 {
-    size_t i = 0;
-    for (; i + 4 <= n; i += 4)
-    {
-        uint64_t v;
-        std::memcpy(&v, src + n - i - 4, 8);
-        v = (v >> 48) | ((v >> 16) & 0xffff0000ull) | ((v << 16) & 0xffff00000000ull) | (v << 48);
-        std::memcpy(dst + i, &v, 8);
-    }
-    for (; i < n; i++) dst[i] = src[n - 1 - i];
+    const uint8_t* c = &h_.consensus[poa * static_cast<size_t>(batch_size_.max_consensus_size)];
+    return c[0] == kKernelError ? static_cast<StatusType>(c[1]) : StatusType::success;
 }
-} // namespace
 
 // D2H of consensus + coverage, then un-reversal into count = poa_count_ slots (strings / vectors whose storage is reused
 // when they have any); statuses of failed windows are logged in window order.
@@ -604,15 +561,15 @@ void PoaBatch::fetch_consensus(std::string* consensus, std::vector<uint16_t>* co
     // D2H of the windows actually in the batch (the reference copies the whole capacity: SURVEY Appendix C.4). The two
     // arrays are neighbours on both sides with the same spacing: one copy when the unused tail of the first is small.
     const size_t n        = static_cast<size_t>(poa_count_) * batch_size_.max_consensus_size;
-    const size_t cons_cap = static_cast<size_t>(reinterpret_cast<uint8_t*>(d_coverage_) - d_consensus_);
+    const size_t cons_cap = layout_.coverage.offset - layout_.consensus.offset; // (on both sides: PoaBlockLayout)
     if (n > 0)
     {
-        if (cons_cap - n <= n / 4 && reinterpret_cast<uint8_t*>(h_coverage_) - h_consensus_ == static_cast<std::ptrdiff_t>(cons_cap))
-            GW_CU_CHECK_ERR(hipMemcpyAsync(h_consensus_, d_consensus_, cons_cap + n * sizeof(uint16_t), hipMemcpyDeviceToHost, stream_));
+        if (cons_cap - n <= n / 4)
+            GW_CU_CHECK_ERR(hipMemcpyAsync(h_.consensus, d_.consensus, cons_cap + n * sizeof(uint16_t), hipMemcpyDeviceToHost, stream_));
         else
         {
-            GW_CU_CHECK_ERR(hipMemcpyAsync(h_consensus_, d_consensus_, n, hipMemcpyDeviceToHost, stream_));
-            GW_CU_CHECK_ERR(hipMemcpyAsync(h_coverage_, d_coverage_, n * sizeof(uint16_t), hipMemcpyDeviceToHost, stream_));
+            GW_CU_CHECK_ERR(hipMemcpyAsync(h_.consensus, d_.consensus, n, hipMemcpyDeviceToHost, stream_));
+            GW_CU_CHECK_ERR(hipMemcpyAsync(h_.coverage, d_.coverage, n * sizeof(uint16_t), hipMemcpyDeviceToHost, stream_));
         }
     }
     const size_t count = static_cast<size_t>(poa_count_);
@@ -624,9 +581,9 @@ void PoaBatch::fetch_consensus(std::string* consensus, std::vector<uint16_t>* co
         // longest read (an estimate: the resize below corrects it either way).
         for (size_t poa = 0; poa < count; poa++)
         {
-            const gwhip_window_details& wd = h_windows_[poa];
+            const gwhip_window_details& wd = h_.windows[poa];
             int32_t longest = 0;
-            for (int32_t k = 0; k < static_cast<int32_t>(wd.num_seqs); k++) longest = std::max(longest, h_seq_lens_[wd.seq_len_buffer_offset + k]);
+            for (int32_t k = 0; k < static_cast<int32_t>(wd.num_seqs); k++) longest = std::max(longest, h_.lengths[wd.seq_len_buffer_offset + k]);
             const size_t hint = std::min(row, static_cast<size_t>(longest) + static_cast<size_t>(longest) / 16 + 16);
             consensus[poa].reserve(hint);
             coverage[poa].reserve(hint);
@@ -641,16 +598,15 @@ void PoaBatch::fetch_consensus(std::string* consensus, std::vector<uint16_t>* co
         alignas(64) uint16_t local_v[kLocalRow];
         for (size_t poa = first; poa < last; poa++)
         {
-            const char* c      = reinterpret_cast<const char*>(&h_consensus_[poa * row]);
-            const uint16_t* cv = &h_coverage_[poa * row];
-            if (static_cast<uint8_t>(c[0]) == kKernelError)
+            const char* c      = reinterpret_cast<const char*>(&h_.consensus[poa * row]);
+            const uint16_t* cv = &h_.coverage[poa * row];
+            output_status[poa] = window_status(poa);
+            if (output_status[poa] != StatusType::success) // logged below, in window order
             {
-                output_status[poa] = static_cast<StatusType>(c[1]); // logged below, in window order
                 consensus[poa].clear();
                 coverage[poa].clear();
                 continue;
             }
-            output_status[poa] = StatusType::success;
             size_t len;
             if (row <= kLocalRow)
             {
@@ -663,21 +619,16 @@ void PoaBatch::fetch_consensus(std::string* consensus, std::vector<uint16_t>* co
             else
                 len = ::strnlen(c, row);
             consensus[poa].resize(len);
-            reversed_copy_u8(&consensus[poa][0], c, len);
+            gwhost::reverse_bytes(&consensus[poa][0], c, len);
             coverage[poa].resize(len);
-            reversed_copy_u16(coverage[poa].data(), cv, len);
+            gwhost::reverse_u16(coverage[poa].data(), cv, len);
         }
     };
     // the windows are independent: 16 at a time on the library's worker pool
     constexpr size_t kPerTask = 16;
     gwhost::parallel_tasks((count + kPerTask - 1) / kPerTask, count >= 256 ? 8 : 1,
                            [&](size_t t) { unpack(t * kPerTask, std::min(count, (t + 1) * kPerTask)); });
-    for (size_t poa = 0; poa < count; poa++)
-        if (output_status[poa] != StatusType::success)
-        {
-            std::vector<StatusType> sink; // log_kernel_error appends the code; the status slot is already filled
-            log_kernel_error(output_status[poa], sink);
-        }
+    log_failed_windows(output_status, count);
 }
 
 StatusType PoaBatch::get_consensus(std::vector<std::string>& consensus, std::vector<std::vector<uint16_t>>& coverage,
@@ -713,8 +664,8 @@ StatusType PoaBatch::get_msa(std::vector<std::vector<std::string>>& msa, std::ve
     const size_t row = static_cast<size_t>(batch_size_.max_consensus_size);
     if (poa_count_ > 0)
     {
-        GW_CU_CHECK_ERR(hipMemcpyAsync(h_msa_, d_msa_, static_cast<size_t>(poa_count_) * max_sequences_per_poa_ * row, hipMemcpyDeviceToHost, stream_));
-        GW_CU_CHECK_ERR(hipMemcpyAsync(h_consensus_, d_consensus_, static_cast<size_t>(poa_count_) * row, hipMemcpyDeviceToHost, stream_));
+        GW_CU_CHECK_ERR(hipMemcpyAsync(h_.msa, d_.msa, static_cast<size_t>(poa_count_) * max_sequences_per_poa_ * row, hipMemcpyDeviceToHost, stream_));
+        GW_CU_CHECK_ERR(hipMemcpyAsync(h_.consensus, d_.consensus, static_cast<size_t>(poa_count_) * row, hipMemcpyDeviceToHost, stream_));
     }
     GW_CU_CHECK_ERR(hipStreamSynchronize(stream_));
     // rows are unpacked behind whatever the caller's vectors already hold; long-read MSAs are hundreds of megabytes of
@@ -726,17 +677,13 @@ StatusType PoaBatch::get_msa(std::vector<std::vector<std::string>>& msa, std::ve
     auto unpack = [&](size_t first, size_t last) {
         for (size_t poa = first; poa < last; poa++)
         {
-            const char* c = reinterpret_cast<const char*>(&h_consensus_[poa * row]);
-            if (static_cast<uint8_t>(c[0]) == kKernelError)
-            {
-                output_status[base_s + poa] = static_cast<StatusType>(c[1]);
-                continue;
-            }
-            const uint16_t num_seqs = h_windows_[poa].num_seqs;
+            output_status[base_s + poa] = window_status(poa);
+            if (output_status[base_s + poa] != StatusType::success) continue;
+            const uint16_t num_seqs = h_.windows[poa].num_seqs;
             std::vector<std::string>& rows = msa[base_m + poa];
             rows.reserve(num_seqs);
             for (int32_t i = 0; i < num_seqs; i++)
-                rows.emplace_back(reinterpret_cast<const char*>(&h_msa_[(poa * max_sequences_per_poa_ + static_cast<size_t>(i)) * row]));
+                rows.emplace_back(reinterpret_cast<const char*>(&h_.msa[(poa * max_sequences_per_poa_ + static_cast<size_t>(i)) * row]));
         }
     };
     // long-read MSAs are hundreds of megabytes of rows: the windows go over the library's worker pool in chunks (joined and
@@ -746,12 +693,7 @@ StatusType PoaBatch::get_msa(std::vector<std::vector<std::string>>& msa, std::ve
     const size_t per_task  = std::max<size_t>(1, (count + 4 * n_threads - 1) / (4 * n_threads));
     gwhost::parallel_tasks((count + per_task - 1) / per_task, n_threads,
                            [&](size_t t) { unpack(t * per_task, std::min(count, (t + 1) * per_task)); });
-    for (size_t poa = 0; poa < count; poa++)
-        if (output_status[base_s + poa] != StatusType::success)
-        {
-            std::vector<StatusType> sink; // log_kernel_error appends the code; the status slot is already filled
-            log_kernel_error(output_status[base_s + poa], sink);
-        }
+    log_failed_windows(output_status.data() + base_s, count);
     return StatusType::success;
 }
 
@@ -762,7 +704,7 @@ void PoaBatch::get_graphs(std::vector<DirectedGraph>& graphs, std::vector<Status
     if (poa_count_ == 0) return;
     const size_t mn = static_cast<size_t>(batch_size_.max_nodes_per_graph);
     const size_t W  = static_cast<size_t>(poa_count_);
-    auto up         = [](size_t v) { return (v + 255) & ~size_t(255); };
+    const auto up   = gwhost::up256;
     // Temporaries in the reference's array layout (303 bytes per node slot), filled by the export kernel. The batch's
     // pool is normally fully committed to the batch block, so they come straight from the runtime -- in chunks of
     // windows of at most ~1 GiB, so that a batch filled to device capacity can still be exported.
@@ -787,8 +729,8 @@ void PoaBatch::get_graphs(std::vector<DirectedGraph>& graphs, std::vector<Status
     std::vector<uint16_t> cnt(chunk * mn), w(chunk * mn * GWHIP_MAX_NODE_EDGES);
     std::vector<int32_t> edges(chunk * mn * GWHIP_MAX_NODE_EDGES);
     std::vector<int32_t> lens(static_cast<size_t>(global_sequence_idx_));
-    GW_CU_CHECK_ERR(hipMemcpyAsync(lens.data(), d_seq_lens_, lens.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-    GW_CU_CHECK_ERR(hipMemcpyAsync(h_consensus_, d_consensus_, W * batch_size_.max_consensus_size, hipMemcpyDeviceToHost, stream_));
+    GW_CU_CHECK_ERR(hipMemcpyAsync(lens.data(), d_.lengths, lens.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+    GW_CU_CHECK_ERR(hipMemcpyAsync(h_.consensus, d_.consensus, W * batch_size_.max_consensus_size, hipMemcpyDeviceToHost, stream_));
     for (size_t first = 0; first < W; first += chunk)
     {
         const size_t n_here = std::min(chunk, W - first);
@@ -807,15 +749,14 @@ void PoaBatch::get_graphs(std::vector<DirectedGraph>& graphs, std::vector<Status
         for (size_t k = 0; k < n_here; k++)
         {
             const size_t poa = first + k;
-            const char* c    = reinterpret_cast<const char*>(&h_consensus_[poa * batch_size_.max_consensus_size]);
-            if (static_cast<uint8_t>(c[0]) == kKernelError)
+            output_status.emplace_back(window_status(poa));
+            if (output_status.back() != StatusType::success)
             {
-                log_kernel_error(static_cast<StatusType>(c[1]), output_status);
+                log_kernel_error(output_status.back());
                 continue;
             }
-            output_status.emplace_back(StatusType::success);
             DirectedGraph& graph    = graphs[poa];
-            const int32_t num_nodes = lens[static_cast<size_t>(h_windows_[poa].seq_len_buffer_offset)];
+            const int32_t num_nodes = lens[static_cast<size_t>(h_.windows[poa].seq_len_buffer_offset)];
             for (int32_t n = 0; n < num_nodes; n++)
             {
                 graph.set_node_label(n, std::string(1, static_cast<char>(nodes[k * mn + n])));
@@ -835,10 +776,10 @@ uint64_t PoaBatch::total_cells()
 {
     scoped_device_switch dev(device_id_);
     if (poa_count_ == 0) return 0;
-    GW_CU_CHECK_ERR(hipMemcpyAsync(h_cells_, d_cells_, static_cast<size_t>(poa_count_) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream_));
+    GW_CU_CHECK_ERR(hipMemcpyAsync(h_.cells, d_.cells, static_cast<size_t>(poa_count_) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream_));
     GW_CU_CHECK_ERR(hipStreamSynchronize(stream_));
     uint64_t t = 0;
-    for (int32_t i = 0; i < poa_count_; i++) t += h_cells_[i];
+    for (int32_t i = 0; i < poa_count_; i++) t += h_.cells[i];
     return t;
 }
 
@@ -869,8 +810,7 @@ std::unique_ptr<Batch> create_batch(int32_t device_id, cudaStream_t stream, int6
         gwhip_poa_config c = make_device_config(batch_size, output_mask, gap_score, mismatch_score, match_score);
         int64_t per_poa = 0, per_matrix = 0;
         gwhip_poa_bytes_per_window(&c, &per_poa, &per_matrix);
-        throw std::runtime_error(std::string("Requires at least ").append(std::to_string(per_poa + per_matrix)).append(
-            " bytes of device memory per CUDAPOA batch to process correctly."));
+        throw requires_at_least(per_poa + per_matrix);
     }
     DefaultDeviceAllocator allocator(static_cast<size_t>(max_mem), stream);
     return create_batch(device_id, stream, allocator, max_mem, output_mask, batch_size, gap_score, mismatch_score, match_score);

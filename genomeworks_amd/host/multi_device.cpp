@@ -5,6 +5,7 @@
 #include <claraparabricks/genomeworks/utils/signed_integer_utils.hpp>
 
 #include "../../include/gwhip.h"
+#include "owned_hip.hpp"
 #include "poa_batch_impl.hpp"
 
 #include <algorithm>
@@ -27,106 +28,166 @@ namespace cudapoa
 
 namespace
 {
-// Streams / events owned for the length of a driver call, released on every exit path (device switched per resource).
-struct OwnedStreams
-{
-    std::vector<std::pair<int32_t, cudaStream_t>> items;
-    OwnedStreams()                               = default;
-    OwnedStreams(const OwnedStreams&)            = delete;
-    OwnedStreams& operator=(const OwnedStreams&) = delete;
-    cudaStream_t create(int32_t device, bool with_priority = false, int priority = 0)
-    {
-        scoped_device_switch dev(device);
-        cudaStream_t s = nullptr;
-        if (with_priority) GW_CU_CHECK_ERR(hipStreamCreateWithPriority(&s, hipStreamDefault, priority));
-        else GW_CU_CHECK_ERR(hipStreamCreate(&s));
-        items.emplace_back(device, s);
-        return s;
-    }
-    ~OwnedStreams()
-    {
-        for (auto& it : items)
-        {
-            scoped_device_switch dev(it.first);
-            (void)hipStreamDestroy(it.second);
-        }
-    }
-};
-struct OwnedEvents
-{
-    std::vector<hipEvent_t> items;
-    OwnedEvents()                              = default;
-    OwnedEvents(const OwnedEvents&)            = delete;
-    OwnedEvents& operator=(const OwnedEvents&) = delete;
-    hipEvent_t create()
-    {
-        hipEvent_t e = nullptr;
-        GW_CU_CHECK_ERR(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        items.push_back(e);
-        return e;
-    }
-    ~OwnedEvents()
-    {
-        for (hipEvent_t e : items) (void)hipEventDestroy(e);
-    }
-};
-// joins whatever was started, also when spawning the next thread throws
-struct JoinAll
-{
-    std::vector<std::thread>& threads;
-    ~JoinAll()
-    {
-        for (std::thread& t : threads)
-            if (t.joinable()) t.join();
-    }
-};
-} // namespace
+using gwhost::JoinAll;
+using gwhost::OwnedEvents;
+using gwhost::OwnedStreams;
+using Clock = std::chrono::steady_clock;
 
-namespace
+// Every worker arrives once (a second arrive() of the same worker returns at once) and leaves when all have arrived, or when
+// the spawn was abandoned: a worker thread that could not be started is not waited for. The last arrival stamps the time.
+struct Rendezvous
 {
+    Rendezvous(size_t workers, size_t expected_arrivals, const std::atomic<bool>& spawn_abandoned)
+        : expected(static_cast<int32_t>(expected_arrivals))
+        , abandoned(spawn_abandoned)
+        , seen(workers, 0)
+    {
+    }
+    void arrive(size_t worker)
+    {
+        if (seen[worker]) return;
+        seen[worker] = 1;
+        if (arrived.fetch_add(1) + 1 == expected) all_arrived = Clock::now(); // (read once the workers have been joined)
+        while (arrived.load() < expected && !abandoned.load()) std::this_thread::yield();
+    }
+    bool complete() const { return arrived.load() == expected; }
+
+    const int32_t expected;
+    const std::atomic<bool>& abandoned;
+    std::vector<char> seen; // [worker], touched by that worker only
+    std::atomic<int32_t> arrived{0};
+    Clock::time_point all_arrived{};
+};
+
+// The moment the last worker had stored its last results (before its Batch is destroyed), relative to `begin`.
+struct ResultClock
+{
+    Clock::time_point begin{};
+    std::atomic<int64_t> ns{0};
+    void stamp()
+    {
+        const int64_t now_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now() - begin).count();
+        int64_t seen         = ns.load();
+        while (seen < now_ns && !ns.compare_exchange_weak(seen, now_ns)) {}
+    }
+    bool stamped() const { return ns.load() > 0; }
+    Clock::time_point last() const { return begin + std::chrono::nanoseconds(ns.load()); }
+};
+
+void prepare_output(MultiDeviceOutput& out, size_t n, bool want_msa)
+{
+    out = MultiDeviceOutput{};
+    out.status.assign(n, StatusType::success);
+    out.worker_of_window.assign(n, -1);
+    if (want_msa)
+        out.msa.resize(n);
+    else
+    {
+        out.consensus.resize(n);
+        out.coverage.resize(n);
+    }
+}
+
+// Window indices still to be taken: order[next ..), or next .. size in ascending order without one.
+struct WindowQueue
+{
+    const std::vector<int32_t>* order = nullptr;
+    size_t size                       = 0;
+    size_t next                       = 0;
+    bool empty() const { return next >= size; }
+    size_t front() const { return order ? static_cast<size_t>((*order)[next]) : next; }
+};
+
+// Moves windows from the queue into the batch until it is full, holds fill_cap windows, or the queue is empty. in_batch gets
+// the global index of every output slot of the launch, windows.size() for a placeholder slot; refusals go to out.status.
+void fill_batch(Batch& batch, std::vector<size_t>& in_batch, WindowQueue& queue, int32_t fill_cap, const std::vector<std::vector<std::string>>& windows,
+                int32_t worker, MultiDeviceOutput& out, const char* holds_no_window)
+{
+    while (!queue.empty() && batch.get_total_poas() < fill_cap)
+    {
+        const size_t w                         = queue.front();
+        const std::vector<std::string>& window = windows[w];
+        Group group;
+        group.reserve(window.size());
+        for (const std::string& read : window) group.push_back(Entry{read.c_str(), nullptr, get_size<int32_t>(read)});
+        std::vector<StatusType> per_read;
+        const StatusType st = batch.add_poa_group(per_read, group);
+        if (st == StatusType::exceeded_maximum_poas)
+        {
+            if (in_batch.empty()) throw std::runtime_error(holds_no_window);
+            break;
+        }
+        out.worker_of_window[w] = worker;
+        if (st == StatusType::success)
+            in_batch.push_back(w);
+        else
+        {
+            out.status[w] = st;
+            // every read was refused after the batch opened a POA for the group (cudapoa_batch.cuh:122-150): the empty POA
+            // owns an output slot of this launch; its window reports the add status
+            if (st == StatusType::empty_poa_group && !window.empty()) in_batch.push_back(windows.size());
+        }
+        queue.next++;
+    }
+}
+
+// get_msa() or get_consensus() of the launch, stored by global window index (placeholder slots are skipped).
+void store_results(Batch& batch, bool want_msa, const std::vector<size_t>& in_batch, MultiDeviceOutput& out)
+{
+    const size_t n = out.status.size();
+    std::vector<StatusType> status;
+    std::vector<std::vector<std::string>> msa;
+    std::vector<std::string> consensus;
+    std::vector<std::vector<uint16_t>> coverage;
+    if (want_msa)
+    {
+        batch.get_msa(msa, status);
+        if (msa.size() != in_batch.size()) throw std::runtime_error("MSA count does not match the windows of the batch");
+    }
+    else
+    {
+        batch.get_consensus(consensus, coverage, status);
+        if (consensus.size() != in_batch.size()) throw std::runtime_error("consensus count does not match the windows of the batch");
+    }
+    for (size_t k = 0; k < in_batch.size(); k++)
+    {
+        const size_t w = in_batch[k];
+        if (w >= n) continue;
+        if (want_msa)
+            out.msa[w] = std::move(msa[k]);
+        else
+        {
+            out.consensus[w] = std::move(consensus[k]);
+            out.coverage[w]  = std::move(coverage[k]);
+        }
+        out.status[w] = status[k];
+    }
+}
+
+void rethrow_first(const std::vector<std::exception_ptr>& errors)
+{
+    for (const std::exception_ptr& e : errors)
+        if (e) std::rethrow_exception(e);
+}
+
+// ---- workers on a shared cursor ---------------------------------------------------------------------------------------------
 struct SharedCursor
 {
     std::mutex mutex;
-    size_t next = 0;
+    WindowQueue queue;
 };
 
 // One worker: fills its batch from the cursor, runs it, stores by global index; until the windows run out.
 // Every worker's Batch exists before any of them fills: the clock of the reference's multi-batch benchmark starts there
 // (cudapoa/benchmarks/multi_batch.hpp: the batches are created in the constructor, process_batches() is what is timed).
-struct CreationGate
-{
-    int32_t workers = 0;
-    std::atomic<int32_t> arrived{0};
-    std::atomic<bool> abandoned{false}; // a worker thread could not be started: nobody waits for it
-    std::mutex m;
-    std::chrono::steady_clock::time_point all_created{};
-    std::chrono::steady_clock::time_point last_done{}; // the moment the last worker had stored its last results (before its Batch is destroyed)
-    void done()
-    {
-        const auto t = std::chrono::steady_clock::now();
-        std::lock_guard<std::mutex> g(m);
-        if (t > last_done) last_done = t;
-    }
-    void arrive()
-    {
-        if (arrived.fetch_add(1) + 1 == workers)
-        {
-            std::lock_guard<std::mutex> g(m);
-            all_created = std::chrono::steady_clock::now();
-        }
-        while (arrived.load() < workers && !abandoned.load()) std::this_thread::yield();
-    }
-};
-
 void worker_loop(int32_t worker, int32_t device, cudaStream_t stream, DefaultDeviceAllocator allocator, int64_t memory,
                  const BatchConfig& batch_size, const MultiDeviceConfig& config, const std::vector<std::vector<std::string>>& windows,
-                 SharedCursor& cursor, MultiDeviceOutput& out, std::atomic<int32_t>& launches, CreationGate& gate, bool& arrived)
+                 SharedCursor& cursor, MultiDeviceOutput& out, std::atomic<int32_t>& launches, Rendezvous& created, ResultClock& results)
 {
     scoped_device_switch dev(device);
     std::unique_ptr<Batch> batch = create_batch(device, stream, allocator, memory, config.output_mask, batch_size, config.gap_score,
                                                 config.mismatch_score, config.match_score);
-    arrived = true;
-    gate.arrive();
+    created.arrive(static_cast<size_t>(worker));
     const bool want_msa = (config.output_mask & OutputType::msa) != 0;
     // A fill stops at a whole number of device rounds: the device runs `resident` windows side by side (one wavefront per SIMD;
     // 0 = a configuration that is not one wavefront per window), and a launch of 1400 windows lasts two rounds like one of 2048
@@ -147,70 +208,18 @@ void worker_loop(int32_t worker, int32_t device, cudaStream_t stream, DefaultDev
         {
             // the cursor only moves under the lock: a window is taken by exactly one worker
             std::lock_guard<std::mutex> guard(cursor.mutex);
-            while (cursor.next < windows.size() && batch->get_total_poas() < fill_cap)
-            {
-                const std::vector<std::string>& window = windows[cursor.next];
-                Group group;
-                group.reserve(window.size());
-                for (const std::string& read : window) group.push_back(Entry{read.c_str(), nullptr, get_size<int32_t>(read)});
-                std::vector<StatusType> per_read;
-                const StatusType st = batch->add_poa_group(per_read, group);
-                if (st == StatusType::exceeded_maximum_poas)
-                {
-                    if (in_batch.empty()) throw std::runtime_error("a batch of this configuration cannot hold a single window");
-                    break;
-                }
-                out.worker_of_window[cursor.next] = worker;
-                if (st == StatusType::success)
-                    in_batch.push_back(cursor.next);
-                else if (st == StatusType::empty_poa_group && !window.empty())
-                {
-                    // every read was refused after the batch opened a POA for the group (cudapoa_batch.cuh:122-150): the
-                    // empty POA owns an output slot of this launch; its window reports the add status
-                    out.status[cursor.next] = st;
-                    in_batch.push_back(windows.size()); // placeholder slot
-                }
-                else
-                    out.status[cursor.next] = st;
-                cursor.next++;
-            }
+            fill_batch(*batch, in_batch, cursor.queue, fill_cap, windows, worker, out, "a batch of this configuration cannot hold a single window");
         }
         if (batch->get_total_poas() == 0)
         {
             // everything this worker took is stored: the timed region of the reference's multi-batch benchmark ends here (its
             // batches outlive process_batches(); releasing a Batch -- its pinned staging block above all -- is not part of it)
-            gate.done();
+            results.stamp();
             break;
         }
         batch->generate_poa();
         launches++;
-        std::vector<StatusType> status;
-        if (want_msa)
-        {
-            std::vector<std::vector<std::string>> msa;
-            batch->get_msa(msa, status);
-            if (msa.size() != in_batch.size()) throw std::runtime_error("MSA count does not match the windows of the batch");
-            for (size_t k = 0; k < in_batch.size(); k++)
-                if (in_batch[k] < windows.size())
-                {
-                    out.msa[in_batch[k]]    = std::move(msa[k]);
-                    out.status[in_batch[k]] = status[k];
-                }
-        }
-        else
-        {
-            std::vector<std::string> consensus;
-            std::vector<std::vector<uint16_t>> coverage;
-            batch->get_consensus(consensus, coverage, status);
-            if (consensus.size() != in_batch.size()) throw std::runtime_error("consensus count does not match the windows of the batch");
-            for (size_t k = 0; k < in_batch.size(); k++)
-                if (in_batch[k] < windows.size())
-                {
-                    out.consensus[in_batch[k]] = std::move(consensus[k]);
-                    out.coverage[in_batch[k]]  = std::move(coverage[k]);
-                    out.status[in_batch[k]]    = status[k];
-                }
-        }
+        store_results(*batch, want_msa, in_batch, out);
     }
 }
 } // namespace
@@ -228,18 +237,8 @@ void process_windows_multi_device(MultiDeviceOutput& out, const std::vector<std:
         if (d < 0 || d >= n_devices) throw std::invalid_argument("device id out of range: " + std::to_string(d));
         entries_of_device[d]++;
     }
-    const size_t n = windows.size();
-    out            = MultiDeviceOutput{};
-    out.status.assign(n, StatusType::success);
-    out.worker_of_window.assign(n, -1);
-    if (config.output_mask & OutputType::msa)
-        out.msa.resize(n);
-    else
-    {
-        out.consensus.resize(n);
-        out.coverage.resize(n);
-    }
-    if (n == 0) return;
+    prepare_output(out, windows.size(), (config.output_mask & OutputType::msa) != 0);
+    if (windows.empty()) return;
 
     // one allocator per entry of `devices`, shared by that entry's batches (as multi_batch.hpp:52-60 shares one)
     struct Group
@@ -270,17 +269,20 @@ void process_windows_multi_device(MultiDeviceOutput& out, const std::vector<std:
     }
 
     SharedCursor cursor;
+    cursor.queue.size = windows.size();
     std::atomic<int32_t> launches{0};
-    const auto t_begin = std::chrono::steady_clock::now();
+    ResultClock results;
+    results.begin = Clock::now();
     // every stream exists before the first worker starts (a failing hipStreamCreate must not leave joinable threads behind)
     OwnedStreams streams;
     for (Group& g : groups)
         for (int32_t b = 0; b < config.batches_per_device; b++) streams.create(g.device);
-    std::vector<std::exception_ptr> errors(groups.size() * static_cast<size_t>(config.batches_per_device));
+    const size_t workers = groups.size() * static_cast<size_t>(config.batches_per_device);
+    std::vector<std::exception_ptr> errors(workers);
     std::vector<std::thread> threads;
-    CreationGate gate;
-    gate.workers = static_cast<int32_t>(groups.size()) * config.batches_per_device;
-    threads.reserve(static_cast<size_t>(gate.workers));
+    std::atomic<bool> abandoned{false};
+    Rendezvous created(workers, workers, abandoned);
+    threads.reserve(workers);
     {
         JoinAll join{threads};
         int32_t worker = 0;
@@ -292,34 +294,32 @@ void process_windows_multi_device(MultiDeviceOutput& out, const std::vector<std:
                     cudaStream_t stream  = streams.items[static_cast<size_t>(worker)].second;
                     const int64_t memory = g.memory / config.batches_per_device;
                     threads.emplace_back([&, worker, stream, memory, device = g.device, allocator = g.allocator]() {
-                        bool arrived = false;
                         try
                         {
-                            worker_loop(worker, device, stream, allocator, memory, batch_size, config, windows, cursor, out, launches, gate, arrived);
+                            worker_loop(worker, device, stream, allocator, memory, batch_size, config, windows, cursor, out, launches, created, results);
                         }
                         catch (...)
                         {
                             errors[static_cast<size_t>(worker)] = std::current_exception();
-                            if (!arrived) gate.arrive(); // a failed creation releases the others
+                            created.arrive(static_cast<size_t>(worker)); // a failed creation releases the others
                         }
                     });
                 }
         }
         catch (...)
         {
-            gate.abandoned.store(true); // std::thread could not start a worker: the started ones must not wait for it
+            abandoned.store(true); // std::thread could not start a worker: the started ones must not wait for it
             throw;
         }
     }
-    const auto t_end = std::chrono::steady_clock::now();
-    out.seconds      = std::chrono::duration<double>(t_end - t_begin).count();
-    if (gate.arrived.load() == gate.workers)
-        out.seconds_after_creation = std::chrono::duration<double>((gate.last_done > gate.all_created ? gate.last_done : t_end) - gate.all_created).count();
+    const auto t_end = Clock::now();
+    out.seconds      = std::chrono::duration<double>(t_end - results.begin).count();
+    if (created.complete())
+        out.seconds_after_creation =
+            std::chrono::duration<double>((results.last() > created.all_arrived ? results.last() : t_end) - created.all_arrived).count();
     out.launches = launches.load();
-    for (const std::exception_ptr& e : errors)
-        if (e) std::rethrow_exception(e);
+    rethrow_first(errors);
 }
-
 // ---- size classes -------------------------------------------------------------------------------------------------------
 void plan_size_classes(SizeClassPlan& plan, const std::vector<int32_t>& longest, const std::vector<int32_t>& reads, bool msa_flag,
                        int32_t band_width, BandMode band_mode, float adaptive_storage_factor, float graph_length_factor,
@@ -385,269 +385,215 @@ std::vector<int32_t> size_class_admission_gates(const SizeClassPlan& plan, int32
     return gate_on;
 }
 
-void process_windows_size_classes(MultiDeviceOutput& out, const std::vector<std::vector<std::string>>& windows,
-                                  const SizeClassPlan& plan, int32_t device, int64_t memory_budget, int8_t output_mask,
-                                  int16_t gap_score, int16_t mismatch_score, int16_t match_score, double* compute_seconds)
+
+namespace
 {
-    const size_t n = windows.size();
-    out            = MultiDeviceOutput{};
-    out.status.assign(n, StatusType::success);
-    out.worker_of_window.assign(n, -1);
-    const bool want_msa = (output_mask & OutputType::msa) != 0;
-    if (want_msa)
-        out.msa.resize(n);
-    else
-    {
-        out.consensus.resize(n);
-        out.coverage.resize(n);
-    }
-    if (compute_seconds) *compute_seconds = 0;
-    const size_t classes = plan.configs.size();
-    if (n == 0 || classes == 0) return;
-    scoped_device_switch dev(device);
-    size_t active_classes = 0;
-    for (size_t k = 0; k < classes; ++k) active_classes += plan.groups[k].empty() ? 0 : 1;
-    if (active_classes == 0) return;
-    // every class gets its planned bytes (+ slack for alignment and one spare window), scaled down when the plan exceeds the budget
-    const int64_t slack_total = static_cast<int64_t>(classes) * (int64_t(64) << 20);
-    std::vector<int64_t> share(classes);
-    double scale = 1.0;
-    {
-        int64_t want = slack_total;
-        for (size_t k = 0; k < classes; ++k) want += (static_cast<int64_t>(plan.groups[k].size()) + 1) * plan.bytes_per_window[k];
-        if (want > memory_budget) scale = static_cast<double>(memory_budget - slack_total) / static_cast<double>(want - slack_total);
-        for (size_t k = 0; k < classes; ++k)
-        {
-            const int64_t planned = (static_cast<int64_t>(plan.groups[k].size()) + 1) * plan.bytes_per_window[k];
-            share[k] = std::max<int64_t>(2 * plan.bytes_per_window[k], static_cast<int64_t>(scale * static_cast<double>(planned))) + (int64_t(64) << 20);
-        }
-    }
-    std::atomic<int32_t> launches{0}, filled{0};
+// One call of process_windows_size_classes: what its class workers share. A worker is one host thread with the stream,
+// the memory share and the Batch of its class.
+struct SizeClassRun
+{
+    const std::vector<std::vector<std::string>>& windows;
+    const SizeClassPlan& plan;
+    MultiDeviceOutput& out;
+    const int32_t device;
+    const int8_t output_mask;
+    const int16_t gap_score, mismatch_score, match_score;
+    const bool want_msa;
+    const bool trace; // GW_SIZE_CLASS_TRACE (debugging): host-side timeline on stderr
+    const size_t classes, active_classes;
+
+    std::vector<int64_t> share; // device bytes of each class
     // The classes' first launches are submitted in plan order (longest reads first) and on streams whose priority falls in
     // the same order: a window is one chain of dependent steps on one CU, the set lasts at least as long as its heaviest
     // window, so that window's class must own its CUs from the first moment instead of queueing behind hundreds of light
     // blocks that happened to be submitted a millisecond earlier.
+    std::vector<int32_t> launch_rank;
     std::atomic<int32_t> launch_turn{0};
-    std::atomic<int64_t> results_done_ns{0}; // when the last class handed over its last results, relative to t_begin
-    std::vector<int32_t> launch_rank(classes, 0);
-    {
-        int32_t rank = 0;
-        for (size_t k = 0; k < classes; ++k)
-            if (!plan.groups[k].empty()) launch_rank[k] = rank++;
-    }
-    int priority_least = 0, priority_greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&priority_least, &priority_greatest);
     // Admission by residency: a window occupies a CU for its whole life, so the device holds about one window per CU at
     // a time. Classes are admitted in plan order while their windows (a quarter more than there are CUs: the first to
     // finish make room at once) fit; the next group of classes is gated, on the device, on the end of the lightest class
     // of the group before it. Admitting everything at once only makes the long chains of the heavy classes queue for CUs
     // behind light windows -- and those chains are what the set waits for at the end.
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
-    const std::vector<int32_t> gate_on = size_class_admission_gates(plan, cus);
-    OwnedEvents class_events; // released on every exit path
-    for (size_t k = 0; k < classes; ++k) class_events.create();
-    const std::vector<hipEvent_t>& class_done = class_events.items;
-    // streams of the class workers, created up front for the same reason
+    std::vector<int32_t> gate_on;
+    OwnedEvents class_done; // [class], recorded behind every launch of the class
     OwnedStreams class_streams;
-    std::vector<cudaStream_t> stream_of(classes, nullptr);
-    for (size_t k = 0; k < classes; ++k)
-        if (!plan.groups[k].empty())
-            // numerically lower = more urgent; the range is narrow (three levels on this hardware), later classes share the last
-            stream_of[k] = class_streams.create(device, true, std::min(priority_least, priority_greatest + launch_rank[k]));
-    std::mutex start_mutex;
-    std::chrono::steady_clock::time_point compute_begin{}, fill_begin{};
-    std::atomic<int32_t> created{0}, create_arrived{0};
-    std::atomic<bool> spawn_failed{false}; // a worker thread could not be started: the barriers below must not wait for it
-    std::vector<std::exception_ptr> errors(classes);
+    std::vector<cudaStream_t> stream_of;
+
+    std::atomic<bool> abandoned{false}; // a worker thread could not be started: nobody waits for it
+    // every class's Batch exists (or its creation failed): the fill-inclusive clock (the reference's multi-batch region,
+    // cudapoa/benchmarks/multi_batch.hpp:72-177, creates all batches first and times all of the filling) starts, and no
+    // class fills before that point -- a class that was created early would otherwise do its filling outside the clock
+    Rendezvous created;
+    // every class's first fill is done (or the class failed): the compute clock starts
+    Rendezvous filled;
+    std::atomic<int32_t> batches_created{0}, launches{0};
+    // the clocks stop when the last results have been handed over: releasing the slabs (hundreds of GB for a long-read set,
+    // most of a second) is not part of generate_poa() + get_msa()
+    ResultClock results;
+    std::vector<std::exception_ptr> errors;
+
+    SizeClassRun(MultiDeviceOutput& out_, const std::vector<std::vector<std::string>>& windows_, const SizeClassPlan& plan_, size_t active, int32_t device_,
+                 int64_t memory_budget, int8_t mask, int16_t gap, int16_t mismatch, int16_t match)
+        : windows(windows_), plan(plan_), out(out_), device(device_), output_mask(mask), gap_score(gap), mismatch_score(mismatch), match_score(match)
+        , want_msa((mask & OutputType::msa) != 0), trace(std::getenv("GW_SIZE_CLASS_TRACE") != nullptr), classes(plan_.configs.size())
+        , active_classes(active), share(classes), launch_rank(classes, 0), stream_of(classes, nullptr), created(classes, active, abandoned)
+        , filled(classes, active, abandoned), errors(classes)
+    {
+        // every class gets its planned bytes (+ slack for alignment and one spare window), scaled down when the plan exceeds the budget
+        const int64_t slack_total = static_cast<int64_t>(classes) * (int64_t(64) << 20);
+        auto planned              = [&](size_t k) { return (static_cast<int64_t>(plan.groups[k].size()) + 1) * plan.bytes_per_window[k]; };
+        int64_t want              = slack_total;
+        for (size_t k = 0; k < classes; ++k) want += planned(k);
+        const double scale = want > memory_budget ? static_cast<double>(memory_budget - slack_total) / static_cast<double>(want - slack_total) : 1.0;
+        for (size_t k = 0; k < classes; ++k)
+            share[k] = std::max<int64_t>(2 * plan.bytes_per_window[k], static_cast<int64_t>(scale * static_cast<double>(planned(k)))) + (int64_t(64) << 20);
+        int32_t rank = 0;
+        for (size_t k = 0; k < classes; ++k)
+            if (!plan.groups[k].empty()) launch_rank[k] = rank++;
+        int priority_least = 0, priority_greatest = 0;
+        (void)hipDeviceGetStreamPriorityRange(&priority_least, &priority_greatest);
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
+        gate_on = size_class_admission_gates(plan, cus);
+        // events and streams of the class workers are created up front: released on every exit path
+        for (size_t k = 0; k < classes; ++k) class_done.create();
+        for (size_t k = 0; k < classes; ++k)
+            if (!plan.groups[k].empty())
+                // numerically lower = more urgent; the range is narrow (three levels on this hardware), later classes share the last
+                stream_of[k] = class_streams.create(device, true, std::min(priority_least, priority_greatest + launch_rank[k]));
+    }
+
+    double since_begin_ms() const { return std::chrono::duration<double, std::milli>(Clock::now() - results.begin).count(); }
+    void wait_for_turn(size_t k) const
+    {
+        while (launch_turn.load() < launch_rank[k] && !abandoned.load()) std::this_thread::yield();
+    }
+
+    // heaviest windows first: blocks are dispatched in window order, and a class that does not fit the free CUs at once
+    // should not keep its long chains for the end
+    std::vector<int32_t> heaviest_first(size_t k) const
+    {
+        std::vector<std::pair<int64_t, int32_t>> keyed;
+        keyed.reserve(plan.groups[k].size());
+        for (int32_t w : plan.groups[k])
+        {
+            int64_t bases = 0;
+            for (const std::string& read : windows[static_cast<size_t>(w)]) bases += static_cast<int64_t>(read.size());
+            keyed.emplace_back(-bases, w);
+        }
+        std::stable_sort(keyed.begin(), keyed.end());
+        std::vector<int32_t> order;
+        for (const auto& kw : keyed) order.push_back(kw.second);
+        return order;
+    }
+
+    void work(size_t k)
+    {
+        scoped_device_switch d(device);
+        cudaStream_t stream = stream_of[k];
+        DefaultDeviceAllocator allocator(static_cast<size_t>(share[k]), stream);
+        std::unique_ptr<Batch> batch =
+            create_batch(device, stream, allocator, share[k], output_mask, plan.configs[k], gap_score, mismatch_score, match_score);
+        batches_created.fetch_add(1);
+        created.arrive(k);
+        const std::vector<int32_t> order = heaviest_first(k);
+        WindowQueue queue{&order, order.size(), 0};
+        bool first_launch = true;
+        std::vector<size_t> in_batch;
+        while (!queue.empty())
+        {
+            batch->reset();
+            in_batch.clear();
+            fill_batch(*batch, in_batch, queue, INT32_MAX, windows, static_cast<int32_t>(k), out, "a batch of this size class cannot hold a single window");
+            filled.arrive(k);
+            if (first_launch) // submission order of the classes' first launches
+            {
+                wait_for_turn(k);
+                // (the gate's event was recorded before its class passed the turn on)
+                if (gate_on[k] >= 0) GW_CU_CHECK_ERR(hipStreamWaitEvent(stream, class_done.items[static_cast<size_t>(gate_on[k])], 0));
+            }
+            if (trace) std::fprintf(stderr, "[size classes] class %zu: generate_poa() called at %.1f ms\n", k, since_begin_ms());
+            if (batch->get_total_poas() > 0) batch->generate_poa();
+            if (trace) std::fprintf(stderr, "[size classes] class %zu: generate_poa() returned at %.1f ms\n", k, since_begin_ms());
+            // the gate of later class groups: (re-)recorded behind EVERY launch of this class, so a waiter that
+            // arrives late waits for the class's last submitted launch, not only for its first
+            GW_CU_CHECK_ERR(hipEventRecord(class_done.items[k], stream));
+            if (first_launch)
+            {
+                first_launch = false;
+                launch_turn.fetch_add(1);
+            }
+            if (batch->get_total_poas() == 0) continue;
+            launches++;
+            if (trace && want_msa)
+            {
+                GW_CU_CHECK_ERR(hipStreamSynchronize(stream));
+                std::fprintf(stderr, "[size classes] class %zu: kernels done at %.1f ms\n", k, since_begin_ms());
+            }
+            store_results(*batch, want_msa, in_batch, out);
+            if (trace && want_msa) std::fprintf(stderr, "[size classes] class %zu: get_msa() returned at %.1f ms\n", k, since_begin_ms());
+            results.stamp();
+        }
+        filled.arrive(k);
+    }
+
+    void run_class(size_t k)
+    {
+        try
+        {
+            work(k);
+        }
+        catch (...)
+        {
+            errors[k] = std::current_exception();
+            created.arrive(k); // the error path releases both rendezvous too
+            filled.arrive(k);
+            // a class that failed before its first launch still passes the turn on
+            wait_for_turn(k);
+            int32_t mine_turn = launch_rank[k];
+            launch_turn.compare_exchange_strong(mine_turn, launch_rank[k] + 1);
+        }
+    }
+};
+} // namespace
+
+void process_windows_size_classes(MultiDeviceOutput& out, const std::vector<std::vector<std::string>>& windows,
+                                  const SizeClassPlan& plan, int32_t device, int64_t memory_budget, int8_t output_mask,
+                                  int16_t gap_score, int16_t mismatch_score, int16_t match_score, double* compute_seconds)
+{
+    prepare_output(out, windows.size(), (output_mask & OutputType::msa) != 0);
+    if (compute_seconds) *compute_seconds = 0;
+    const size_t classes = plan.configs.size();
+    if (windows.empty() || classes == 0) return;
+    scoped_device_switch dev(device);
+    size_t active_classes = 0;
+    for (size_t k = 0; k < classes; ++k) active_classes += plan.groups[k].empty() ? 0 : 1;
+    if (active_classes == 0) return;
+    SizeClassRun run(out, windows, plan, active_classes, device, memory_budget, output_mask, gap_score, mismatch_score, match_score);
     std::vector<std::thread> threads;
     JoinAll join_on_exit{threads};
-    const auto t_begin = std::chrono::steady_clock::now();
+    run.results.begin = Clock::now();
     threads.reserve(classes);
     try
     {
-    for (size_t k = 0; k < classes; ++k)
-    {
-        if (plan.groups[k].empty()) continue;
-        threads.emplace_back([&, k]() {
-            bool counted = false;
-            auto arrive  = [&] { // first fill of this worker is done (or it failed): the compute clock starts when all have arrived
-                if (counted) return;
-                counted = true;
-                if (filled.fetch_add(1) + 1 == static_cast<int32_t>(active_classes))
-                {
-                    std::lock_guard<std::mutex> g(start_mutex);
-                    compute_begin = std::chrono::steady_clock::now();
-                }
-                while (filled.load() < static_cast<int32_t>(active_classes) && !spawn_failed.load()) std::this_thread::yield();
-            };
-            bool counted_created = false;
-            auto arrive_created  = [&](bool ok) { // this worker's Batch exists (or its creation failed): barrier before any filling
-                if (counted_created) return;
-                counted_created = true;
-                if (ok) created.fetch_add(1);
-                if (create_arrived.fetch_add(1) + 1 == static_cast<int32_t>(active_classes))
-                {
-                    std::lock_guard<std::mutex> g(start_mutex);
-                    fill_begin = std::chrono::steady_clock::now();
-                }
-                while (create_arrived.load() < static_cast<int32_t>(active_classes) && !spawn_failed.load()) std::this_thread::yield();
-            };
-            try
-            {
-                scoped_device_switch d(device);
-                cudaStream_t stream = stream_of[k];
-                {
-                    DefaultDeviceAllocator allocator(static_cast<size_t>(share[k]), stream);
-                    std::unique_ptr<Batch> batch = create_batch(device, stream, allocator, share[k], output_mask, plan.configs[k], gap_score,
-                                                                mismatch_score, match_score);
-                    // every class's Batch exists: the fill-inclusive clock (the reference's multi-batch region,
-                    // cudapoa/benchmarks/multi_batch.hpp:72-177, creates all batches first and times all of the filling)
-                    // starts, and no class fills before that point -- a class that was created early would otherwise do
-                    // its filling outside the clock
-                    arrive_created(true);
-                    // heaviest windows first: blocks are dispatched in window order, and a class that does not fit the free CUs
-                    // at once should not keep its long chains for the end
-                    std::vector<int32_t> mine = plan.groups[k];
-                    {
-                        auto bases = [&](int32_t w) {
-                            int64_t b = 0;
-                            for (const std::string& read : windows[static_cast<size_t>(w)]) b += static_cast<int64_t>(read.size());
-                            return b;
-                        };
-                        std::vector<std::pair<int64_t, int32_t>> keyed;
-                        keyed.reserve(mine.size());
-                        for (int32_t w : mine) keyed.emplace_back(-bases(w), w);
-                        std::stable_sort(keyed.begin(), keyed.end());
-                        for (size_t i = 0; i < mine.size(); i++) mine[i] = keyed[i].second;
-                    }
-                    bool first_launch = true;
-                    size_t next = 0;
-                    std::vector<size_t> in_batch;
-                    while (next < mine.size())
-                    {
-                        batch->reset();
-                        in_batch.clear();
-                        while (next < mine.size())
-                        {
-                            const size_t w = static_cast<size_t>(mine[next]);
-                            Group group;
-                            for (const std::string& read : windows[w]) group.push_back(Entry{read.c_str(), nullptr, get_size<int32_t>(read)});
-                            std::vector<StatusType> per_read;
-                            const StatusType st = batch->add_poa_group(per_read, group);
-                            if (st == StatusType::exceeded_maximum_poas)
-                            {
-                                if (in_batch.empty()) throw std::runtime_error("a batch of this size class cannot hold a single window");
-                                break;
-                            }
-                            out.worker_of_window[w] = static_cast<int32_t>(k);
-                            if (st == StatusType::success)
-                                in_batch.push_back(w);
-                            else
-                            {
-                                out.status[w] = st;
-                                if (st == StatusType::empty_poa_group && !windows[w].empty()) in_batch.push_back(n); // its empty POA owns a slot
-                            }
-                            next++;
-                        }
-                        arrive();
-                        if (first_launch) // submission order of the classes' first launches
-                        {
-                            while (launch_turn.load() < launch_rank[k] && !spawn_failed.load()) std::this_thread::yield();
-                            // (the gate's event was recorded before its class passed the turn on)
-                            if (gate_on[k] >= 0) GW_CU_CHECK_ERR(hipStreamWaitEvent(stream, class_done[static_cast<size_t>(gate_on[k])], 0));
-                        }
-                        const bool trace = std::getenv("GW_SIZE_CLASS_TRACE") != nullptr; // debugging: host-side timeline on stderr
-                        auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
-                        if (trace) std::fprintf(stderr, "[size classes] class %zu: generate_poa() called at %.1f ms\n", k, since());
-                        if (batch->get_total_poas() > 0) batch->generate_poa();
-                        if (trace) std::fprintf(stderr, "[size classes] class %zu: generate_poa() returned at %.1f ms\n", k, since());
-                        // the gate of later class groups: (re-)recorded behind EVERY launch of this class, so a waiter that
-                        // arrives late waits for the class's last submitted launch, not only for its first
-                        GW_CU_CHECK_ERR(hipEventRecord(class_done[k], stream));
-                        if (first_launch)
-                        {
-                            first_launch = false;
-                            launch_turn.fetch_add(1);
-                        }
-                        if (batch->get_total_poas() == 0) continue;
-                        launches++;
-                        std::vector<StatusType> status;
-                        if (want_msa)
-                        {
-                            std::vector<std::vector<std::string>> msa;
-                            if (trace)
-                            {
-                                GW_CU_CHECK_ERR(hipStreamSynchronize(stream));
-                                std::fprintf(stderr, "[size classes] class %zu: kernels done at %.1f ms\n", k, since());
-                            }
-                            batch->get_msa(msa, status);
-                            if (trace) std::fprintf(stderr, "[size classes] class %zu: get_msa() returned at %.1f ms\n", k, since());
-                            for (size_t i = 0; i < in_batch.size(); i++)
-                                if (in_batch[i] < n)
-                                {
-                                    out.msa[in_batch[i]]    = std::move(msa[i]);
-                                    out.status[in_batch[i]] = status[i];
-                                }
-                        }
-                        else
-                        {
-                            std::vector<std::string> consensus;
-                            std::vector<std::vector<uint16_t>> coverage;
-                            batch->get_consensus(consensus, coverage, status);
-                            for (size_t i = 0; i < in_batch.size(); i++)
-                                if (in_batch[i] < n)
-                                {
-                                    out.consensus[in_batch[i]] = std::move(consensus[i]);
-                                    out.coverage[in_batch[i]]  = std::move(coverage[i]);
-                                    out.status[in_batch[i]]    = status[i];
-                                }
-                        }
-                        // the compute clock stops when the last results have been handed over: releasing the slabs (hundreds
-                        // of GB for a long-read set, most of a second) is not part of generate_poa() + get_msa()
-                        {
-                            const int64_t now_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_begin).count();
-                            int64_t seen         = results_done_ns.load();
-                            while (seen < now_ns && !results_done_ns.compare_exchange_weak(seen, now_ns)) {}
-                        }
-                    }
-                    arrive();
-                }
-            }
-            catch (...)
-            {
-                errors[k] = std::current_exception();
-                arrive_created(false); // releases the creation barrier on the error path too
-                arrive();
-                // a class that failed before its first launch still passes the turn on
-                while (launch_turn.load() < launch_rank[k] && !spawn_failed.load()) std::this_thread::yield();
-                int32_t mine_turn = launch_rank[k];
-                launch_turn.compare_exchange_strong(mine_turn, launch_rank[k] + 1);
-            }
-        });
-    }
+        for (size_t k = 0; k < classes; ++k)
+            if (!plan.groups[k].empty()) threads.emplace_back([&run, k]() { run.run_class(k); });
     }
     catch (...)
     {
         // std::thread could not start a worker (std::system_error): the started ones must not spin at the barriers for it;
         // JoinAll joins them on the way out and the error surfaces
-        spawn_failed.store(true);
+        run.abandoned.store(true);
         throw;
     }
     for (std::thread& t : threads) t.join();
-    const auto t_end = std::chrono::steady_clock::now();
-    out.seconds      = std::chrono::duration<double>(t_end - t_begin).count();
-    if (compute_seconds)
-    {
-        const auto t_results = t_begin + std::chrono::nanoseconds(results_done_ns.load());
-        *compute_seconds     = results_done_ns.load() > 0 ? std::chrono::duration<double>(t_results - compute_begin).count()
-                                                          : std::chrono::duration<double>(t_end - compute_begin).count();
-    }
-    out.launches = launches.load();
-    if (created.load() == static_cast<int32_t>(active_classes) && results_done_ns.load() > 0)
-        out.seconds_after_creation = std::chrono::duration<double>(t_begin + std::chrono::nanoseconds(results_done_ns.load()) - fill_begin).count();
-    for (const std::exception_ptr& e : errors)
-        if (e) std::rethrow_exception(e);
+    const auto t_end = Clock::now();
+    out.seconds      = std::chrono::duration<double>(t_end - run.results.begin).count();
+    if (compute_seconds) *compute_seconds = std::chrono::duration<double>((run.results.stamped() ? run.results.last() : t_end) - run.filled.all_arrived).count();
+    out.launches = run.launches.load();
+    if (run.batches_created.load() == static_cast<int32_t>(active_classes) && run.results.stamped())
+        out.seconds_after_creation = std::chrono::duration<double>(run.results.last() - run.created.all_arrived).count();
+    rethrow_first(run.errors);
 }
 
 } // namespace cudapoa

@@ -3,6 +3,7 @@
 #include <claraparabricks/genomeworks/cudapoa/batch.hpp>
 
 #include "../../include/gwhip.h"
+#include "host_common.hpp"
 
 namespace claraparabricks
 {
@@ -18,6 +19,46 @@ void bin_poa_groups(std::vector<BatchConfig>& list_of_batch_sizes, std::vector<s
                     const std::vector<int32_t>& capacity, const std::vector<int32_t>& longest, const std::vector<int32_t>& reads,
                     int32_t band_width, BandMode band_mode, float adaptive_storage_factor, float graph_length_factor,
                     int32_t max_pred_distance, const std::vector<int32_t>* bins_capacity);
+
+/// The arrays of a batch, in the order they lie in its block.
+struct PoaSections
+{
+    uint8_t* sequences            = nullptr;
+    int8_t* weights               = nullptr;
+    int32_t* lengths              = nullptr;
+    gwhip_window_details* windows = nullptr;
+    uint8_t* consensus            = nullptr;
+    uint16_t* coverage            = nullptr;
+    uint8_t* msa                  = nullptr; // null unless the batch produces MSAs
+    uint64_t* cells               = nullptr;
+    uint32_t* work_counters       = nullptr; // 256 bytes behind the cell counters: the window counter of a persistent launch
+};
+
+/// Where those arrays start in the device block of a batch of some number of windows: [sequences | weights | lengths |
+/// windows | consensus | coverage | msa | cells | work counters | kernel workspace]. The pinned staging block is the same
+/// without the workspace, so consensus and coverage are neighbours with the same spacing on both sides (fetch_consensus()).
+struct PoaBlockLayout
+{
+    gwhost::BlockLayout block;
+    size_t sequence_bytes = 0; // of `sequences`, and of `weights`: the reads padded to 4 bytes, 4096 bytes of slack, rounded up
+    gwhost::BlockLayout::Slot<uint8_t> sequences;
+    gwhost::BlockLayout::Slot<int8_t> weights;
+    gwhost::BlockLayout::Slot<int32_t> lengths;
+    gwhost::BlockLayout::Slot<gwhip_window_details> windows;
+    gwhost::BlockLayout::Slot<uint8_t> consensus;
+    gwhost::BlockLayout::Slot<uint16_t> coverage;
+    gwhost::BlockLayout::Slot<uint8_t> msa;
+    bool has_msa = false;
+    gwhost::BlockLayout::Slot<uint64_t> cells;
+    gwhost::BlockLayout::Slot<uint32_t> work_counters;
+    gwhost::BlockLayout::Slot<char> workspace;
+
+    PoaSections in(char* b) const
+    {
+        return PoaSections{sequences.in(b), weights.in(b), lengths.in(b), windows.in(b),      consensus.in(b),
+                           coverage.in(b),  has_msa ? msa.in(b) : nullptr, cells.in(b), work_counters.in(b)};
+    }
+};
 
 class PoaBatch : public Batch
 {
@@ -59,11 +100,14 @@ private:
     StatusType add_poa();
     StatusType add_seq_to_poa(const char* seq, const int8_t* weights, int32_t seq_len);
     void upload_inputs();
+    void restore_lengths(); ///< a launch overwrote the length of each window's first read with its node count
     void launch(void* event_after_graph_build = nullptr, uint64_t* phase_cycles = nullptr);
     gwhip_poa_args kernel_args() const;
-    void log_kernel_error(StatusType error_type, std::vector<StatusType>& output_status);
+    StatusType window_status(size_t poa) const; ///< of the fetched consensus row: success, or the code behind the kernels' error marker
+    void log_kernel_error(StatusType error_type);
+    void log_failed_windows(const StatusType* status, size_t count); ///< in window order
     void fetch_consensus(std::string* consensus, std::vector<uint16_t>* coverage, StatusType* output_status, bool presize);
-    size_t plan(int32_t n_poas, size_t* offsets) const;
+    PoaBlockLayout plan(int32_t n_poas) const;
 
     int32_t max_sequences_per_poa_ = 0;
     int32_t device_id_             = 0;
@@ -84,34 +128,14 @@ private:
     size_t next_scores_offset_      = 0;
     size_t score_buffer_bytes_      = 0;
 
-    // device block
-    char* device_block_        = nullptr;
-    size_t device_block_bytes_ = 0;
-    size_t workspace_bytes_    = 0;
-    size_t input_capacity_     = 0;
-    uint8_t* d_sequences_      = nullptr;
-    int8_t* d_weights_         = nullptr;
-    int32_t* d_seq_lens_       = nullptr;
-    gwhip_window_details* d_windows_ = nullptr;
-    uint8_t* d_consensus_      = nullptr;
-    uint16_t* d_coverage_      = nullptr;
-    uint8_t* d_msa_            = nullptr;
-    uint64_t* d_cells_         = nullptr;
-    uint32_t* d_work_counters_ = nullptr; // two zeroed words behind the cell counters: the window counter of a persistent launch
-    char* d_workspace_         = nullptr;
-
-    // pinned staging block
-    char* host_block_        = nullptr;
-    size_t host_block_bytes_ = 0;
-    size_t host_block_capacity_ = 0; // what the pinned cache handed out (pinned_release wants it back)
-    uint8_t* h_sequences_    = nullptr;
-    int8_t* h_weights_       = nullptr;
-    int32_t* h_seq_lens_     = nullptr;
-    gwhip_window_details* h_windows_ = nullptr;
-    uint8_t* h_consensus_    = nullptr;
-    uint16_t* h_coverage_    = nullptr;
-    uint8_t* h_msa_          = nullptr;
-    uint64_t* h_cells_       = nullptr;
+    PoaBlockLayout layout_;
+    size_t workspace_bytes_ = 0;
+    size_t input_capacity_  = 0;
+    char* device_block_     = nullptr;
+    PoaSections d_;
+    char* host_block_           = nullptr; // pinned staging
+    size_t host_block_capacity_ = 0;       // what the pinned cache handed out (pinned_release wants it back)
+    PoaSections h_;
 };
 
 } // namespace cudapoa

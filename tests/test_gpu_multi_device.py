@@ -56,3 +56,40 @@ def test_msa_mode_and_error_paths():
         cudapoa.process_windows_multi_device(windows[:1], 16, 256, devices=(0,), batches_per_device=0)
     empty = cudapoa.process_windows_multi_device([], 16, 256, devices=(0,))
     assert empty["status"] == [] and empty["launches"] == 0
+
+
+def test_size_classes_with_a_gated_class_second_fills_and_a_refused_window():
+    """process_windows_size_classes on a plan of three classes whose last is gated on the device, under a budget that leaves
+    every class little more than its slack (the first and the last class need further fills), with one window whose only
+    read is too long for its class: every MSA and status equals the oracle's, every window was run by its class."""
+    import torch
+    from genomeworks_amd import cudapoa, synthetic
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    room = cus + cus // 4  # windows the device admits at once (size_class_admission_gates)
+    counts, shapes = (40, 20, room - 50), ((520, 4), (200, 6), (100, 4))  # windows per class; backbone length and reads
+    planned = [[r.decode() for r in synthetic.generate_window(9000 + w, *shapes[k], 8, 4, 4)]
+               for k in range(3) for w in range(sum(counts[:k]), sum(counts[:k + 1]))]
+    plan = cudapoa.SizeClassPlan(planned, msa_flag=True, band_width=128, band_mode="full_band")
+    assert [len(g) for g in plan.groups] == list(counts)
+    assert plan.admission_gates(cus) == [-1, -1, 1]  # the third class waits for the second
+    windows = list(planned)
+    refused = counts[0] + 5
+    windows[refused] = ["ACGT" * 100]  # longer than its class's max_sequence_size: refused at add time, its empty POA owns a slot
+    assert len(windows[refused][0]) > plan.configs[1]["max_sequence_size"]
+    # the slack of 64 MiB per class and two windows: 18 of the first class's 40 windows at 4 MB each fit one fill
+    out = cudapoa.process_windows_size_classes(windows, plan, memory_budget=3 * (64 << 20) + (1 << 20), output_type="msa")
+    assert out["launches"] > 3 and out["compute_seconds"] > 0 and out["seconds_after_creation"] > 0
+    assert out["worker"] == [k for k in range(3) for _ in range(counts[k])]
+    for k in range(3):
+        c = plan.configs[k]
+        cfg = O.make_cfg(c["max_sequence_size"], c["max_sequences_per_poa"], 128, 0, output_mask=2)
+        for field in ("max_consensus_size", "max_nodes_per_graph", "matrix_sequence_dimension", "max_banded_pred_distance"):
+            assert getattr(cfg, field) == c[field], field
+        O.lib().poa_cfg_select_types(cfg)
+        with O.Workspace(cfg) as ws:
+            for w in plan.groups[k]:
+                if w == refused:
+                    continue
+                ref = ws.process(windows[w])
+                assert out["status"][w] == ref["status"] == 0 and out["msa"][w] == ref["msa"], w
+    assert out["status"][refused] == cudapoa.empty_poa_group and out["msa"][refused] == []
