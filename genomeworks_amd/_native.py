@@ -219,6 +219,17 @@ def mapper():
         L.gw_mapper_index_host_copy_to_device.argtypes = [vp, vp, vp]
         L.gw_mapper_index_host_copy_destroy.restype = None
         L.gw_mapper_index_host_copy_destroy.argtypes = [vp]
+        L.gw_mapper_window_overlaps.restype = vp
+        L.gw_mapper_window_overlaps.argtypes = [vp, i64, vp, vp, i32, u32, vp, vp, i32, u32, i32, i32, i64, vp]
+        L.gw_mapper_window_segments.restype = vp
+        L.gw_mapper_window_segments.argtypes = [vp, i64, vp, vp, i32, u32, vp, vp, i32, u32, i32, i64, vp]
+        L.gw_mapper_windows_counts.argtypes = [vp, vp]
+        L.gw_mapper_windows_copy_segments.argtypes = [vp, vp, vp, vp, vp]
+        L.gw_mapper_windows_copy_windows.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.gw_mapper_windows_destroy.restype = None
+        L.gw_mapper_windows_destroy.argtypes = [vp]
+        L.gw_mapper_select_layers.restype = i64
+        L.gw_mapper_select_layers.argtypes = [vp, i64, vp, i64, i32, u32, vp, i32, u32, i32, i32, vp, i64, vp, vp, i64]
         L.gwm_align_bytes_needed.restype = i64
         L.gwm_align_bytes_needed.argtypes = [i32, i32, i32]
         _mapper = L

@@ -35,8 +35,9 @@ EXTENDER_HOST_SRCS = ["extender/extender.cpp"]
 SEMIGLOBAL_KERNEL_SRCS = ["semiglobal/gws_ends.hip"]
 # cudamapper likewise
 MAPPER_KERNEL_SRCS = ["mapper/gwm_mapper.hip", "mapper/gwm_postprocess.hip", "mapper/gwm_align.hip",
-                      "mapper/gwm_index_cache.hip"]
-MAPPER_HOST_SRCS = ["mapper/mapper.cpp", "mapper/gwm_driver.cpp", "mapper/gwm_index_batcher.cpp"]
+                      "mapper/gwm_segments.hip", "mapper/gwm_index_cache.hip"]
+MAPPER_HOST_SRCS = ["mapper/mapper.cpp", "mapper/gwm_driver.cpp", "mapper/gwm_index_batcher.cpp",
+                    "mapper/gwm_windows.cpp"]
 
 # no fast-math, no FMA contraction: band placement is IEEE fp32
 KERNEL_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=off",
@@ -190,9 +191,10 @@ def build_extender(force=False):
 
 
 def build_mapper(force=False):
-    """libcudamapper.so: the sketch / index / matcher / overlapper / post-processing / overlap alignment kernels with
-    their rocPRIM scans, selects and sorts (hipcc, gfx950), linked against libgwhip.so for the aligner, and the Index /
-    Matcher handles, the index batcher and the batched driver behind the C API (g++);
+    """libcudamapper.so: the sketch / index / matcher / overlapper / post-processing / overlap alignment / window
+    segment kernels with their rocPRIM scans, selects and sorts (hipcc, gfx950), linked against libgwhip.so for the
+    aligner, and the Index / Matcher handles, the index batcher, the batched driver and polishing's layer selection
+    behind the C API (g++);
     then bin/cudamapper, which links it and libgenomeworks_amd.so (built before this)."""
     headers = [os.path.join(ROOT, "include", "gwhip_mapper.h"), os.path.join(ROOT, "include", "gwhip.h")]
     host_sig = _digest(_deps("mapper", (".cpp", ".h", ".hpp")), HOST_FLAGS)

@@ -14,6 +14,8 @@ gfx950), over the flat C API of include/gw_mapper_capi.h.
     overlaps = map_reads_batched(reads, query_indices_in_host_memory=10, query_indices_in_device_memory=5)  # -Q -q
     copy = index.to_host(); index = copy.to_device()               # packed copy in pinned host memory and back
     text = format_paf(overlaps, names, lengths, names, lengths, 15, cigars=cigars)
+    segments, offsets, edit_distances = window_segments(overlaps, reads, targets, window_length=500)
+    windows = overlap_windows(overlaps, reads, targets, window_length=500, max_depth=30)   # polisher.polish feeds on it
 
 Index arrays carry the reference's names (representations, read_ids, positions_in_reads, directions_of_reads,
 unique_representations, first_occurrence_of_representations) and come back as numpy arrays."""
@@ -31,6 +33,10 @@ OVERLAP = np.dtype({"names": ["query_read_id", "target_read_id", "query_start_po
                               "target_end_position_in_read", "relative_strand", "num_residues", "overlap_complete"],
                     "formats": ["<u4"] * 6 + ["u1", "<u4", "u1"],
                     "offsets": [0, 4, 8, 12, 16, 20, 24, 28, 32], "itemsize": 36})
+
+# gwm_segment: what one overlap's alignment covers of one window of its target read
+SEGMENT = np.dtype([("overlap", "<u4"), ("window", "<u4"), ("target_first", "<u4"), ("target_last", "<u4"),
+                    ("query_begin", "<u4"), ("query_end", "<u4")])
 
 FORWARD, REVERSE = 0, 1  # SketchElement::DirectionOfRepresentation
 
@@ -344,6 +350,98 @@ def align_overlaps(overlaps, query_reads, target_reads=None, first_query_read_id
     if timings is not None:
         timings.update(gather=float(ms[0]), align=float(ms[1]), cigar_text=float(ms[2]))
     return _split_cigars(text, offsets), edits
+
+
+def _window_overlaps(overlaps, query_reads, target_reads, window_length, max_depth, first_query_read_id,
+                     first_target_read_id, max_device_bytes, stream, timings):
+    """gw_mapper_window_overlaps and everything it holds, as host arrays; max_depth None: gw_mapper_window_segments, the
+    segments pass alone"""
+    L = _native.mapper()
+    o = np.ascontiguousarray(overlaps, OVERLAP)
+    q, t = _read_set_args(query_reads, target_reads)
+    if max_depth is None:
+        h = L.gw_mapper_window_segments(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id,
+                                        int(window_length), int(max_device_bytes), _stream(stream))
+    else:
+        h = L.gw_mapper_window_overlaps(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id,
+                                        int(window_length), int(max_depth), int(max_device_bytes), _stream(stream))
+    if not h:
+        raise _err(L)
+    try:
+        counts = np.zeros(4, np.int64)
+        L.gw_mapper_windows_counts(h, _p(counts))
+        n_win, n_seq, n_bases, n_seg = (int(x) for x in counts)
+        segments, seg_offsets = np.zeros(n_seg, SEGMENT), np.zeros(len(o) + 1, np.int64)
+        edits, ms = np.zeros(len(o), np.int32), np.zeros(4, np.float32)
+        L.gw_mapper_windows_copy_segments(h, _p(segments), _p(seg_offsets), _p(edits), _p(ms))
+        bases, seq_offsets = np.zeros(max(n_bases, 1), np.uint8), np.zeros(n_seq + 1, np.int64)
+        per_window, reads, index = np.zeros(n_win, np.int32), np.zeros(n_win, np.uint32), np.zeros(n_win, np.uint32)
+        L.gw_mapper_windows_copy_windows(h, _p(bases), _p(seq_offsets), _p(per_window), _p(reads), _p(index))
+    finally:
+        L.gw_mapper_windows_destroy(h)
+    if timings is not None:
+        timings.update(gather=float(ms[0]), align=float(ms[1]), segments=float(ms[2]), window_gather=float(ms[3]),
+                       bytes_to_host=o.nbytes + segments.nbytes + seg_offsets.nbytes + edits.nbytes + n_bases,
+                       segment_bytes=segments.nbytes, window_bases=n_bases)
+    return (segments, seg_offsets, edits), (bases[:n_bases], seq_offsets, per_window, reads, index)
+
+
+def window_segments(overlaps, query_reads, target_reads=None, window_length=500, first_query_read_id=0,
+                    first_target_read_id=0, max_device_bytes=0, stream=None, timings=None):
+    """What every overlap's alignment covers of every window of its target read, computed on the device from the
+    alignment states (gwm_window_segments): the overlaps are aligned exactly as align_overlaps aligns them, and per
+    window k = target position // window_length that holds an aligned column (match or mismatch) one SEGMENT record
+    gives the smallest and largest target position (forward coordinates) and the query positions [query_begin,
+    query_end) of those columns. Returns (segments, segment_offsets, edit_distances): records ordered by overlap, then
+    by ascending window; those of overlap i are segments[segment_offsets[i]:segment_offsets[i + 1]]; edit_distances as
+    align_overlaps returns them. Arguments, chunking and errors as for align_overlaps; window_length < 1 raises.
+    Nothing but the records, their offsets and the edit distances comes back: no window is selected or gathered.
+    `timings`, if a dict, receives gather, align and segments (device ms; window_gather is 0) and bytes_to_host."""
+    return _window_overlaps(overlaps, query_reads, target_reads, window_length, None, first_query_read_id,
+                            first_target_read_id, max_device_bytes, stream, timings)[0]
+
+
+def overlap_windows(overlaps, query_reads, target_reads=None, window_length=500, max_depth=30, first_query_read_id=0,
+                    first_target_read_id=0, max_device_bytes=0, stream=None, timings=None):
+    """The POA windows of the target reads: [(target_read, window, [backbone, layer, ...]), ...] by target read (its
+    position in the target set), then by window; every target read of L > 0 bases has windows 0 .. (L - 1) //
+    window_length. The backbone is the target's bases of the window; the layers are the query slices whose alignment
+    spans it, chosen by select_layers from the records of window_segments and cut out of the reads on the device ('-'
+    layers reversed through the aligner's table, "TGAC"[(c >> 1) & 3]). Sequences are bytes. `timings` as for
+    window_segments, plus bytes_to_host."""
+    _, (bases, offsets, per_window, reads, index) = _window_overlaps(
+        overlaps, query_reads, target_reads, window_length, max_depth, first_query_read_id, first_target_read_id,
+        max_device_bytes, stream, timings)
+    flat = bases.tobytes()
+    out, at = [], 0
+    for n, r, k in zip(per_window.tolist(), reads.tolist(), index.tolist()):
+        out.append((r, k, [flat[offsets[i]:offsets[i + 1]] for i in range(at, at + n)]))
+        at += n
+    return out
+
+
+def select_layers(segments, overlaps, n_queries, target_lengths, window_length=500, max_depth=30,
+                  first_query_read_id=0, first_target_read_id=0):
+    """Polishing's layer selection over host arrays, without a device (gw_mapper_select_layers; the rules are in
+    INTEGRATION.md section 3j): one overlap per query read is kept (the longest query span, the first on ties); a
+    SEGMENT record of a kept overlap is a layer when it reaches within window_length // 100 of both ends of its window
+    and holds 1 .. 2 * window_length query bases; the layers of a window are ordered by (target_first, overlap) and
+    cut at max_depth. Returns (plan, windows): plan[i] = (set, read, begin, end, reversed) of sequence i, set 0 the
+    queries and 1 the targets; windows[j] = (target_read, window, first_sequence, n_sequences), backbone first."""
+    L = _native.mapper()
+    s = np.ascontiguousarray(segments, SEGMENT)
+    o = np.ascontiguousarray(overlaps, OVERLAP)
+    lengths = np.ascontiguousarray(target_lengths, np.int64)
+    args = (_p(s), len(s), _p(o), len(o), int(n_queries), first_query_read_id, _p(lengths), len(lengths),
+            first_target_read_id, int(window_length), int(max_depth))
+    n_windows = C.c_int64(0)
+    n = L.gw_mapper_select_layers(*args, None, 0, C.byref(n_windows), None, 0)
+    if n < 0:
+        raise _err(L)
+    plan, table = np.zeros((n, 5), np.uint32), np.zeros((n_windows.value, 4), np.uint32)
+    if L.gw_mapper_select_layers(*args, _p(plan), n, C.byref(n_windows), _p(table), len(table)) != n:
+        raise _err(L)
+    return [tuple(int(x) for x in row) for row in plan], [tuple(int(x) for x in row) for row in table]
 
 
 def group_reads_into_indices(read_lengths, max_basepairs_per_index):

@@ -1,28 +1,26 @@
 // gwm_align.hip -- cudamapper on gfx950: the alignment of final overlaps with everything kept on the device
-// (include/gwhip_mapper.h, gwm_align_overlaps). Per chunk of consecutive overlaps: a gather kernel cuts the query and
-// target slices out of the resident read sets into the layout the default aligner takes (the target slice reverse-
-// complemented with the aligner's table on '-'), gwhip_hirschberg_myers of libgwhip.so aligns them as it stands, and a
-// CIGAR writer turns the per-column states into the text of Alignment::convert_to_cigar() and the edit distance. Neither
+// (include/gwhip_mapper.h, gwm_align_overlaps). Per chunk of consecutive overlaps (the loop of gwm_align_chunks.hpp): a
+// gather kernel cuts the query and target slices out of the resident read sets into the layout the default aligner
+// takes (the target slice reverse-complemented with the aligner's table on '-'), gwhip_hirschberg_myers of libgwhip.so
+// aligns them as it stands, and the CIGAR writer here, the loop's consumer, turns the per-column states into the text
+// of Alignment::convert_to_cigar() and the edit distance. Neither
 // the bases nor the states cross to the host; the overlap records (36 B each) are read there to size the chunks.
 //
-// Gather: one block per slice, consecutive lanes on consecutive output bytes. CIGAR text: one wave64 per alignment over
+// CIGAR text: one wave64 per alignment over
 // tiles of 64 columns -- symbol per lane, run heads by comparison with the neighbouring lane, a 64-bit ballot, run
 // lengths from the distance to the next lower set bit, the open run carried between tiles in wave-uniform registers;
 // a counting pass, an exclusive scan of the byte counts, a writing pass. No LDS, no scratch.
-#include "gwhip_mapper.h"
+#include "gwm_align_chunks.hpp"
 
 #include "gwhip.h"
-#include "gwm_device_utils.hpp"
 
 #include <deque>
-#include <vector>
 
 namespace
 {
 
-constexpr unsigned kWavesPerBlock = kThreads / 64;
-constexpr int64_t kPad            = 64;      // bytes behind the gathered bases and the state slots (the host aligner pads 16)
-constexpr int64_t kMaxChunk       = 1 << 20; // alignments per aligner call
+constexpr int64_t kPad      = 64;      // bytes behind the gathered bases and the state slots (the host aligner pads 16)
+constexpr int64_t kMaxChunk = 1 << 20; // alignments per aligner call
 
 // bad[0] |= 1: a read id outside its read set; |= 2: an end beyond its read; |= 4: a start behind its end
 __global__ void __launch_bounds__(kThreads) align_validate_kernel(const gwm_overlap* __restrict__ o, int64_t n, ReadSet q,
@@ -200,30 +198,149 @@ __global__ void __launch_bounds__(kThreads) cigar_kernel(const uint8_t* __restri
     }
 }
 
-void exclusive_sum(const int64_t* in, int64_t* out, int64_t n, Temp& t, hipStream_t s)
-{
-    size_t bytes = 0;
-    GWM_CHECK(rocprim::exclusive_scan(nullptr, bytes, in, out, int64_t(0), static_cast<size_t>(n), rocprim::plus<int64_t>(), s));
-    GWM_CHECK(rocprim::exclusive_scan(t.get(bytes), bytes, in, out, int64_t(0), static_cast<size_t>(n),
-                                      rocprim::plus<int64_t>(), s));
-}
-
-template <typename T>
-void grow(dbuf<T>& b, int64_t n)
-{
-    if (n > b.n)
-        b.resize(n);
-}
-
 // Device bytes of one chunk of m alignments whose slices hold `bases` bases: gathered bases, state slots, slice lengths and
 // starts, result lengths, CIGAR byte counts and offsets, the aligner's workspace, and the text at its upper bound of two
 // bytes per column (runs of one column).
-int64_t chunk_bytes(int64_t m, int64_t bases, size_t workspace)
+inline int64_t chunk_bytes(int64_t m, int64_t bases, size_t workspace)
 {
     return 2 * (bases + kPad) + 2 * (2 * m + 1) * 8 + m * 4 + 2 * (m + 1) * 8 + static_cast<int64_t>(workspace) + 2 * bases;
 }
 
 } // namespace
+
+namespace gwm
+{
+
+void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, const char* query_bases,
+                  const int64_t* query_offsets, int32_t n_queries, uint32_t first_query_read_id,
+                  const char* target_bases, const int64_t* target_offsets, int32_t n_targets,
+                  uint32_t first_target_read_id, int64_t max_device_bytes, hipStream_t s, float* stage_ms,
+                  const std::function<void(const AlignedChunk&)>& consume)
+{
+    const std::string who = std::string(name) + ": ";
+    const ReadSet q{reinterpret_cast<const uint8_t*>(query_bases), query_offsets, static_cast<uint32_t>(n_queries),
+                    first_query_read_id};
+    const ReadSet t{reinterpret_cast<const uint8_t*>(target_bases), target_offsets, static_cast<uint32_t>(n_targets),
+                    first_target_read_id};
+    {
+        dbuf<uint32_t> bad(1);
+        GWM_CHECK(hipMemsetAsync(bad.p, 0, sizeof(uint32_t), s));
+        align_validate_kernel<<<grid_for(n), kThreads, 0, s>>>(overlaps, n, q, t, bad.p);
+        GWM_CHECK(hipGetLastError());
+        const uint32_t what = to_host(bad.p, s);
+        if (what & 1u)
+            throw std::invalid_argument(who + "an overlap names a read outside the read set");
+        if (what & 4u)
+            throw std::invalid_argument(who + "an overlap starts behind its end");
+        if (what & 2u)
+            throw std::invalid_argument(who + "an overlap lies beyond the end of its read");
+    }
+    // the records on the host, for sizing only: slice starts of the whole call and the longest query slice
+    std::vector<gwm_overlap> records(static_cast<size_t>(n));
+    GWM_CHECK(hipMemcpyAsync(records.data(), overlaps, sizeof(gwm_overlap) * records.size(), hipMemcpyDeviceToHost, s));
+    GWM_CHECK(hipStreamSynchronize(s));
+    std::vector<int64_t> host_starts(2 * records.size() + 1, 0);
+    int64_t max_query_length = 0;
+    for (size_t i = 0; i < records.size(); ++i)
+    {
+        const int64_t ql       = records[i].query_end_position_in_read - records[i].query_start_position_in_read;
+        const int64_t tl       = records[i].target_end_position_in_read - records[i].target_start_position_in_read;
+        host_starts[2 * i + 1] = host_starts[2 * i] + ql;
+        host_starts[2 * i + 2] = host_starts[2 * i + 1] + tl;
+        max_query_length       = std::max(max_query_length, ql);
+    }
+    if (max_query_length > INT32_MAX)
+        throw std::invalid_argument(who + "a query slice of 2^31 bases or more");
+    const int32_t capacity = static_cast<int32_t>(max_query_length);
+    int64_t budget         = max_device_bytes;
+    if (budget == 0)
+    {
+        size_t free_bytes = 0, total_bytes = 0;
+        GWM_CHECK(hipMemGetInfo(&free_bytes, &total_bytes));
+        budget = static_cast<int64_t>(free_bytes / 2);
+    }
+    auto cost = [&](int64_t first, int64_t m) {
+        const int64_t* hs = host_starts.data() + 2 * first;
+        return chunk_bytes(m, hs[2 * m] - hs[0],
+                           gwhip_hirschberg_myers_workspace_bytes(static_cast<int32_t>(m), hs, capacity));
+    };
+
+    Temp temp;
+    dbuf<uint8_t> sequences, results;
+    dbuf<int64_t> lengths, starts;
+    dbuf<int32_t> result_lengths;
+    dbuf<char> workspace;
+    Events ev(4);
+    for (int64_t first = 0; first < n;)
+    {
+        if (cost(first, 1) > budget)
+            throw std::invalid_argument(who + "overlap " + std::to_string(first) + " needs " +
+                                        std::to_string(cost(first, 1)) + " device bytes, max_device_bytes allows " +
+                                        std::to_string(budget));
+        // the longest run of overlaps from `first` that doubling and then bisection find within the budget
+        const int64_t most = std::min(n - first, kMaxChunk);
+        int64_t m = 1, too_many = most + 1;
+        while (m < most && too_many > most)
+        {
+            const int64_t twice = std::min(2 * m, most);
+            if (cost(first, twice) <= budget)
+                m = twice;
+            else
+                too_many = twice;
+        }
+        while (too_many - m > 1)
+        {
+            const int64_t mid = m + (too_many - m) / 2;
+            if (cost(first, mid) <= budget)
+                m = mid;
+            else
+                too_many = mid;
+        }
+        const int64_t* hs     = host_starts.data() + 2 * first;
+        const int64_t bases   = hs[2 * m] - hs[0];
+        const size_t ws_bytes = gwhip_hirschberg_myers_workspace_bytes(static_cast<int32_t>(m), hs, capacity);
+        const gwm_overlap* o  = overlaps + first;
+        grow(sequences, bases + kPad);
+        grow(results, bases + kPad);
+        grow(lengths, 2 * m + 1);
+        grow(starts, 2 * m + 1);
+        grow(result_lengths, m);
+        grow(workspace, static_cast<int64_t>(ws_bytes));
+
+        ev.record(0, s);
+        slice_lengths_kernel<<<grid_for(m + 1), kThreads, 0, s>>>(o, m, lengths.p);
+        GWM_CHECK(hipGetLastError());
+        exclusive_sum(lengths.p, starts.p, 2 * m + 1, temp, s);
+        gather_kernel<<<static_cast<unsigned>(2 * m), kThreads, 0, s>>>(o, q, t, starts.p, sequences.p);
+        GWM_CHECK(hipGetLastError());
+        ev.record(1, s);
+        gwhip_hirschberg_args a{};
+        a.n_alignments     = static_cast<int32_t>(m);
+        a.sequences        = reinterpret_cast<const char*>(sequences.p);
+        a.sequence_starts  = starts.p;
+        a.max_query_length = capacity;
+        a.results          = reinterpret_cast<int8_t*>(results.p);
+        a.result_lengths   = result_lengths.p;
+        a.workspace        = workspace.p;
+        a.workspace_bytes  = ws_bytes;
+        if (gwhip_hirschberg_myers(&a, s) != 0)
+        {
+            char text[512] = "";
+            gwhip_last_error_string(text, sizeof(text));
+            throw std::runtime_error(who + text);
+        }
+        ev.record(2, s);
+        consume(AlignedChunk{first, m, static_cast<unsigned>((m + kWavesPerBlock - 1) / kWavesPerBlock), o, results.p,
+                             starts.p, result_lengths.p});
+        ev.record(3, s);
+        for (int k = 0; k < 3; ++k)
+            stage_ms[k] += ev.ms(k, k + 1);
+        first += m;
+    }
+}
+
+
+} // namespace gwm
 
 extern "C" {
 
@@ -260,143 +377,33 @@ int gwm_align_overlaps(const gwm_overlap* overlaps, int64_t n, const char* query
         if (n >= (int64_t(1) << 31))
             throw std::invalid_argument("gwm_align_overlaps: 2^31 overlaps or more");
         hipStream_t s = static_cast<hipStream_t>(stream);
-        const ReadSet q{reinterpret_cast<const uint8_t*>(query_bases), query_offsets, static_cast<uint32_t>(n_queries),
-                        first_query_read_id};
-        const ReadSet t{reinterpret_cast<const uint8_t*>(target_bases), target_offsets,
-                        static_cast<uint32_t>(n_targets), first_target_read_id};
-        {
-            dbuf<uint32_t> bad(1);
-            GWM_CHECK(hipMemsetAsync(bad.p, 0, sizeof(uint32_t), s));
-            align_validate_kernel<<<grid_for(n), kThreads, 0, s>>>(overlaps, n, q, t, bad.p);
-            GWM_CHECK(hipGetLastError());
-            const uint32_t what = to_host(bad.p, s);
-            if (what & 1u)
-                throw std::invalid_argument("gwm_align_overlaps: an overlap names a read outside the read set");
-            if (what & 4u)
-                throw std::invalid_argument("gwm_align_overlaps: an overlap starts behind its end");
-            if (what & 2u)
-                throw std::invalid_argument("gwm_align_overlaps: an overlap lies beyond the end of its read");
-        }
-        // the records on the host, for sizing only: slice starts of the whole call and the longest query slice
-        std::vector<gwm_overlap> records(static_cast<size_t>(n));
-        GWM_CHECK(hipMemcpyAsync(records.data(), overlaps, sizeof(gwm_overlap) * records.size(), hipMemcpyDeviceToHost, s));
-        GWM_CHECK(hipStreamSynchronize(s));
-        std::vector<int64_t> host_starts(2 * records.size() + 1, 0);
-        int64_t max_query_length = 0;
-        for (size_t i = 0; i < records.size(); ++i)
-        {
-            const int64_t ql       = records[i].query_end_position_in_read - records[i].query_start_position_in_read;
-            const int64_t tl       = records[i].target_end_position_in_read - records[i].target_start_position_in_read;
-            host_starts[2 * i + 1] = host_starts[2 * i] + ql;
-            host_starts[2 * i + 2] = host_starts[2 * i + 1] + tl;
-            max_query_length       = std::max(max_query_length, ql);
-        }
-        if (max_query_length > INT32_MAX)
-            throw std::invalid_argument("gwm_align_overlaps: a query slice of 2^31 bases or more");
-        const int32_t capacity = static_cast<int32_t>(max_query_length);
-        int64_t budget         = max_device_bytes;
-        if (budget == 0)
-        {
-            size_t free_bytes = 0, total_bytes = 0;
-            GWM_CHECK(hipMemGetInfo(&free_bytes, &total_bytes));
-            budget = static_cast<int64_t>(free_bytes / 2);
-        }
-        auto cost = [&](int64_t first, int64_t m) {
-            const int64_t* hs = host_starts.data() + 2 * first;
-            return chunk_bytes(m, hs[2 * m] - hs[0],
-                               gwhip_hirschberg_myers_workspace_bytes(static_cast<int32_t>(m), hs, capacity));
-        };
-
-        dbuf<int64_t> counts(n + 1), offsets(n + 1);
+        dbuf<int64_t> counts(n + 1), offsets(n + 1), local_offsets;
         dbuf<int32_t> edit_distances(n);
         GWM_CHECK(hipMemsetAsync(counts.p, 0, sizeof(int64_t) * static_cast<size_t>(n + 1), s));
-        Temp temp;
-        dbuf<uint8_t> sequences, results;
-        dbuf<int64_t> lengths, starts, local_offsets;
-        dbuf<int32_t> result_lengths;
-        dbuf<char> workspace;
         std::deque<dbuf<char>> texts; // one per chunk
         std::vector<int64_t> text_sizes;
-        Events ev(4);
-        for (int64_t first = 0; first < n;)
-        {
-            if (cost(first, 1) > budget)
-                throw std::invalid_argument("gwm_align_overlaps: overlap " + std::to_string(first) + " needs " +
-                                            std::to_string(cost(first, 1)) + " device bytes, max_device_bytes allows " +
-                                            std::to_string(budget));
-            // the longest run of overlaps from `first` that doubling and then bisection find within the budget
-            const int64_t most = std::min(n - first, kMaxChunk);
-            int64_t m = 1, too_many = most + 1;
-            while (m < most && too_many > most)
-            {
-                const int64_t twice = std::min(2 * m, most);
-                if (cost(first, twice) <= budget)
-                    m = twice;
-                else
-                    too_many = twice;
-            }
-            while (too_many - m > 1)
-            {
-                const int64_t mid = m + (too_many - m) / 2;
-                if (cost(first, mid) <= budget)
-                    m = mid;
-                else
-                    too_many = mid;
-            }
-            const int64_t* hs      = host_starts.data() + 2 * first;
-            const int64_t bases    = hs[2 * m] - hs[0];
-            const size_t ws_bytes  = gwhip_hirschberg_myers_workspace_bytes(static_cast<int32_t>(m), hs, capacity);
-            const gwm_overlap* o   = overlaps + first;
-            const unsigned m_waves = static_cast<unsigned>((m + kWavesPerBlock - 1) / kWavesPerBlock);
-            grow(sequences, bases + kPad);
-            grow(results, bases + kPad);
-            grow(lengths, 2 * m + 1);
-            grow(starts, 2 * m + 1);
-            grow(local_offsets, m + 1);
-            grow(result_lengths, m);
-            grow(workspace, static_cast<int64_t>(ws_bytes));
-
-            ev.record(0, s);
-            slice_lengths_kernel<<<grid_for(m + 1), kThreads, 0, s>>>(o, m, lengths.p);
+        // the CIGAR writer: byte counts, their scan, the text of the chunk
+        Temp temp;
+        auto write_cigars = [&](const AlignedChunk& c) {
+            grow(local_offsets, c.m + 1);
+            cigar_kernel<false><<<c.m_waves, kThreads, 0, s>>>(c.results, c.starts, c.result_lengths, c.m,
+                                                              counts.p + c.first, edit_distances.p + c.first, nullptr,
+                                                              nullptr);
             GWM_CHECK(hipGetLastError());
-            exclusive_sum(lengths.p, starts.p, 2 * m + 1, temp, s);
-            gather_kernel<<<static_cast<unsigned>(2 * m), kThreads, 0, s>>>(o, q, t, starts.p, sequences.p);
-            GWM_CHECK(hipGetLastError());
-            ev.record(1, s);
-            gwhip_hirschberg_args a{};
-            a.n_alignments     = static_cast<int32_t>(m);
-            a.sequences        = reinterpret_cast<const char*>(sequences.p);
-            a.sequence_starts  = starts.p;
-            a.max_query_length = capacity;
-            a.results          = reinterpret_cast<int8_t*>(results.p);
-            a.result_lengths   = result_lengths.p;
-            a.workspace        = workspace.p;
-            a.workspace_bytes  = ws_bytes;
-            if (gwhip_hirschberg_myers(&a, s) != 0)
-            {
-                char text[512] = "";
-                gwhip_last_error_string(text, sizeof(text));
-                throw std::runtime_error(std::string("gwm_align_overlaps: ") + text);
-            }
-            ev.record(2, s);
-            cigar_kernel<false><<<m_waves, kThreads, 0, s>>>(results.p, starts.p, result_lengths.p, m, counts.p + first,
-                                                            edit_distances.p + first, nullptr, nullptr);
-            GWM_CHECK(hipGetLastError());
-            exclusive_sum(counts.p + first, local_offsets.p, m + 1, temp, s); // entry m of the input is not summed
-            const int64_t text_bytes = to_host(local_offsets.p + m, s);
+            exclusive_sum(counts.p + c.first, local_offsets.p, c.m + 1, temp, s); // entry m of the input is not summed
+            const int64_t text_bytes = to_host(local_offsets.p + c.m, s);
             texts.emplace_back(text_bytes);
             text_sizes.push_back(text_bytes);
             if (text_bytes > 0)
             {
-                cigar_kernel<true><<<m_waves, kThreads, 0, s>>>(results.p, starts.p, result_lengths.p, m, nullptr, nullptr,
-                                                               local_offsets.p, texts.back().p);
+                cigar_kernel<true><<<c.m_waves, kThreads, 0, s>>>(c.results, c.starts, c.result_lengths, c.m, nullptr,
+                                                                 nullptr, local_offsets.p, texts.back().p);
                 GWM_CHECK(hipGetLastError());
             }
-            ev.record(3, s);
-            for (int k = 0; k < 3; ++k)
-                out->stage_ms[k] += ev.ms(k, k + 1);
-            first += m;
-        }
+        };
+        gwm::align_chunks("gwm_align_overlaps", overlaps, n, query_bases, query_offsets, n_queries, first_query_read_id,
+                     target_bases, target_offsets, n_targets, first_target_read_id, max_device_bytes, s, out->stage_ms,
+                     write_cigars);
         exclusive_sum(counts.p, offsets.p, n + 1, temp, s);
         int64_t total = 0;
         for (int64_t b : text_sizes)

@@ -6,6 +6,7 @@
 
 #include "gwhip_mapper.h"
 #include "gwm_host_utils.hpp"
+#include "gwm_windows.hpp"
 
 #include <algorithm>
 #include <memory>
@@ -143,6 +144,18 @@ struct gw_mapper_cigars
     ~gw_mapper_cigars() { gwm_cigars_free(&c); }
     gw_mapper_cigars(const gw_mapper_cigars&) = delete;
     gw_mapper_cigars& operator=(const gw_mapper_cigars&) = delete;
+};
+
+// The windows of one gw_mapper_window_overlaps call, on the host
+struct gw_mapper_windows
+{
+    std::vector<gwm_segment> segments;
+    std::vector<int64_t> segment_offsets{0};
+    std::vector<int32_t> edit_distances;
+    float stage_ms[4] = {0.f, 0.f, 0.f, 0.f}; // gather, align, segments, window gather
+    std::vector<gwm::window_record> windows;
+    std::vector<int64_t> sequence_offsets{0};
+    std::vector<char> bases;
 };
 
 #endif

@@ -1,0 +1,323 @@
+// gwm_segments.hip -- cudamapper on gfx950: from aligned overlaps to POA windows (include/gwhip_mapper.h,
+// gwm_window_segments and gwm_gather_sequences). gwm_window_segments runs the chunk loop of gwm_align_chunks.hpp with
+// the segment writer as its consumer: where gwm_align_overlaps turns the per-column states into text, this turns them
+// into one 24 B record per (overlap, window of the target read) and leaves the states where they are. Only those
+// records cross to the host, where the layers of every window are chosen (gwm_windows.cpp); gwm_gather_sequences then
+// cuts backbones and layers out of the resident read sets.
+//
+// Segments: one wave64 per alignment over tiles of 64 columns in forward column order -- state per lane, the query and
+// target positions of a column from ballots of the columns that consume a query / a target base and popcounts over the
+// lower lanes, the running counts and the last aligned column's (window, target position, query position) carried
+// between tiles in wave-uniform registers. An aligned column whose window differs from the previous aligned column's
+// is a head: it opens a record and closes the one before it; lane 0 closes the last one behind the tiles. A counting
+// pass, an exclusive scan of the record counts, a writing pass. Forward column order is ascending target order on '+'
+// and descending on '-', where the record of the r-th head goes to the r-th place from the end: records come out
+// window-ascending on both strands. No LDS, no scratch.
+#include "gwm_align_chunks.hpp"
+
+#include <deque>
+
+namespace
+{
+
+// One wave64 per alignment of the chunk (states as AlignedChunk lays them out; o: the chunk's first overlap record,
+// first: its position in the call). kWrite false: counts[i] = records of alignment i, edit_distances[i] = columns that
+// are not a match (-1: no result although a slice was not empty). kWrite true: the records at segments[offsets[i]].
+template <bool kWrite>
+__global__ void __launch_bounds__(kThreads) segment_kernel(const gwm_overlap* __restrict__ o,
+                                                           const uint8_t* __restrict__ results,
+                                                           const int64_t* __restrict__ starts,
+                                                           const int32_t* __restrict__ result_lengths, int64_t m,
+                                                           uint32_t first, uint32_t window_length,
+                                                           int64_t* __restrict__ counts,
+                                                           int32_t* __restrict__ edit_distances,
+                                                           const int64_t* __restrict__ offsets,
+                                                           gwm_segment* __restrict__ segments)
+{
+    const int64_t i     = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (i >= m)
+        return; // whole waves leave together
+    const gwm_overlap x  = o[i];
+    const int64_t slot   = starts[2 * i];
+    const int32_t stored = result_lengths[i];
+    const uint32_t len   = static_cast<uint32_t>(stored < 0 ? -stored : stored); // as the host aligner reads it
+    const uint8_t* s     = results + slot;
+    const bool reverse   = x.relative_strand == '-';
+    const uint32_t qs = x.query_start_position_in_read, ts = x.target_start_position_in_read,
+                   te      = x.target_end_position_in_read;
+    const uint32_t total   = kWrite ? static_cast<uint32_t>(offsets[i + 1] - offsets[i]) : 0u;
+    gwm_segment* out       = kWrite ? segments + offsets[i] : nullptr;
+    const uint64_t lower   = (1ull << lane) - 1;
+    // wave-uniform: columns walked so far that consume a query / a target base, the last aligned column, records opened
+    uint32_t query_run = 0, target_run = 0;
+    bool has_last   = false;
+    uint32_t last_k = 0, last_t = 0, last_q = 0;
+    uint32_t records = 0, edits = 0;
+    for (uint32_t base = 0; base < len; base += 64)
+    {
+        const bool valid          = lane < min(64u, len - base);
+        const uint32_t state      = valid ? s[len - 1 - base - lane] : 0u;
+        const uint64_t in_query   = __ballot(valid && state != 2);
+        const uint64_t in_target  = __ballot(valid && state != 3);
+        const bool aligned        = valid && state < 2;
+        const uint64_t aligned_at = __ballot(aligned);
+        if (!kWrite)
+            edits += static_cast<uint32_t>(__popcll(__ballot(valid && state != 0)));
+        const uint32_t q = qs + query_run + static_cast<uint32_t>(__popcll(in_query & lower));
+        const uint32_t b = target_run + static_cast<uint32_t>(__popcll(in_target & lower));
+        const uint32_t t = reverse ? te - 1 - b : ts + b;
+        const uint32_t k = aligned ? t / window_length : 0u;
+        // the previous aligned column: the next lower aligned lane of the tile, or the one carried in
+        const uint64_t below = aligned_at & lower;
+        const int from       = below ? 63 - __clzll(below) : 0;
+        uint32_t pk = __shfl(k, from, 64), pt = __shfl(t, from, 64), pq = __shfl(q, from, 64);
+        bool has_prev = true;
+        if (!below)
+        {
+            pk = last_k, pt = last_t, pq = last_q;
+            has_prev = has_last;
+        }
+        const bool head      = aligned && (!has_prev || k != pk);
+        const uint64_t heads = __ballot(head);
+        if (kWrite && head)
+        {
+            const uint32_t r = records + static_cast<uint32_t>(__popcll(heads & lower));
+            if (has_prev && r >= 1 && r - 1 < total) // closes the record before it
+            {
+                gwm_segment& c = out[reverse ? total - r : r - 1];
+                c.query_end    = pq + 1;
+                (reverse ? c.target_first : c.target_last) = pt;
+            }
+            if (r < total)
+            {
+                gwm_segment& c = out[reverse ? total - 1 - r : r];
+                c.overlap      = first + static_cast<uint32_t>(i);
+                c.window       = k;
+                c.query_begin  = q;
+                (reverse ? c.target_last : c.target_first) = t;
+            }
+        }
+        records += static_cast<uint32_t>(__popcll(heads));
+        if (aligned_at)
+        {
+            const int last = 63 - __clzll(aligned_at);
+            last_k = __shfl(k, last, 64), last_t = __shfl(t, last, 64), last_q = __shfl(q, last, 64);
+            has_last = true;
+        }
+        query_run += static_cast<uint32_t>(__popcll(in_query));
+        target_run += static_cast<uint32_t>(__popcll(in_target));
+    }
+    if (lane != 0)
+        return;
+    if (kWrite)
+    {
+        if (has_last && records >= 1 && records - 1 < total)
+        {
+            gwm_segment& c = out[reverse ? total - records : records - 1];
+            c.query_end    = last_q + 1;
+            (reverse ? c.target_first : c.target_last) = last_t;
+        }
+    }
+    else
+    {
+        counts[i]         = records;
+        edit_distances[i] = len ? static_cast<int32_t>(edits) : (starts[2 * i + 2] == slot ? 0 : -1);
+    }
+}
+
+// bad[0] |= 1: a set other than 0 / 1 or a read outside its set; |= 2: begin > end or an end beyond its read;
+// |= 4: the sequence does not lie within out
+__global__ void __launch_bounds__(kThreads) plan_validate_kernel(const gwm_gather_entry* __restrict__ plan, int64_t n,
+                                                                 const int64_t* __restrict__ out_starts, ReadSet q,
+                                                                 ReadSet t, int64_t out_bytes,
+                                                                 uint32_t* __restrict__ bad)
+{
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const gwm_gather_entry e = plan[i];
+    const ReadSet& set       = e.set ? t : q;
+    if (e.set > 1 || e.read >= set.n_reads)
+    {
+        atomicOr(bad, 1u);
+        return;
+    }
+    const uint64_t length = static_cast<uint64_t>(set.offsets[e.read + 1] - set.offsets[e.read]);
+    if (e.begin > e.end || e.end > length)
+    {
+        atomicOr(bad, 2u);
+        return;
+    }
+    const int64_t at = out_starts[i];
+    if (at < 0 || at > out_bytes || static_cast<int64_t>(e.end - e.begin) > out_bytes - at)
+        atomicOr(bad, 4u);
+}
+
+// Block b writes sequence b of the plan to out[out_starts[b] ..): lane L of a pass takes output byte L, ascending
+// addresses on both sides, or descending ones on the read side when reversed -- one segment per wave either way.
+__global__ void __launch_bounds__(kThreads) gather_sequences_kernel(const gwm_gather_entry* __restrict__ plan,
+                                                                    const int64_t* __restrict__ out_starts, ReadSet qs,
+                                                                    ReadSet ts, uint8_t* __restrict__ out)
+{
+    const gwm_gather_entry e = plan[blockIdx.x];
+    const ReadSet& set       = e.set ? ts : qs;
+    const uint8_t* src       = set.bases + set.offsets[e.read] + e.begin;
+    const uint32_t len       = e.end - e.begin;
+    uint8_t* dst             = out + out_starts[blockIdx.x];
+    if (e.reversed)
+    {
+        for (uint32_t j = threadIdx.x; j < len; j += kThreads)
+            dst[j] = static_cast<uint8_t>("TGAC"[(src[len - 1 - j] >> 1) & 3]);
+    }
+    else
+    {
+        for (uint32_t j = threadIdx.x; j < len; j += kThreads)
+            dst[j] = src[j];
+    }
+}
+
+} // namespace
+
+extern "C" {
+
+void gwm_segments_free(gwm_segments* segments)
+{
+    if (!segments)
+        return;
+    (void)hipFree(segments->segments);
+    (void)hipFree(segments->segment_offsets);
+    (void)hipFree(segments->edit_distances);
+    *segments = gwm_segments{};
+}
+
+int gwm_window_segments(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                        int32_t n_queries, uint32_t first_query_read_id, const char* target_bases,
+                        const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
+                        int32_t window_length, int64_t max_device_bytes, void* stream, gwm_segments* out)
+{
+    *out = gwm_segments{};
+    try
+    {
+        if (n_queries < 0 || n_targets < 0)
+            throw std::invalid_argument("gwm_window_segments: negative number of reads");
+        if (max_device_bytes < 0)
+            throw std::invalid_argument("gwm_window_segments: negative max_device_bytes");
+        if (window_length < 1)
+            throw std::invalid_argument("gwm_window_segments: window_length below 1");
+        if (n <= 0)
+            return 0;
+        if (n >= (int64_t(1) << 31))
+            throw std::invalid_argument("gwm_window_segments: 2^31 overlaps or more");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        dbuf<int64_t> counts(n + 1), offsets(n + 1), local_offsets;
+        dbuf<int32_t> edit_distances(n);
+        GWM_CHECK(hipMemsetAsync(counts.p, 0, sizeof(int64_t) * static_cast<size_t>(n + 1), s));
+        std::deque<dbuf<gwm_segment>> parts; // one per chunk
+        std::vector<int64_t> part_sizes;
+        // the segment writer: record counts, their scan, the records of the chunk
+        Temp temp;
+        auto write_segments = [&](const AlignedChunk& c) {
+            grow(local_offsets, c.m + 1);
+            segment_kernel<false><<<c.m_waves, kThreads, 0, s>>>(
+                c.overlaps, c.results, c.starts, c.result_lengths, c.m, static_cast<uint32_t>(c.first),
+                static_cast<uint32_t>(window_length), counts.p + c.first, edit_distances.p + c.first, nullptr, nullptr);
+            GWM_CHECK(hipGetLastError());
+            exclusive_sum(counts.p + c.first, local_offsets.p, c.m + 1, temp, s); // entry m of the input is not summed
+            const int64_t records = to_host(local_offsets.p + c.m, s);
+            parts.emplace_back(records);
+            part_sizes.push_back(records);
+            if (records > 0)
+            {
+                segment_kernel<true><<<c.m_waves, kThreads, 0, s>>>(
+                    c.overlaps, c.results, c.starts, c.result_lengths, c.m, static_cast<uint32_t>(c.first),
+                    static_cast<uint32_t>(window_length), nullptr, nullptr, local_offsets.p, parts.back().p);
+                GWM_CHECK(hipGetLastError());
+            }
+        };
+        gwm::align_chunks("gwm_window_segments", overlaps, n, query_bases, query_offsets, n_queries, first_query_read_id,
+                     target_bases, target_offsets, n_targets, first_target_read_id, max_device_bytes, s, out->stage_ms,
+                     write_segments);
+        exclusive_sum(counts.p, offsets.p, n + 1, temp, s);
+        int64_t total = 0;
+        for (int64_t b : part_sizes)
+            total += b;
+        dbuf<gwm_segment> segments;
+        if (parts.size() == 1)
+            segments.p = parts[0].release();
+        else
+        {
+            segments.resize(total);
+            int64_t at = 0;
+            for (size_t c = 0; c < parts.size(); at += part_sizes[c], ++c)
+                if (part_sizes[c] > 0)
+                    GWM_CHECK(hipMemcpyAsync(segments.p + at, parts[c].p,
+                                             sizeof(gwm_segment) * static_cast<size_t>(part_sizes[c]),
+                                             hipMemcpyDeviceToDevice, s));
+        }
+        GWM_CHECK(hipStreamSynchronize(s));
+        out->n               = n;
+        out->n_segments      = total;
+        out->segments        = segments.release();
+        out->segment_offsets = offsets.release();
+        out->edit_distances  = edit_distances.release();
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        gwm_set_error(e.what());
+        *out = gwm_segments{};
+        return -1;
+    }
+}
+
+int gwm_gather_sequences(const gwm_gather_entry* plan, int64_t n, const int64_t* out_starts, const char* query_bases,
+                         const int64_t* query_offsets, int32_t n_queries, const char* target_bases,
+                         const int64_t* target_offsets, int32_t n_targets, char* out, int64_t out_bytes, void* stream,
+                         float* gather_ms)
+{
+    try
+    {
+        if (gather_ms)
+            *gather_ms = 0.f;
+        if (n_queries < 0 || n_targets < 0)
+            throw std::invalid_argument("gwm_gather_sequences: negative number of reads");
+        if (out_bytes < 0)
+            throw std::invalid_argument("gwm_gather_sequences: negative out_bytes");
+        if (n <= 0)
+            return 0;
+        if (n >= (int64_t(1) << 31))
+            throw std::invalid_argument("gwm_gather_sequences: 2^31 sequences or more");
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        const ReadSet q{reinterpret_cast<const uint8_t*>(query_bases), query_offsets, static_cast<uint32_t>(n_queries), 0};
+        const ReadSet t{reinterpret_cast<const uint8_t*>(target_bases), target_offsets, static_cast<uint32_t>(n_targets), 0};
+        dbuf<uint32_t> bad(1);
+        GWM_CHECK(hipMemsetAsync(bad.p, 0, sizeof(uint32_t), s));
+        plan_validate_kernel<<<grid_for(n), kThreads, 0, s>>>(plan, n, out_starts, q, t, out_bytes, bad.p);
+        GWM_CHECK(hipGetLastError());
+        const uint32_t what = to_host(bad.p, s);
+        if (what & 1u)
+            throw std::invalid_argument("gwm_gather_sequences: a sequence names a read outside the read sets");
+        if (what & 2u)
+            throw std::invalid_argument("gwm_gather_sequences: a sequence lies beyond the end of its read");
+        if (what & 4u)
+            throw std::invalid_argument("gwm_gather_sequences: a sequence does not lie within the output");
+        Events ev(2);
+        ev.record(0, s);
+        gather_sequences_kernel<<<static_cast<unsigned>(n), kThreads, 0, s>>>(plan, out_starts, q, t,
+                                                                             reinterpret_cast<uint8_t*>(out));
+        GWM_CHECK(hipGetLastError());
+        ev.record(1, s);
+        const float ms = ev.ms(0, 1); // waits
+        if (gather_ms)
+            *gather_ms = ms;
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        gwm_set_error(e.what());
+        return -1;
+    }
+}
+
+} // extern "C"

@@ -40,6 +40,72 @@ gw_mapper_overlaps* map_batched_guarded(const reads_view& queries, const reads_v
                    static_cast<gw_mapper_overlaps*>(nullptr));
 }
 
+// gw_mapper_window_overlaps, or with max_depth < 0 its segments pass alone: no selection, no gather, no windows
+gw_mapper_windows* window_overlaps(const void* overlaps, int64_t n, const reads_view& query_reads,
+                                   uint32_t first_query_read_id, const reads_view& target_reads,
+                                   uint32_t first_target_read_id, int32_t window_length, int32_t max_depth,
+                                   int64_t max_device_bytes, void* stream)
+{
+    return guarded([&] {
+        std::unique_ptr<gw_mapper_windows> h(new gw_mapper_windows());
+        if (n < 0)
+            throw std::invalid_argument("gw_mapper_window_overlaps: negative number of overlaps");
+        const gwm_overlap* host_overlaps = static_cast<const gwm_overlap*>(overlaps);
+        read_sets reads(query_reads, target_reads);
+        reads.upload(); // once: the segments pass and the window gather read the same device copies
+        dbuf<gwm_overlap> d;
+        d.upload(host_overlaps, n);
+        const reads_view &q = reads.device_queries, &t = reads.device_targets;
+        // segments on the device, their records (24 B each) to the host
+        struct owned_segments
+        {
+            gwm_segments s{};
+            ~owned_segments() { gwm_segments_free(&s); }
+        } device;
+        throw_on(gwm_window_segments(d.p, n, q.bases, q.offsets, reads.queries.n, first_query_read_id, t.bases, t.offsets,
+                                     reads.targets.n, first_target_read_id, window_length, max_device_bytes, stream,
+                                     &device.s));
+        const gwm_segments& s = device.s;
+        h->segments.resize(static_cast<size_t>(s.n_segments));
+        copy_out(h->segments.data(), s.segments, s.n_segments);
+        h->segment_offsets.assign(static_cast<size_t>(n) + 1, 0);
+        copy_out(h->segment_offsets.data(), s.segment_offsets, s.n > 0 ? s.n + 1 : 0);
+        h->edit_distances.resize(static_cast<size_t>(n));
+        copy_out(h->edit_distances.data(), s.edit_distances, s.n);
+        std::memcpy(h->stage_ms, s.stage_ms, sizeof(s.stage_ms));
+        if (max_depth < 0)
+            return h.release();
+        // the layers of every window, on the host
+        std::vector<int64_t> target_lengths(static_cast<size_t>(reads.targets.n));
+        for (int32_t r = 0; r < reads.targets.n; ++r)
+            target_lengths[r] = reads.targets.offsets[r + 1] - reads.targets.offsets[r];
+        window_selection selection =
+            select_layers(h->segments.data(), s.n_segments, host_overlaps, n, reads.queries.n, first_query_read_id,
+                          target_lengths.data(), reads.targets.n, first_target_read_id, window_length, max_depth);
+        h->windows = std::move(selection.windows);
+        const std::vector<gwm_gather_entry>& plan = selection.plan;
+        h->sequence_offsets.assign(plan.size() + 1, 0);
+        for (size_t i = 0; i < plan.size(); ++i)
+            h->sequence_offsets[i + 1] = h->sequence_offsets[i] + (plan[i].end - plan[i].begin);
+        // their bases, gathered on the device and copied out once
+        const int64_t total = h->sequence_offsets.back();
+        h->bases.resize(static_cast<size_t>(total));
+        if (total > 0)
+        {
+            dbuf<gwm_gather_entry> device_plan;
+            dbuf<int64_t> device_starts;
+            dbuf<char> device_bases(total);
+            device_plan.upload(plan.data(), static_cast<int64_t>(plan.size()));
+            device_starts.upload(h->sequence_offsets.data(), static_cast<int64_t>(plan.size()));
+            throw_on(gwm_gather_sequences(device_plan.p, static_cast<int64_t>(plan.size()), device_starts.p, q.bases,
+                                          q.offsets, reads.queries.n, t.bases, t.offsets, reads.targets.n, device_bases.p,
+                                          total, stream, &h->stage_ms[3]));
+            copy_out(h->bases.data(), device_bases.p, total);
+        }
+        return h.release();
+    }, static_cast<gw_mapper_windows*>(nullptr));
+}
+
 } // namespace
 
 extern "C" {
@@ -288,6 +354,104 @@ int gw_mapper_cigars_copy(const gw_mapper_cigars* cigars, char* text, int64_t* o
 }
 
 void gw_mapper_cigars_destroy(gw_mapper_cigars* cigars) { delete cigars; }
+
+gw_mapper_windows* gw_mapper_window_overlaps(const void* overlaps, int64_t n, const char* query_bases,
+                                             const int64_t* query_offsets, int32_t n_queries,
+                                             uint32_t first_query_read_id, const char* target_bases,
+                                             const int64_t* target_offsets, int32_t n_targets,
+                                             uint32_t first_target_read_id, int32_t window_length, int32_t max_depth,
+                                             int64_t max_device_bytes, void* stream)
+{
+    if (max_depth < 0)
+    {
+        g_capi_error = "gw_mapper_window_overlaps: negative max_depth";
+        return nullptr;
+    }
+    return window_overlaps(overlaps, n, {query_bases, query_offsets, n_queries}, first_query_read_id,
+                           {target_bases, target_offsets, n_targets}, first_target_read_id, window_length, max_depth,
+                           max_device_bytes, stream);
+}
+
+gw_mapper_windows* gw_mapper_window_segments(const void* overlaps, int64_t n, const char* query_bases,
+                                             const int64_t* query_offsets, int32_t n_queries,
+                                             uint32_t first_query_read_id, const char* target_bases,
+                                             const int64_t* target_offsets, int32_t n_targets,
+                                             uint32_t first_target_read_id, int32_t window_length,
+                                             int64_t max_device_bytes, void* stream)
+{
+    return window_overlaps(overlaps, n, {query_bases, query_offsets, n_queries}, first_query_read_id,
+                           {target_bases, target_offsets, n_targets}, first_target_read_id, window_length, -1,
+                           max_device_bytes, stream);
+}
+
+int gw_mapper_windows_counts(const gw_mapper_windows* windows, int64_t* counts)
+{
+    counts[0] = static_cast<int64_t>(windows->windows.size());
+    counts[1] = static_cast<int64_t>(windows->sequence_offsets.size()) - 1;
+    counts[2] = static_cast<int64_t>(windows->bases.size());
+    counts[3] = static_cast<int64_t>(windows->segments.size());
+    return 0;
+}
+
+int gw_mapper_windows_copy_segments(const gw_mapper_windows* windows, void* segments, int64_t* segment_offsets,
+                                    int32_t* edit_distances, float* stage_ms)
+{
+    const gw_mapper_windows& w = *windows;
+    if (segments && !w.segments.empty())
+        std::memcpy(segments, w.segments.data(), sizeof(gwm_segment) * w.segments.size());
+    if (segment_offsets)
+        std::memcpy(segment_offsets, w.segment_offsets.data(), sizeof(int64_t) * w.segment_offsets.size());
+    if (edit_distances && !w.edit_distances.empty())
+        std::memcpy(edit_distances, w.edit_distances.data(), sizeof(int32_t) * w.edit_distances.size());
+    if (stage_ms)
+        std::memcpy(stage_ms, w.stage_ms, sizeof(w.stage_ms));
+    return 0;
+}
+
+int gw_mapper_windows_copy_windows(const gw_mapper_windows* windows, char* bases, int64_t* sequence_offsets,
+                                   int32_t* sequences_per_window, uint32_t* window_target_read, uint32_t* window_index)
+{
+    const gw_mapper_windows& w = *windows;
+    if (bases && !w.bases.empty())
+        std::memcpy(bases, w.bases.data(), w.bases.size());
+    if (sequence_offsets)
+        std::memcpy(sequence_offsets, w.sequence_offsets.data(), sizeof(int64_t) * w.sequence_offsets.size());
+    for (size_t i = 0; i < w.windows.size(); ++i)
+    {
+        if (sequences_per_window)
+            sequences_per_window[i] = static_cast<int32_t>(w.windows[i].n_sequences);
+        if (window_target_read)
+            window_target_read[i] = w.windows[i].target_read;
+        if (window_index)
+            window_index[i] = w.windows[i].window;
+    }
+    return 0;
+}
+
+void gw_mapper_windows_destroy(gw_mapper_windows* windows) { delete windows; }
+
+int64_t gw_mapper_select_layers(const void* segments, int64_t n_segments, const void* overlaps, int64_t n_overlaps,
+                                int32_t n_queries, uint32_t first_query_read_id, const int64_t* target_lengths,
+                                int32_t n_targets, uint32_t first_target_read_id, int32_t window_length,
+                                int32_t max_depth, uint32_t* plan, int64_t plan_capacity, int64_t* n_windows,
+                                uint32_t* window_table, int64_t window_capacity)
+{
+    return guarded([&] {
+        const window_selection s = select_layers(
+            static_cast<const gwm_segment*>(segments), n_segments, static_cast<const gwm_overlap*>(overlaps), n_overlaps,
+            n_queries, first_query_read_id, target_lengths, n_targets, first_target_read_id, window_length, max_depth);
+        const int64_t sequences = static_cast<int64_t>(s.plan.size()), windows = static_cast<int64_t>(s.windows.size());
+        static_assert(sizeof(gwm_gather_entry) == 5 * sizeof(uint32_t) && sizeof(window_record) == 4 * sizeof(uint32_t),
+                      "the flat layouts of gw_mapper_select_layers");
+        if (plan && sequences <= plan_capacity && sequences > 0)
+            std::memcpy(plan, s.plan.data(), sizeof(gwm_gather_entry) * s.plan.size());
+        if (window_table && windows <= window_capacity && windows > 0)
+            std::memcpy(window_table, s.windows.data(), sizeof(window_record) * s.windows.size());
+        if (n_windows)
+            *n_windows = windows;
+        return sequences;
+    }, int64_t(GW_MAPPER_ERROR));
+}
 
 gw_mapper_overlaps* gw_mapper_map_batched(const char* query_bases, const int64_t* query_offsets, int32_t n_queries,
                                           const char* target_bases, const int64_t* target_offsets, int32_t n_targets,

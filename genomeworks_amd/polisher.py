@@ -1,0 +1,85 @@
+"""Polishing: a draft sequence corrected by the reads that map to it, through the three engines of this package --
+cudamapper finds and aligns the overlaps, the aligned overlaps are cut into windows of the draft on the device
+(cudamapper.overlap_windows), cudapoa builds the consensus of every window, and the windows are stitched.
+
+    polished, report = polish(reads, [draft])                      # maps the reads first
+    polished, report = polish(reads, [draft], overlaps=overlaps)   # overlaps of cudamapper, fused records included
+
+The rules -- which overlap speaks for a read, which of its pieces become layers of a window, their order and number --
+are in INTEGRATION.md section 3j. Windows that fewer than 2 layers span keep the draft's bases, and so do windows whose
+POA does not succeed; nothing is trimmed."""
+import time
+
+from . import cudamapper, cudapoa
+
+
+def poa_batch_shape(window_length, max_depth, band_width):
+    """(max_sequence_size, max_sequences_per_poa, alignment_band_width) of the cudapoa batches polish() runs: layers
+    hold up to 2 * window_length bases, a window its backbone and max_depth layers; the band as cudapoa aligns it, to a
+    multiple of 128, which a batch's reads may not be shorter than."""
+    band = (int(band_width) + 127) // 128 * 128
+    return max(2 * int(window_length), band), int(max_depth) + 1, band
+
+
+def polish(reads, targets, overlaps=None, window_length=500, max_depth=30, band_width=256, band_mode="static_band",
+           devices=(0,), timings=None, poa_memory_per_device=4 << 30, **mapping_parameters):
+    """`targets` polished by `reads`: (polished_targets, report). polished_targets[i] is a str, the concatenation of
+    the results of target i's windows in window order: the consensus of cudapoa (scores 8 / -6 / -8, no weights,
+    band_mode with band_width) over the backbone and its layers where at least 2 layers span the window and the POA's
+    status is 0, the backbone otherwise. report has one dict per window, by target, then by window: target_read,
+    window, layers, status (of the POA; None where it was not run) and backbone_kept.
+
+    overlaps: OVERLAP records of reads (queries) against targets whose read ids are positions in the two lists, in
+    the order cudamapper returned them; None maps first, with map_reads_batched(reads, targets, **mapping_parameters)
+    over the defaults post_process=True, rescue_overlap_ends=True and filtering_parameter=1.0 -- the frequency filter
+    off: map_reads_batched's own 1e-5 is meant for indices of many megabases, and in the index of a draft of a few
+    hundred kilobases its threshold is 0 occurrences, so nothing would map and the draft would come back as it is;
+    pass filtering_parameter for large inputs. Reads shorter than k + w - 1 then raise ValueError: the index
+    would skip them and shift the read ids behind them. devices: the cudapoa workers' devices
+    (process_windows_multi_device), each with a pool of poa_memory_per_device bytes (-1: cudapoa's share of the free
+    memory, which takes seconds to set up on a large device); mapping and windows run on the current device.
+    `timings`, if a dict, receives the device times (ms) chain_fuse_filter, fuse, rescue (when mapping), gather, align,
+    segments, window_gather, the host times (s) map_seconds, windows_seconds, poa_seconds, stitch_seconds, and
+    bytes_to_host of the windows step."""
+    if window_length < 1:
+        raise ValueError("window_length must be >= 1")
+    if max_depth < 0:
+        raise ValueError("max_depth must be >= 0")
+    times = {} if timings is None else timings
+    t0 = time.perf_counter()
+    if overlaps is None:
+        shortest = mapping_parameters.get("k", 15) + mapping_parameters.get("w", 10) - 1
+        if any(len(r) < shortest for r in list(reads) + list(targets)):
+            raise ValueError("polish: a read shorter than k + w - 1 = %d bases cannot be mapped" % shortest)
+        if mapping_parameters.get("align"):
+            raise ValueError("polish: the overlaps are aligned by the windows step")
+        parameters = dict(dict(post_process=True, rescue_overlap_ends=True, filtering_parameter=1.0),
+                          **mapping_parameters)
+        overlaps = cudamapper.map_reads_batched(reads, targets, timings=times, **parameters)
+    elif mapping_parameters:
+        raise TypeError("polish: mapping parameters given together with overlaps")
+    t1 = time.perf_counter()
+    windows = cudamapper.overlap_windows(overlaps, reads, targets, window_length, max_depth, timings=times)
+    t2 = time.perf_counter()
+    deep = [i for i, (_, _, seqs) in enumerate(windows) if len(seqs) - 1 >= 2]
+    status, consensus = {}, {}
+    if deep:
+        size, depth, band = poa_batch_shape(window_length, max_depth, band_width)
+        out = cudapoa.process_windows_multi_device([windows[i][2] for i in deep], depth, size, devices=tuple(devices),
+                                                   memory_per_device=poa_memory_per_device, output_type="consensus",
+                                                   band_mode=band_mode, alignment_band_width=band, gap_score=-8,
+                                                   mismatch_score=-6, match_score=8)
+        for j, i in enumerate(deep):
+            status[i], consensus[i] = int(out["status"][j]), out["consensus"][j]
+    t3 = time.perf_counter()
+    pieces = [[] for _ in targets]
+    report = []
+    for i, (target, window, seqs) in enumerate(windows):
+        kept = status.get(i) != 0
+        pieces[target].append(seqs[0].decode("latin-1") if kept else consensus[i])
+        report.append(dict(target_read=target, window=window, layers=len(seqs) - 1, status=status.get(i),
+                           backbone_kept=kept))
+    polished = ["".join(p) for p in pieces]
+    t4 = time.perf_counter()
+    times.update(map_seconds=t1 - t0, windows_seconds=t2 - t1, poa_seconds=t3 - t2, stitch_seconds=t4 - t3)
+    return polished, report

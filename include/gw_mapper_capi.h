@@ -2,7 +2,7 @@
  * gw_mapper_capi.h -- flat C API of cudamapper (libcudamapper.so), for foreign-function bindings
  * (genomeworks_amd/cudamapper.py): index creation from host reads, the anchor matcher, the triggered overlapper, one
  * call for a whole mapping of one index pair, overlap post-processing, end rescue and alignment of overlaps into
- * CIGARs, packed host copies of indices, the index batcher and the cached batched driver behind the cudamapper tool.
+ * CIGARs, their cutting into POA windows for polishing, packed host copies of indices, the index batcher and the cached batched driver behind the cudamapper tool.
  * Functions returning int give 0 on success; those returning a count give it, or GW_MAPPER_ERROR; creators return NULL.
  * On an error the exception text is in gw_mapper_last_error().
  *
@@ -112,6 +112,57 @@ int64_t gw_mapper_cigars_text_bytes(const gw_mapper_cigars* cigars);
 int gw_mapper_cigars_copy(const gw_mapper_cigars* cigars, char* text, int64_t* offsets, int32_t* edit_distances,
                           float* stage_ms);
 void gw_mapper_cigars_destroy(gw_mapper_cigars* cigars);
+
+/* ---- polishing: aligned overlaps cut into POA windows --------------------------------------------------------------
+   The target reads are cut into windows of window_length bases; every window is its backbone, target[k W, end_k),
+   followed by its layers: the slices of the query reads whose alignment spans the window. Segments are
+   gwm_window_segments of gwhip_mapper.h (24 B records of six uint32: overlap, window, target_first, target_last,
+   query_begin, query_end); the selection rules are spelled out next to gwm::select_layers in mapper/gwm_windows.hpp and
+   in INTEGRATION.md section 3j. */
+
+/* The windows of n host overlaps over host reads (target_bases NULL: the target set is the query set). The reads are
+   uploaded once; the overlaps are aligned as gw_mapper_align_overlaps aligns them and their segments written on the
+   device; the records (24 B each) are copied to the host, where the layers are selected; then the sequences of every
+   window are gathered on the device and copied out once. Errors as for gw_mapper_align_overlaps, plus
+   window_length < 1 and max_depth < 0 (NULL). */
+typedef struct gw_mapper_windows gw_mapper_windows;
+gw_mapper_windows* gw_mapper_window_overlaps(const void* overlaps, int64_t n, const char* query_bases,
+                                             const int64_t* query_offsets, int32_t n_queries,
+                                             uint32_t first_query_read_id, const char* target_bases,
+                                             const int64_t* target_offsets, int32_t n_targets,
+                                             uint32_t first_target_read_id, int32_t window_length, int32_t max_depth,
+                                             int64_t max_device_bytes, void* stream);
+/* The segments pass of gw_mapper_window_overlaps alone: reads and overlaps uploaded, the segment records, their
+   offsets and the edit distances copied out; no selection, no gather, so the window counts are 0 and the fourth
+   stage time is 0. */
+gw_mapper_windows* gw_mapper_window_segments(const void* overlaps, int64_t n, const char* query_bases,
+                                             const int64_t* query_offsets, int32_t n_queries,
+                                             uint32_t first_query_read_id, const char* target_bases,
+                                             const int64_t* target_offsets, int32_t n_targets,
+                                             uint32_t first_target_read_id, int32_t window_length,
+                                             int64_t max_device_bytes, void* stream);
+/* counts[4]: windows, sequences, bases, segments */
+int gw_mapper_windows_counts(const gw_mapper_windows* windows, int64_t* counts);
+/* segments (24 B each), segment_offsets[n + 1], edit_distances[n] (as gw_mapper_cigars_copy) and stage_ms[4]: device
+   time of gather, align, segments and the window gather; any pointer may be NULL */
+int gw_mapper_windows_copy_segments(const gw_mapper_windows* windows, void* segments, int64_t* segment_offsets,
+                                    int32_t* edit_distances, float* stage_ms);
+/* bases (back to back), sequence_offsets[sequences + 1], and per window its number of sequences (backbone first), its
+   target read (position in the target set) and its index in that read; windows come by target read, then by index.
+   Any pointer may be NULL. */
+int gw_mapper_windows_copy_windows(const gw_mapper_windows* windows, char* bases, int64_t* sequence_offsets,
+                                   int32_t* sequences_per_window, uint32_t* window_target_read, uint32_t* window_index);
+void gw_mapper_windows_destroy(gw_mapper_windows* windows);
+
+/* The selection alone, over host arrays; it needs no device. Returns the number of sequences, or GW_MAPPER_ERROR;
+   *n_windows is the number of windows. plan (5 uint32 per sequence: set -- 0 query, 1 target --, read, begin, end,
+   reversed) and window_table (4 uint32 per window: target read, window, first sequence, sequences) are written when
+   they are not NULL and their capacities (in sequences / windows) suffice. */
+int64_t gw_mapper_select_layers(const void* segments, int64_t n_segments, const void* overlaps, int64_t n_overlaps,
+                                int32_t n_queries, uint32_t first_query_read_id, const int64_t* target_lengths,
+                                int32_t n_targets, uint32_t first_target_read_id, int32_t window_length,
+                                int32_t max_depth, uint32_t* plan, int64_t plan_capacity, int64_t* n_windows,
+                                uint32_t* window_table, int64_t window_capacity);
 
 /* group_reads_into_indices: consecutive reads while the running base count stays <= max_basepairs_per_index; a longer
    read gets an index of its own. The reference's loop as it stands: when the very first read is longer than the limit

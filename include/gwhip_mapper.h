@@ -218,6 +218,71 @@ void gwm_cigars_free(gwm_cigars* cigars);
  * Host arithmetic only. */
 int64_t gwm_align_bytes_needed(int32_t query_length, int32_t target_length, int32_t max_query_length);
 
+/* ---- polishing: from aligned overlaps to POA windows ----------------------------------------------------------------
+ * The target reads are cut into windows of window_length bases: window k of a read is its bases [k W, (k + 1) W). */
+
+/* What one overlap's alignment covers of one window of its target read (24 B). Over the aligned columns (match or
+ * mismatch) of the overlap whose target base lies in the window: */
+typedef struct gwm_segment
+{
+    uint32_t overlap;      /* position of the overlap in the call */
+    uint32_t window;       /* target position / window_length */
+    uint32_t target_first; /* smallest target position, forward target coordinates */
+    uint32_t target_last;  /* largest target position */
+    uint32_t query_begin;  /* smallest query position */
+    uint32_t query_end;    /* largest query position + 1 */
+} gwm_segment;
+
+/* The segments of n overlaps. Device arrays, owned by the struct; free them with gwm_segments_free. */
+typedef struct gwm_segments
+{
+    int64_t n;                /* overlaps */
+    int64_t n_segments;       /* segment_offsets[n] */
+    gwm_segment* segments;    /* device: ordered by overlap, then by ascending window; NULL when there are none */
+    int64_t* segment_offsets; /* device [n + 1]: the records of overlap i are [segment_offsets[i], segment_offsets[i + 1]) */
+    int32_t* edit_distances;  /* device [n], as in gwm_cigars */
+    float stage_ms[3];        /* HIP events, summed over the chunks: gather, align, segments */
+} gwm_segments;
+
+/* gwm_align_overlaps with another consumer of the alignment states: the same arguments, slices, strand, aligner,
+ * chunking (and its independence of max_device_bytes) and errors, plus window_length < 1 as an error; instead of CIGAR
+ * text it leaves the segments of every overlap on the device. With the per-column states in forward column order
+ * (0 match, 1 mismatch, 2 a target base only, 3 a query base only), a(j) / b(j) the number of columns before j whose
+ * state is not 2 / not 3, an aligned column (state < 2) has query position query start + a(j), target position
+ * target start + b(j) on '+' and target end - 1 - b(j) on '-', and window target position / window_length. Every window
+ * that holds an aligned column of the overlap gives one record; a window of nothing but state 2 gives none, and
+ * neither does an alignment without columns (no result, or two empty slices). One wave64 per alignment over tiles of 64
+ * columns; a counting pass, a scan and a writing pass. The states are not copied anywhere. max_device_bytes bounds a
+ * chunk's working set exactly as for gwm_align_overlaps (gwm_align_bytes_needed, whose two bytes per column stand for
+ * the chunk's records here); the records themselves, 24 B each and kept for all chunks until the call returns, are the
+ * result and lie outside that budget, as the CIGAR text of earlier chunks does there. */
+int gwm_window_segments(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                        int32_t n_queries, uint32_t first_query_read_id, const char* target_bases,
+                        const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
+                        int32_t window_length, int64_t max_device_bytes, void* stream, gwm_segments* out);
+void gwm_segments_free(gwm_segments* segments);
+
+/* One sequence of a gather plan (20 B): bases [begin, end) of read `read` (position in its set) of the query set
+ * (set 0) or the target set (set 1); reversed != 0: back to front, every byte through "TGAC"[(c >> 1) & 3]. */
+typedef struct gwm_gather_entry
+{
+    uint32_t set;
+    uint32_t read;
+    uint32_t begin;
+    uint32_t end;
+    uint32_t reversed;
+} gwm_gather_entry;
+
+/* Writes the n sequences of a device plan into the device array out[0 .. out_bytes): sequence i at out_starts[i]
+ * (device, caller-given), end - begin bytes. Read sets as for gwm_align_overlaps (device arrays). One block per
+ * sequence. A set other than 0 / 1, a read outside its set, begin > end, an end beyond its read or a sequence that
+ * does not lie within out return -1 before anything is written. gather_ms (device time) may be NULL. Synchronous on
+ * `stream` when it returns. */
+int gwm_gather_sequences(const gwm_gather_entry* plan, int64_t n, const int64_t* out_starts, const char* query_bases,
+                         const int64_t* query_offsets, int32_t n_queries, const char* target_bases,
+                         const int64_t* target_offsets, int32_t n_targets, char* out, int64_t out_bytes, void* stream,
+                         float* gather_ms);
+
 const char* gwm_last_error(void);
 
 #ifdef __cplusplus
