@@ -230,6 +230,17 @@ def mapper():
         L.gw_mapper_windows_destroy.argtypes = [vp]
         L.gw_mapper_select_layers.restype = i64
         L.gw_mapper_select_layers.argtypes = [vp, i64, vp, i64, i32, u32, vp, i32, u32, i32, i32, vp, i64, vp, vp, i64]
+        L.gw_mapper_select_pairs.restype = i64
+        L.gw_mapper_select_pairs.argtypes = [vp, i64, vp, i64]
+        L.gw_mapper_select_correction_layers.restype = i64
+        L.gw_mapper_select_correction_layers.argtypes = [vp, i64, vp, i64, vp, i64, vp, i32, u32, i32, i32, vp, i64, vp,
+                                                         vp, i64]
+        L.gw_mapper_correction_windows.restype = vp
+        L.gw_mapper_correction_windows.argtypes = [vp, i64, vp, vp, i32, u32, i32, i32, i64, vp]
+        L.gw_mapper_pair_segments.restype = vp
+        L.gw_mapper_pair_segments.argtypes = [vp, i64, vp, vp, i32, u32, i32, i64, vp]
+        L.gw_mapper_windows_copy_query_role_segments.restype = i64
+        L.gw_mapper_windows_copy_query_role_segments.argtypes = [vp, vp, i64, vp, vp, vp, vp]
         L.gwm_align_bytes_needed.restype = i64
         L.gwm_align_bytes_needed.argtypes = [i32, i32, i32]
         _mapper = L

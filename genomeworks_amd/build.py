@@ -193,7 +193,7 @@ def build_extender(force=False):
 def build_mapper(force=False):
     """libcudamapper.so: the sketch / index / matcher / overlapper / post-processing / overlap alignment / window
     segment kernels with their rocPRIM scans, selects and sorts (hipcc, gfx950), linked against libgwhip.so for the
-    aligner, and the Index / Matcher handles, the index batcher, the batched driver and polishing's layer selection
+    aligner, and the Index / Matcher handles, the index batcher, the batched driver and the host rules of polishing and read correction
     behind the C API (g++);
     then bin/cudamapper, which links it and libgenomeworks_amd.so (built before this)."""
     headers = [os.path.join(ROOT, "include", "gwhip_mapper.h"), os.path.join(ROOT, "include", "gwhip.h")]

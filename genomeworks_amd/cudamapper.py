@@ -16,6 +16,9 @@ gfx950), over the flat C API of include/gw_mapper_capi.h.
     text = format_paf(overlaps, names, lengths, names, lengths, 15, cigars=cigars)
     segments, offsets, edit_distances = window_segments(overlaps, reads, targets, window_length=500)
     windows = overlap_windows(overlaps, reads, targets, window_length=500, max_depth=30)   # polisher.polish feeds on it
+    pairs = overlaps[select_pairs(overlaps)]                       # read correction: one record per pair of reads
+    (target_role, offsets, edit_distances), (query_role, query_role_offsets) = pair_segments(pairs, reads, 500)
+    windows = correction_windows(overlaps, reads, window_length=500, max_depth=30)   # polisher.correct_reads feeds on it
 
 Index arrays carry the reference's names (representations, read_ids, positions_in_reads, directions_of_reads,
 unique_representations, first_occurrence_of_representations) and come back as numpy arrays."""
@@ -412,6 +415,10 @@ def overlap_windows(overlaps, query_reads, target_reads=None, window_length=500,
     _, (bases, offsets, per_window, reads, index) = _window_overlaps(
         overlaps, query_reads, target_reads, window_length, max_depth, first_query_read_id, first_target_read_id,
         max_device_bytes, stream, timings)
+    return _split_windows(bases, offsets, per_window, reads, index)
+
+
+def _split_windows(bases, offsets, per_window, reads, index):
     flat = bases.tobytes()
     out, at = [], 0
     for n, r, k in zip(per_window.tolist(), reads.tolist(), index.tolist()):
@@ -434,14 +441,124 @@ def select_layers(segments, overlaps, n_queries, target_lengths, window_length=5
     lengths = np.ascontiguousarray(target_lengths, np.int64)
     args = (_p(s), len(s), _p(o), len(o), int(n_queries), first_query_read_id, _p(lengths), len(lengths),
             first_target_read_id, int(window_length), int(max_depth))
+    return _plan_and_table(L.gw_mapper_select_layers, args)
+
+
+def select_pairs(overlaps):
+    """Read correction's pair selection over host records, without a device (gw_mapper_select_pairs; rule C1 of
+    INTEGRATION.md section 3k): records of a read with itself are dropped, and of the records of an unordered pair of
+    reads, in either direction, the one with the greatest query span is kept, the first on ties. Returns the kept
+    positions (int64, ascending): overlaps[select_pairs(overlaps)] are the pairs."""
+    L = _native.mapper()
+    o = np.ascontiguousarray(overlaps, OVERLAP)
+    positions = np.zeros(len(o), np.int64)
+    n = L.gw_mapper_select_pairs(_p(o), len(o), _p(positions), len(positions))
+    if n < 0:
+        raise _err(L)
+    return positions[:n]
+
+
+def _correction_windows(overlaps, reads, window_length, max_depth, first_read_id, max_device_bytes, stream, timings):
+    """gw_mapper_correction_windows and everything it holds, as host arrays; max_depth None: gw_mapper_pair_segments,
+    the segments pass alone over records that are pairs already"""
+    L = _native.mapper()
+    o = np.ascontiguousarray(overlaps, OVERLAP)
+    (bases_p, offsets_p, n_reads), _ = _read_set_args(reads, None)
+    if max_depth is None:
+        h = L.gw_mapper_pair_segments(_p(o), len(o), bases_p, offsets_p, n_reads, first_read_id, int(window_length),
+                                      int(max_device_bytes), _stream(stream))
+    else:
+        h = L.gw_mapper_correction_windows(_p(o), len(o), bases_p, offsets_p, n_reads, first_read_id,
+                                           int(window_length), int(max_depth), int(max_device_bytes), _stream(stream))
+    if not h:
+        raise _err(L)
+    try:
+        counts, n_pairs, query_ms = np.zeros(4, np.int64), C.c_int64(0), C.c_float(0.0)
+        L.gw_mapper_windows_counts(h, _p(counts))
+        n_win, n_seq, n_bases, n_seg = (int(x) for x in counts)
+        n_query_role = L.gw_mapper_windows_copy_query_role_segments(h, None, 0, None, None, C.byref(n_pairs), None)
+        n_pairs = n_pairs.value
+        segments, seg_offsets = np.zeros(n_seg, SEGMENT), np.zeros(n_pairs + 1, np.int64)
+        edits, ms = np.zeros(n_pairs, np.int32), np.zeros(4, np.float32)
+        L.gw_mapper_windows_copy_segments(h, _p(segments), _p(seg_offsets), _p(edits), _p(ms))
+        query_role, query_offsets = np.zeros(n_query_role, SEGMENT), np.zeros(n_pairs + 1, np.int64)
+        positions = np.zeros(n_pairs, np.int64)
+        L.gw_mapper_windows_copy_query_role_segments(h, _p(query_role), n_query_role, _p(query_offsets), _p(positions),
+                                                     None, C.byref(query_ms))
+        bases, seq_offsets = np.zeros(max(n_bases, 1), np.uint8), np.zeros(n_seq + 1, np.int64)
+        per_window, owners, index = np.zeros(n_win, np.int32), np.zeros(n_win, np.uint32), np.zeros(n_win, np.uint32)
+        L.gw_mapper_windows_copy_windows(h, _p(bases), _p(seq_offsets), _p(per_window), _p(owners), _p(index))
+    finally:
+        L.gw_mapper_windows_destroy(h)
+    if timings is not None:
+        timings.update(gather=float(ms[0]), align=float(ms[1]), segments=float(ms[2]), window_gather=float(ms[3]),
+                       query_role_segments=float(query_ms.value), overlaps_in=len(o), pairs=n_pairs,
+                       bytes_to_host=(n_pairs * OVERLAP.itemsize + segments.nbytes + query_role.nbytes +
+                                      2 * seg_offsets.nbytes + edits.nbytes + n_bases),
+                       segment_bytes=segments.nbytes + query_role.nbytes, window_bases=n_bases)
+    return ((segments, seg_offsets, edits), (query_role, query_offsets), positions,
+            (bases[:n_bases], seq_offsets, per_window, owners, index))
+
+
+def pair_segments(pairs, reads, window_length=500, first_read_id=0, max_device_bytes=0, stream=None, timings=None):
+    """The segments of both reads of every pair out of one alignment (gwm_pair_segments): `pairs` are OVERLAP records
+    whose query and target ids both name reads of `reads`, each aligned once, exactly as align_overlaps(pairs, reads)
+    aligns it. Returns ((target_role, segment_offsets, edit_distances), (query_role, query_role_offsets)): the first is
+    what window_segments(pairs, reads) returns, byte for byte; the second holds, per window k = query position //
+    window_length of the *query* read that holds an aligned column, one SEGMENT record whose target_first / target_last
+    are the smallest and largest query position and whose [query_begin, query_end) are the target positions of those
+    columns -- target_* describe the read that owns the window and query_* the read that supplies the layer, in either
+    role. Records are ordered by pair, then by ascending window. No pair is selected here: see select_pairs. Arguments,
+    chunking and errors as for window_segments. `timings` additionally receives query_role_segments (device ms)."""
+    target_role, query_role, _, _ = _correction_windows(pairs, reads, window_length, None, first_read_id,
+                                                        max_device_bytes, stream, timings)
+    return target_role, query_role
+
+
+def _plan_and_table(call, args):
+    """the two calls of a selection entry point of the C API: sizes first, then the arrays"""
+    L = _native.mapper()
     n_windows = C.c_int64(0)
-    n = L.gw_mapper_select_layers(*args, None, 0, C.byref(n_windows), None, 0)
+    n = call(*args, None, 0, C.byref(n_windows), None, 0)
     if n < 0:
         raise _err(L)
     plan, table = np.zeros((n, 5), np.uint32), np.zeros((n_windows.value, 4), np.uint32)
-    if L.gw_mapper_select_layers(*args, _p(plan), n, C.byref(n_windows), _p(table), len(table)) != n:
+    if call(*args, _p(plan), n, C.byref(n_windows), _p(table), len(table)) != n:
         raise _err(L)
     return [tuple(int(x) for x in row) for row in plan], [tuple(int(x) for x in row) for row in table]
+
+
+def select_correction_layers(target_role, query_role, pairs, read_lengths, window_length=500, max_depth=30,
+                             first_read_id=0):
+    """Read correction's layer selection over host arrays, without a device (gw_mapper_select_correction_layers; rules
+    C3 and C4 of INTEGRATION.md section 3k): every record of either role of pair_segments is a layer of (its owner,
+    its window) when it reaches within window_length // 100 of both ends of the window and holds 1 .. 2 * window_length
+    bases of the other read; the owner is the pair's target read for target-role records and its query read for
+    query-role ones. The layers of a window are ordered by (target_first, pair, target role first) and cut at
+    max_depth. Returns (plan, windows) as select_layers does, with every plan entry of set 0 and windows[j][0] the
+    owner."""
+    L = _native.mapper()
+    a = np.ascontiguousarray(target_role, SEGMENT)
+    b = np.ascontiguousarray(query_role, SEGMENT)
+    o = np.ascontiguousarray(pairs, OVERLAP)
+    lengths = np.ascontiguousarray(read_lengths, np.int64)
+    return _plan_and_table(L.gw_mapper_select_correction_layers,
+                           (_p(a), len(a), _p(b), len(b), _p(o), len(o), _p(lengths), len(lengths), first_read_id,
+                            int(window_length), int(max_depth)))
+
+
+def correction_windows(overlaps, reads, window_length=500, max_depth=30, first_read_id=0, max_device_bytes=0,
+                       stream=None, timings=None):
+    """The POA windows of every read of a set mapped against itself: [(read, window, [backbone, layer, ...]), ...] by
+    read, then by window; every read of L > 0 bases has windows 0 .. (L - 1) // window_length. `overlaps` are the
+    records of the all-against-all mapping as cudamapper returned them, self overlaps and both directions included:
+    select_pairs keeps one per pair of reads, that one is aligned once, and both of its reads get layers from it
+    (pair_segments, select_correction_layers). Sequences are bytes. All windows are built at once and come back
+    together: host memory for up to (1 + max_depth) sequences of up to 2 * window_length bases per window. `timings`
+    as for pair_segments, plus overlaps_in, pairs, window_gather and bytes_to_host."""
+    _, _, _, (bases, offsets, per_window, owners, index) = _correction_windows(
+        overlaps, reads, window_length, max_depth, first_read_id, max_device_bytes, stream, timings)
+    return _split_windows(bases, offsets, per_window, owners, index)
 
 
 def group_reads_into_indices(read_lengths, max_basepairs_per_index):

@@ -146,16 +146,21 @@ struct gw_mapper_cigars
     gw_mapper_cigars& operator=(const gw_mapper_cigars&) = delete;
 };
 
-// The windows of one gw_mapper_window_overlaps call, on the host
+// The windows of one gw_mapper_window_overlaps or gw_mapper_correction_windows call, on the host
 struct gw_mapper_windows
 {
-    std::vector<gwm_segment> segments;
+    std::vector<gwm_segment> segments; // in read correction: the target-role records of the pairs
     std::vector<int64_t> segment_offsets{0};
     std::vector<int32_t> edit_distances;
     float stage_ms[4] = {0.f, 0.f, 0.f, 0.f}; // gather, align, segments, window gather
     std::vector<gwm::window_record> windows;
     std::vector<int64_t> sequence_offsets{0};
     std::vector<char> bases;
+    // read correction only: the input positions of the pairs, their query-role records and those records' device time
+    std::vector<int64_t> pair_positions;
+    std::vector<gwm_segment> query_role_segments;
+    std::vector<int64_t> query_role_offsets{0};
+    float query_role_ms = 0.f;
 };
 
 #endif

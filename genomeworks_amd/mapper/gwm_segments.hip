@@ -1,6 +1,6 @@
 // gwm_segments.hip -- cudamapper on gfx950: from aligned overlaps to POA windows (include/gwhip_mapper.h,
-// gwm_window_segments and gwm_gather_sequences). gwm_window_segments runs the chunk loop of gwm_align_chunks.hpp with
-// the segment writer as its consumer: where gwm_align_overlaps turns the per-column states into text, this turns them
+// gwm_window_segments, gwm_pair_segments and gwm_gather_sequences). gwm_window_segments runs the chunk loop of
+// gwm_align_chunks.hpp with the segment writer as its consumer: where gwm_align_overlaps turns the per-column states into text, this turns them
 // into one 24 B record per (overlap, window of the target read) and leaves the states where they are. Only those
 // records cross to the host, where the layers of every window are chosen (gwm_windows.cpp); gwm_gather_sequences then
 // cuts backbones and layers out of the resident read sets.
@@ -13,6 +13,10 @@
 // pass, an exclusive scan of the record counts, a writing pass. Forward column order is ascending target order on '+'
 // and descending on '-', where the record of the r-th head goes to the r-th place from the end: records come out
 // window-ascending on both strands. No LDS, no scratch.
+//
+// gwm_pair_segments (read correction, both reads of a pair out of one alignment) runs the same kernel a second time per
+// chunk in its query role: the windows are those of the query read, whose positions ascend in forward column order on
+// both strands, and the ranges of the record are those of the target positions.
 #include "gwm_align_chunks.hpp"
 
 #include <deque>
@@ -21,9 +25,17 @@ namespace
 {
 
 // One wave64 per alignment of the chunk (states as AlignedChunk lays them out; o: the chunk's first overlap record,
-// first: its position in the call). kWrite false: counts[i] = records of alignment i, edit_distances[i] = columns that
-// are not a match (-1: no result although a slice was not empty). kWrite true: the records at segments[offsets[i]].
-template <bool kWrite>
+// first: its position in the call). kWrite false: counts[i] = records of alignment i and, where edit_distances is
+// given, edit_distances[i] = columns that are not a match (-1: no result although a slice was not empty). kWrite true:
+// the records at segments[offsets[i]].
+// kQueryRole says whose windows the records describe. An aligned column has a position in the read that owns the
+// windows (`own`: the target position, or in the query role the query position) and one in the read that supplies
+// the layer (`other`). own / window_length is the column's window; a record's target_first / target_last are the
+// smallest and largest own, its query_begin / query_end the smallest other and the largest + 1. Forward column order
+// is descending target order on '-' and ascending in everything else, so own descends in the target role on '-' and
+// other does in the query role on '-'. Records are placed window-ascending: the r-th head at the r-th place, from the
+// end where own descends.
+template <bool kWrite, bool kQueryRole>
 __global__ void __launch_bounds__(kThreads) segment_kernel(const gwm_overlap* __restrict__ o,
                                                            const uint8_t* __restrict__ results,
                                                            const int64_t* __restrict__ starts,
@@ -44,6 +56,7 @@ __global__ void __launch_bounds__(kThreads) segment_kernel(const gwm_overlap* __
     const uint32_t len   = static_cast<uint32_t>(stored < 0 ? -stored : stored); // as the host aligner reads it
     const uint8_t* s     = results + slot;
     const bool reverse   = x.relative_strand == '-';
+    const bool own_down = !kQueryRole && reverse, other_down = kQueryRole && reverse;
     const uint32_t qs = x.query_start_position_in_read, ts = x.target_start_position_in_read,
                    te      = x.target_end_position_in_read;
     const uint32_t total   = kWrite ? static_cast<uint32_t>(offsets[i + 1] - offsets[i]) : 0u;
@@ -52,7 +65,7 @@ __global__ void __launch_bounds__(kThreads) segment_kernel(const gwm_overlap* __
     // wave-uniform: columns walked so far that consume a query / a target base, the last aligned column, records opened
     uint32_t query_run = 0, target_run = 0;
     bool has_last   = false;
-    uint32_t last_k = 0, last_t = 0, last_q = 0;
+    uint32_t last_k = 0, last_own = 0, last_other = 0;
     uint32_t records = 0, edits = 0;
     for (uint32_t base = 0; base < len; base += 64)
     {
@@ -64,18 +77,20 @@ __global__ void __launch_bounds__(kThreads) segment_kernel(const gwm_overlap* __
         const uint64_t aligned_at = __ballot(aligned);
         if (!kWrite)
             edits += static_cast<uint32_t>(__popcll(__ballot(valid && state != 0)));
-        const uint32_t q = qs + query_run + static_cast<uint32_t>(__popcll(in_query & lower));
-        const uint32_t b = target_run + static_cast<uint32_t>(__popcll(in_target & lower));
-        const uint32_t t = reverse ? te - 1 - b : ts + b;
-        const uint32_t k = aligned ? t / window_length : 0u;
+        const uint32_t q     = qs + query_run + static_cast<uint32_t>(__popcll(in_query & lower));
+        const uint32_t b     = target_run + static_cast<uint32_t>(__popcll(in_target & lower));
+        const uint32_t t     = reverse ? te - 1 - b : ts + b;
+        const uint32_t own   = kQueryRole ? q : t;
+        const uint32_t other = kQueryRole ? t : q;
+        const uint32_t k     = aligned ? own / window_length : 0u;
         // the previous aligned column: the next lower aligned lane of the tile, or the one carried in
         const uint64_t below = aligned_at & lower;
         const int from       = below ? 63 - __clzll(below) : 0;
-        uint32_t pk = __shfl(k, from, 64), pt = __shfl(t, from, 64), pq = __shfl(q, from, 64);
+        uint32_t pk = __shfl(k, from, 64), p_own = __shfl(own, from, 64), p_other = __shfl(other, from, 64);
         bool has_prev = true;
         if (!below)
         {
-            pk = last_k, pt = last_t, pq = last_q;
+            pk = last_k, p_own = last_own, p_other = last_other;
             has_prev = has_last;
         }
         const bool head      = aligned && (!has_prev || k != pk);
@@ -85,24 +100,30 @@ __global__ void __launch_bounds__(kThreads) segment_kernel(const gwm_overlap* __
             const uint32_t r = records + static_cast<uint32_t>(__popcll(heads & lower));
             if (has_prev && r >= 1 && r - 1 < total) // closes the record before it
             {
-                gwm_segment& c = out[reverse ? total - r : r - 1];
-                c.query_end    = pq + 1;
-                (reverse ? c.target_first : c.target_last) = pt;
+                gwm_segment& c = out[own_down ? total - r : r - 1];
+                (own_down ? c.target_first : c.target_last) = p_own;
+                if (other_down)
+                    c.query_begin = p_other;
+                else
+                    c.query_end = p_other + 1;
             }
             if (r < total)
             {
-                gwm_segment& c = out[reverse ? total - 1 - r : r];
+                gwm_segment& c = out[own_down ? total - 1 - r : r];
                 c.overlap      = first + static_cast<uint32_t>(i);
                 c.window       = k;
-                c.query_begin  = q;
-                (reverse ? c.target_last : c.target_first) = t;
+                (own_down ? c.target_last : c.target_first) = own;
+                if (other_down)
+                    c.query_end = other + 1;
+                else
+                    c.query_begin = other;
             }
         }
         records += static_cast<uint32_t>(__popcll(heads));
         if (aligned_at)
         {
             const int last = 63 - __clzll(aligned_at);
-            last_k = __shfl(k, last, 64), last_t = __shfl(t, last, 64), last_q = __shfl(q, last, 64);
+            last_k = __shfl(k, last, 64), last_own = __shfl(own, last, 64), last_other = __shfl(other, last, 64);
             has_last = true;
         }
         query_run += static_cast<uint32_t>(__popcll(in_query));
@@ -114,15 +135,19 @@ __global__ void __launch_bounds__(kThreads) segment_kernel(const gwm_overlap* __
     {
         if (has_last && records >= 1 && records - 1 < total)
         {
-            gwm_segment& c = out[reverse ? total - records : records - 1];
-            c.query_end    = last_q + 1;
-            (reverse ? c.target_first : c.target_last) = last_t;
+            gwm_segment& c = out[own_down ? total - records : records - 1];
+            (own_down ? c.target_first : c.target_last) = last_own;
+            if (other_down)
+                c.query_begin = last_other;
+            else
+                c.query_end = last_other + 1;
         }
     }
     else
     {
-        counts[i]         = records;
-        edit_distances[i] = len ? static_cast<int32_t>(edits) : (starts[2 * i + 2] == slot ? 0 : -1);
+        counts[i] = records;
+        if (edit_distances)
+            edit_distances[i] = len ? static_cast<int32_t>(edits) : (starts[2 * i + 2] == slot ? 0 : -1);
     }
 }
 
@@ -177,6 +202,82 @@ __global__ void __launch_bounds__(kThreads) gather_sequences_kernel(const gwm_ga
     }
 }
 
+// The records of one role over the chunks of a call: the segment writer (record counts, their scan, the records of the
+// chunk) as a consumer of align_chunks(), and what is left of it when the chunks are through.
+struct RoleRecords
+{
+    dbuf<int64_t> counts, local_offsets;
+    std::deque<dbuf<gwm_segment>> parts; // one per chunk
+    std::vector<int64_t> part_sizes;
+    RoleRecords(int64_t n, hipStream_t s)
+        : counts(n + 1)
+    {
+        GWM_CHECK(hipMemsetAsync(counts.p, 0, sizeof(int64_t) * static_cast<size_t>(n + 1), s));
+    }
+    // edit_distances: of the call, or nullptr to leave them alone
+    template <bool kQueryRole>
+    void write(const AlignedChunk& c, int32_t window_length, int32_t* edit_distances, Temp& temp, hipStream_t s)
+    {
+        grow(local_offsets, c.m + 1);
+        segment_kernel<false, kQueryRole><<<c.m_waves, kThreads, 0, s>>>(
+            c.overlaps, c.results, c.starts, c.result_lengths, c.m, static_cast<uint32_t>(c.first),
+            static_cast<uint32_t>(window_length), counts.p + c.first,
+            edit_distances ? edit_distances + c.first : nullptr, nullptr, nullptr);
+        GWM_CHECK(hipGetLastError());
+        exclusive_sum(counts.p + c.first, local_offsets.p, c.m + 1, temp, s); // entry m of the input is not summed
+        const int64_t records = to_host(local_offsets.p + c.m, s);
+        parts.emplace_back(records);
+        part_sizes.push_back(records);
+        if (records > 0)
+        {
+            segment_kernel<true, kQueryRole><<<c.m_waves, kThreads, 0, s>>>(
+                c.overlaps, c.results, c.starts, c.result_lengths, c.m, static_cast<uint32_t>(c.first),
+                static_cast<uint32_t>(window_length), nullptr, nullptr, local_offsets.p, parts.back().p);
+            GWM_CHECK(hipGetLastError());
+        }
+    }
+    // the offsets of the call and the records of its chunks in one array, into *out; queued on s, so this object
+    // outlives the caller's wait for s
+    void finish(int64_t n, Temp& temp, hipStream_t s, gwm_segments* out)
+    {
+        dbuf<int64_t> offsets(n + 1);
+        exclusive_sum(counts.p, offsets.p, n + 1, temp, s);
+        int64_t total = 0;
+        for (int64_t b : part_sizes)
+            total += b;
+        dbuf<gwm_segment> segments;
+        if (parts.size() == 1)
+            segments.p = parts[0].release();
+        else
+        {
+            segments.resize(total);
+            int64_t at = 0;
+            for (size_t c = 0; c < parts.size(); at += part_sizes[c], ++c)
+                if (part_sizes[c] > 0)
+                    GWM_CHECK(hipMemcpyAsync(segments.p + at, parts[c].p,
+                                             sizeof(gwm_segment) * static_cast<size_t>(part_sizes[c]),
+                                             hipMemcpyDeviceToDevice, s));
+        }
+        out->n               = n;
+        out->n_segments      = total;
+        out->segments        = segments.release();
+        out->segment_offsets = offsets.release();
+    }
+};
+
+void check_segment_arguments(const std::string& who, int32_t n_queries, int32_t n_targets, int64_t max_device_bytes,
+                             int32_t window_length, int64_t n)
+{
+    if (n_queries < 0 || n_targets < 0)
+        throw std::invalid_argument(who + ": negative number of reads");
+    if (max_device_bytes < 0)
+        throw std::invalid_argument(who + ": negative max_device_bytes");
+    if (window_length < 1)
+        throw std::invalid_argument(who + ": window_length below 1");
+    if (n >= (int64_t(1) << 31))
+        throw std::invalid_argument(who + ": 2^31 overlaps or more");
+}
+
 } // namespace
 
 extern "C" {
@@ -199,74 +300,71 @@ int gwm_window_segments(const gwm_overlap* overlaps, int64_t n, const char* quer
     *out = gwm_segments{};
     try
     {
-        if (n_queries < 0 || n_targets < 0)
-            throw std::invalid_argument("gwm_window_segments: negative number of reads");
-        if (max_device_bytes < 0)
-            throw std::invalid_argument("gwm_window_segments: negative max_device_bytes");
-        if (window_length < 1)
-            throw std::invalid_argument("gwm_window_segments: window_length below 1");
+        check_segment_arguments("gwm_window_segments", n_queries, n_targets, max_device_bytes, window_length, n);
         if (n <= 0)
             return 0;
-        if (n >= (int64_t(1) << 31))
-            throw std::invalid_argument("gwm_window_segments: 2^31 overlaps or more");
         hipStream_t s = static_cast<hipStream_t>(stream);
-        dbuf<int64_t> counts(n + 1), offsets(n + 1), local_offsets;
         dbuf<int32_t> edit_distances(n);
-        GWM_CHECK(hipMemsetAsync(counts.p, 0, sizeof(int64_t) * static_cast<size_t>(n + 1), s));
-        std::deque<dbuf<gwm_segment>> parts; // one per chunk
-        std::vector<int64_t> part_sizes;
-        // the segment writer: record counts, their scan, the records of the chunk
+        RoleRecords records(n, s);
         Temp temp;
-        auto write_segments = [&](const AlignedChunk& c) {
-            grow(local_offsets, c.m + 1);
-            segment_kernel<false><<<c.m_waves, kThreads, 0, s>>>(
-                c.overlaps, c.results, c.starts, c.result_lengths, c.m, static_cast<uint32_t>(c.first),
-                static_cast<uint32_t>(window_length), counts.p + c.first, edit_distances.p + c.first, nullptr, nullptr);
-            GWM_CHECK(hipGetLastError());
-            exclusive_sum(counts.p + c.first, local_offsets.p, c.m + 1, temp, s); // entry m of the input is not summed
-            const int64_t records = to_host(local_offsets.p + c.m, s);
-            parts.emplace_back(records);
-            part_sizes.push_back(records);
-            if (records > 0)
-            {
-                segment_kernel<true><<<c.m_waves, kThreads, 0, s>>>(
-                    c.overlaps, c.results, c.starts, c.result_lengths, c.m, static_cast<uint32_t>(c.first),
-                    static_cast<uint32_t>(window_length), nullptr, nullptr, local_offsets.p, parts.back().p);
-                GWM_CHECK(hipGetLastError());
-            }
-        };
         gwm::align_chunks("gwm_window_segments", overlaps, n, query_bases, query_offsets, n_queries, first_query_read_id,
                      target_bases, target_offsets, n_targets, first_target_read_id, max_device_bytes, s, out->stage_ms,
-                     write_segments);
-        exclusive_sum(counts.p, offsets.p, n + 1, temp, s);
-        int64_t total = 0;
-        for (int64_t b : part_sizes)
-            total += b;
-        dbuf<gwm_segment> segments;
-        if (parts.size() == 1)
-            segments.p = parts[0].release();
-        else
-        {
-            segments.resize(total);
-            int64_t at = 0;
-            for (size_t c = 0; c < parts.size(); at += part_sizes[c], ++c)
-                if (part_sizes[c] > 0)
-                    GWM_CHECK(hipMemcpyAsync(segments.p + at, parts[c].p,
-                                             sizeof(gwm_segment) * static_cast<size_t>(part_sizes[c]),
-                                             hipMemcpyDeviceToDevice, s));
-        }
+                     [&](const AlignedChunk& c) {
+                         records.write<false>(c, window_length, edit_distances.p, temp, s);
+                     });
+        records.finish(n, temp, s, out);
         GWM_CHECK(hipStreamSynchronize(s));
-        out->n               = n;
-        out->n_segments      = total;
-        out->segments        = segments.release();
-        out->segment_offsets = offsets.release();
-        out->edit_distances  = edit_distances.release();
+        out->edit_distances = edit_distances.release();
         return 0;
     }
     catch (const std::exception& e)
     {
         gwm_set_error(e.what());
-        *out = gwm_segments{};
+        gwm_segments_free(out);
+        return -1;
+    }
+}
+
+int gwm_pair_segments(const gwm_overlap* pairs, int64_t n, const char* bases, const int64_t* offsets, int32_t n_reads,
+                      uint32_t first_read_id, int32_t window_length, int64_t max_device_bytes, void* stream,
+                      gwm_segments* target_role, gwm_segments* query_role)
+{
+    *target_role = *query_role = gwm_segments{};
+    try
+    {
+        check_segment_arguments("gwm_pair_segments", n_reads, n_reads, max_device_bytes, window_length, n);
+        if (n <= 0)
+            return 0;
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        dbuf<int32_t> edit_distances(n);
+        RoleRecords of_target(n, s), of_query(n, s);
+        Temp temp;
+        Events ev(3);
+        float role_ms[2] = {0.f, 0.f}; // the consumer's time, which align_chunks() sums for both, apart for each role
+        gwm::align_chunks("gwm_pair_segments", pairs, n, bases, offsets, n_reads, first_read_id, bases, offsets, n_reads,
+                          first_read_id, max_device_bytes, s, target_role->stage_ms, [&](const AlignedChunk& c) {
+                              ev.record(0, s);
+                              of_target.write<false>(c, window_length, edit_distances.p, temp, s);
+                              ev.record(1, s);
+                              of_query.write<true>(c, window_length, nullptr, temp, s);
+                              ev.record(2, s);
+                              role_ms[0] += ev.ms(0, 1);
+                              role_ms[1] += ev.ms(1, 2);
+                          });
+        of_target.finish(n, temp, s, target_role);
+        of_query.finish(n, temp, s, query_role);
+        GWM_CHECK(hipStreamSynchronize(s));
+        target_role->edit_distances = edit_distances.release();
+        std::copy(target_role->stage_ms, target_role->stage_ms + 2, query_role->stage_ms);
+        target_role->stage_ms[2] = role_ms[0];
+        query_role->stage_ms[2]  = role_ms[1];
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        gwm_set_error(e.what());
+        gwm_segments_free(target_role);
+        gwm_segments_free(query_role);
         return -1;
     }
 }

@@ -1,6 +1,8 @@
-// gwm_windows.hpp -- polishing's layer selection: plain host arithmetic over the segment records of
-// gwm_window_segments, the overlap records and the target read lengths. No HIP call and no HIP header, so it is tested
-// without a device (gw_mapper_select_layers) and under the host sanitizers (tests/cpp/select_layers_sanitized.cpp).
+// gwm_windows.hpp -- polishing's and read correction's layer selection: plain host arithmetic over the segment records
+// of gwm_window_segments / gwm_pair_segments, the overlap records and the read lengths. No HIP call and no HIP header,
+// so it is tested without a device (gw_mapper_select_layers, gw_mapper_select_pairs,
+// gw_mapper_select_correction_layers) and under the host sanitizers (tests/cpp/select_layers_sanitized.cpp,
+// tests/cpp/select_correction_sanitized.cpp).
 #ifndef GWM_WINDOWS_HPP
 #define GWM_WINDOWS_HPP
 
@@ -12,7 +14,7 @@
 namespace gwm
 {
 
-// One window of a target read and where its sequences stand in the gather plan: the backbone, then the layers.
+// One window of a target read (in read correction: of the read that owns it) and where its sequences stand in the gather plan: the backbone, then the layers.
 struct window_record
 {
     uint32_t target_read; // position in the target set
@@ -40,6 +42,24 @@ window_selection select_layers(const gwm_segment* segments, int64_t n_segments, 
                                int64_t n_overlaps, int32_t n_queries, uint32_t first_query_read_id,
                                const int64_t* target_lengths, int32_t n_targets, uint32_t first_target_read_id,
                                int32_t window_length, int32_t max_depth);
+
+// Read correction, C1 of INTEGRATION.md section 3k: the records of an all-against-all mapping that are aligned. Records
+// of a read with itself are dropped; of the remaining records of an unordered pair of reads, in either direction, the
+// one with the greatest query end - query start is kept, on ties the first. Returns the kept positions, ascending.
+// Throws std::invalid_argument for a negative count and a record that starts behind its end.
+std::vector<int64_t> select_pairs(const gwm_overlap* overlaps, int64_t n_overlaps);
+
+// Read correction, C3 and C4: the windows of every read of the one set with their layers, from the records of both
+// roles of gwm_pair_segments. A record's owner is its pair's target read in the target role and its query read in the
+// query role; the record is a layer of (owner, window) under rule 2 above with the owner's length. Layers are ordered
+// by (target_first, pair position, target role first) and cut at max_depth. A target-role layer is
+// query[query_begin, query_end), a query-role layer target[query_begin, query_end), either reversed on '-'. Backbones
+// and windows as in rule 5. Every plan entry is of set 0; window_record::target_read is the owner. Throws as
+// select_layers does.
+window_selection select_correction_layers(const gwm_segment* target_role, int64_t n_target_role,
+                                          const gwm_segment* query_role, int64_t n_query_role, const gwm_overlap* pairs,
+                                          int64_t n_pairs, const int64_t* read_lengths, int32_t n_reads,
+                                          uint32_t first_read_id, int32_t window_length, int32_t max_depth);
 
 } // namespace gwm
 

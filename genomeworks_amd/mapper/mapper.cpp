@@ -40,6 +40,46 @@ gw_mapper_overlaps* map_batched_guarded(const reads_view& queries, const reads_v
                    static_cast<gw_mapper_overlaps*>(nullptr));
 }
 
+// the windows of a selection into h: their table, and their bases gathered on the device and copied out once
+void gather_windows(gw_mapper_windows& h, window_selection selection, const reads_view& q, const reads_view& t,
+                    void* stream)
+{
+    h.windows = std::move(selection.windows);
+    const std::vector<gwm_gather_entry>& plan = selection.plan;
+    h.sequence_offsets.assign(plan.size() + 1, 0);
+    for (size_t i = 0; i < plan.size(); ++i)
+        h.sequence_offsets[i + 1] = h.sequence_offsets[i] + (plan[i].end - plan[i].begin);
+    const int64_t total = h.sequence_offsets.back();
+    h.bases.resize(static_cast<size_t>(total));
+    if (total > 0)
+    {
+        dbuf<gwm_gather_entry> device_plan;
+        dbuf<int64_t> device_starts;
+        dbuf<char> device_bases(total);
+        device_plan.upload(plan.data(), static_cast<int64_t>(plan.size()));
+        device_starts.upload(h.sequence_offsets.data(), static_cast<int64_t>(plan.size()));
+        throw_on(gwm_gather_sequences(device_plan.p, static_cast<int64_t>(plan.size()), device_starts.p, q.bases,
+                                      q.offsets, q.n, t.bases, t.offsets, t.n, device_bases.p, total, stream,
+                                      &h.stage_ms[3]));
+        copy_out(h.bases.data(), device_bases.p, total);
+    }
+}
+
+struct owned_segments
+{
+    gwm_segments s{};
+    ~owned_segments() { gwm_segments_free(&s); }
+};
+
+// the records of one role and their offsets to the host
+void copy_segments(const gwm_segments& s, int64_t n, std::vector<gwm_segment>& segments, std::vector<int64_t>& offsets)
+{
+    segments.resize(static_cast<size_t>(s.n_segments));
+    copy_out(segments.data(), s.segments, s.n_segments);
+    offsets.assign(static_cast<size_t>(n) + 1, 0);
+    copy_out(offsets.data(), s.segment_offsets, s.n > 0 ? s.n + 1 : 0);
+}
+
 // gw_mapper_window_overlaps, or with max_depth < 0 its segments pass alone: no selection, no gather, no windows
 gw_mapper_windows* window_overlaps(const void* overlaps, int64_t n, const reads_view& query_reads,
                                    uint32_t first_query_read_id, const reads_view& target_reads,
@@ -57,19 +97,12 @@ gw_mapper_windows* window_overlaps(const void* overlaps, int64_t n, const reads_
         d.upload(host_overlaps, n);
         const reads_view &q = reads.device_queries, &t = reads.device_targets;
         // segments on the device, their records (24 B each) to the host
-        struct owned_segments
-        {
-            gwm_segments s{};
-            ~owned_segments() { gwm_segments_free(&s); }
-        } device;
+        owned_segments device;
         throw_on(gwm_window_segments(d.p, n, q.bases, q.offsets, reads.queries.n, first_query_read_id, t.bases, t.offsets,
                                      reads.targets.n, first_target_read_id, window_length, max_device_bytes, stream,
                                      &device.s));
         const gwm_segments& s = device.s;
-        h->segments.resize(static_cast<size_t>(s.n_segments));
-        copy_out(h->segments.data(), s.segments, s.n_segments);
-        h->segment_offsets.assign(static_cast<size_t>(n) + 1, 0);
-        copy_out(h->segment_offsets.data(), s.segment_offsets, s.n > 0 ? s.n + 1 : 0);
+        copy_segments(s, n, h->segments, h->segment_offsets);
         h->edit_distances.resize(static_cast<size_t>(n));
         copy_out(h->edit_distances.data(), s.edit_distances, s.n);
         std::memcpy(h->stage_ms, s.stage_ms, sizeof(s.stage_ms));
@@ -82,26 +115,61 @@ gw_mapper_windows* window_overlaps(const void* overlaps, int64_t n, const reads_
         window_selection selection =
             select_layers(h->segments.data(), s.n_segments, host_overlaps, n, reads.queries.n, first_query_read_id,
                           target_lengths.data(), reads.targets.n, first_target_read_id, window_length, max_depth);
-        h->windows = std::move(selection.windows);
-        const std::vector<gwm_gather_entry>& plan = selection.plan;
-        h->sequence_offsets.assign(plan.size() + 1, 0);
-        for (size_t i = 0; i < plan.size(); ++i)
-            h->sequence_offsets[i + 1] = h->sequence_offsets[i] + (plan[i].end - plan[i].begin);
-        // their bases, gathered on the device and copied out once
-        const int64_t total = h->sequence_offsets.back();
-        h->bases.resize(static_cast<size_t>(total));
-        if (total > 0)
+        gather_windows(*h, std::move(selection), q, t, stream);
+        return h.release();
+    }, static_cast<gw_mapper_windows*>(nullptr));
+}
+
+// gw_mapper_correction_windows; with max_depth < 0 gw_mapper_pair_segments: the records are taken for pairs as they
+// stand and nothing is selected or gathered
+gw_mapper_windows* correction_windows(const void* overlaps, int64_t n, const reads_view& host_reads,
+                                      uint32_t first_read_id, int32_t window_length, int32_t max_depth,
+                                      int64_t max_device_bytes, void* stream)
+{
+    return guarded([&] {
+        std::unique_ptr<gw_mapper_windows> h(new gw_mapper_windows());
+        if (n < 0)
+            throw std::invalid_argument("gw_mapper_correction_windows: negative number of overlaps");
+        const gwm_overlap* given = static_cast<const gwm_overlap*>(overlaps);
+        std::vector<gwm_overlap> pairs;
+        if (max_depth < 0)
         {
-            dbuf<gwm_gather_entry> device_plan;
-            dbuf<int64_t> device_starts;
-            dbuf<char> device_bases(total);
-            device_plan.upload(plan.data(), static_cast<int64_t>(plan.size()));
-            device_starts.upload(h->sequence_offsets.data(), static_cast<int64_t>(plan.size()));
-            throw_on(gwm_gather_sequences(device_plan.p, static_cast<int64_t>(plan.size()), device_starts.p, q.bases,
-                                          q.offsets, reads.queries.n, t.bases, t.offsets, reads.targets.n, device_bases.p,
-                                          total, stream, &h->stage_ms[3]));
-            copy_out(h->bases.data(), device_bases.p, total);
+            pairs.assign(given, given + n);
+            for (int64_t i = 0; i < n; ++i)
+                h->pair_positions.push_back(i);
         }
+        else
+        {
+            h->pair_positions = select_pairs(given, n);
+            for (int64_t i : h->pair_positions)
+                pairs.push_back(given[i]);
+        }
+        const int64_t n_pairs = static_cast<int64_t>(pairs.size());
+        read_sets reads(host_reads, reads_view{nullptr, nullptr, 0});
+        reads.upload(); // once: the segments pass and the window gather read the same device copy
+        dbuf<gwm_overlap> d;
+        d.upload(pairs.data(), n_pairs);
+        const reads_view& r = reads.device_queries;
+        owned_segments target_role, query_role;
+        throw_on(gwm_pair_segments(d.p, n_pairs, r.bases, r.offsets, r.n, first_read_id, window_length, max_device_bytes,
+                                   stream, &target_role.s, &query_role.s));
+        copy_segments(target_role.s, n_pairs, h->segments, h->segment_offsets);
+        copy_segments(query_role.s, n_pairs, h->query_role_segments, h->query_role_offsets);
+        h->edit_distances.resize(static_cast<size_t>(n_pairs));
+        copy_out(h->edit_distances.data(), target_role.s.edit_distances, target_role.s.n);
+        std::memcpy(h->stage_ms, target_role.s.stage_ms, sizeof(target_role.s.stage_ms));
+        h->query_role_ms = query_role.s.stage_ms[2];
+        if (max_depth < 0)
+            return h.release();
+        std::vector<int64_t> lengths(static_cast<size_t>(host_reads.n));
+        for (int32_t i = 0; i < host_reads.n; ++i)
+            lengths[i] = host_reads.offsets[i + 1] - host_reads.offsets[i];
+        gather_windows(*h,
+                       select_correction_layers(h->segments.data(), target_role.s.n_segments,
+                                                h->query_role_segments.data(), query_role.s.n_segments, pairs.data(),
+                                                n_pairs, lengths.data(), host_reads.n, first_read_id, window_length,
+                                                max_depth),
+                       r, r, stream);
         return h.release();
     }, static_cast<gw_mapper_windows*>(nullptr));
 }
@@ -451,6 +519,80 @@ int64_t gw_mapper_select_layers(const void* segments, int64_t n_segments, const 
             *n_windows = windows;
         return sequences;
     }, int64_t(GW_MAPPER_ERROR));
+}
+
+int64_t gw_mapper_select_pairs(const void* overlaps, int64_t n_overlaps, int64_t* positions, int64_t capacity)
+{
+    return guarded([&] {
+        const std::vector<int64_t> kept = select_pairs(static_cast<const gwm_overlap*>(overlaps), n_overlaps);
+        const int64_t n = static_cast<int64_t>(kept.size());
+        if (positions && n <= capacity && n > 0)
+            std::memcpy(positions, kept.data(), sizeof(int64_t) * kept.size());
+        return n;
+    }, int64_t(GW_MAPPER_ERROR));
+}
+
+int64_t gw_mapper_select_correction_layers(const void* target_role, int64_t n_target_role, const void* query_role,
+                                           int64_t n_query_role, const void* pairs, int64_t n_pairs,
+                                           const int64_t* read_lengths, int32_t n_reads, uint32_t first_read_id,
+                                           int32_t window_length, int32_t max_depth, uint32_t* plan, int64_t plan_capacity,
+                                           int64_t* n_windows, uint32_t* window_table, int64_t window_capacity)
+{
+    return guarded([&] {
+        const window_selection s = select_correction_layers(
+            static_cast<const gwm_segment*>(target_role), n_target_role, static_cast<const gwm_segment*>(query_role),
+            n_query_role, static_cast<const gwm_overlap*>(pairs), n_pairs, read_lengths, n_reads, first_read_id,
+            window_length, max_depth);
+        const int64_t sequences = static_cast<int64_t>(s.plan.size()), windows = static_cast<int64_t>(s.windows.size());
+        if (plan && sequences <= plan_capacity && sequences > 0)
+            std::memcpy(plan, s.plan.data(), sizeof(gwm_gather_entry) * s.plan.size());
+        if (window_table && windows <= window_capacity && windows > 0)
+            std::memcpy(window_table, s.windows.data(), sizeof(window_record) * s.windows.size());
+        if (n_windows)
+            *n_windows = windows;
+        return sequences;
+    }, int64_t(GW_MAPPER_ERROR));
+}
+
+gw_mapper_windows* gw_mapper_correction_windows(const void* overlaps, int64_t n, const char* bases,
+                                                const int64_t* offsets, int32_t n_reads, uint32_t first_read_id,
+                                                int32_t window_length, int32_t max_depth, int64_t max_device_bytes,
+                                                void* stream)
+{
+    if (max_depth < 0)
+    {
+        g_capi_error = "gw_mapper_correction_windows: negative max_depth";
+        return nullptr;
+    }
+    return correction_windows(overlaps, n, {bases, offsets, n_reads}, first_read_id, window_length, max_depth,
+                              max_device_bytes, stream);
+}
+
+gw_mapper_windows* gw_mapper_pair_segments(const void* pairs, int64_t n, const char* bases, const int64_t* offsets,
+                                           int32_t n_reads, uint32_t first_read_id, int32_t window_length,
+                                           int64_t max_device_bytes, void* stream)
+{
+    return correction_windows(pairs, n, {bases, offsets, n_reads}, first_read_id, window_length, -1, max_device_bytes,
+                              stream);
+}
+
+int64_t gw_mapper_windows_copy_query_role_segments(const gw_mapper_windows* windows, void* segments, int64_t capacity,
+                                                   int64_t* query_role_offsets, int64_t* pair_positions, int64_t* n_pairs,
+                                                   float* query_role_ms)
+{
+    const gw_mapper_windows& w = *windows;
+    const int64_t n            = static_cast<int64_t>(w.query_role_segments.size());
+    if (segments && n <= capacity && n > 0)
+        std::memcpy(segments, w.query_role_segments.data(), sizeof(gwm_segment) * w.query_role_segments.size());
+    if (query_role_offsets)
+        std::memcpy(query_role_offsets, w.query_role_offsets.data(), sizeof(int64_t) * w.query_role_offsets.size());
+    if (pair_positions && !w.pair_positions.empty())
+        std::memcpy(pair_positions, w.pair_positions.data(), sizeof(int64_t) * w.pair_positions.size());
+    if (n_pairs)
+        *n_pairs = static_cast<int64_t>(w.pair_positions.size());
+    if (query_role_ms)
+        *query_role_ms = w.query_role_ms;
+    return n;
 }
 
 gw_mapper_overlaps* gw_mapper_map_batched(const char* query_bases, const int64_t* query_offsets, int32_t n_queries,

@@ -7,7 +7,14 @@ cudamapper finds and aligns the overlaps, the aligned overlaps are cut into wind
 
 The rules -- which overlap speaks for a read, which of its pieces become layers of a window, their order and number --
 are in INTEGRATION.md section 3j. Windows that fewer than 2 layers span keep the draft's bases, and so do windows whose
-POA does not succeed; nothing is trimmed."""
+POA does not succeed; nothing is trimmed.
+
+    corrected, report = correct_reads(reads)                       # the reads of a set corrected with each other
+
+polish(reads, reads) is not that: rule 1 of section 3j keeps one overlap per query read, the one with the longest
+span, and for a set mapped against itself that is every read's overlap with itself, so the reads come back unchanged.
+correct_reads() drops the self overlaps, keeps one record per pair of reads, aligns it once and cuts the windows of
+both of its reads out of that one alignment."""
 import time
 
 from . import cudamapper, cudapoa
@@ -61,6 +68,17 @@ def polish(reads, targets, overlaps=None, window_length=500, max_depth=30, band_
     t1 = time.perf_counter()
     windows = cudamapper.overlap_windows(overlaps, reads, targets, window_length, max_depth, timings=times)
     t2 = time.perf_counter()
+    polished, report, t3 = _consensus_of_windows(windows, len(targets), window_length, max_depth, band_width, band_mode,
+                                                 devices, poa_memory_per_device)
+    t4 = time.perf_counter()
+    times.update(map_seconds=t1 - t0, windows_seconds=t2 - t1, poa_seconds=t3 - t2, stitch_seconds=t4 - t3)
+    return polished, report
+
+
+def _consensus_of_windows(windows, n_reads, window_length, max_depth, band_width, band_mode, devices,
+                          poa_memory_per_device):
+    """The POA of every window of overlap_windows / correction_windows that at least 2 layers span, and the results
+    stitched per read: (sequences, report, the time the POA was through)."""
     deep = [i for i, (_, _, seqs) in enumerate(windows) if len(seqs) - 1 >= 2]
     status, consensus = {}, {}
     if deep:
@@ -72,14 +90,52 @@ def polish(reads, targets, overlaps=None, window_length=500, max_depth=30, band_
         for j, i in enumerate(deep):
             status[i], consensus[i] = int(out["status"][j]), out["consensus"][j]
     t3 = time.perf_counter()
-    pieces = [[] for _ in targets]
+    pieces = [[] for _ in range(n_reads)]
     report = []
     for i, (target, window, seqs) in enumerate(windows):
         kept = status.get(i) != 0
         pieces[target].append(seqs[0].decode("latin-1") if kept else consensus[i])
         report.append(dict(target_read=target, window=window, layers=len(seqs) - 1, status=status.get(i),
                            backbone_kept=kept))
-    polished = ["".join(p) for p in pieces]
+    return ["".join(p) for p in pieces], report, t3
+
+
+def correct_reads(reads, overlaps=None, window_length=500, max_depth=30, band_width=256, band_mode="static_band",
+                  devices=(0,), timings=None, poa_memory_per_device=4 << 30, **mapping_parameters):
+    """`reads` corrected with each other: (corrected_reads, report), both as polish() returns them, with every read in
+    the place of a target: corrected_reads[i] is the concatenation of the results of read i's windows, and report has
+    one dict per window, by read, then by window, whose target_read is the read that owns the window.
+
+    overlaps: OVERLAP records of the reads mapped against themselves, whose read ids are positions in the list, as
+    cudamapper returned them -- self overlaps and both directions of a pair may be among them; None maps first, with
+    map_reads_batched(reads, None, **mapping_parameters) over polish()'s defaults, and reads shorter than k + w - 1
+    raise ValueError as there. One record per pair of reads is aligned, once, and both of its reads get layers from
+    it (cudamapper.correction_windows; the rules are in INTEGRATION.md section 3k). All windows of all reads are built
+    at once, so the host holds up to (1 + max_depth) sequences of up to 2 * window_length bases per window of every
+    read; reads are not corrected in batches. The remaining arguments as for polish(). `timings` receives what
+    polish() gives it and pairs, overlaps_in (records aligned, records given) and query_role_segments (device ms)."""
+    if window_length < 1:
+        raise ValueError("window_length must be >= 1")
+    if max_depth < 0:
+        raise ValueError("max_depth must be >= 0")
+    times = {} if timings is None else timings
+    t0 = time.perf_counter()
+    if overlaps is None:
+        shortest = mapping_parameters.get("k", 15) + mapping_parameters.get("w", 10) - 1
+        if any(len(r) < shortest for r in reads):
+            raise ValueError("correct_reads: a read shorter than k + w - 1 = %d bases cannot be mapped" % shortest)
+        if mapping_parameters.get("align"):
+            raise ValueError("correct_reads: the pairs are aligned by the windows step")
+        parameters = dict(dict(post_process=True, rescue_overlap_ends=True, filtering_parameter=1.0),
+                          **mapping_parameters)
+        overlaps = cudamapper.map_reads_batched(reads, None, timings=times, **parameters)
+    elif mapping_parameters:
+        raise TypeError("correct_reads: mapping parameters given together with overlaps")
+    t1 = time.perf_counter()
+    windows = cudamapper.correction_windows(overlaps, reads, window_length, max_depth, timings=times)
+    t2 = time.perf_counter()
+    corrected, report, t3 = _consensus_of_windows(windows, len(reads), window_length, max_depth, band_width, band_mode,
+                                                  devices, poa_memory_per_device)
     t4 = time.perf_counter()
     times.update(map_seconds=t1 - t0, windows_seconds=t2 - t1, poa_seconds=t3 - t2, stitch_seconds=t4 - t3)
-    return polished, report
+    return corrected, report

@@ -164,6 +164,50 @@ int64_t gw_mapper_select_layers(const void* segments, int64_t n_segments, const 
                                 int32_t max_depth, uint32_t* plan, int64_t plan_capacity, int64_t* n_windows,
                                 uint32_t* window_table, int64_t window_capacity);
 
+/* ---- read correction: POA windows of both reads from one alignment --------------------------------------------------
+   There is one read set, and the overlaps are those of the set mapped against itself. The rules (C1 to C4) are in
+   INTEGRATION.md section 3k and next to gwm::select_pairs / gwm::select_correction_layers in mapper/gwm_windows.hpp. */
+
+/* C1, over host records; it needs no device. Records of a read with itself are dropped; per unordered pair of reads
+   the record with the greatest query end - query start is kept, on ties the first. Returns the number of pairs, or
+   GW_MAPPER_ERROR; positions (input positions of the pairs, ascending) is written when it is not NULL and capacity
+   suffices. */
+int64_t gw_mapper_select_pairs(const void* overlaps, int64_t n_overlaps, int64_t* positions, int64_t capacity);
+
+/* C3 and C4, over host arrays; it needs no device. target_role / query_role: the records of gwm_pair_segments for
+   `pairs`. Returns, and writes plan and window_table, as gw_mapper_select_layers does; every plan entry is of set 0
+   and a window's "target read" is the read that owns it. */
+int64_t gw_mapper_select_correction_layers(const void* target_role, int64_t n_target_role, const void* query_role,
+                                           int64_t n_query_role, const void* pairs, int64_t n_pairs,
+                                           const int64_t* read_lengths, int32_t n_reads, uint32_t first_read_id,
+                                           int32_t window_length, int32_t max_depth, uint32_t* plan, int64_t plan_capacity,
+                                           int64_t* n_windows, uint32_t* window_table, int64_t window_capacity);
+
+/* The windows of every read of the set: pairs selected on the host (C1), uploaded and aligned once each, the records of
+   both roles written on the device (gwm_pair_segments) and copied to the host, the layers selected there (C3, C4), the
+   sequences gathered on the device and copied out once. All windows of all reads are built at once: the handle holds
+   the bases of every backbone and layer, at most (1 + max_depth) sequences of up to 2 * window_length bases per
+   window, and the device holds the read set once plus that gather. The accessors of gw_mapper_windows serve the
+   handle: its segments, offsets and edit distances are the target-role records of the pairs, by pair. Errors as for
+   gw_mapper_window_overlaps. */
+gw_mapper_windows* gw_mapper_correction_windows(const void* overlaps, int64_t n, const char* bases,
+                                                const int64_t* offsets, int32_t n_reads, uint32_t first_read_id,
+                                                int32_t window_length, int32_t max_depth, int64_t max_device_bytes,
+                                                void* stream);
+/* The segments pass alone over records that are taken for pairs as they stand: no pair selection, no layer selection,
+   no gather. */
+gw_mapper_windows* gw_mapper_pair_segments(const void* pairs, int64_t n, const char* bases, const int64_t* offsets,
+                                           int32_t n_reads, uint32_t first_read_id, int32_t window_length,
+                                           int64_t max_device_bytes, void* stream);
+/* What a handle of the two calls above holds beyond the others. Returns the number of query-role records; *n_pairs is
+   the number of pairs. segments (24 B each, written when capacity suffices), query_role_offsets[pairs + 1],
+   pair_positions[pairs] (the pairs' positions in the input) and *query_role_ms (device time of the query-role records;
+   stage_ms[2] of gw_mapper_windows_copy_segments is that of the target-role ones); any pointer may be NULL. A handle
+   of gw_mapper_window_overlaps holds none of it: 0 records, 0 pairs. */
+int64_t gw_mapper_windows_copy_query_role_segments(const gw_mapper_windows* windows, void* segments, int64_t capacity,
+                                                   int64_t* query_role_offsets, int64_t* pair_positions, int64_t* n_pairs,
+                                                   float* query_role_ms);
+
 /* group_reads_into_indices: consecutive reads while the running base count stays <= max_basepairs_per_index; a longer
    read gets an index of its own. The reference's loop as it stands: when the very first read is longer than the limit
    a descriptor of zero reads comes first, and no reads at all give the one descriptor {0, 0}. Returns the number of

@@ -262,6 +262,22 @@ int gwm_window_segments(const gwm_overlap* overlaps, int64_t n, const char* quer
                         int32_t window_length, int64_t max_device_bytes, void* stream, gwm_segments* out);
 void gwm_segments_free(gwm_segments* segments);
 
+/* Read correction: the segments of both reads of every pair out of one alignment. There is one read set, and query and
+ * target ids both name reads of it. Pair i is aligned exactly as gwm_align_overlaps(pairs, n, bases, ..., bases, ...)
+ * aligns it, once. *target_role gets what gwm_window_segments gives for the same arguments, byte for byte, the edit
+ * distances included. *query_role gets the records of the query read's windows: an aligned column with query position
+ * q and target position t (both as above) lies in window q / window_length of the query read, and every such window
+ * that holds an aligned column gives one record {overlap = i, window, target_first = min q, target_last = max q,
+ * query_begin = min t, query_end = max t + 1} -- target_* describe the read that owns the window, query_* the read
+ * that supplies the layer, in either role. A window of nothing but state 3 gives none. Records are ordered by pair,
+ * then by ascending window; query_role->edit_distances is NULL (the edit distances are filled once, in *target_role).
+ * stage_ms[0..1] are the same in both; stage_ms[2] is each role's own kernels and scan. Both roles are written by the
+ * same chunk consumer, the states of a chunk are read on the device by both and copied nowhere; the query-role records
+ * lie outside max_device_bytes like the others. Errors as for gwm_window_segments; both structs are left zeroed. */
+int gwm_pair_segments(const gwm_overlap* pairs, int64_t n, const char* bases, const int64_t* offsets, int32_t n_reads,
+                      uint32_t first_read_id, int32_t window_length, int64_t max_device_bytes, void* stream,
+                      gwm_segments* target_role, gwm_segments* query_role);
+
 /* One sequence of a gather plan (20 B): bases [begin, end) of read `read` (position in its set) of the query set
  * (set 0) or the target set (set 1); reversed != 0: back to front, every byte through "TGAC"[(c >> 1) & 3]. */
 typedef struct gwm_gather_entry
