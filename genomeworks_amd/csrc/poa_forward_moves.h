@@ -15,17 +15,20 @@
 //     one DPP shift); 1 previous row, band moved by one quad (registers + DPP lane shift: no LDS round trip; the
 //     read characters of the next quad are prefetched one band move ahead); 2 one predecessor 1..7 rows up (LDS
 //     ring); 3 two to six predecessors (LDS ring); 4 everything else (general 32-bit routine, HBM matrix).
-//   * ROW DESCRIPTORS in registers: 64 rows at a time every lane decodes its row's table word into a ready-made
-//     32-bit descriptor (kind, band start, ring slots and distances of the predecessors) and the base replicated
-//     into four bytes; the row loop fetches them with v_readlane (one issue slot, no LDS latency, no scalar decode
-//     for the common kinds).
+//   * ROW DESCRIPTORS in registers: 63 rows at a time every lane packs its row's table word into ready-made operands
+//     (poa_forward_row_operands.h: descriptor kind -- table kind 3 split by predecessor count --, scores-to-HBM bit and
+//     read address in one word, the base replicated into four bytes, ring slot addresses, band start in bytes, packed
+//     move constants); the row loop fetches what a kind needs with v_readlane (one issue slot each, no LDS latency, no
+//     scalar decode) and dispatches once per row to a body that ends in its own stores.
 //   * TWO PHASES: rows whose band starts at column 0 (the first ~band/2 rows of a read: their left boundary is a
 //     real cell) and the rest (left boundary = min_score by construction) run in separate instantiations, so the
 //     bulk of the rows carries no boundary code at all.
-//   * Stores go through per-lane running pointers (one 64-bit add per row and stream).
+//   * Stores go through per-lane pointers to row 0 plus the row's scalar offset (one 64-bit add per row and stream).
 //
 // Preconditions are those of poa_forward_packed.h (checked by nw_banded).
 #pragma once
+
+#include "poa_forward_row_operands.h"
 
 namespace gwhip
 {
@@ -72,6 +75,9 @@ template <int MAXD = kPkMaxDist, bool TBRULES = false>
 __device__ __forceinline__ int32_t classify_kinds(RowInfo<true>* rowinfo, int32_t graph_count, int lane, const uint64_t* xpred, int32_t dbg = 0)
 {
     int32_t first_moved = graph_count + 1;
+    // (bit 30 is also the top bit of the row loop's profiling selector: with bit 13, which makes that selector name a
+    // descriptor kind, it demotes nothing)
+    const bool demote_many = (dbg & (1 << 30)) != 0 && (dbg & (1 << 13)) == 0;
     for (int32_t r = 1 + lane; r <= graph_count; r += kWave)
     {
         RowInfo<true> ri  = rowinfo[r];
@@ -79,7 +85,7 @@ __device__ __forceinline__ int32_t classify_kinds(RowInfo<true>* rowinfo, int32_
         uint64_t kind     = 4;
         // 4..6 predecessors: rows 3..5 from the side table build_rowinfo left (a row that lost its slot stays kind 4)
         const uint64_t xe  = (cnt > 3 && cnt <= 6 && xpred != nullptr) ? xpred[r & 255] : 0ull;
-        const bool many_ok = cnt > 3 && cnt <= 6 && xpred_hit(xe, r, cnt) && !(dbg & (1 << 30));
+        const bool many_ok = cnt > 3 && cnt <= 6 && xpred_hit(xe, r, cnt) && !demote_many;
         if (cnt >= 1 && (cnt <= 3 || many_ok))
         {
             bool ok    = true;
@@ -98,7 +104,7 @@ __device__ __forceinline__ int32_t classify_kinds(RowInfo<true>* rowinfo, int32_
         }
         // A/B selectors (GWHIP_DEBUG, debug instantiation): demote kinds so that the routines can be checked against each
         // other -- bit 10: registers -> ring (kinds 0, 1 -> 2), bit 15: kind 1 -> 2, bit 9: ring -> general (2, 3 -> 4),
-        // bit 11: registers -> general (0, 1 -> 4), bit 30 (above): rows with 4..6 predecessors -> general
+        // bit 11: registers -> general (0, 1 -> 4), bit 30 without bit 13 (above): rows with 4..6 predecessors -> general
         if ((dbg & 1024) && kind <= 1) kind = 2;
         if ((dbg & 32768) && kind == 1) kind = 2;
         if ((dbg & 512) && (kind == 2 || kind == 3)) kind = 4;
@@ -176,10 +182,19 @@ __device__ __forceinline__ void banded_forward_moves(const GraphView<IdT>& g, Ro
     const bool ab_ring = !(abl && (dbg & (1 << 20))), ab_guard = !(abl && (dbg & (1 << 19))), ab_scan = !(abl && (dbg & (1 << 18))),
                ab_moves = !(abl && (dbg & (1 << 17))), ab_rows = !(abl && (dbg & (1 << 16)));
     // profiling (GWHIP_DEBUG bits 28-30 = row kind + 1): cycles spent in rows of that kind, or with bit 12 their number;
-    // arrives in the "other" phase accumulator
+    // arrives in the "other" phase accumulator. The kind is a TABLE kind (3 = every multi-predecessor ring row), or with bit 13
+    // a DESCRIPTOR kind (poa_forward_row_operands.h: 3 two, 5 three, 6 four to six predecessors); with bit 13 a counted row
+    // adds 2^32 in the phase of band start 0 and 2^48 in the moved phase, which keeps both counts exact above the phase's ticks
+    // (up to 65 535 rows per window, phase and launch).
     const int32_t ksel = prof_acc ? ((dbg >> 28) & 7) - 1 : -1;
+    const bool kfine   = (dbg & (1 << 13)) != 0;
     const bool kcount  = (dbg & (1 << 12)) != 0;
     uint64_t kacc      = 0;
+    auto kselected = [&](uint32_t dk) -> bool { return ksel == (int32_t)((kfine || dk < kDkRingThree) ? dk : (uint32_t)kDkRingTwo); };
+    const bool ksel_prev = kselected(kDkPrev), ksel_moved = kselected(kDkPrevMoved), ksel_one = kselected(kDkRingOne),
+               ksel_two = kselected(kDkRingTwo), ksel_three = kselected(kDkRingThree), ksel_many = kselected(kDkRingMany),
+               ksel_general = kselected(kDkGeneral);
+    static_assert(kRowOpSlots == kPkSlots && kRowOpSlotBytes == kPkSlotBytes, "the row operands fold the ring's geometry in");
     static_assert(BW == 128 || BW == 256, "band widths of the packed pass");
     constexpr int32_t band_width = BW;
     constexpr int32_t stride     = band_width + kRightPad;
@@ -232,9 +247,10 @@ __device__ __forceinline__ void banded_forward_moves(const GraphView<IdT>& g, Ro
     uint32_t rd4n = lds_load_u32(read_base + lane4 + 4);
     uint32_t a1   = (uint32_t)lane8;
     uint32_t ga   = (a1 + guard_off) & (kPkSlotBytes - 1);
-    // per-lane pointers to the lane's quad in the HBM score row / to its four bytes in the move row of the CURRENT row
-    uint8_t* const score_base = reinterpret_cast<uint8_t*>(scores) + lane8 + 2 * (1 + kRelShift); // the lane's quad in row 0
-    uint8_t* move_ptr  = moves + lane4 + (1 + kRelShift);
+    // per-lane pointers to the lane's quad in the HBM score row / to its four bytes in the move row of row 0: a row adds its
+    // scalar offset (a running pointer would be two more registers copied across the row loop's edge)
+    uint8_t* const score_base = reinterpret_cast<uint8_t*>(scores) + lane8 + 2 * (1 + kRelShift);
+    uint8_t* const move_base  = moves + lane4 + (1 + kRelShift);
 
     // row 0 into ring slot 0
     if (BW == 256 || band_lane) lds_store_u64(ring_base + a1, P01, P23);
@@ -275,7 +291,6 @@ __device__ __forceinline__ void banded_forward_moves(const GraphView<IdT>& g, Ro
     // the finished row (P01/P23) of row r: HBM score row, ring slot r & 7 with its guard quad, and its move bytes
     auto store_row = [&](auto bs0_tag, int32_t r, int32_t rel0_val, uint32_t mv4, bool scores_to_hbm) {
         constexpr bool BS0 = decltype(bs0_tag)::value;
-        move_ptr += stride;
         const uint32_t sbase = ring_base + (((uint32_t)r & (kPkSlots - 1)) * kPkSlotBytes);
         if (BS0 || __builtin_expect(scores_to_hbm, 0)) // (wave-uniform)
         {
@@ -292,7 +307,7 @@ __device__ __forceinline__ void banded_forward_moves(const GraphView<IdT>& g, Ro
         }
         else if (ab_guard)
             lds_store_guard(sbase + ga, SENT2, GUARD_HI_MIN);
-        if (st_moves && (BW == 256 || band_lane)) *reinterpret_cast<uint32_t*>(move_ptr) = mv4;
+        if (st_moves && (BW == 256 || band_lane)) *reinterpret_cast<uint32_t*>(move_base + (uint32_t)r * (uint32_t)stride) = mv4;
     };
     // four move bytes from two registers of 16-bit moves
     auto pack_moves = [&](uint32_t m01, uint32_t m23) -> uint32_t {
@@ -392,7 +407,6 @@ __device__ __forceinline__ void banded_forward_moves(const GraphView<IdT>& g, Ro
         scan_row(pk_make(s0, s1), pk_make(s2, s3), fe + gap_score);
         // stores (either flavour of left boundary)
         uint8_t* score_ptr = score_base + (uint32_t)r * (uint32_t)(stride * 2);
-        move_ptr += stride;
         const uint32_t sbase  = ring_base + (((uint32_t)r & (kPkSlots - 1)) * kPkSlotBytes);
         const uint32_t rel0pk = ((uint32_t)kPkSentinel & 0xffffu) | ((uint32_t)rel0_val << 16);
         if (BW == 256 || band_lane)
@@ -402,7 +416,7 @@ __device__ __forceinline__ void banded_forward_moves(const GraphView<IdT>& g, Ro
         }
         lds_store_guard(sbase + ga, SENT2, is_lane16 ? rel0pk : SENT2);
         if (bs == 0) gstore_u16_lane0_below(score_ptr, (uint32_t)rel0_val);
-        if (BW == 256 || band_lane) *reinterpret_cast<uint32_t*>(move_ptr) = 0u;
+        if (BW == 256 || band_lane) *reinterpret_cast<uint32_t*>(move_base + (uint32_t)r * (uint32_t)stride) = 0u;
         prev_rel0_io = rel0_val;
     };
 
@@ -425,7 +439,7 @@ __device__ __forceinline__ void banded_forward_moves(const GraphView<IdT>& g, Ro
             a1   = (a1 + 8) & (kPkSlotBytes - 1);
             ga   = (ga + 8) & (kPkSlotBytes - 1);
             rd4  = rd4n;
-            rd4n = lds_load_u32(read_base + (((d0 >> 3) & 0x1ffu) << 2) + lane4 + 4);
+            rd4n = lds_load_u32((d0 >> kRowOpReadShift) + lane4 + 4);
         }
         int32_t cu = min_score + 2 * gap_score, rel0_val = min_score;
         if constexpr (BS0)
@@ -451,210 +465,229 @@ __device__ __forceinline__ void banded_forward_moves(const GraphView<IdT>& g, Ro
         store_row(bs0_tag, r, rel0_val, mv4, scores_to_hbm);
     };
 
+    // ---------------- kinds 2, 3, 5, 6: predecessors from the LDS ring ----------------
+    // Everything a ring row needs beyond d0 / base4 comes ready-made from the block's operand registers (OPv) at the row's
+    // lane k: slot addresses, band start in bytes, packed move constants (poa_forward_row_operands.h). A body has no test of
+    // the predecessor count: NP = 1, 2, 3 predecessors in the operands, 4 = three there and predecessors 3..5 in the side table.
+    auto ring_row = [&](auto bs0_tag, auto np_tag, int32_t r, int32_t k, uint32_t d0, uint32_t base4, const RowOperands& OPv) {
+        constexpr bool BS0 = decltype(bs0_tag)::value;
+        constexpr int NP   = decltype(np_tag)::value;
+        auto fetch = [&](uint32_t v) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int32_t)v, k); };
+        const uint32_t b0 = fetch(OPv.slot0), bs2 = fetch(OPv.bs2), m0 = fetch(OPv.mv0), m1 = fetch(OPv.mv1);
+        const uint32_t b1 = NP >= 2 ? fetch(OPv.slot1) : 0u, m2 = NP >= 2 ? fetch(OPv.mv2) : 0u;
+        const uint32_t b2 = NP >= 3 ? fetch(OPv.slot2) : 0u, m3 = NP >= 3 ? fetch(OPv.mv3) : 0u;
+        const uint32_t rdb = (d0 >> kRowOpReadShift) + (uint32_t)lane4;
+        const bool scores_to_hbm = (d0 & kRowOpScoresToHbm) != 0;
+        a1 = (bs2 + (uint32_t)lane8) & (kPkSlotBytes - 1);
+        ga = (a1 + guard_off) & (kPkSlotBytes - 1);
+        const uint32_t a0     = (a1 - 4) & (kPkSlotBytes - 1); // dword whose high half is the cell of column c
+        const uint32_t sent16 = (uint32_t)kPkSentinel & 0xffffu;
+        // the predecessor's column-0 value (left boundary in band)
+        auto rel0_in = [&](uint32_t b) -> int32_t { return (int32_t)(int16_t)wave_first((int32_t)(lds_load_u32(b + kPkSlotBytes - 4) >> 16)); };
+        if constexpr (NP == 1)
+        {
+            // all loads first (one LDS round trip), then the arithmetic
+            const uint32_t x0 = lds_load_u32(b0 + a0);
+            const uint2 q0    = lds_load_u64(b0 + a1);
+            rd4  = lds_load_u32(rdb);
+            rd4n = lds_load_u32(rdb + 4);
+            int32_t cu = min_score + 2 * gap_score, rel0_val = min_score;
+            if constexpr (BS0)
+            {
+                rel0_val = max(min_score, rel0_in(b0)) + gap_score;
+                cu       = rel0_val + gap_score;
+            }
+            uint32_t c01, c23, D01, D23, V01, V23;
+            costs(base4, c01, c23);
+            from_pred(x0, q0.x, q0.y, c01, c23, D01, D23, V01, V23);
+            const bool outside = (q0.x & 0xffffu) == sent16; // chunk beyond the predecessor's band
+            const uint32_t s01 = pk_max(D01, V01), s23 = pk_max(D23, V23);
+            scan_row(outside ? MIN2 : s01, outside ? MIN2 : s23, cu);
+            // move = H == D ? 2 d + 1 : H == V ? 2 d : 1  ==  (2 d + 1) + [H != D] * (-1 + [H != V] * (1 - 2 d)): m0 = 2 d + 1, m1 = 1 - 2 d
+            const uint32_t m01 = pk_mad_u16_vvs(nz(P01, D01), pk_mad_u16_vsv(nz(P01, V01), m1, NEG1), m0);
+            const uint32_t m23 = pk_mad_u16_vvs(nz(P23, D23), pk_mad_u16_vsv(nz(P23, V23), m1, NEG1), m0);
+            const uint32_t mv4 = outside ? 0u : pack_moves(m01, m23);
+            store_row(bs0_tag, r, rel0_val, mv4, scores_to_hbm);
+        }
+        else
+        {
+            const uint32_t x0 = lds_load_u32(b0 + a0);
+            const uint2 q0    = lds_load_u64(b0 + a1);
+            const uint32_t x1 = lds_load_u32(b1 + a0);
+            const uint2 q1    = lds_load_u64(b1 + a1);
+            uint32_t x2 = 0;
+            uint2 q2 = make_uint2(0, 0);
+            if constexpr (NP > 2)
+            {
+                x2 = lds_load_u32(b2 + a0);
+                q2 = lds_load_u64(b2 + a1);
+            }
+            rd4  = lds_load_u32(rdb);
+            rd4n = lds_load_u32(rdb + 4);
+            int32_t fe = min_score + gap_score;
+            if constexpr (BS0) // left boundary in band: carry-in from the predecessors' column-0 values (:293-326)
+            {
+                int32_t pen = max(min_score, rel0_in(b0));
+                pen = max(pen, rel0_in(b1));
+                if constexpr (NP > 2) pen = max(pen, rel0_in(b2));
+                fe = pen + gap_score;
+            }
+            uint32_t c01, c23;
+            costs(base4, c01, c23);
+            // best diagonal / vertical candidate over the predecessors and the move of the first slot that attains it
+            uint32_t D0a, D0b, V0a, V0b, D1a, D1b, V1a, V1b;
+            from_pred(x0, q0.x, q0.y, c01, c23, D0a, D0b, V0a, V0b);
+            from_pred(x1, q1.x, q1.y, c01, c23, D1a, D1b, V1a, V1b);
+            const bool out0 = (q0.x & 0xffffu) == sent16, out1 = (q1.x & 0xffffu) == sent16;
+            bool undecided  = out0 | out1;
+            D0a = out0 ? MIN2 : D0a; D0b = out0 ? MIN2 : D0b; V0a = out0 ? MIN2 : V0a; V0b = out0 ? MIN2 : V0b;
+            D1a = out1 ? MIN2 : D1a; D1b = out1 ? MIN2 : D1b; V1a = out1 ? MIN2 : V1a; V1b = out1 ? MIN2 : V1b;
+            uint32_t bD01 = pk_max(D0a, D1a), bD23 = pk_max(D0b, D1b), bV01 = pk_max(V0a, V1a), bV23 = pk_max(V0b, V1b);
+            // diagonal move through slot k = 2 d_k + 1, vertical = 2 d_k: first attaining slot
+            //   A = mD0 + n0 * (E1 + n1 * E2),  E1 = 2 (d1 - d0), E2 = 2 (d2 - d1),  n_k = [slot k misses the maximum]
+            // (m0 = mD0, m1 = mV0, m2 = E1, m3 = E2)
+            const uint32_t E1v = pin_vgpr(m2);
+            uint32_t A01, A23, B01, B23;
+            if constexpr (NP > 2)
+            {
+                uint32_t D2a, D2b, V2a, V2b;
+                from_pred(x2, q2.x, q2.y, c01, c23, D2a, D2b, V2a, V2b);
+                const bool out2 = (q2.x & 0xffffu) == sent16;
+                undecided       = undecided | out2;
+                D2a = out2 ? MIN2 : D2a; D2b = out2 ? MIN2 : D2b; V2a = out2 ? MIN2 : V2a; V2b = out2 ? MIN2 : V2b;
+                bD01 = pk_max(bD01, D2a); bD23 = pk_max(bD23, D2b); bV01 = pk_max(bV01, V2a); bV23 = pk_max(bV23, V2b);
+                const uint32_t E2 = pin_vgpr(m3);
+                A01 = pk_mad_u16_vvs(nz(bD01, D0a), pk_mad_u16(nz(bD01, D1a), E2, E1v), m0);
+                A23 = pk_mad_u16_vvs(nz(bD23, D0b), pk_mad_u16(nz(bD23, D1b), E2, E1v), m0);
+                B01 = pk_mad_u16_vvs(nz(bV01, V0a), pk_mad_u16(nz(bV01, V1a), E2, E1v), m1);
+                B23 = pk_mad_u16_vvs(nz(bV23, V0b), pk_mad_u16(nz(bV23, V1b), E2, E1v), m1);
+            }
+            else
+            {
+                A01 = pk_mad_u16_vvs(nz(bD01, D0a), E1v, m0); A23 = pk_mad_u16_vvs(nz(bD23, D0b), E1v, m0);
+                B01 = pk_mad_u16_vvs(nz(bV01, V0a), E1v, m1); B23 = pk_mad_u16_vvs(nz(bV23, V0b), E1v, m1);
+            }
+            if constexpr (NP > 3)
+            {
+                // predecessors 3..5 (rows from the side table, cells from the ring): they raise the maxima; where only
+                // they attain a maximum the first attaining slot is >= 3, whose distance the pass does not track -> move 0
+                const uint64_t xe     = wave_first64(xpred[r & 255]);
+                const int32_t cnt_all = (int32_t)((xe >> 13) & 63u);
+                uint32_t xD01 = MIN2, xD23 = MIN2, xV01 = MIN2, xV23 = MIN2;
+                int32_t pen_x = min_score;
+                for (int32_t kk = 3; kk < cnt_all; kk++)
+                {
+                    const uint32_t bk = ring_base + (((uint32_t)xpred_row(xe, kk) & 7u) * kPkSlotBytes);
+                    const uint32_t xk = lds_load_u32(bk + a0);
+                    const uint2 qk    = lds_load_u64(bk + a1);
+                    uint32_t Da, Db, Va, Vb;
+                    from_pred(xk, qk.x, qk.y, c01, c23, Da, Db, Va, Vb);
+                    const bool outk = (qk.x & 0xffffu) == sent16;
+                    undecided       = undecided | outk;
+                    xD01 = pk_max(xD01, outk ? MIN2 : Da); xD23 = pk_max(xD23, outk ? MIN2 : Db);
+                    xV01 = pk_max(xV01, outk ? MIN2 : Va); xV23 = pk_max(xV23, outk ? MIN2 : Vb);
+                    if constexpr (BS0) pen_x = max(pen_x, rel0_in(bk));
+                }
+                if constexpr (BS0) fe = max(fe - gap_score, pen_x) + gap_score;
+                const uint32_t fD01 = pk_max(bD01, xD01), fD23 = pk_max(bD23, xD23), fV01 = pk_max(bV01, xV01), fV23 = pk_max(bV23, xV23);
+                // A *= [max of the first three == overall max]
+                A01 = pk_mad_u16(nz(bD01, fD01), pk_sub(0u, A01), A01); A23 = pk_mad_u16(nz(bD23, fD23), pk_sub(0u, A23), A23);
+                B01 = pk_mad_u16(nz(bV01, fV01), pk_sub(0u, B01), B01); B23 = pk_mad_u16(nz(bV23, fV23), pk_sub(0u, B23), B23);
+                bD01 = fD01; bD23 = fD23; bV01 = fV01; bV23 = fV23;
+            }
+            const int32_t rel0_val = BS0 ? fe : min_score;
+            scan_row(pk_max(bD01, bV01), pk_max(bD23, bV23), fe + gap_score);
+            // move = H == bestD ? A : H == bestV ? B : 1
+            auto move_of = [&](uint32_t H, uint32_t bD, uint32_t bV, uint32_t A, uint32_t B) -> uint32_t {
+                const uint32_t t1 = pk_mad_u16(nz(H, bV), pk_sub(ONE2, B), B);
+                return pk_mad_u16(nz(H, bD), pk_sub(t1, A), A);
+            };
+            const uint32_t m01 = move_of(P01, bD01, bV01, A01, B01);
+            const uint32_t m23 = move_of(P23, bD23, bV23, A23, B23);
+            const uint32_t mv4 = undecided ? 0u : pack_moves(m01, m23);
+            store_row(bs0_tag, r, rel0_val, mv4, scores_to_hbm);
+        }
+    };
+
     // ---------------- the rows of one phase ----------------
+    // Blocks of 63 rows: lane 63's descriptor is always "end of block", so the fetch of the next row's descriptor needs
+    // neither a wrap of the lane index nor a select at the block's end.
+    constexpr int32_t kBlockRows = kWave - 1;
     auto run_rows = [&](auto bs0_tag, int32_t r_from, int32_t r_to) {
         constexpr bool BS0 = decltype(bs0_tag)::value;
+        const uint64_t kone = !kfine ? 1ull : (BS0 ? 1ull << 32 : 1ull << 48); // what a counted row adds
         int32_t r = r_from;
         while (r <= r_to)
         {
-            // descriptors of rows r .. r + 63, one per lane
-            const int32_t r0   = r;
-            uint32_t D0v, D1v;
-            {
-                const int32_t rr    = min(r0 + lane, graph_count);
-                const uint64_t w    = rowinfo[rr].w;
-                const uint32_t kind = (uint32_t)(w >> kKindShift) & 7u;
-                const uint32_t cnt  = (uint32_t)(w >> 8) & 0x3fu;
-                const uint32_t bs4  = (uint32_t)(w >> 15) & 0x1ffu;
-                const uint32_t p0 = (uint32_t)(w >> 24) & 0xfffu, p1 = (uint32_t)(w >> 36) & 0xfffu, p2 = (uint32_t)(w >> 48) & 0xfffu;
-                const uint32_t slots = (p0 & 7u) | ((p1 & 7u) << 3) | ((p2 & 7u) << 6);
-                const uint32_t dists = (((uint32_t)rr - p0) & 7u) | ((((uint32_t)rr - p1) & 7u) << 3) | ((((uint32_t)rr - p2) & 7u) << 6);
-                D0v = kind | (bs4 << 3) | (slots << 12) | (dists << 21) | ((cnt <= 3 ? cnt : 0u) << 30);
-                D1v = ((uint32_t)w & 0xffu) * 0x01010101u;
-            }
-            // rows past the end of the phase read as kind 7 = "end of block"
-            D0v = (r0 + lane <= r_to) ? D0v : 7u;
-            // bit j: row r0 + j writes its score row to HBM (mark_score_rows)
-            const uint64_t need64 = BS0 ? ~0ull : __ballot((rowinfo[min(r0 + lane, graph_count)].w & kRowScoresInHbm) != 0);
-            int32_t k      = 0;
-            uint32_t d0    = (uint32_t)__builtin_amdgcn_readlane((int32_t)D0v, 0);
-            uint32_t base4 = (uint32_t)__builtin_amdgcn_readlane((int32_t)D1v, 0);
-            uint32_t kind  = d0 & 7u;
-            auto advance = [&]() {
-                r++;
-                k++;
-                const uint32_t nd = (uint32_t)__builtin_amdgcn_readlane((int32_t)D0v, k & (kWave - 1));
-                base4 = (uint32_t)__builtin_amdgcn_readlane((int32_t)D1v, k & (kWave - 1));
-                d0    = k == kWave ? 7u : nd; // a select, not a branch
-                kind  = d0 & 7u;
+            // operands of rows r .. r + 62, one row per lane; lanes past the end of the phase (and lane 63) read as kind 7
+            const int32_t rr     = min(r + lane, graph_count);
+            const RowOperands OPv = pack_row_operands(rowinfo[rr].w, (uint32_t)rr, lane < kBlockRows && r + lane <= r_to, ring_base, read_base);
+            // Only the lane index k is carried from row to row (the row is r0 + k): a body that is not part of a streak leaves the
+            // fetch of the next row's descriptor to the top of the dispatch, so nothing but k crosses the loop's edge in scalar
+            // registers.
+            const int32_t r0 = r;
+            int32_t k        = 0;
+            uint32_t d0, base4;
+            auto fetch = [&]() {
+                d0    = (uint32_t)__builtin_amdgcn_readlane((int32_t)OPv.d0, k); // (k <= 63: lane 63 ends the block)
+                base4 = (uint32_t)__builtin_amdgcn_readlane((int32_t)OPv.base4, k);
             };
+            // one row of a kind other than 0, with its timer / counter (debug instantiation), then straight to the next dispatch
+            auto timed = [&](auto dk_tag, bool selected, auto&& body) {
+                const uint64_t t = selected ? clock64() : 0;
+                body();
+                if (selected) kacc += kcount ? kone : clock64() - t;
+                k++;
+                asm volatile("; end of a row of kind %0" ::"n"(decltype(dk_tag)::value)); // (distinct per body: the tails stay apart)
+            };
+            // one dispatch per row, the kinds in the order of their frequency; every body ends in its own stores
             for (;;)
             {
-                // streak of rows whose predecessor is the previous row and whose band did not move
-                const uint64_t t_k0 = ksel == 0 ? clock64() : 0;
-                const int32_t r_k0  = r;
-                while (kind == 0)
+                fetch();
+                // streak of rows whose predecessor is the previous row and whose band did not move (the next descriptor is
+                // fetched behind the row's stores)
+                const uint64_t t_k0 = ksel_prev ? clock64() : 0;
+                const int32_t k_k0  = k;
+                while ((d0 & 7u) == kDkPrev)
                 {
-                    reg_row(bs0_tag, std::false_type{}, r, d0, base4, ((need64 >> k) & 1ull) != 0);
-                    advance();
+                    reg_row(bs0_tag, std::false_type{}, r0 + k, d0, base4, (d0 & kRowOpScoresToHbm) != 0);
+                    k++;
+                    fetch();
                 }
-                if (ksel == 0) kacc += kcount ? (uint64_t)(r - r_k0) : clock64() - t_k0;
-                if (kind == 7u) break;
-                const int32_t kind_now = (int32_t)min(kind, 4u);
-                const uint64_t t_kx    = ksel == kind_now ? clock64() : 0;
-                const bool scores_to_hbm = ((need64 >> k) & 1ull) != 0;
-                if (kind == 1)
-                    reg_row(bs0_tag, std::true_type{}, r, d0, base4, scores_to_hbm);
-                else if (kind <= 3)
+                if (ksel_prev) kacc += kcount ? (uint64_t)(k - k_k0) * kone : clock64() - t_k0;
+                if (d0 & kRowOpIsRingTwo)
                 {
-                    // ===== predecessors from the LDS ring =====
-                    const uint32_t bs = ((d0 >> 3) & 0x1ffu) << 2;
-                    a1 = (2u * bs + (uint32_t)lane8) & (kPkSlotBytes - 1);
-                    ga = (a1 + guard_off) & (kPkSlotBytes - 1);
-                    const uint32_t a0 = (a1 - 4) & (kPkSlotBytes - 1); // dword whose high half is the cell of column c
-                    const uint32_t b0 = ring_base + (((d0 >> 12) & 7u) * kPkSlotBytes);
-                    const uint32_t sent16 = (uint32_t)kPkSentinel & 0xffffu;
-                    const uint32_t dd0 = (d0 >> 21) & 7u;
-                    if (kind == 2)
-                    {
-                        // all loads first (one LDS round trip), then the arithmetic
-                        const uint32_t x0 = lds_load_u32(b0 + a0);
-                        const uint2 q0    = lds_load_u64(b0 + a1);
-                        rd4  = lds_load_u32(read_base + bs + lane4);
-                        rd4n = lds_load_u32(read_base + bs + lane4 + 4);
-                        int32_t cu = min_score + 2 * gap_score, rel0_val = min_score;
-                        if constexpr (BS0)
-                        {
-                            rel0_val = max(min_score, (int32_t)(int16_t)wave_first((int32_t)(lds_load_u32(b0 + kPkSlotBytes - 4) >> 16))) + gap_score;
-                            cu       = rel0_val + gap_score;
-                        }
-                        uint32_t c01, c23, D01, D23, V01, V23;
-                        costs(base4, c01, c23);
-                        from_pred(x0, q0.x, q0.y, c01, c23, D01, D23, V01, V23);
-                        const bool outside = (q0.x & 0xffffu) == sent16; // chunk beyond the predecessor's band
-                        const uint32_t s01 = pk_max(D01, V01), s23 = pk_max(D23, V23);
-                        scan_row(outside ? MIN2 : s01, outside ? MIN2 : s23, cu);
-                        // move = H == D ? 2 d + 1 : H == V ? 2 d : 1  ==  (2 d + 1) + [H != D] * (-1 + [H != V] * (1 - 2 d))
-                        const uint32_t cD = pk_dup((int32_t)(2u * dd0 + 1u)), cV = pk_dup(1 - (int32_t)(2u * dd0));
-                        const uint32_t m01 = pk_mad_u16_vvs(nz(P01, D01), pk_mad_u16_vsv(nz(P01, V01), cV, NEG1), cD);
-                        const uint32_t m23 = pk_mad_u16_vvs(nz(P23, D23), pk_mad_u16_vsv(nz(P23, V23), cV, NEG1), cD);
-                        const uint32_t mv4 = outside ? 0u : pack_moves(m01, m23);
-                        store_row(bs0_tag, r, rel0_val, mv4, scores_to_hbm);
-                    }
-                    else
-                    {
-                        const uint32_t cnt3    = d0 >> 30;              // 2, 3, or 0 = more than three
-                        const int32_t cnt      = cnt3 == 2 ? 2 : 3;     // predecessors in the descriptor
-                        const uint32_t b1 = ring_base + (((d0 >> 15) & 7u) * kPkSlotBytes);
-                        const uint32_t b2 = cnt > 2 ? ring_base + (((d0 >> 18) & 7u) * kPkSlotBytes) : b0;
-                        const uint32_t dd1 = (d0 >> 24) & 7u, dd2 = (d0 >> 27) & 7u;
-                        const uint32_t x0 = lds_load_u32(b0 + a0);
-                        const uint2 q0    = lds_load_u64(b0 + a1);
-                        const uint32_t x1 = lds_load_u32(b1 + a0);
-                        const uint2 q1    = lds_load_u64(b1 + a1);
-                        uint32_t x2 = 0;
-                        uint2 q2 = make_uint2(0, 0);
-                        if (cnt > 2)
-                        {
-                            x2 = lds_load_u32(b2 + a0);
-                            q2 = lds_load_u64(b2 + a1);
-                        }
-                        rd4  = lds_load_u32(read_base + bs + lane4);
-                        rd4n = lds_load_u32(read_base + bs + lane4 + 4);
-                        int32_t fe = min_score + gap_score;
-                        if constexpr (BS0) // left boundary in band: carry-in from the predecessors' column-0 values (:293-326)
-                        {
-                            int32_t pen = max(min_score, (int32_t)(int16_t)wave_first((int32_t)(lds_load_u32(b0 + kPkSlotBytes - 4) >> 16)));
-                            pen = max(pen, (int32_t)(int16_t)wave_first((int32_t)(lds_load_u32(b1 + kPkSlotBytes - 4) >> 16)));
-                            if (cnt > 2) pen = max(pen, (int32_t)(int16_t)wave_first((int32_t)(lds_load_u32(b2 + kPkSlotBytes - 4) >> 16)));
-                            fe = pen + gap_score;
-                        }
-                        uint32_t c01, c23;
-                        costs(base4, c01, c23);
-                        // best diagonal / vertical candidate over the predecessors and the move of the first slot that attains it
-                        uint32_t D0a, D0b, V0a, V0b, D1a, D1b, V1a, V1b;
-                        from_pred(x0, q0.x, q0.y, c01, c23, D0a, D0b, V0a, V0b);
-                        from_pred(x1, q1.x, q1.y, c01, c23, D1a, D1b, V1a, V1b);
-                        const bool out0 = (q0.x & 0xffffu) == sent16, out1 = (q1.x & 0xffffu) == sent16;
-                        bool undecided  = out0 | out1;
-                        D0a = out0 ? MIN2 : D0a; D0b = out0 ? MIN2 : D0b; V0a = out0 ? MIN2 : V0a; V0b = out0 ? MIN2 : V0b;
-                        D1a = out1 ? MIN2 : D1a; D1b = out1 ? MIN2 : D1b; V1a = out1 ? MIN2 : V1a; V1b = out1 ? MIN2 : V1b;
-                        uint32_t bD01 = pk_max(D0a, D1a), bD23 = pk_max(D0b, D1b), bV01 = pk_max(V0a, V1a), bV23 = pk_max(V0b, V1b);
-                        // diagonal move through slot k = 2 d_k + 1, vertical = 2 d_k: first attaining slot
-                        //   A = mD0 + n0 * (E1 + n1 * E2),  E1 = 2 (d1 - d0), E2 = 2 (d2 - d1),  n_k = [slot k misses the maximum]
-                        const uint32_t mD0 = pk_dup((int32_t)(2u * dd0 + 1u)), mV0 = pk_dup((int32_t)(2u * dd0));
-                        const uint32_t E1  = pk_dup(2 * ((int32_t)dd1 - (int32_t)dd0));
-                        uint32_t A01, A23, B01, B23;
-                        if (cnt > 2)
-                        {
-                            uint32_t D2a, D2b, V2a, V2b;
-                            from_pred(x2, q2.x, q2.y, c01, c23, D2a, D2b, V2a, V2b);
-                            const bool out2 = (q2.x & 0xffffu) == sent16;
-                            undecided       = undecided | out2;
-                            D2a = out2 ? MIN2 : D2a; D2b = out2 ? MIN2 : D2b; V2a = out2 ? MIN2 : V2a; V2b = out2 ? MIN2 : V2b;
-                            bD01 = pk_max(bD01, D2a); bD23 = pk_max(bD23, D2b); bV01 = pk_max(bV01, V2a); bV23 = pk_max(bV23, V2b);
-                            const uint32_t E2  = pin_vgpr(pk_dup(2 * ((int32_t)dd2 - (int32_t)dd1)));
-                            const uint32_t E1v = pin_vgpr(E1);
-                            A01 = pk_mad_u16_vvs(nz(bD01, D0a), pk_mad_u16(nz(bD01, D1a), E2, E1v), mD0);
-                            A23 = pk_mad_u16_vvs(nz(bD23, D0b), pk_mad_u16(nz(bD23, D1b), E2, E1v), mD0);
-                            B01 = pk_mad_u16_vvs(nz(bV01, V0a), pk_mad_u16(nz(bV01, V1a), E2, E1v), mV0);
-                            B23 = pk_mad_u16_vvs(nz(bV23, V0b), pk_mad_u16(nz(bV23, V1b), E2, E1v), mV0);
-                        }
-                        else
-                        {
-                            const uint32_t E1v = pin_vgpr(E1);
-                            A01 = pk_mad_u16_vvs(nz(bD01, D0a), E1v, mD0); A23 = pk_mad_u16_vvs(nz(bD23, D0b), E1v, mD0);
-                            B01 = pk_mad_u16_vvs(nz(bV01, V0a), E1v, mV0); B23 = pk_mad_u16_vvs(nz(bV23, V0b), E1v, mV0);
-                        }
-                        if (cnt3 == 0)
-                        {
-                            // predecessors 3..5 (rows from the side table, cells from the ring): they raise the maxima; where only
-                            // they attain a maximum the first attaining slot is >= 3, whose distance the pass does not track -> move 0
-                            const uint64_t xe     = wave_first64(xpred[r & 255]);
-                            const int32_t cnt_all = (int32_t)((xe >> 13) & 63u);
-                            uint32_t xD01 = MIN2, xD23 = MIN2, xV01 = MIN2, xV23 = MIN2;
-                            int32_t pen_x = min_score;
-                            for (int32_t kk = 3; kk < cnt_all; kk++)
-                            {
-                                const uint32_t bk = ring_base + (((uint32_t)xpred_row(xe, kk) & 7u) * kPkSlotBytes);
-                                const uint32_t xk = lds_load_u32(bk + a0);
-                                const uint2 qk    = lds_load_u64(bk + a1);
-                                uint32_t Da, Db, Va, Vb;
-                                from_pred(xk, qk.x, qk.y, c01, c23, Da, Db, Va, Vb);
-                                const bool outk = (qk.x & 0xffffu) == sent16;
-                                undecided       = undecided | outk;
-                                xD01 = pk_max(xD01, outk ? MIN2 : Da); xD23 = pk_max(xD23, outk ? MIN2 : Db);
-                                xV01 = pk_max(xV01, outk ? MIN2 : Va); xV23 = pk_max(xV23, outk ? MIN2 : Vb);
-                                if constexpr (BS0) pen_x = max(pen_x, (int32_t)(int16_t)wave_first((int32_t)(lds_load_u32(bk + kPkSlotBytes - 4) >> 16)));
-                            }
-                            if constexpr (BS0) fe = max(fe - gap_score, pen_x) + gap_score;
-                            const uint32_t fD01 = pk_max(bD01, xD01), fD23 = pk_max(bD23, xD23), fV01 = pk_max(bV01, xV01), fV23 = pk_max(bV23, xV23);
-                            // A *= [max of the first three == overall max]
-                            A01 = pk_mad_u16(nz(bD01, fD01), pk_sub(0u, A01), A01); A23 = pk_mad_u16(nz(bD23, fD23), pk_sub(0u, A23), A23);
-                            B01 = pk_mad_u16(nz(bV01, fV01), pk_sub(0u, B01), B01); B23 = pk_mad_u16(nz(bV23, fV23), pk_sub(0u, B23), B23);
-                            bD01 = fD01; bD23 = fD23; bV01 = fV01; bV23 = fV23;
-                        }
-                        const int32_t rel0_val = BS0 ? fe : min_score;
-                        scan_row(pk_max(bD01, bV01), pk_max(bD23, bV23), fe + gap_score);
-                        // move = H == bestD ? A : H == bestV ? B : 1
-                        auto move_of = [&](uint32_t H, uint32_t bD, uint32_t bV, uint32_t A, uint32_t B) -> uint32_t {
-                            const uint32_t t1 = pk_mad_u16(nz(H, bV), pk_sub(ONE2, B), B);
-                            return pk_mad_u16(nz(H, bD), pk_sub(t1, A), A);
-                        };
-                        const uint32_t m01 = move_of(P01, bD01, bV01, A01, B01);
-                        const uint32_t m23 = move_of(P23, bD23, bV23, A23, B23);
-                        const uint32_t mv4 = undecided ? 0u : pack_moves(m01, m23);
-                        store_row(bs0_tag, r, rel0_val, mv4, scores_to_hbm);
-                    }
+                    timed(std::integral_constant<uint32_t, kDkRingTwo>{}, ksel_two, [&]() { ring_row(bs0_tag, std::integral_constant<int, 2>{}, r0 + k, k, d0, base4, OPv); });
+                    continue;
                 }
-                else
+                if (d0 & kRowOpIsRingOne)
                 {
-                    general_row(r, prev_rel0);
+                    timed(std::integral_constant<uint32_t, kDkRingOne>{}, ksel_one, [&]() { ring_row(bs0_tag, std::integral_constant<int, 1>{}, r0 + k, k, d0, base4, OPv); });
+                    continue;
+                }
+                if (d0 & kRowOpIsPrevMoved)
+                {
+                    timed(std::integral_constant<uint32_t, kDkPrevMoved>{}, ksel_moved, [&]() { reg_row(bs0_tag, std::true_type{}, r0 + k, d0, base4, (d0 & kRowOpScoresToHbm) != 0); });
+                    continue;
+                }
+                if (d0 & kRowOpIsEnd) break;
+                const uint32_t kind = d0 & 7u;
+                if (kind == kDkRingThree)
+                {
+                    timed(std::integral_constant<uint32_t, kDkRingThree>{}, ksel_three, [&]() { ring_row(bs0_tag, std::integral_constant<int, 3>{}, r0 + k, k, d0, base4, OPv); });
+                    continue;
+                }
+                if (kind == kDkRingMany)
+                {
+                    timed(std::integral_constant<uint32_t, kDkRingMany>{}, ksel_many, [&]() { ring_row(bs0_tag, std::integral_constant<int, 4>{}, r0 + k, k, d0, base4, OPv); });
+                    continue;
+                }
+                timed(std::integral_constant<uint32_t, kDkGeneral>{}, ksel_general, [&]() {
+                    general_row(r0 + k, prev_rel0);
                     if constexpr (!BS0) prev_rel0 = min_score;
-                }
-                if (ksel == kind_now) kacc += kcount ? 1 : clock64() - t_kx;
-                advance();
+                });
             }
+            r = r0 + k;
         }
     };
 

@@ -63,6 +63,11 @@ __global__ __launch_bounds__(kWave) void rows_kernel(MbArgs a)
             else if (m >= 10 && m <= 14) { cnt = r >= 2 ? 2 : 1; p1 = r - 2; }
             else if (m == 15) { cnt = r >= 3 ? 3 : 1; p1 = r - 2; p2 = r - 3; }
             break;
+        case 6: cnt = r >= 3 ? 3 : 1; p1 = r - 2; p2 = r - 3; break;        // three predecessors from the ring
+        case 7:                                                             // four: the fourth (row r - 4) in the side table
+            cnt = r >= 4 ? 4 : 1; p1 = r - 2; p2 = r - 3;
+            if (r >= 4) xpred[r & 255] = (uint64_t)r | (1ull << 12) | (4ull << 13) | ((uint64_t)(r - 4) << 20);
+            break;
         default: break;                                                     // 0, 3, 4: the previous row
         }
         RowInfo<true> ri;
@@ -98,9 +103,13 @@ int main(int argc, char** argv)
     }
     hipMemset(a.slabs, 0, a.per_block * blocks);
     hipFuncSetAttribute(reinterpret_cast<const void*>(&rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
+    // (the names of patterns 0..5 are those of the earlier profiles; "kind 3" is the table kind: descriptor kinds 3 / 5 / 6 by
+    // predecessor count, poa_forward_row_operands.h)
     const char* pattern_name[] = {"kind 0 (previous row, band fixed)", "kind 3 (rows r-1 and r-2 from the ring)", "kind 2 (row r-2 from the ring)",
                                   "kind 1 (previous row, band moves every row)", "kinds 0+1 (band moves every 5th row)",
-                                  "mix 7/16 kinds 0-1, 3/16 kind 2, 6/16 kind 3"};
+                                  "mix 7/16 kinds 0-1, 3/16 kind 2, 6/16 kind 3",
+                                  "kind 3, three predecessors (rows r-1, r-2, r-3 from the ring)",
+                                  "kind 3, four predecessors (rows r-1 .. r-4 from the ring, 255-row passes)"};
     struct Abl { const char* name; int bits; };
     const Abl abl[] = {{"full row", 0},
                        {"no score-row store", 1 << 26},
@@ -120,9 +129,11 @@ int main(int argc, char** argv)
     hipEventCreate(&e1);
     printf("{\"blocks\": %d, \"rows_per_pass\": %d, \"passes\": %d, \"results\": [\n", blocks, a.graph_count, reps);
     bool first = true;
-    for (int p = 0; p < 6; p++)
+    for (int p = 0; p < 8; p++)
         for (const Abl& ab : abl)
         {
+            // the side table of predecessors 3..5 has one entry per row & 255: a pass of the four-predecessor pattern is 255 rows
+            a.graph_count = p == 7 ? 255 : 1400;
             if (p != 0 && p != 5 && ab.bits != 0 && ab.bits != ((1 << 26) | (1 << 27)) && ab.bits != (1 << 16)) continue; // full ablation table for kind 0 and the mix
             a.pattern = p;
             a.dbg     = ab.bits ? (ab.bits | (1 << 14)) : 0; // (bit 14 enables the ablation bits, poa_forward_moves.h)
