@@ -269,13 +269,23 @@ __global__ __launch_bounds__(kWave * NW) void poa_window_kernel(KernelArgs a)
         const uint8_t* lds_read = lds_read_buf;
         if constexpr (LDS_READ)
         {
+            // 16 bytes per lane: the whole span is at most two wave-wide requests of 1 KB (the array may be mapped host memory,
+            // gwhip_poa_reads_host_sequences). A read starts on a 4-byte boundary only. (Issued ahead of the row table's
+            // loads, to hide the link's latency behind its HBM round trips, they hold 8 VGPRs across that routine: the
+            // comparison of the two orders is in DESIGN.md section 3.1 "Inputs".)
+            typedef uint32_t StageVec __attribute__((ext_vector_type(4)));
+            typedef StageVec StageVecA4 __attribute__((aligned(4)));
+            static_assert(kReadLds % 16 == 0 && (kRingBytes + kRowInfoBytes) % 16 == 0, "16-byte fetches fill the LDS copy of the read");
             // adaptive bands may widen to 1536 columns: the staged span covers max(read, band) + read-ahead
             const int32_t stage_bytes = min(kReadLds, ((max(seq_len, kMaxAdaptiveBand) + 8) + 3) & ~3);
-            for (int32_t i = lane * 4; i < stage_bytes; i += kWave * 4)
-                *reinterpret_cast<uint32_t*>(lds_read_buf + i) = *reinterpret_cast<const uint32_t*>(sequence + i);
+            for (int32_t i = lane * 16; i < stage_bytes; i += kWave * 16)
+                *reinterpret_cast<StageVec*>(lds_read_buf + i) = *reinterpret_cast<const StageVecA4*>(sequence + i);
         }
         wave_sync();
         pc.tick(kPhRowInfo);
+        // the score-matrix routine's own `read` (its lane-0 fallback walk; the sliding window of graphs beyond the LDS tables): the
+        // LDS copy where the whole read is staged, so that the array is touched by the backbone and the staging fetches alone
+        const uint8_t* banded_read = LDS_READ ? lds_read : sequence;
 
         int32_t alen = 0;
         // traceback-buffer modes with int16 scores, an int16 trace region and the tables in LDS: the packed pass first
@@ -329,12 +339,12 @@ __global__ __launch_bounds__(kWave * NW) void poa_window_kernel(KernelArgs a)
         }
         else if (BM == GWHIP_ADAPTIVE_BAND && c.alignment_band_width < kMaxAdaptiveBand)
         {
-            alen = nw_banded<ScoreT, IdT, RowT, true, LDS_READ, PV>(g, rowinfo, node_count, sequence, lds_read, seq_len, scores, ring, ring_bytes,
+            alen = nw_banded<ScoreT, IdT, RowT, true, LDS_READ, PV>(g, rowinfo, node_count, banded_read, lds_read, seq_len, scores, ring, ring_bytes,
                                                 banded_buffer_size, alignment_graph, alignment_read, c.alignment_band_width,
                                                 c.gap_score, c.mismatch_score, c.match_score, 0, cells, pc, debug_flags, codes, lds_code_tile, lds_read_window, lds_bs_ring,
                                                 mw_args, mw_shared);
             if (alen == kShiftLeft || alen == kShiftRight)
-                alen = nw_banded<ScoreT, IdT, RowT, true, LDS_READ, PV>(g, rowinfo, node_count, sequence, lds_read, seq_len, scores, ring, ring_bytes,
+                alen = nw_banded<ScoreT, IdT, RowT, true, LDS_READ, PV>(g, rowinfo, node_count, banded_read, lds_read, seq_len, scores, ring, ring_bytes,
                                                     banded_buffer_size, alignment_graph, alignment_read,
                                                     c.alignment_band_width, c.gap_score, c.mismatch_score, c.match_score,
                                                     alen, cells, pc, debug_flags, codes, lds_code_tile, lds_read_window, lds_bs_ring,
@@ -342,7 +352,7 @@ __global__ __launch_bounds__(kWave * NW) void poa_window_kernel(KernelArgs a)
         }
         else if (BM == GWHIP_STATIC_BAND || BM == GWHIP_ADAPTIVE_BAND)
         {
-            alen = nw_banded<ScoreT, IdT, RowT, false, LDS_READ, PV>(g, rowinfo, node_count, sequence, lds_read, seq_len, scores, ring, ring_bytes,
+            alen = nw_banded<ScoreT, IdT, RowT, false, LDS_READ, PV>(g, rowinfo, node_count, banded_read, lds_read, seq_len, scores, ring, ring_bytes,
                                                  banded_buffer_size, alignment_graph, alignment_read, c.alignment_band_width,
                                                  c.gap_score, c.mismatch_score, c.match_score, 0, cells, pc, debug_flags, codes, lds_code_tile, lds_read_window, lds_bs_ring);
         }
@@ -398,11 +408,15 @@ __global__ __launch_bounds__(kWave * NW) void poa_window_kernel(KernelArgs a)
                 status_and_count = -1;
             }
         }
+        // The merge takes the read's bases from the LDS copy where the whole read is there and nothing has reused its region yet
+        // (the topsort below does): the array itself may be host memory then. The traceback-buffer modes keep the array, which
+        // their fallback alignment routine reads as well.
+        const uint8_t* merge_read = (LDS_READ && !TB) ? lds_read : sequence;
         if constexpr (LDS_TABLES)
         {
             int32_t new_count = 0;
             par_rc = add_alignment_parallel<IdT, MSA>(new_count, g, node_count, alen, alignment_graph, alignment_read,
-                                                      sequence, base_weights, seq_len, MSA ? g.seq_begin + s : nullptr,
+                                                      merge_read, base_weights, seq_len, MSA ? g.seq_begin + s : nullptr,
                                                       (uint16_t)s, (uint32_t)c.max_sequences_per_poa,
                                                       c.max_nodes_per_graph, reinterpret_cast<int16_t*>(smem),
                                                       reinterpret_cast<int16_t*>(smem) + 2048,
@@ -422,7 +436,7 @@ __global__ __launch_bounds__(kWave * NW) void poa_window_kernel(KernelArgs a)
         if (lane == 0 && par_rc < 0)
         {
             int32_t new_count = 0;
-            uint8_t e = add_alignment_to_graph<IdT, MSA>(new_count, g, node_count, alen, alignment_graph, sequence,
+            uint8_t e = add_alignment_to_graph<IdT, MSA>(new_count, g, node_count, alen, alignment_graph, merge_read,
                                                          alignment_read, base_weights, MSA ? g.seq_begin + s : nullptr,
                                                          (uint16_t)s, (uint32_t)c.max_sequences_per_poa,
                                                          (uint32_t)c.max_nodes_per_graph);
@@ -925,6 +939,15 @@ int32_t gwhip_poa_resident_windows(const gwhip_poa_config* cfg)
         cus = 256;
     }
     return 4 * cus;
+}
+
+int32_t gwhip_poa_reads_host_sequences(const gwhip_poa_config* cfg)
+{
+    if (cfg == nullptr) return 0;
+    // launch_msa_split()'s condition for the LDS-table kernels, and the band modes whose every consumer of a read but the
+    // backbone and the staging loop takes it from the LDS copy (poa_window_kernel: LDS_READ && !TB)
+    const bool lds = !cfg->size32 && cfg->max_nodes_per_graph + 2 <= kRowInfoLds && cfg->max_sequence_size + 16 <= kReadLds;
+    return lds && (cfg->band_mode == GWHIP_STATIC_BAND || cfg->band_mode == GWHIP_ADAPTIVE_BAND) ? 1 : 0;
 }
 
 int gwhip_poa_generate(const gwhip_poa_args* args, gwhip_stream_t stream_)

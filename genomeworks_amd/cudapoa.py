@@ -57,6 +57,9 @@ def _bind(L):
     for name in ("gw_poa_get_total_poas", "gw_poa_generate_poa", "gw_poa_batch_id", "gw_poa_reset", "gw_poa_max_poas",
                  "gw_poa_relaunch"):
         getattr(L, name).argtypes = [vp]
+    if hasattr(L, "gw_poa_last_generate_read_host"):  # (a host library from before host input lacks it)
+        L.gw_poa_last_generate_read_host.argtypes = [vp]
+        L.gw_poa_last_generate_read_host.restype = i32
     L.gw_poa_get_consensus.argtypes = [vp, C.POINTER(i32)]
     L.gw_poa_get_consensus_in_place.argtypes = [vp, C.POINTER(i32)]
     L.gw_poa_consensus_str.restype = C.POINTER(C.c_char)
@@ -200,6 +203,11 @@ class CudaPoaBatch:
     @property
     def max_poas(self):
         return self._L.gw_poa_max_poas(self._h)
+
+    @property
+    def last_generate_read_host(self):
+        """True when the last generate_poa() let the kernel take the reads from the pinned staging block (no sequence upload)."""
+        return self._L.gw_poa_last_generate_read_host(self._h) == 1
 
     def generate_poa(self):
         """Run asynchronous partial order alignment on all POA groups in batch."""

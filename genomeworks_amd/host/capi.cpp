@@ -146,6 +146,7 @@ int gw_poa_add_poa_group(gw_poa_batch* b, int32_t n, const char* const* seqs, co
 int32_t gw_poa_get_total_poas(gw_poa_batch* b) { return b->batch->get_total_poas(); }
 int32_t gw_poa_batch_id(gw_poa_batch* b) { return b->batch->batch_id(); }
 int32_t gw_poa_max_poas(gw_poa_batch* b) { return b->impl ? b->impl->max_poas() : -1; }
+int32_t gw_poa_last_generate_read_host(gw_poa_batch* b) { return b->impl ? (b->impl->last_generate_read_host() ? 1 : 0) : -1; }
 
 int gw_poa_generate_poa(gw_poa_batch* b)
 {

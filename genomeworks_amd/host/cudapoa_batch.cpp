@@ -233,8 +233,20 @@ PoaBatch::PoaBatch(int32_t device_id, cudaStream_t stream, DefaultDeviceAllocato
     host_block_ = cudaaligner::pinned_acquire(layout_.workspace.offset, &host_block_capacity_);
     h_          = layout_.in(host_block_);
     // (the staging arrays are not cleared: an upload covers exactly the bytes add_seq_to_poa() wrote, padding included, and
-    // the read-ahead slack is zeroed on the device -- clearing 2 x 600 MB of pinned memory was most of the construction time of
+    // the read-ahead slack is zeroed where the kernel reads it, per launch -- clearing 2 x 600 MB of pinned memory was most of the construction time of
     // a BatchConfig(1024, 200) batch with tens of GB of device memory)
+
+    // Where the graph-build kernel copies every read into LDS once, it can take the reads from this block itself and the
+    // upload, a pass over memory with the device idle behind it, falls away (generate_poa()). The block is mapped for the
+    // device when it is the runtime's pinned memory.
+    if (gwhip_poa_reads_host_sequences(&cfg_) != 0)
+    {
+        void* mapped = nullptr;
+        if (hipHostGetDevicePointer(&mapped, h_.sequences, 0) == hipSuccess)
+            host_sequences_dev_ = static_cast<const uint8_t*>(mapped);
+        else
+            (void)hipGetLastError();
+    }
 
     live_batches(device_id_).fetch_add(1);
     debug_message(" Initializing batch on device ");
@@ -245,7 +257,12 @@ PoaBatch::~PoaBatch()
 {
     debug_message(" Destroyed buffers on device ");
     scoped_device_switch dev(device_id_);
+    // a launch in flight may still read the pinned block, which pinned_release() can hand to another batch or give back to the
+    // system: the stream first, then the launch's own event (a stream that failed to synchronise does not skip it)
     (void)hipStreamSynchronize(stream_);
+    if (host_reads_pending_) (void)hipEventSynchronize(static_cast<hipEvent_t>(host_reads_done_));
+    host_reads_pending_ = false;
+    if (host_reads_done_ != nullptr) (void)hipEventDestroy(static_cast<hipEvent_t>(host_reads_done_));
     live_batches(device_id_).fetch_sub(1);
     if (host_block_ != nullptr) cudaaligner::pinned_release(host_block_, host_block_capacity_);
     if (device_block_ != nullptr) allocator_.deallocate(device_block_, layout_.block.bytes);
@@ -280,8 +297,20 @@ PoaBlockLayout PoaBatch::plan(int32_t n_poas) const
     return l;
 }
 
+// A host-input launch reads h_.sequences until its graph-build kernel ends (and the copies in front of it read the other
+// staging arrays): whoever rewrites the pinned block, or gives it back, waits for the event recorded behind that kernel first.
+// It costs nothing once the results of the launch were fetched.
+void PoaBatch::wait_for_host_reads()
+{
+    if (!host_reads_pending_) return;
+    GW_CU_CHECK_ERR(hipEventSynchronize(static_cast<hipEvent_t>(host_reads_done_)));
+    host_reads_pending_ = false;
+}
+
 void PoaBatch::reset()
 {
+    wait_for_host_reads();
+    device_sequences_current_ = false;
     poa_count_              = 0;
     num_nucleotides_copied_ = 0;
     global_sequence_idx_    = 0;
@@ -398,6 +427,8 @@ StatusType PoaBatch::add_poa_group(std::vector<StatusType>& per_seq_status, cons
     }
     if (!reserve_buf(longest->length)) return StatusType::exceeded_maximum_poas;
     per_seq_status.clear();
+    wait_for_host_reads(); // a refill behind a launch: the kernel may still be reading the block this group is written to
+    device_sequences_current_ = false;
     StatusType status = add_poa();
     if (status != StatusType::success) return status;
     bool poa_empty = true;
@@ -430,17 +461,45 @@ gwhip_poa_args PoaBatch::kernel_args() const
     return a;
 }
 
-void PoaBatch::upload_inputs()
+// GW_POA_HOST_INPUT=0 (read per call: the same-binary A/B arm) keeps the upload.
+bool PoaBatch::use_host_input() const
+{
+    if (host_sequences_dev_ == nullptr) return false;
+    const char* e = std::getenv("GW_POA_HOST_INPUT");
+    return !(e != nullptr && e[0] == '0');
+}
+
+void PoaBatch::upload_sequences()
 {
     GW_CU_CHECK_ERR(hipMemcpyAsync(d_.sequences, h_.sequences, static_cast<size_t>(num_nucleotides_copied_), hipMemcpyHostToDevice, stream_));
+    // zero the 2 KiB read-ahead slack behind the last read (it may hold an older batch's bases)
+    GW_CU_CHECK_ERR(hipMemsetAsync(d_.sequences + num_nucleotides_copied_, 0, 2048, stream_));
+    device_sequences_current_ = true;
+}
+
+void PoaBatch::ensure_resident_sequences()
+{
+    if (!device_sequences_current_) upload_sequences();
+}
+
+void PoaBatch::upload_inputs(bool host_input)
+{
+    if (!host_input)
+        GW_CU_CHECK_ERR(hipMemcpyAsync(d_.sequences, h_.sequences, static_cast<size_t>(num_nucleotides_copied_), hipMemcpyHostToDevice, stream_));
     // a batch whose reads all came without base weights (the common case, and the benchmark's) needs no weight upload:
     // every consumed byte is 1 (padding bytes are never read), so the device array is filled in place
     if (unit_weights_only_)
         GW_CU_CHECK_ERR(hipMemsetAsync(d_.weights, 1, static_cast<size_t>(num_nucleotides_copied_), stream_));
     else
         GW_CU_CHECK_ERR(hipMemcpyAsync(d_.weights, h_.weights, static_cast<size_t>(num_nucleotides_copied_), hipMemcpyHostToDevice, stream_));
-    // zero the 2 KiB read-ahead slack behind the last read (it may hold an older batch's bases)
-    GW_CU_CHECK_ERR(hipMemsetAsync(d_.sequences + num_nucleotides_copied_, 0, 2048, stream_));
+    // zero the 2 KiB read-ahead slack behind the last read (it may hold an older batch's bases): where the kernel will read
+    if (!host_input)
+    {
+        GW_CU_CHECK_ERR(hipMemsetAsync(d_.sequences + num_nucleotides_copied_, 0, 2048, stream_));
+        device_sequences_current_ = true;
+    }
+    else
+        std::memset(h_.sequences + num_nucleotides_copied_, 0, 2048);
     GW_CU_CHECK_ERR(hipMemcpyAsync(d_.windows, h_.windows, static_cast<size_t>(poa_count_) * sizeof(gwhip_window_details), hipMemcpyHostToDevice, stream_));
     restore_lengths();
 }
@@ -451,9 +510,10 @@ void PoaBatch::restore_lengths()
     GW_CU_CHECK_ERR(hipMemcpyAsync(d_.lengths, h_.lengths, static_cast<size_t>(global_sequence_idx_) * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
 }
 
-void PoaBatch::launch(void* event_after_graph_build, uint64_t* phase_cycles)
+void PoaBatch::launch(void* event_after_graph_build, uint64_t* phase_cycles, const uint8_t* sequences)
 {
     gwhip_poa_args a          = kernel_args();
+    if (sequences != nullptr) a.sequences = sequences;
     a.event_after_graph_build = event_after_graph_build;
     a.phase_cycles            = phase_cycles;
     // (A launch gate that kept concurrent batches from overlapping on the device beyond one wavefront per SIMD was built and
@@ -477,9 +537,30 @@ void PoaBatch::generate_poa()
         debug_message(" No POA was added to compute! ");
         return;
     }
-    upload_inputs();
+    // Host input: no sequence H2D -- the graph-build kernel fetches every read from the pinned block when it stages it in LDS
+    // (the block's device address; gwhip_poa_reads_host_sequences). The block then belongs to the kernel until the event
+    // recorded behind it has passed (wait_for_host_reads()).
+    const bool host_input    = use_host_input();
+    last_generate_read_host_ = host_input;
+    if (host_input)
+    {
+        wait_for_host_reads(); // (a second launch of the same fill: the slack below is rewritten)
+        if (host_reads_done_ == nullptr)
+        {
+            hipEvent_t e = nullptr;
+            GW_CU_CHECK_ERR(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            host_reads_done_ = e;
+        }
+    }
+    upload_inputs(host_input);
     debug_message(" Launching kernel for " + std::to_string(poa_count_) + " on device ");
-    launch();
+    if (host_input)
+    {
+        host_reads_pending_ = true; // (before the call: whatever it enqueued before failing may read the block)
+        launch(host_reads_done_, nullptr, host_sequences_dev_);
+    }
+    else
+        launch();
     debug_message(" Launched kernel on device ");
 }
 
@@ -487,6 +568,7 @@ void PoaBatch::relaunch_resident()
 {
     scoped_device_switch dev(device_id_);
     if (poa_count_ == 0) return;
+    ensure_resident_sequences();
     restore_lengths();
     launch();
 }
@@ -497,6 +579,7 @@ void PoaBatch::relaunch_resident_timed(float* graph_build_ms, float* output_ms)
     if (poa_count_ == 0) return;
     gwhost::OwnedEvents events;
     const hipEvent_t e0 = events.create(hipEventDefault), e1 = events.create(hipEventDefault), e2 = events.create(hipEventDefault);
+    ensure_resident_sequences();
     restore_lengths();
     GW_CU_CHECK_ERR(hipEventRecord(e0, stream_));
     launch(e1);
@@ -524,6 +607,7 @@ void PoaBatch::profile_phases_per_window(std::vector<uint64_t>& ticks)
     if (n == 0) return;
     uint64_t* d = nullptr;
     GW_CU_CHECK_ERR(hipMalloc(reinterpret_cast<void**>(&d), n * sizeof(uint64_t)));
+    ensure_resident_sequences();
     restore_lengths();
     launch(nullptr, d);
     GW_CU_CHECK_ERR(hipMemcpyAsync(ticks.data(), d, n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream_));

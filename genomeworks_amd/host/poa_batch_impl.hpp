@@ -83,8 +83,12 @@ public:
     StatusType get_consensus_in_place(std::vector<std::string>& consensus, std::vector<std::vector<uint16_t>>& coverage,
                                       std::vector<StatusType>& output_status);
     int32_t max_poas() const { return max_poas_; }
+    /// The last generate_poa() let the graph-build kernel read the pinned staging block (no sequence upload).
+    bool last_generate_read_host() const { return last_generate_read_host_; }
     uint64_t total_cells();    ///< DP cells computed by the last generate_poa() (device counters)
-    void relaunch_resident();  ///< re-run the kernels on the inputs already resident in HBM (no H2D)
+    /// Re-run the kernels on the inputs resident in HBM (no H2D -- but for the reads of a fill that generate_poa() let the kernel
+    /// take from the pinned block: the first relaunch of such a fill uploads them once).
+    void relaunch_resident();
     /// Same, timed with HIP events on the batch's stream: graph-build kernel and output kernel (milliseconds).
     void relaunch_resident_timed(float* graph_build_ms, float* output_ms);
     /// Profiling aid: relaunch with per-phase cycle accounting; out[6] = mean ticks per window of
@@ -99,9 +103,14 @@ private:
     bool reserve_buf(int32_t max_seq_length);
     StatusType add_poa();
     StatusType add_seq_to_poa(const char* seq, const int8_t* weights, int32_t seq_len);
-    void upload_inputs();
+    void upload_inputs(bool host_input);
+    void upload_sequences();         ///< the reads and the zeroed read-ahead slack behind them, into HBM
+    void ensure_resident_sequences(); ///< upload_sequences() unless the device copy already holds this fill's reads
     void restore_lengths(); ///< a launch overwrote the length of each window's first read with its node count
-    void launch(void* event_after_graph_build = nullptr, uint64_t* phase_cycles = nullptr);
+    /// `sequences`: where the graph-build kernel takes the reads from (null: the device copy).
+    void launch(void* event_after_graph_build = nullptr, uint64_t* phase_cycles = nullptr, const uint8_t* sequences = nullptr);
+    bool use_host_input() const;     ///< this call of generate_poa() lets the kernel read the pinned block (see cudapoa_batch.cpp)
+    void wait_for_host_reads();      ///< until no launch in flight reads the pinned block
     gwhip_poa_args kernel_args() const;
     StatusType window_status(size_t poa) const; ///< of the fetched consensus row: success, or the code behind the kernels' error marker
     void log_kernel_error(StatusType error_type);
@@ -136,6 +145,14 @@ private:
     char* host_block_           = nullptr; // pinned staging
     size_t host_block_capacity_ = 0;       // what the pinned cache handed out (pinned_release wants it back)
     PoaSections h_;
+
+    // Host input: the graph-build kernel takes the reads from the pinned block itself (generate_poa()).
+    const uint8_t* host_sequences_dev_ = nullptr; ///< device address of h_.sequences; null when the configuration's kernel needs
+                                                  ///< the reads in HBM or the pinned block is not mapped for the device
+    bool device_sequences_current_ = false;       ///< d_.sequences holds this fill's reads (and the zeroed slack)
+    void* host_reads_done_         = nullptr;     ///< hipEvent_t behind the graph-build kernel of a host-input launch
+    bool host_reads_pending_       = false;       ///< recorded and not yet waited for
+    bool last_generate_read_host_  = false;
 };
 
 } // namespace cudapoa

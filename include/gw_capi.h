@@ -88,6 +88,9 @@ int gw_poa_generate_poa(gw_poa_batch* b);
 int32_t gw_poa_batch_id(gw_poa_batch* b);
 int gw_poa_reset(gw_poa_batch* b);
 int32_t gw_poa_max_poas(gw_poa_batch* b);
+/* 1 when the last generate_poa() let the graph-build kernel read the reads from the pinned staging block (no sequence upload;
+   GW_POA_HOST_INPUT=0 keeps the upload), 0 when it uploaded them */
+int32_t gw_poa_last_generate_read_host(gw_poa_batch* b);
 
 /* Batch::get_consensus (cudapoa/include/.../batch.hpp:83-86) the way the reference's benchmark calls it
    (cudapoa/benchmarks/single_batch.hpp:86-93): three fresh vectors through the public virtual call; the handle then owns

@@ -78,7 +78,9 @@ typedef struct gwhip_poa_args
     gwhip_poa_config cfg;
     int32_t total_windows;
     /* inputs, device resident (the four arrays CudapoaBatch::generate_poa uploads, cudapoa_batch.cuh:171-178).
-       `sequences` / `base_weights` must be followed by >= 2048 readable zero bytes. */
+       `sequences` / `base_weights` must be followed by >= 2048 readable zero bytes. `sequences` may instead be the device
+       address of mapped pinned host memory where gwhip_poa_reads_host_sequences(cfg) says so; that memory must stay valid
+       and unchanged until the graph-build kernel has finished. */
     const uint8_t* sequences;
     const int8_t* base_weights;
     int32_t* sequence_lengths; /* [sum num_seqs]; element [seq_len_buffer_offset] of each window is overwritten
@@ -128,6 +130,13 @@ void gwhip_poa_bytes_per_window(const gwhip_poa_config* cfg, int64_t* per_poa, i
    spreads windows over several batches fills them in multiples of it (2048 full-band windows as 1400 + 648: 145 ms; as
    1024 + 1024: 107 ms; profiles/r06_multibatch_timeline.txt). */
 int32_t gwhip_poa_resident_windows(const gwhip_poa_config* cfg);
+
+/* 1 when the graph-build kernel of this configuration may take gwhip_poa_args::sequences from mapped host memory: the
+   kernels with their tables in LDS that copy every read into LDS once (16 bytes per lane, at most two wave-wide requests
+   of 1 KB) and touch the array nowhere else but for the backbone of a window -- the static and the adaptive band with a
+   score matrix. 0 for the others, which keep reading the array while they align: the full band, the traceback-buffer
+   modes (their fallback routine), and graphs beyond the LDS tables (long reads). Host function, no GPU needed. */
+int32_t gwhip_poa_reads_host_sequences(const gwhip_poa_config* cfg);
 
 int gwhip_poa_generate(const gwhip_poa_args* args, gwhip_stream_t stream);
 
