@@ -43,3 +43,18 @@ def test_random_aligner_batches_equal_the_oracles():
             bad.append((k, c["kind"], len(c["pairs"]), c["max_bandwidth"]))
     assert kinds == {"banded", "default", "ukkonen", "myers"}
     assert not bad, bad
+
+
+def test_low_complexity_aligner_batches_equal_the_oracles():
+    """The same sweep over absent-base runs, unequal homopolymers and tandem repeats (tests/low_complexity_cases.py), where the
+    kernels' multi-word additions pass carries through whole words -- which uniformly random queries never make them do."""
+    F = _fuzz()
+    rng = random.Random(9)
+    kinds, bad = set(), []
+    for k in range(40):
+        c = F.low_complexity_aligner_case(rng)
+        kinds.add(c["kind"])
+        if not F.run_aligner(c):
+            bad.append((k, c["kind"], len(c["pairs"]), c["max_bandwidth"]))
+    assert kinds == {"banded", "default", "ukkonen", "myers"}
+    assert not bad, bad

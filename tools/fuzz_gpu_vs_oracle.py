@@ -72,6 +72,20 @@ def aligner_case(rng):
     return dict(kind=kind, pairs=pairs, max_bandwidth=rng.choice([32, 150, 512, 1024]))
 
 
+def low_complexity_aligner_case(rng):
+    """Batches from the families of tests/low_complexity_cases.py -- absent-base runs, unequal homopolymers, tandem repeats --
+    which make the bit-vector kernels' words pass carries on; aligner_case's uniformly random queries never do. Drawn apart
+    from aligner_case, whose draw order stays what it was. The band is wider than every length difference, and the Ukkonen
+    class gets pairs within its limit of 10 % of the longest sequence."""
+    import low_complexity_cases as LC
+    kind = rng.choice(["banded", "banded", "default", "ukkonen", "myers"])
+    n = rng.randint(1, 24)
+    pairs = [LC.fuzz_pair(rng, max_diff=60 if kind == "ukkonen" else None) for _ in range(n)]
+    widest = max(abs(len(q) - len(t)) for q, t in pairs)
+    max_bandwidth = widest + rng.choice([34, 100, 500])
+    return dict(kind=kind, pairs=pairs, max_bandwidth=max_bandwidth + (max_bandwidth % 32 == 1))  # (the class refuses 32 k + 1)
+
+
 def run_aligner(c):
     pairs, kind = c["pairs"], c["kind"]
     mx = max(max(len(q), len(t)) for q, t in pairs) + 1
