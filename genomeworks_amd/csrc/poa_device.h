@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "poa_layout.h"
+#include "poa_pred_rows.h"
 
 namespace gwhip
 {
@@ -55,8 +56,7 @@ template <> struct alignas(8) RowInfo<true>
     __device__ __forceinline__ int32_t pred(int k) const { return (int32_t)((w >> (24 + 12 * k)) & 0xfff); }
     __device__ __forceinline__ void set(int32_t base, int32_t cnt, bool sink, int32_t p0, int32_t p1, int32_t p2)
     {
-        w = (uint64_t)(base & 0xff) | ((uint64_t)(cnt & 0x3f) << 8) | ((uint64_t)(sink ? 1 : 0) << 14) |
-            ((uint64_t)(p0 & 0xfff) << 24) | ((uint64_t)(p1 & 0xfff) << 36) | ((uint64_t)(p2 & 0xfff) << 48);
+        w = table_word(base, cnt, sink, p0, p1, p2);
     }
     __device__ __forceinline__ void set_bs(int32_t bs) { w = (w & ~(0x1ffull << 15)) | ((uint64_t)((bs >> 2) & 0x1ff) << 15); }
 };
@@ -929,8 +929,7 @@ __device__ __forceinline__ void build_rowinfo(const GraphView<IdT>& g, int32_t g
                 ri.set(bas[u], cnt[u], oc[u] == 0, cnt[u] > 0 ? q0[u] + 1 : 0, cnt[u] > 1 ? q1[u] + 1 : 0, cnt[u] > 2 ? q2[u] + 1 : 0);
                 rowinfo[r] = ri;
                 if (xpred != nullptr && cnt[u] > 3)
-                    xpred[r & 255] = (uint64_t)((uint32_t)r | (1u << 12) | ((uint32_t)(cnt[u] & 63) << 13) | ((uint32_t)((q3[u] + 1) & 0xfff) << 20)) |
-                                     ((uint64_t)((q4[u] + 1) & 0xfff) << 32) | ((uint64_t)((q5[u] + 1) & 0xfff) << 44);
+                    xpred[r & (kSideTableSlots - 1)] = xpred_entry(r, cnt[u], q3[u] + 1, q4[u] + 1, q5[u] + 1);
             }
         }
     }
@@ -2394,14 +2393,16 @@ __device__ __forceinline__ int32_t nw_banded(const GraphView<IdT>& g, RowT* rowi
             aligned_nodes = traceback_moves<int16_t, IdT, RowInfo<true>, ADAPTIVE>(b, g, rowinfo, graph_count, lds_read, read_length, wave_first(best_i),
                                                            alignment_graph, alignment_read, gap_score, mismatch_score, match_score,
                                                            rerun, reinterpret_cast<uint8_t*>(ring_base), codes, nullptr,
-                                                           packed_selective ? ((dbg & (1 << 23)) ? 2 : 0) : 1);
+                                                           packed_selective ? ((dbg & (1 << 23)) ? 2 : 0) : 1,
+                                                           reinterpret_cast<const uint64_t*>(code_tile));
             if (aligned_nodes == kNwNeedScoreRows)
             {
                 // the walk met a cell it has to step by recomputation in a row whose scores stayed out of HBM (the band's first
                 // cell, a chunk outside a predecessor's band): the same pass again with every row stored, then the same walk
                 // (GWHIP_DEBUG, debug instantiation: bit 24 counts these reruns into the "other" phase accumulator, bit 23 makes
-                // every recomputed step below row 0 take this path, bit 25 stores every row in the first place)
-                if (pc.acc && (dbg & (1 << 24))) pc.acc[kPhOther] += 1;
+                // every recomputed step below row 0 take this path, bit 25 stores every row in the first place; with bit 13 a
+                // rerun adds 2^40, which keeps the count exact above the phase's ticks -- without a row-kind selector of bits 28-30)
+                if (pc.acc && (dbg & (1 << 24))) pc.acc[kPhOther] += (dbg & (1 << 13)) ? (1ull << 40) : 1ull;
                 if (band_width == 256)
                     banded_forward_moves<IdT, 256>(g, rowinfo, graph_count, lds_read, scores, codes, reinterpret_cast<uint8_t*>(ring_base),
                                                    reinterpret_cast<const uint64_t*>(code_tile), max_column, gap_score, mismatch_score, match_score,
@@ -2413,7 +2414,8 @@ __device__ __forceinline__ int32_t nw_banded(const GraphView<IdT>& g, RowT* rowi
                 wave_sync();
                 aligned_nodes = traceback_moves<int16_t, IdT, RowInfo<true>, ADAPTIVE>(b, g, rowinfo, graph_count, lds_read, read_length, wave_first(best_i),
                                                                alignment_graph, alignment_read, gap_score, mismatch_score, match_score,
-                                                               rerun, reinterpret_cast<uint8_t*>(ring_base), codes, nullptr, 1);
+                                                               rerun, reinterpret_cast<uint8_t*>(ring_base), codes, nullptr, 1,
+                                                               reinterpret_cast<const uint64_t*>(code_tile));
             }
             tb_done = true;
         }

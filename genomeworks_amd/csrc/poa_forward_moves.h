@@ -84,15 +84,15 @@ __device__ __forceinline__ int32_t classify_kinds(RowInfo<true>* rowinfo, int32_
         const int32_t cnt = ri.cnt(), bs = ri.bs();
         uint64_t kind     = 4;
         // 4..6 predecessors: rows 3..5 from the side table build_rowinfo left (a row that lost its slot stays kind 4)
-        const uint64_t xe  = (cnt > 3 && cnt <= 6 && xpred != nullptr) ? xpred[r & 255] : 0ull;
-        const bool many_ok = cnt > 3 && cnt <= 6 && xpred_hit(xe, r, cnt) && !demote_many;
-        if (cnt >= 1 && (cnt <= 3 || many_ok))
+        const uint64_t xe  = (pred_rows_want_entry(cnt) && xpred != nullptr) ? xpred[r & (kSideTableSlots - 1)] : 0ull;
+        const bool many_ok = pred_rows_in_lds(r, cnt, xe) && !demote_many;
+        if (cnt >= 1 && (cnt <= kTablePreds || many_ok))
         {
             bool ok    = true;
             int32_t d0 = 0, pbs0 = 0;
             for (int32_t k = 0; k < cnt; k++)
             {
-                const int32_t p   = k < 3 ? ri.pred(k) : xpred_row(xe, k);
+                const int32_t p   = lds_pred_row(ri.w, xe, k);
                 const int32_t d   = r - p;
                 const RowInfo<true> pri = rowinfo[p];
                 const int32_t pbs = pri.bs(); // row 0 holds band start 0
@@ -123,26 +123,69 @@ __device__ __forceinline__ int32_t classify_kinds(RowInfo<true>* rowinfo, int32_
 // than three predecessors -- together with its predecessors, and the sink rows (sink selection). Every other row keeps its
 // score row out of HBM: move bytes, ring and registers carry it (a launch of the metric batch used to write 22.6 GB of score
 // rows of which well under 1 GB is ever read). Needs the row kinds in the table. all_rows: mark everything (A/B, reruns).
+//
+// Where the predecessor rows come from: the table word and, for a row with 4..6 predecessors, its side-table entry (xpred, the
+// table classify_kinds reads; poa_pred_rows.h) -- LDS, no trip to HBM inside the 64-row loop. The rows that are left over (slot
+// lost to a later row, more than six predecessors, no side table) are compacted over the whole read into `leftover` (LDS, room
+// for graph_count 16-bit rows: the ring region, idle until row 0 is stored) and served behind the loop, one lane per row, the
+// loads of a dependent level (row -> node -> in-edges -> their rows) issued together: three round trips per read for all of
+// them, where every 64-row chunk holding such a row used to wait for its own chain.
 // ------------------------------------------------------------------------------------------------
 constexpr uint64_t kRowScoresInHbm = 1ull << 63;
 template <typename IdT>
-__device__ __forceinline__ void mark_score_rows(const GraphView<IdT>& g, RowInfo<true>* rowinfo, int32_t graph_count, int lane, bool all_rows)
+__device__ __forceinline__ void mark_score_rows(const GraphView<IdT>& g, RowInfo<true>* rowinfo, int32_t graph_count, int lane, bool all_rows,
+                                                uint16_t* leftover, const uint64_t* xpred = nullptr)
 {
     auto mark = [&](int32_t row) {
         __hip_atomic_fetch_or(reinterpret_cast<uint32_t*>(&rowinfo[row].w) + 1, 0x80000000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
-    for (int32_t r = 1 + lane; r <= graph_count; r += kWave)
+    int32_t n_left = 0; // (wave-uniform)
+    for (int32_t r0 = 1; r0 <= graph_count; r0 += kWave)
     {
-        const uint64_t w    = rowinfo[r].w;
-        const uint32_t kind = (uint32_t)(w >> kKindShift) & 7u;
-        const int32_t cnt   = (int32_t)((w >> 8) & 0x3fu);
-        const bool reads_or_recomputes = kind >= 4u || cnt > 3;
-        if (reads_or_recomputes || ((w >> 14) & 1u) != 0 || all_rows) mark(r);
-        if (reads_or_recomputes)
+        const int32_t r = r0 + lane;
+        bool left       = false;
+        if (r <= graph_count)
         {
-            const int32_t node_id = cnt > 3 ? (int32_t)g.sorted_poa[r - 1] : 0;
-            for (int32_t k = 0; k < cnt; k++)
-                mark(k < 3 ? (int32_t)((w >> (24 + 12 * k)) & 0xfffu) : (int32_t)g.node_id_to_pos[g.incoming_edges[(int64_t)node_id * kEdges + k]] + 1);
+            const uint64_t w    = rowinfo[r].w;
+            const uint32_t kind = (uint32_t)(w >> kKindShift) & 7u;
+            const int32_t cnt   = table_pred_count(w);
+            const bool reads_or_recomputes = kind >= 4u || cnt > kTablePreds;
+            if (reads_or_recomputes || ((w >> 14) & 1u) != 0 || all_rows) mark(r);
+            if (reads_or_recomputes)
+            {
+                const uint64_t xe = (pred_rows_want_entry(cnt) && xpred != nullptr) ? xpred[r & (kSideTableSlots - 1)] : 0ull;
+                left              = !pred_rows_in_lds(r, cnt, xe);
+                const int32_t n   = left ? kTablePreds : cnt; // (a left-over row: predecessors 3 and up in the trailing pass)
+                for (int32_t k = 0; k < n; k++) mark(lds_pred_row(w, xe, k));
+            }
+        }
+        const uint64_t m = __ballot(left);
+        if (m != 0)
+        {
+            if (left) leftover[n_left + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)r;
+            n_left += __popcll(m);
+        }
+    }
+    if (n_left != 0)
+    {
+        constexpr int kB = 6; // in-edges per lane in flight
+        wave_sync();
+        for (int32_t i = lane; i < n_left; i += kWave)
+        {
+            const int32_t r       = leftover[i];
+            const int32_t cnt     = table_pred_count(rowinfo[r].w);
+            const int64_t edges   = (int64_t)g.sorted_poa[r - 1] * kEdges;
+            // slots past the row's last in-edge repeat it (a row is marked by an OR: once or several times is the same)
+            for (int32_t k0 = kTablePreds; k0 < cnt; k0 += kB)
+            {
+                int32_t e[kB], q[kB];
+#pragma unroll
+                for (int u = 0; u < kB; u++) e[u] = (int32_t)g.incoming_edges[edges + min(k0 + u, cnt - 1)];
+#pragma unroll
+                for (int u = 0; u < kB; u++) q[u] = (int32_t)g.node_id_to_pos[e[u]];
+#pragma unroll
+                for (int u = 0; u < kB; u++) mark(q[u] + 1);
+            }
         }
     }
     wave_sync();
@@ -204,11 +247,16 @@ __device__ __forceinline__ void banded_forward_moves(const GraphView<IdT>& g, Ro
     const int32_t lane4 = lane * 4, lane8 = lane * 8;
     const int32_t min_score = Limits<int16_t>::min / 2;
 
+    // profiling: bit 12 without a row-kind selector times the per-read prologue (classify_kinds + mark_score_rows) into "other"
+    const bool time_prologue  = prof_acc != nullptr && ksel < 0 && kcount;
+    const uint64_t t_prologue = time_prologue ? clock64() : 0;
     const int32_t first_moved = classify_kinds(rowinfo, graph_count, lane, xpred, dbg);
     wave_sync();
     // rows past the first band move write their score row to HBM only when it will be read back (mark_score_rows); the rows
     // whose band starts at column 0 (a tenth of them) keep storing theirs together with the real left-boundary value
-    mark_score_rows<IdT>(g, rowinfo, graph_count, lane, store_all);
+    static_assert(kPkSlots * kPkSlotBytes >= 4096 * (int)sizeof(uint16_t), "the ring region holds the list of left-over rows (rows <= 4095)");
+    mark_score_rows<IdT>(g, rowinfo, graph_count, lane, store_all, reinterpret_cast<uint16_t*>(ring), xpred);
+    if (time_prologue && lane == 0) *prof_acc += clock64() - t_prologue;
 
     const uint32_t MIN2   = pin_vgpr(pk_dup(min_score));
     const uint32_t SENT2  = pin_vgpr(pk_dup(kPkSentinel));
@@ -331,7 +379,24 @@ __device__ __forceinline__ void banded_forward_moves(const GraphView<IdT>& g, Ro
         const int32_t cp2 = (((rd4 >> 16) & 0xff) == base) ? match_score : mismatch_score;
         const int32_t cp3 = ((rd4 >> 24) == base) ? match_score : mismatch_score;
         const int32_t R0 = pk_lo(P01), R1 = pk_hi(P01), R2 = pk_lo(P23), R3 = pk_hi(P23);
-        bool synced = false;
+        // Every predecessor row ONCE, predecessor k in lane k (lanes past the last one repeat it: the row takes maxima only):
+        // from the table word, the side-table entry when it hits (poa_pred_rows.h), else from the HBM edge list -- all lanes
+        // load their in-edge together, then its row together (two round trips behind the node's, whatever the count).
+        const int32_t np    = max(pred_count, 1);
+        const int32_t kk    = min(lane, np - 1);
+        const uint64_t xe   = (pred_rows_want_entry(pred_count) && xpred != nullptr) ? wave_first64(xpred[r & (kSideTableSlots - 1)]) : 0ull;
+        // (kk clamped to the side table's last predecessor: a row with more takes the branch below, which overwrites this)
+        int32_t prow_v      = pred_count == 0 ? 0 : lds_pred_row(ri.w, xe, min(kk, kSideTablePreds - 1));
+        if (!pred_rows_in_lds(r, pred_count, xe)) // (wave-uniform)
+        {
+            const int32_t node_id = wave_first((int32_t)g.sorted_poa[r - 1]);
+            const int32_t edge    = (int32_t)g.incoming_edges[(int64_t)node_id * kEdges + kk];
+            prow_v                = (int32_t)g.node_id_to_pos[edge] + 1;
+        }
+        const bool is_prev_v = prow_v == r - 1;
+        const int32_t pbs_v  = prow_v == 0 ? 0 : rowinfo[prow_v].bs();
+        // the rows read from HBM were stored by other lanes: one fence before the first load
+        if (__ballot(!is_prev_v) != 0) wave_sync();
         auto from_regs = [&](int32_t& t0, int32_t& t1, int32_t& t2, int32_t& t3) {
             const int32_t q    = (bs - prev_bs) >> 2;
             const int32_t pend = min(prev_bs + band_width - kCellsPerLane, max_column);
@@ -346,63 +411,76 @@ __device__ __forceinline__ void banded_forward_moves(const GraphView<IdT>& g, Ro
             t2 = valid ? max(S2 + cp2, S3 + gap_score) : min_score;
             t3 = valid ? max(S3 + cp3, S4 + gap_score) : min_score;
         };
-        auto from_hbm = [&](int32_t prow, int32_t& t0, int32_t& t1, int32_t& t2, int32_t& t3) {
-            const int32_t pbs  = prow == 0 ? 0 : uniform_row(rowinfo[prow]).bs();
-            const int32_t pend = min(pbs + band_width - kCellsPerLane, max_column);
-            const bool valid   = !(c > pend || c < pbs);
-            if (!synced) { wave_sync(); synced = true; }
-            // no divergent branch in this routine (the row loop stays scalar control flow): lanes outside the predecessor's
-            // band load from the row's first quad and discard it
-            const int16_t* rowp = scores + (int64_t)prow * stride + (valid ? (c - pbs) : 0) + kRelShift;
-            int32_t S0 = rowp[0];
-            const Quad<int16_t> qd = *reinterpret_cast<const Quad<int16_t>*>(rowp + 1);
-            const int32_t S1 = qd.v[0], S2 = qd.v[1], S3 = qd.v[2], S4 = qd.v[3];
-            if (pbs > 0 && c == pbs) S0 = min_score; // relative-0 slot of a row whose band starts past column 0
-            t0 = valid ? max(S0 + cp0, S1 + gap_score) : min_score;
-            t1 = valid ? max(S1 + cp1, S2 + gap_score) : min_score;
-            t2 = valid ? max(S2 + cp2, S3 + gap_score) : min_score;
-            t3 = valid ? max(S3 + cp3, S4 + gap_score) : min_score;
+        // The score loads of a row are issued together, before the first of them is consumed: the predecessors' column-0
+        // values (lane k: predecessor k's, one load for all of them) and the cells of up to kGenBatch predecessors that are not
+        // the previous row. No divergent branch in this routine (the row loop stays scalar control flow): a lane outside a
+        // predecessor's band loads from that row's first quad, a lane whose predecessor has no column-0 cell in HBM loads the
+        // slot all the same, and both discard what they get.
+        constexpr int kGenBatch = 4;
+        const bool want_penalty = pred_count != 0 && !(bs > kCellsPerLane && pred_count == 1); // (wave-uniform)
+        int32_t col0_v = 0;
+        if (want_penalty) col0_v = (int32_t)scores[(int64_t)prow_v * stride + kRelShift];
+        struct PredCellsHbm { int32_t prow, pbs, S0; Quad<int16_t> qd; bool valid; };
+        auto issue_hbm = [&](int32_t p) -> PredCellsHbm {
+            PredCellsHbm pc;
+            pc.prow = __builtin_amdgcn_readlane(prow_v, p);
+            pc.pbs  = __builtin_amdgcn_readlane(pbs_v, p);
+            const int32_t pend = min(pc.pbs + band_width - kCellsPerLane, max_column);
+            pc.valid           = !(c > pend || c < pc.pbs);
+            const int16_t* rowp = scores + (int64_t)pc.prow * stride + (pc.valid ? (c - pc.pbs) : 0) + kRelShift;
+            pc.S0 = rowp[0];
+            pc.qd = *reinterpret_cast<const Quad<int16_t>*>(rowp + 1);
+            return pc;
         };
-        auto rel0_of = [&](int32_t prow) -> int32_t {
-            if (prow == r - 1) return prev_rel0_io;
-            const int32_t pbs = prow == 0 ? 0 : uniform_row(rowinfo[prow]).bs();
-            if (pbs > 0) return min_score;
-            if (!synced) { wave_sync(); synced = true; }
-            return wave_first((int32_t)scores[(int64_t)prow * stride + kRelShift]);
+        auto from_hbm = [&](const PredCellsHbm& pc, int32_t& t0, int32_t& t1, int32_t& t2, int32_t& t3) {
+            int32_t S0 = pc.S0;
+            const int32_t S1 = pc.qd.v[0], S2 = pc.qd.v[1], S3 = pc.qd.v[2], S4 = pc.qd.v[3];
+            if (pc.pbs > 0 && c == pc.pbs) S0 = min_score; // relative-0 slot of a row whose band starts past column 0
+            t0 = pc.valid ? max(S0 + cp0, S1 + gap_score) : min_score;
+            t1 = pc.valid ? max(S1 + cp1, S2 + gap_score) : min_score;
+            t2 = pc.valid ? max(S2 + cp2, S3 + gap_score) : min_score;
+            t3 = pc.valid ? max(S3 + cp3, S4 + gap_score) : min_score;
         };
-        const int32_t node_id = (pred_count > 3) ? (int32_t)g.sorted_poa[r - 1] : 0;
-        auto pred_row = [&](int32_t p) -> int32_t {
-            if (pred_count == 0) return 0;
-            if (p < 3) return ri.pred(p);
-            return wave_first((int32_t)g.node_id_to_pos[g.incoming_edges[(int64_t)node_id * kEdges + p]] + 1);
-        };
-        int32_t fe = 0, rel0_val = min_score;
-        if (pred_count == 0)
-        {
-            if (bs == 0) rel0_val = gap_score; // carry-in stays 0 (reference quirk)
-        }
-        else
-        {
-            if (bs > kCellsPerLane && pred_count == 1)
-                fe = min_score + gap_score;
-            else
-            {
-                int32_t penalty = min_score;
-                for (int32_t p = 0; p < pred_count; p++) penalty = max(penalty, rel0_of(pred_row(p)));
-                fe = penalty + gap_score;
-            }
-            if (bs == 0) rel0_val = fe;
-        }
         int32_t s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-        const int32_t np = max(pred_count, 1);
-        for (int32_t p = 0; p < np; p++)
+        int32_t fe = 0, rel0_val = min_score;
+        for (int32_t p0 = 0; p0 < np; p0 += kGenBatch)
         {
-            const int32_t prow = pred_row(p);
-            int32_t t0, t1, t2, t3;
-            if (prow == r - 1) from_regs(t0, t1, t2, t3);
-            else from_hbm(prow, t0, t1, t2, t3);
-            if (p == 0) { s0 = t0; s1 = t1; s2 = t2; s3 = t3; }
-            else { s0 = max(s0, t0); s1 = max(s1, t1); s2 = max(s2, t2); s3 = max(s3, t3); }
+            PredCellsHbm pc[kGenBatch];
+#pragma unroll
+            for (int u = 0; u < kGenBatch; u++) pc[u] = issue_hbm(min(p0 + u, np - 1)); // (past the last one: loaded again, not used)
+            if (p0 == 0)
+            {
+                // left boundary: gap + the greatest column-0 value among the predecessors (the previous row's from the carried
+                // state, min_score for a row whose band starts past column 0)
+                if (pred_count == 0)
+                {
+                    if (bs == 0) rel0_val = gap_score; // carry-in stays 0 (reference quirk)
+                }
+                else
+                {
+                    if (!want_penalty)
+                        fe = min_score + gap_score;
+                    else
+                    {
+                        const int32_t rel0_v = is_prev_v ? prev_rel0_io : (pbs_v > 0 ? min_score : col0_v);
+                        fe = max(min_score, wave_bcast(wave_inclusive_max(rel0_v), kWave - 1)) + gap_score;
+                    }
+                    if (bs == 0) rel0_val = fe;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kGenBatch; u++)
+            {
+                const int32_t p = p0 + u;
+                if (p < np) // (wave-uniform)
+                {
+                    int32_t t0, t1, t2, t3;
+                    if (pc[u].prow == r - 1) from_regs(t0, t1, t2, t3);
+                    else from_hbm(pc[u], t0, t1, t2, t3);
+                    if (p == 0) { s0 = t0; s1 = t1; s2 = t2; s3 = t3; }
+                    else { s0 = max(s0, t0); s1 = max(s1, t1); s2 = max(s2, t2); s3 = max(s3, t3); }
+                }
+            }
         }
         scan_row(pk_make(s0, s1), pk_make(s2, s3), fe + gap_score);
         // stores (either flavour of left boundary)

@@ -43,7 +43,9 @@ __device__ __forceinline__ void full_forward_moves(const GraphView<IdT>& g, RowI
     // a score row goes to HBM only when somebody will read it back (mark_score_rows, poa_forward_moves.h): 98 % of the rows of
     // the metric windows keep theirs in move bytes, ring and registers. Column 0 is stored for every row (the walk along column
     // 0). GWHIP_DEBUG bit 25 (debug instantiation): every row stores its scores (A/B).
-    mark_score_rows<IdT>(g, rowinfo, graph_count, lane, (dbg & (1 << 25)) != 0);
+    // (the list of rows whose predecessors are not all in LDS goes into the ring region, which is idle until row 0 is stored)
+    static_assert(kWdSlots * kWdSlotBytes >= 4096 * (int)sizeof(uint16_t), "the ring region holds the list of left-over rows (rows <= 4095)");
+    mark_score_rows<IdT>(g, rowinfo, graph_count, lane, (dbg & (1 << 25)) != 0, reinterpret_cast<uint16_t*>(ring), xpred);
 
     const uint32_t GAP2   = pin_vgpr(pk_dup(gap_score));
     const uint32_t MAT2   = pin_vgpr(pk_dup(match_score));
@@ -474,7 +476,7 @@ __device__ __forceinline__ int32_t nw_full_packed(const GraphView<IdT>& g, RowIn
     b.gradient   = __fdiv_rn((float)(read_length + 1), (float)(graph_count + 1));
     b.min_score  = Limits<int16_t>::min;
     return traceback_moves<int16_t, IdT, RowInfo<true>, false>(b, g, rowinfo, graph_count, read, read_length, wave_first(best_i), alignment_graph,
-                                                               alignment_read, gap_score, mismatch_score, match_score, 0, ring, moves);
+                                                               alignment_read, gap_score, mismatch_score, match_score, 0, ring, moves, nullptr, 1, xpred);
 }
 
 } // namespace gwhip

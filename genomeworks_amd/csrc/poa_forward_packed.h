@@ -5,6 +5,8 @@
 // that lived here -- row classes 0..3, trace codes resolved through the row table -- was retired with its traceback).
 #pragma once
 
+#include "poa_pred_rows.h"
+
 namespace gwhip
 {
 
@@ -69,15 +71,7 @@ __device__ __forceinline__ void lds_store_u64(uint32_t addr, uint32_t lo, uint32
 // all lanes. (Rounds 1-3 masked lanes 17..63 off around the store: s_mov_b64 exec twice per row.)
 __device__ __forceinline__ void lds_store_guard(uint32_t addr, uint32_t lo, uint32_t hi) { lds_store_u64(addr, lo, hi); }
 
-// ------------------------------------------------------------------------------------------------
-// Side table of predecessor rows 3..5 (build_rowinfo, poa_device.h): one 64-bit entry per row & 255
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool xpred_hit(uint64_t e, int32_t row, int32_t cnt)
-{
-    return (int32_t)(e & 0xfffu) == row && ((e >> 12) & 1u) != 0 && (int32_t)((e >> 13) & 63u) == cnt;
-}
-__device__ __forceinline__ int32_t xpred_row(uint64_t e, int32_t k) { return (int32_t)((e >> (20 + 12 * (k - 3))) & 0xfffu); } // k = 3..5
-
+// (the side table of predecessor rows 3..5 -- xpred_hit, xpred_row -- is decoded in poa_pred_rows.h)
 
 __device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b)
 {

@@ -65,8 +65,10 @@ __device__ __forceinline__ int32_t traceback_moves(const BandedCtx<ScoreT>& b, c
                                                    int32_t graph_count, const uint8_t* read, int32_t read_length, int32_t start_i,
                                                    int32_t* alignment_graph, int32_t* alignment_read, int32_t gap_score,
                                                    int32_t mismatch_score, int32_t match_score, int32_t rerun, uint8_t* tile_region,
-                                                   const uint8_t* moves, const uint8_t* plane1 = nullptr, int32_t score_rows = 1)
+                                                   const uint8_t* moves, const uint8_t* plane1 = nullptr, int32_t score_rows = 1,
+                                                   const uint64_t* xpred = nullptr)
 {
+    // xpred (row table in LDS only): the side table of predecessor rows 3..5 the forward pass read, still in place
     constexpr bool kWide    = !std::is_same<RowT, RowInfo<true>>::value;
     constexpr int kMtStride = MtGeometry<kWide>::kStride, kMtZeroRows = MtGeometry<kWide>::kZeroRows;
     constexpr int kHalf = 31;
@@ -367,9 +369,15 @@ __device__ __forceinline__ int32_t traceback_moves(const BandedCtx<ScoreT>& b, c
             else
                 crow = pred_count != 0 ? (p == 0 ? pr0 : (p == 1 ? pr1 : pr2)) : 0;
             crow          = (is_horiz | is_self) ? i : crow;
-            if (pred_count > 3) // predecessor slots beyond the three packed ones live in the HBM edge list
+            if (pred_count > kTablePreds) // predecessor slots beyond the three packed ones: the side table (poa_pred_rows.h), else the HBM edge list
             {
-                if (en && !is_horiz && p >= 3)
+                uint64_t xe = 0;
+                if constexpr (!kWide)
+                    if (pred_rows_want_entry(pred_count) && xpred != nullptr) xe = wave_first64(xpred[i & (kSideTableSlots - 1)]);
+                const bool beyond = en && !is_horiz && p >= kTablePreds;
+                if (!kWide && pred_rows_in_lds(i, pred_count, xe)) // (wave-uniform)
+                    crow = beyond ? xpred_row(xe, min(p, kSideTablePreds - 1)) : crow;
+                else if (beyond)
                 {
                     const int32_t node_id = g.sorted_poa[i - 1];
                     crow = (int32_t)g.node_id_to_pos[g.incoming_edges[(int64_t)node_id * kEdges + p]] + 1;
