@@ -241,6 +241,19 @@ def mapper():
         L.gw_mapper_pair_segments.argtypes = [vp, i64, vp, vp, i32, u32, i32, i64, vp]
         L.gw_mapper_windows_copy_query_role_segments.restype = i64
         L.gw_mapper_windows_copy_query_role_segments.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+        L.gw_mapper_window_overlaps_weighted.restype = vp
+        L.gw_mapper_window_overlaps_weighted.argtypes = [vp, i64, vp, vp, i32, u32, vp, vp, i32, u32, vp, vp, i32, i32, i32,
+                                                         i64, vp]
+        L.gw_mapper_correction_windows_weighted.restype = vp
+        L.gw_mapper_correction_windows_weighted.argtypes = [vp, i64, vp, vp, i32, u32, vp, i32, i32, i32, i64, vp]
+        L.gw_mapper_windows_copy_weights.argtypes = [vp, vp, vp, vp, vp]
+        L.gw_mapper_select_layers_weighted.restype = i64
+        L.gw_mapper_select_layers_weighted.argtypes = [vp, i64, vp, i64, i32, u32, vp, i32, u32, i32, i32, vp, i32, vp, i64,
+                                                       vp, vp, i64]
+        L.gw_mapper_select_correction_layers_weighted.restype = i64
+        L.gw_mapper_select_correction_layers_weighted.argtypes = [vp, i64, vp, i64, vp, i64, vp, i32, u32, i32, i32, vp, vp,
+                                                                  i32, vp, i64, vp, vp, i64]
+        L.gw_mapper_segment_quality_sums.argtypes = [vp, i64, vp, i64, i32, vp, vp, i32, u32, vp, vp, vp]
         L.gwm_align_bytes_needed.restype = i64
         L.gwm_align_bytes_needed.argtypes = [i32, i32, i32]
         _mapper = L

@@ -35,7 +35,7 @@ EXTENDER_HOST_SRCS = ["extender/extender.cpp"]
 SEMIGLOBAL_KERNEL_SRCS = ["semiglobal/gws_ends.hip"]
 # cudamapper likewise
 MAPPER_KERNEL_SRCS = ["mapper/gwm_mapper.hip", "mapper/gwm_postprocess.hip", "mapper/gwm_align.hip",
-                      "mapper/gwm_segments.hip", "mapper/gwm_index_cache.hip"]
+                      "mapper/gwm_segments.hip", "mapper/gwm_qualities.hip", "mapper/gwm_index_cache.hip"]
 MAPPER_HOST_SRCS = ["mapper/mapper.cpp", "mapper/gwm_driver.cpp", "mapper/gwm_index_batcher.cpp",
                     "mapper/gwm_windows.cpp"]
 

@@ -19,6 +19,8 @@ gfx950), over the flat C API of include/gw_mapper_capi.h.
     pairs = overlaps[select_pairs(overlaps)]                       # read correction: one record per pair of reads
     (target_role, offsets, edit_distances), (query_role, query_role_offsets) = pair_segments(pairs, reads, 500)
     windows = correction_windows(overlaps, reads, window_length=500, max_depth=30)   # polisher.correct_reads feeds on it
+    windows = overlap_windows_weighted(overlaps, reads, targets, query_qualities=phred33)   # + weights per sequence
+    windows = correction_windows_weighted(overlaps, reads, phred33)
 
 Index arrays carry the reference's names (representations, read_ids, positions_in_reads, directions_of_reads,
 unique_representations, first_occurrence_of_representations) and come back as numpy arrays."""
@@ -89,6 +91,39 @@ def _read_set_args(query_reads, target_reads):
         return (_p(qb), _p(qo), len(query_reads)), (None, None, 0)
     tb, to = pack_reads(target_reads)
     return (_p(qb), _p(qo), len(query_reads)), (_p(tb), _p(to), len(target_reads))
+
+
+def pack_qualities(qualities, reads, who="qualities"):
+    """The qualities of a read set as the C API takes them: Phred+33 bytes back to back, which share the offsets of
+    the set's bases. `qualities` is a list of str / bytes, one per read and of the read's length, every byte in
+    33..126; anything else raises ValueError. None gives None: the set has no qualities."""
+    if qualities is None:
+        return None
+    if len(qualities) != len(reads):
+        raise ValueError("%s: %d quality strings for %d reads" % (who, len(qualities), len(reads)))
+    qs = [q.encode("latin-1") if isinstance(q, str) else bytes(q) for q in qualities]
+    for i, (q, r) in enumerate(zip(qs, reads)):
+        if len(q) != len(r):
+            raise ValueError("%s: read %d has %d bases and %d qualities" % (who, i, len(r), len(q)))
+    flat = np.frombuffer(b"".join(qs) or b"!", np.uint8).copy()
+    if any(qs) and (flat.min() < 33 or flat.max() > 126):
+        raise ValueError("%s: a quality byte outside 33..126" % who)
+    return flat
+
+
+def _threshold(min_mean_quality):
+    if int(min_mean_quality) < 0:
+        raise ValueError("min_mean_quality must be >= 0")
+    return int(min_mean_quality)
+
+
+def _copy_weights(L, h, n_bases, n_records, n_query_role_records):
+    """what a handle of the weighted calls holds beyond the others: (weights, quality_sums, query_role_quality_sums,
+    ms[2]); arrays the call did not fill stay zero and are cut by the caller"""
+    weights, ms = np.zeros(max(n_bases, 1), np.int8), np.zeros(2, np.float32)
+    sums, query_role_sums = np.zeros(max(n_records, 1), np.uint32), np.zeros(max(n_query_role_records, 1), np.uint32)
+    L.gw_mapper_windows_copy_weights(h, _p(weights), _p(sums), _p(query_role_sums), _p(ms))
+    return weights[:n_bases], sums[:n_records], query_role_sums[:n_query_role_records], ms
 
 
 class _Handle:
@@ -356,13 +391,20 @@ def align_overlaps(overlaps, query_reads, target_reads=None, first_query_read_id
 
 
 def _window_overlaps(overlaps, query_reads, target_reads, window_length, max_depth, first_query_read_id,
-                     first_target_read_id, max_device_bytes, stream, timings):
+                     first_target_read_id, max_device_bytes, stream, timings, weighted=None):
     """gw_mapper_window_overlaps and everything it holds, as host arrays; max_depth None: gw_mapper_window_segments, the
-    segments pass alone"""
+    segments pass alone. weighted: None, or a dict with query_qualities, target_qualities (pack_qualities) and
+    min_mean_quality for gw_mapper_window_overlaps_weighted, which receives weights and quality_sums."""
     L = _native.mapper()
     o = np.ascontiguousarray(overlaps, OVERLAP)
     q, t = _read_set_args(query_reads, target_reads)
-    if max_depth is None:
+    if weighted is not None:
+        qq, tq = weighted["query_qualities"], weighted["target_qualities"]
+        h = L.gw_mapper_window_overlaps_weighted(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id,
+                                                 None if qq is None else _p(qq), None if tq is None else _p(tq),
+                                                 weighted["min_mean_quality"], int(window_length), int(max_depth),
+                                                 int(max_device_bytes), _stream(stream))
+    elif max_depth is None:
         h = L.gw_mapper_window_segments(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id,
                                         int(window_length), int(max_device_bytes), _stream(stream))
     else:
@@ -380,12 +422,18 @@ def _window_overlaps(overlaps, query_reads, target_reads, window_length, max_dep
         bases, seq_offsets = np.zeros(max(n_bases, 1), np.uint8), np.zeros(n_seq + 1, np.int64)
         per_window, reads, index = np.zeros(n_win, np.int32), np.zeros(n_win, np.uint32), np.zeros(n_win, np.uint32)
         L.gw_mapper_windows_copy_windows(h, _p(bases), _p(seq_offsets), _p(per_window), _p(reads), _p(index))
+        if weighted is not None:
+            weights, sums, _, quality_ms = _copy_weights(L, h, n_bases, n_seg if qq is not None else 0, 0)
+            weighted.update(weights=weights, quality_sums=sums)
     finally:
         L.gw_mapper_windows_destroy(h)
     if timings is not None:
         timings.update(gather=float(ms[0]), align=float(ms[1]), segments=float(ms[2]), window_gather=float(ms[3]),
                        bytes_to_host=o.nbytes + segments.nbytes + seg_offsets.nbytes + edits.nbytes + n_bases,
                        segment_bytes=segments.nbytes, window_bases=n_bases)
+        if weighted is not None:
+            timings.update(quality_sums=float(quality_ms[0]), weight_gather=float(quality_ms[1]),
+                           bytes_to_host=timings["bytes_to_host"] + weights.nbytes + sums.nbytes)
     return (segments, seg_offsets, edits), (bases[:n_bases], seq_offsets, per_window, reads, index)
 
 
@@ -427,21 +475,92 @@ def _split_windows(bases, offsets, per_window, reads, index):
     return out
 
 
+def _split_weighted_windows(bases, weights, offsets, per_window, reads, index):
+    """_split_windows with the weights of every sequence as a fourth entry: views of the one array of the call"""
+    out, at = [], 0
+    offsets = offsets.tolist()
+    for r, k, seqs in _split_windows(bases, offsets, per_window, reads, index):
+        out.append((r, k, seqs, [weights[offsets[i]:offsets[i + 1]] for i in range(at, at + len(seqs))]))
+        at += len(seqs)
+    return out
+
+
+def segment_quality_sums(segments, overlaps, qualities, first_read_id=0, query_role=False, stream=None, timings=None):
+    """Q1 of INTEGRATION.md section 3l on the device (gwm_segment_quality_sums): per SEGMENT record the sum of c - 33
+    over the quality bytes [query_begin, query_end) of the read that supplies its layer -- its overlap's query read,
+    or with query_role its target read (the query-role records of pair_segments) --, a uint32 array in record order,
+    saturating at 2**32 - 1. `qualities`: the supplying set's Phred+33 strings (str / bytes, bytes in 33..126, else
+    ValueError), read ids counting from first_read_id. A record that names an overlap or a read that does not exist,
+    or a range beyond its read, raises MapperError. `timings` receives quality_sums (device ms)."""
+    L = _native.mapper()
+    s = np.ascontiguousarray(segments, SEGMENT)
+    o = np.ascontiguousarray(overlaps, OVERLAP)
+    flat = pack_qualities(qualities, qualities)
+    _, offsets = pack_reads(qualities)
+    sums, ms = np.zeros(max(len(s), 1), np.uint32), C.c_float(0.0)
+    if L.gw_mapper_segment_quality_sums(_p(s), len(s), _p(o), len(o), int(bool(query_role)), _p(flat), _p(offsets),
+                                        len(qualities), first_read_id, _p(sums), _stream(stream), C.byref(ms)) != 0:
+        raise _err(L)
+    if timings is not None:
+        timings.update(quality_sums=float(ms.value))
+    return sums[:len(s)]
+
+
+def overlap_windows_weighted(overlaps, query_reads, target_reads=None, query_qualities=None, target_qualities=None,
+                             window_length=500, max_depth=30, min_mean_quality=10, first_query_read_id=0,
+                             first_target_read_id=0, max_device_bytes=0, stream=None, timings=None):
+    """overlap_windows with base qualities: [(target_read, window, [backbone, layer, ...],
+    [weights, ...]), ...], the weights of a sequence an np.int8 array with one entry per base. Qualities are lists of
+    Phred+33 str / bytes, one per read and of its length, or None for a set that has none (a FASTA draft). They are
+    uploaded once and stay on the device. With query qualities, a record is a layer only if its quality sum
+    (segment_quality_sums) is > 0 and >= min_mean_quality * its bases (racon's -q), before the ordering and the
+    max_depth cut; without, the layers are those of overlap_windows. Weights are c - 33, cut out on the device by the
+    plan of the bases, reversed and not complemented on '-' layers; sequences of a set without qualities get 1
+    throughout. Without target_reads the targets are the queries, with the queries' qualities. Wrong lengths, bytes
+    outside 33..126 and a negative min_mean_quality raise ValueError before any device call. `timings` as for
+    overlap_windows, plus quality_sums and weight_gather (device ms); bytes_to_host grows by 4 B per record and one
+    byte per window base."""
+    weighted = dict(query_qualities=pack_qualities(query_qualities, query_reads, "query_qualities"),
+                    target_qualities=None if target_reads is None else
+                    pack_qualities(target_qualities, target_reads, "target_qualities"),
+                    min_mean_quality=_threshold(min_mean_quality))
+    _, (bases, offsets, per_window, reads, index) = _window_overlaps(
+        overlaps, query_reads, target_reads, window_length, max_depth, first_query_read_id, first_target_read_id,
+        max_device_bytes, stream, timings, weighted)
+    return _split_weighted_windows(bases, weighted["weights"], offsets, per_window, reads, index)
+
+
 def select_layers(segments, overlaps, n_queries, target_lengths, window_length=500, max_depth=30,
-                  first_query_read_id=0, first_target_read_id=0):
+                  first_query_read_id=0, first_target_read_id=0, quality_sums=None, min_mean_quality=0):
     """Polishing's layer selection over host arrays, without a device (gw_mapper_select_layers; the rules are in
     INTEGRATION.md section 3j): one overlap per query read is kept (the longest query span, the first on ties); a
     SEGMENT record of a kept overlap is a layer when it reaches within window_length // 100 of both ends of its window
     and holds 1 .. 2 * window_length query bases; the layers of a window are ordered by (target_first, overlap) and
     cut at max_depth. Returns (plan, windows): plan[i] = (set, read, begin, end, reversed) of sequence i, set 0 the
-    queries and 1 the targets; windows[j] = (target_read, window, first_sequence, n_sequences), backbone first."""
+    queries and 1 the targets; windows[j] = (target_read, window, first_sequence, n_sequences), backbone first.
+    quality_sums (one per record, as segment_quality_sums gives them; None: no filter): a record is a layer only if
+    its sum is also > 0 and >= min_mean_quality * (query_end - query_begin), rule Q2 of section 3l
+    (gw_mapper_select_layers_weighted); a negative min_mean_quality raises MapperError."""
     L = _native.mapper()
     s = np.ascontiguousarray(segments, SEGMENT)
     o = np.ascontiguousarray(overlaps, OVERLAP)
     lengths = np.ascontiguousarray(target_lengths, np.int64)
     args = (_p(s), len(s), _p(o), len(o), int(n_queries), first_query_read_id, _p(lengths), len(lengths),
             first_target_read_id, int(window_length), int(max_depth))
-    return _plan_and_table(L.gw_mapper_select_layers, args)
+    if quality_sums is None and min_mean_quality == 0:
+        return _plan_and_table(L.gw_mapper_select_layers, args)
+    sums = _sums_for(quality_sums, len(s))
+    return _plan_and_table(L.gw_mapper_select_layers_weighted,
+                           args + (None if sums is None else _p(sums), int(min_mean_quality)))
+
+
+def _sums_for(quality_sums, n_records):
+    if quality_sums is None:
+        return None
+    sums = np.ascontiguousarray(quality_sums, np.uint32)
+    if len(sums) != n_records:
+        raise ValueError("%d quality sums for %d records" % (len(sums), n_records))
+    return sums
 
 
 def select_pairs(overlaps):
@@ -458,13 +577,22 @@ def select_pairs(overlaps):
     return positions[:n]
 
 
-def _correction_windows(overlaps, reads, window_length, max_depth, first_read_id, max_device_bytes, stream, timings):
+def _correction_windows(overlaps, reads, window_length, max_depth, first_read_id, max_device_bytes, stream, timings,
+                        weighted=None):
     """gw_mapper_correction_windows and everything it holds, as host arrays; max_depth None: gw_mapper_pair_segments,
-    the segments pass alone over records that are pairs already"""
+    the segments pass alone over records that are pairs already. weighted: None, or a dict with qualities
+    (pack_qualities) and min_mean_quality for gw_mapper_correction_windows_weighted, which receives weights,
+    quality_sums and query_role_quality_sums."""
     L = _native.mapper()
     o = np.ascontiguousarray(overlaps, OVERLAP)
     (bases_p, offsets_p, n_reads), _ = _read_set_args(reads, None)
-    if max_depth is None:
+    if weighted is not None:
+        qq = weighted["qualities"]
+        h = L.gw_mapper_correction_windows_weighted(_p(o), len(o), bases_p, offsets_p, n_reads, first_read_id,
+                                                    None if qq is None else _p(qq), weighted["min_mean_quality"],
+                                                    int(window_length), int(max_depth), int(max_device_bytes),
+                                                    _stream(stream))
+    elif max_depth is None:
         h = L.gw_mapper_pair_segments(_p(o), len(o), bases_p, offsets_p, n_reads, first_read_id, int(window_length),
                                       int(max_device_bytes), _stream(stream))
     else:
@@ -488,6 +616,10 @@ def _correction_windows(overlaps, reads, window_length, max_depth, first_read_id
         bases, seq_offsets = np.zeros(max(n_bases, 1), np.uint8), np.zeros(n_seq + 1, np.int64)
         per_window, owners, index = np.zeros(n_win, np.int32), np.zeros(n_win, np.uint32), np.zeros(n_win, np.uint32)
         L.gw_mapper_windows_copy_windows(h, _p(bases), _p(seq_offsets), _p(per_window), _p(owners), _p(index))
+        if weighted is not None:
+            weights, sums, query_role_sums, quality_ms = _copy_weights(
+                L, h, n_bases, n_seg if qq is not None else 0, n_query_role if qq is not None else 0)
+            weighted.update(weights=weights, quality_sums=sums, query_role_quality_sums=query_role_sums)
     finally:
         L.gw_mapper_windows_destroy(h)
     if timings is not None:
@@ -496,6 +628,10 @@ def _correction_windows(overlaps, reads, window_length, max_depth, first_read_id
                        bytes_to_host=(n_pairs * OVERLAP.itemsize + segments.nbytes + query_role.nbytes +
                                       2 * seg_offsets.nbytes + edits.nbytes + n_bases),
                        segment_bytes=segments.nbytes + query_role.nbytes, window_bases=n_bases)
+        if weighted is not None:
+            timings.update(quality_sums=float(quality_ms[0]), weight_gather=float(quality_ms[1]),
+                           bytes_to_host=timings["bytes_to_host"] + weights.nbytes + sums.nbytes +
+                           query_role_sums.nbytes)
     return ((segments, seg_offsets, edits), (query_role, query_offsets), positions,
             (bases[:n_bases], seq_offsets, per_window, owners, index))
 
@@ -529,22 +665,29 @@ def _plan_and_table(call, args):
 
 
 def select_correction_layers(target_role, query_role, pairs, read_lengths, window_length=500, max_depth=30,
-                             first_read_id=0):
+                             first_read_id=0, target_role_quality_sums=None, query_role_quality_sums=None,
+                             min_mean_quality=0):
     """Read correction's layer selection over host arrays, without a device (gw_mapper_select_correction_layers; rules
     C3 and C4 of INTEGRATION.md section 3k): every record of either role of pair_segments is a layer of (its owner,
     its window) when it reaches within window_length // 100 of both ends of the window and holds 1 .. 2 * window_length
     bases of the other read; the owner is the pair's target read for target-role records and its query read for
     query-role ones. The layers of a window are ordered by (target_first, pair, target role first) and cut at
     max_depth. Returns (plan, windows) as select_layers does, with every plan entry of set 0 and windows[j][0] the
-    owner."""
+    owner. The quality sums of the records of either role (None: that role is not filtered) and min_mean_quality as
+    for select_layers (gw_mapper_select_correction_layers_weighted)."""
     L = _native.mapper()
     a = np.ascontiguousarray(target_role, SEGMENT)
     b = np.ascontiguousarray(query_role, SEGMENT)
     o = np.ascontiguousarray(pairs, OVERLAP)
     lengths = np.ascontiguousarray(read_lengths, np.int64)
-    return _plan_and_table(L.gw_mapper_select_correction_layers,
-                           (_p(a), len(a), _p(b), len(b), _p(o), len(o), _p(lengths), len(lengths), first_read_id,
-                            int(window_length), int(max_depth)))
+    args = (_p(a), len(a), _p(b), len(b), _p(o), len(o), _p(lengths), len(lengths), first_read_id, int(window_length),
+            int(max_depth))
+    if target_role_quality_sums is None and query_role_quality_sums is None and min_mean_quality == 0:
+        return _plan_and_table(L.gw_mapper_select_correction_layers, args)
+    sa, sb = _sums_for(target_role_quality_sums, len(a)), _sums_for(query_role_quality_sums, len(b))
+    return _plan_and_table(L.gw_mapper_select_correction_layers_weighted,
+                           args + (None if sa is None else _p(sa), None if sb is None else _p(sb),
+                                   int(min_mean_quality)))
 
 
 def correction_windows(overlaps, reads, window_length=500, max_depth=30, first_read_id=0, max_device_bytes=0,
@@ -559,6 +702,20 @@ def correction_windows(overlaps, reads, window_length=500, max_depth=30, first_r
     _, _, _, (bases, offsets, per_window, owners, index) = _correction_windows(
         overlaps, reads, window_length, max_depth, first_read_id, max_device_bytes, stream, timings)
     return _split_windows(bases, offsets, per_window, owners, index)
+
+
+def correction_windows_weighted(overlaps, reads, qualities, window_length=500, max_depth=30, min_mean_quality=10,
+                                first_read_id=0, max_device_bytes=0, stream=None, timings=None):
+    """correction_windows with the base qualities of the set: [(read, window, [backbone,
+    layer, ...], [weights, ...]), ...] as overlap_windows_weighted returns them. The records of both roles are
+    filtered by their quality sums -- a target-role record's layer comes from the pair's query read, a query-role
+    record's from its target read --, and every sequence, backbones included, gets the weights c - 33 of its bases.
+    qualities None: unit weights and the layers of correction_windows. Refusals and `timings` as for
+    overlap_windows_weighted."""
+    weighted = dict(qualities=pack_qualities(qualities, reads), min_mean_quality=_threshold(min_mean_quality))
+    _, _, _, (bases, offsets, per_window, owners, index) = _correction_windows(
+        overlaps, reads, window_length, max_depth, first_read_id, max_device_bytes, stream, timings, weighted)
+    return _split_weighted_windows(bases, weighted["weights"], offsets, per_window, owners, index)
 
 
 def group_reads_into_indices(read_lengths, max_basepairs_per_index):

@@ -349,13 +349,21 @@ def process_windows_multi_device(windows, max_sequences_per_poa, max_sequence_si
                                  memory_per_device=-1, output_type="consensus", band_mode="static_band",
                                  alignment_band_width=256, max_consensus_size=None, max_nodes_per_graph=None,
                                  matrix_sequence_dimension=None, max_banded_pred_distance=None, gap_score=-8,
-                                 mismatch_score=-6, match_score=8):
+                                 mismatch_score=-6, match_score=8, weights=None):
     """cudapoa::process_windows_multi_device: every window through one worker (host thread + stream + Batch) per entry of
     `devices` x batches_per_device; a device id may repeat (logical shards of one device). Windows are pulled from a shared
     cursor and results are placed by global window index, so the output does not depend on the worker layout.
-    Returns dict(consensus, coverage | msa, status, worker, launches, seconds)."""
+    Returns dict(consensus, coverage | msa, status, worker, launches, seconds).
+    weights: None, or per window a list of per-read None (unit weights) or int8 sequences of the read's length, as
+    CudaPoaBatch.add_poa_group takes them (gw_poa_multi_device_run_weighted). Weights that do not match the windows
+    raise ValueError; a negative weight raises RuntimeError. A window one of whose reads has nothing but zero weights
+    reports status zero_weighted_poa_sequence, comes back empty and takes part in no launch."""
     L = _bind(_native.host())
     vp, i32 = C.c_void_p, C.c_int32
+    L.gw_poa_multi_device_run_weighted.restype = vp
+    L.gw_poa_multi_device_run_weighted.argtypes = [i32, C.POINTER(i32), C.POINTER(C.c_char_p), C.POINTER(i32),
+                                                   C.POINTER(vp), C.POINTER(_native.PoaBatchConfig), C.POINTER(i32), i32,
+                                                   i32, C.c_int64, C.c_int8, C.c_int16, C.c_int16, C.c_int16]
     L.gw_poa_multi_device_run.restype = vp
     L.gw_poa_multi_device_run.argtypes = [i32, C.POINTER(i32), C.POINTER(C.c_char_p), C.POINTER(i32),
                                           C.POINTER(_native.PoaBatchConfig), C.POINTER(i32), i32, i32, C.c_int64, C.c_int8,
@@ -393,8 +401,20 @@ def process_windows_multi_device(windows, max_sequences_per_poa, max_sequence_si
     lens = (i32 * max(len(flat), 1))(*[len(b) for b in flat])
     devs = (i32 * len(devices))(*devices)
     mask = 2 if output_type == "msa" else 1
-    h = L.gw_poa_multi_device_run(n, per_window, seqs, lens, C.byref(cfg), devs, len(devices), batches_per_device,
-                                  int(memory_per_device), mask, gap_score, mismatch_score, match_score)
+    if weights is None:
+        h = L.gw_poa_multi_device_run(n, per_window, seqs, lens, C.byref(cfg), devs, len(devices), batches_per_device,
+                                      int(memory_per_device), mask, gap_score, mismatch_score, match_score)
+    else:
+        if len(weights) != n or any(len(ws) != len(w) for ws, w in zip(weights, raw)):
+            raise ValueError("weights: one entry per window and per read is needed")
+        keep = [None if x is None else np.ascontiguousarray(x, dtype=np.int8) for ws in weights for x in ws]
+        if any(x is not None and (x.ndim != 1 or len(x) != len(b)) for x, b in zip(keep, flat)):
+            raise ValueError("weights: a read's weights must be None or one per base")
+        # (the array interface gives the address without building a ctypes object per read)
+        wptr = (vp * max(len(flat), 1))(*[None if x is None else x.__array_interface__["data"][0] for x in keep])
+        h = L.gw_poa_multi_device_run_weighted(n, per_window, seqs, lens, wptr, C.byref(cfg), devs, len(devices),
+                                               batches_per_device, int(memory_per_device), mask, gap_score,
+                                               mismatch_score, match_score)
     if not h:
         raise RuntimeError(L.gw_last_error().decode())
     try:

@@ -728,10 +728,11 @@ struct gw_poa_multi
     poa::MultiDeviceOutput out;
 };
 
-gw_poa_multi* gw_poa_multi_device_run(int32_t n_windows, const int32_t* reads_per_window, const char* const* seqs,
-                                      const int32_t* lengths, const gw_poa_batch_config* cfg, const int32_t* devices,
-                                      int32_t n_devices, int32_t batches_per_device, int64_t memory_per_device, int8_t output_mask,
-                                      int16_t gap_score, int16_t mismatch_score, int16_t match_score)
+// gw_poa_multi_device_run and gw_poa_multi_device_run_weighted (weights NULL: the call without weights)
+static gw_poa_multi* multi_device_run(int32_t n_windows, const int32_t* reads_per_window, const char* const* seqs,
+                                      const int32_t* lengths, const int8_t* const* weights, const gw_poa_batch_config* cfg,
+                                      const int32_t* devices, int32_t n_devices, int32_t batches_per_device, int64_t memory_per_device,
+                                      int8_t output_mask, int16_t gap_score, int16_t mismatch_score, int16_t match_score)
 {
     GW_TRY
     const std::vector<std::vector<std::string>> windows = unpack_windows(n_windows, reads_per_window, seqs, lengths);
@@ -745,9 +746,42 @@ gw_poa_multi* gw_poa_multi_device_run(int32_t n_windows, const int32_t* reads_pe
     mc.mismatch_score     = mismatch_score;
     mc.match_score        = match_score;
     auto h = std::make_unique<gw_poa_multi>();
-    poa::process_windows_multi_device(h->out, windows, c, mc);
+    if (weights == nullptr)
+        poa::process_windows_multi_device(h->out, windows, c, mc);
+    else
+    {
+        std::vector<std::vector<std::vector<int8_t>>> per_window(windows.size());
+        size_t at = 0;
+        for (size_t w = 0; w < windows.size(); ++w)
+            for (const std::string& read : windows[w])
+            {
+                per_window[w].emplace_back();
+                if (weights[at] != nullptr) per_window[w].back().assign(weights[at], weights[at] + read.size());
+                ++at;
+            }
+        poa::process_windows_multi_device(h->out, windows, per_window, c, mc);
+    }
     return h.release();
     GW_CATCH(nullptr)
+}
+
+gw_poa_multi* gw_poa_multi_device_run(int32_t n_windows, const int32_t* reads_per_window, const char* const* seqs,
+                                      const int32_t* lengths, const gw_poa_batch_config* cfg, const int32_t* devices,
+                                      int32_t n_devices, int32_t batches_per_device, int64_t memory_per_device, int8_t output_mask,
+                                      int16_t gap_score, int16_t mismatch_score, int16_t match_score)
+{
+    return multi_device_run(n_windows, reads_per_window, seqs, lengths, nullptr, cfg, devices, n_devices, batches_per_device,
+                            memory_per_device, output_mask, gap_score, mismatch_score, match_score);
+}
+
+gw_poa_multi* gw_poa_multi_device_run_weighted(int32_t n_windows, const int32_t* reads_per_window, const char* const* seqs,
+                                               const int32_t* lengths, const int8_t* const* weights, const gw_poa_batch_config* cfg,
+                                               const int32_t* devices, int32_t n_devices, int32_t batches_per_device,
+                                               int64_t memory_per_device, int8_t output_mask, int16_t gap_score,
+                                               int16_t mismatch_score, int16_t match_score)
+{
+    return multi_device_run(n_windows, reads_per_window, seqs, lengths, weights, cfg, devices, n_devices, batches_per_device,
+                            memory_per_device, output_mask, gap_score, mismatch_score, match_score);
 }
 
 void gw_poa_multi_destroy(gw_poa_multi* h) { delete h; }

@@ -98,18 +98,31 @@ struct WindowQueue
     size_t front() const { return order ? static_cast<size_t>((*order)[next]) : next; }
 };
 
+using WindowWeights = std::vector<std::vector<std::vector<int8_t>>>; // [window][read][base]; an empty read: unit weights
+
 // Moves windows from the queue into the batch until it is full, holds fill_cap windows, or the queue is empty. in_batch gets
 // the global index of every output slot of the launch, windows.size() for a placeholder slot; refusals go to out.status.
+// weights: nullptr, or the checked weights of a weighted call (check_weights), whose refused windows are passed over.
 void fill_batch(Batch& batch, std::vector<size_t>& in_batch, WindowQueue& queue, int32_t fill_cap, const std::vector<std::vector<std::string>>& windows,
-                int32_t worker, MultiDeviceOutput& out, const char* holds_no_window)
+                int32_t worker, MultiDeviceOutput& out, const char* holds_no_window, const WindowWeights* weights = nullptr)
 {
     while (!queue.empty() && batch.get_total_poas() < fill_cap)
     {
         const size_t w                         = queue.front();
         const std::vector<std::string>& window = windows[w];
+        if (weights != nullptr && out.status[w] != StatusType::success) // refused by check_weights: it takes no slot
+        {
+            out.worker_of_window[w] = worker;
+            queue.next++;
+            continue;
+        }
         Group group;
         group.reserve(window.size());
-        for (const std::string& read : window) group.push_back(Entry{read.c_str(), nullptr, get_size<int32_t>(read)});
+        for (size_t r = 0; r < window.size(); r++)
+        {
+            const int8_t* of_read = weights != nullptr && !(*weights)[w][r].empty() ? (*weights)[w][r].data() : nullptr;
+            group.push_back(Entry{window[r].c_str(), of_read, get_size<int32_t>(window[r])});
+        }
         std::vector<StatusType> per_read;
         const StatusType st = batch.add_poa_group(per_read, group);
         if (st == StatusType::exceeded_maximum_poas)
@@ -182,7 +195,8 @@ struct SharedCursor
 // (cudapoa/benchmarks/multi_batch.hpp: the batches are created in the constructor, process_batches() is what is timed).
 void worker_loop(int32_t worker, int32_t device, cudaStream_t stream, DefaultDeviceAllocator allocator, int64_t memory,
                  const BatchConfig& batch_size, const MultiDeviceConfig& config, const std::vector<std::vector<std::string>>& windows,
-                 SharedCursor& cursor, MultiDeviceOutput& out, std::atomic<int32_t>& launches, Rendezvous& created, ResultClock& results)
+                 SharedCursor& cursor, MultiDeviceOutput& out, std::atomic<int32_t>& launches, Rendezvous& created, ResultClock& results,
+                 const WindowWeights* weights)
 {
     scoped_device_switch dev(device);
     std::unique_ptr<Batch> batch = create_batch(device, stream, allocator, memory, config.output_mask, batch_size, config.gap_score,
@@ -208,7 +222,7 @@ void worker_loop(int32_t worker, int32_t device, cudaStream_t stream, DefaultDev
         {
             // the cursor only moves under the lock: a window is taken by exactly one worker
             std::lock_guard<std::mutex> guard(cursor.mutex);
-            fill_batch(*batch, in_batch, cursor.queue, fill_cap, windows, worker, out, "a batch of this configuration cannot hold a single window");
+            fill_batch(*batch, in_batch, cursor.queue, fill_cap, windows, worker, out, "a batch of this configuration cannot hold a single window", weights);
         }
         if (batch->get_total_poas() == 0)
         {
@@ -222,10 +236,53 @@ void worker_loop(int32_t worker, int32_t device, cudaStream_t stream, DefaultDev
         store_results(*batch, want_msa, in_batch, out);
     }
 }
+// The weights of a weighted call against its windows: one entry per window and per read, a read's weights empty or as many
+// as its bases, none of them negative -- anything else throws before a worker starts. A window one of whose reads carries
+// nothing but zeros is refused as a whole, with the status a Batch gives that read, and never reaches a batch.
+void check_weights(const std::vector<std::vector<std::string>>& windows, const WindowWeights& weights, MultiDeviceOutput& out)
+{
+    if (weights.size() != windows.size()) throw std::invalid_argument("weights: one entry per window is needed");
+    for (size_t w = 0; w < windows.size(); w++)
+    {
+        if (weights[w].size() != windows[w].size()) throw std::invalid_argument("weights: window " + std::to_string(w) + " needs one entry per read");
+        for (size_t r = 0; r < windows[w].size(); r++)
+        {
+            const std::vector<int8_t>& of_read = weights[w][r];
+            if (of_read.empty()) continue;
+            if (of_read.size() != windows[w][r].size())
+                throw std::invalid_argument("weights: read " + std::to_string(r) + " of window " + std::to_string(w) + " needs one weight per base");
+            bool all_zero = true;
+            for (int8_t x : of_read)
+            {
+                throw_on_negative(x, "Base weights need to be non-negative");
+                if (x > 0) all_zero = false;
+            }
+            if (all_zero) out.status[w] = StatusType::zero_weighted_poa_sequence;
+        }
+    }
+}
+
+void run_multi_device(MultiDeviceOutput& out, const std::vector<std::vector<std::string>>& windows, const WindowWeights* weights,
+                      const BatchConfig& batch_size, const MultiDeviceConfig& config);
 } // namespace
 
 void process_windows_multi_device(MultiDeviceOutput& out, const std::vector<std::vector<std::string>>& windows,
                                   const BatchConfig& batch_size, const MultiDeviceConfig& config)
+{
+    run_multi_device(out, windows, nullptr, batch_size, config);
+}
+
+void process_windows_multi_device(MultiDeviceOutput& out, const std::vector<std::vector<std::string>>& windows,
+                                  const std::vector<std::vector<std::vector<int8_t>>>& weights, const BatchConfig& batch_size,
+                                  const MultiDeviceConfig& config)
+{
+    run_multi_device(out, windows, &weights, batch_size, config);
+}
+
+namespace
+{
+void run_multi_device(MultiDeviceOutput& out, const std::vector<std::vector<std::string>>& windows, const WindowWeights* weights,
+                      const BatchConfig& batch_size, const MultiDeviceConfig& config)
 {
     if (config.devices.empty()) throw std::invalid_argument("at least one device is needed");
     if (config.batches_per_device < 1) throw std::invalid_argument("batches_per_device has to be at least 1");
@@ -238,6 +295,7 @@ void process_windows_multi_device(MultiDeviceOutput& out, const std::vector<std:
         entries_of_device[d]++;
     }
     prepare_output(out, windows.size(), (config.output_mask & OutputType::msa) != 0);
+    if (weights != nullptr) check_weights(windows, *weights, out);
     if (windows.empty()) return;
 
     // one allocator per entry of `devices`, shared by that entry's batches (as multi_batch.hpp:52-60 shares one)
@@ -296,7 +354,7 @@ void process_windows_multi_device(MultiDeviceOutput& out, const std::vector<std:
                     threads.emplace_back([&, worker, stream, memory, device = g.device, allocator = g.allocator]() {
                         try
                         {
-                            worker_loop(worker, device, stream, allocator, memory, batch_size, config, windows, cursor, out, launches, created, results);
+                            worker_loop(worker, device, stream, allocator, memory, batch_size, config, windows, cursor, out, launches, created, results, weights);
                         }
                         catch (...)
                         {
@@ -320,6 +378,8 @@ void process_windows_multi_device(MultiDeviceOutput& out, const std::vector<std:
     out.launches = launches.load();
     rethrow_first(errors);
 }
+} // namespace
+
 // ---- size classes -------------------------------------------------------------------------------------------------------
 void plan_size_classes(SizeClassPlan& plan, const std::vector<int32_t>& longest, const std::vector<int32_t>& reads, bool msa_flag,
                        int32_t band_width, BandMode band_mode, float adaptive_storage_factor, float graph_length_factor,

@@ -161,6 +161,11 @@ struct gw_mapper_windows
     std::vector<gwm_segment> query_role_segments;
     std::vector<int64_t> query_role_offsets{0};
     float query_role_ms = 0.f;
+    // weighted calls only: one weight per byte of `bases`, the quality sums of `segments` and of query_role_segments
+    // (empty where the supplying set has no qualities), and the device time of the sums and of the weight gather
+    std::vector<int8_t> weights;
+    std::vector<uint32_t> quality_sums, query_role_quality_sums;
+    float quality_ms[2] = {0.f, 0.f};
 };
 
 #endif

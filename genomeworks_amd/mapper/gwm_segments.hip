@@ -18,6 +18,7 @@
 // chunk in its query role: the windows are those of the query read, whose positions ascend in forward column order on
 // both strands, and the ranges of the record are those of the target positions.
 #include "gwm_align_chunks.hpp"
+#include "gwm_gather_plan.hpp"
 
 #include <deque>
 
@@ -149,34 +150,6 @@ __global__ void __launch_bounds__(kThreads) segment_kernel(const gwm_overlap* __
         if (edit_distances)
             edit_distances[i] = len ? static_cast<int32_t>(edits) : (starts[2 * i + 2] == slot ? 0 : -1);
     }
-}
-
-// bad[0] |= 1: a set other than 0 / 1 or a read outside its set; |= 2: begin > end or an end beyond its read;
-// |= 4: the sequence does not lie within out
-__global__ void __launch_bounds__(kThreads) plan_validate_kernel(const gwm_gather_entry* __restrict__ plan, int64_t n,
-                                                                 const int64_t* __restrict__ out_starts, ReadSet q,
-                                                                 ReadSet t, int64_t out_bytes,
-                                                                 uint32_t* __restrict__ bad)
-{
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= n)
-        return;
-    const gwm_gather_entry e = plan[i];
-    const ReadSet& set       = e.set ? t : q;
-    if (e.set > 1 || e.read >= set.n_reads)
-    {
-        atomicOr(bad, 1u);
-        return;
-    }
-    const uint64_t length = static_cast<uint64_t>(set.offsets[e.read + 1] - set.offsets[e.read]);
-    if (e.begin > e.end || e.end > length)
-    {
-        atomicOr(bad, 2u);
-        return;
-    }
-    const int64_t at = out_starts[i];
-    if (at < 0 || at > out_bytes || static_cast<int64_t>(e.end - e.begin) > out_bytes - at)
-        atomicOr(bad, 4u);
 }
 
 // Block b writes sequence b of the plan to out[out_starts[b] ..): lane L of a pass takes output byte L, ascending
@@ -389,17 +362,7 @@ int gwm_gather_sequences(const gwm_gather_entry* plan, int64_t n, const int64_t*
         hipStream_t s = static_cast<hipStream_t>(stream);
         const ReadSet q{reinterpret_cast<const uint8_t*>(query_bases), query_offsets, static_cast<uint32_t>(n_queries), 0};
         const ReadSet t{reinterpret_cast<const uint8_t*>(target_bases), target_offsets, static_cast<uint32_t>(n_targets), 0};
-        dbuf<uint32_t> bad(1);
-        GWM_CHECK(hipMemsetAsync(bad.p, 0, sizeof(uint32_t), s));
-        plan_validate_kernel<<<grid_for(n), kThreads, 0, s>>>(plan, n, out_starts, q, t, out_bytes, bad.p);
-        GWM_CHECK(hipGetLastError());
-        const uint32_t what = to_host(bad.p, s);
-        if (what & 1u)
-            throw std::invalid_argument("gwm_gather_sequences: a sequence names a read outside the read sets");
-        if (what & 2u)
-            throw std::invalid_argument("gwm_gather_sequences: a sequence lies beyond the end of its read");
-        if (what & 4u)
-            throw std::invalid_argument("gwm_gather_sequences: a sequence does not lie within the output");
+        validate_plan("gwm_gather_sequences", plan, n, out_starts, q, t, out_bytes, s);
         Events ev(2);
         ev.record(0, s);
         gather_sequences_kernel<<<static_cast<unsigned>(n), kThreads, 0, s>>>(plan, out_starts, q, t,

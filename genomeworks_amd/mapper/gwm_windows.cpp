@@ -42,6 +42,12 @@ bool spans_its_window(const gwm_segment& s, int64_t length, int64_t W)
     return s.target_first - k * W <= slack && end_k - 1 - s.target_last <= slack && bases >= 1 && bases <= 2 * W;
 }
 
+// Q2 of section 3l: does a record that supplies `bases` bases of the quality sum `sum` pass the quality filter
+bool passes_quality(uint32_t sum, int64_t bases, int32_t min_mean_quality)
+{
+    return sum > 0 && static_cast<int64_t>(sum) >= static_cast<int64_t>(min_mean_quality) * bases;
+}
+
 struct layer
 {
     int64_t slot; // position of the window in the table
@@ -97,10 +103,13 @@ namespace gwm
 window_selection select_layers(const gwm_segment* segments, int64_t n_segments, const gwm_overlap* overlaps,
                                int64_t n_overlaps, int32_t n_queries, uint32_t first_query_read_id,
                                const int64_t* target_lengths, int32_t n_targets, uint32_t first_target_read_id,
-                               int32_t window_length, int32_t max_depth)
+                               int32_t window_length, int32_t max_depth, const uint32_t* quality_sums,
+                               int32_t min_mean_quality)
 {
     if (window_length < 1)
         throw std::invalid_argument("select_layers: window_length below 1");
+    if (min_mean_quality < 0)
+        throw std::invalid_argument("select_layers: negative min_mean_quality");
     if (max_depth < 0)
         throw std::invalid_argument("select_layers: negative max_depth");
     if (n_segments < 0 || n_overlaps < 0 || n_queries < 0 || n_targets < 0)
@@ -138,6 +147,9 @@ window_selection select_layers(const gwm_segment* segments, int64_t n_segments, 
         if (!lies_in_its_window(s, first_window[t + 1] - first_window[t], target_lengths[t], W))
             throw std::invalid_argument("select_layers: segment " + std::to_string(j) + " does not lie in its window");
         if (kept[o.query_read_id - first_query_read_id] != static_cast<int64_t>(s.overlap))
+            continue;
+        if (quality_sums &&
+            !passes_quality(quality_sums[j], static_cast<int64_t>(s.query_end) - s.query_begin, min_mean_quality))
             continue;
         if (spans_its_window(s, target_lengths[t], W))
             layers.push_back({first_window[t] + s.window, s.target_first, s.overlap, 0u, &s});
@@ -183,11 +195,15 @@ std::vector<int64_t> select_pairs(const gwm_overlap* overlaps, int64_t n_overlap
 window_selection select_correction_layers(const gwm_segment* target_role, int64_t n_target_role,
                                           const gwm_segment* query_role, int64_t n_query_role, const gwm_overlap* pairs,
                                           int64_t n_pairs, const int64_t* read_lengths, int32_t n_reads,
-                                          uint32_t first_read_id, int32_t window_length, int32_t max_depth)
+                                          uint32_t first_read_id, int32_t window_length, int32_t max_depth,
+                                          const uint32_t* target_role_quality_sums,
+                                          const uint32_t* query_role_quality_sums, int32_t min_mean_quality)
 {
     const std::string who = "select_correction_layers";
     if (window_length < 1)
         throw std::invalid_argument(who + ": window_length below 1");
+    if (min_mean_quality < 0)
+        throw std::invalid_argument(who + ": negative min_mean_quality");
     if (max_depth < 0)
         throw std::invalid_argument(who + ": negative max_depth");
     if (n_target_role < 0 || n_query_role < 0 || n_pairs < 0 || n_reads < 0)
@@ -207,6 +223,7 @@ window_selection select_correction_layers(const gwm_segment* target_role, int64_
     {
         const gwm_segment* segments = role ? query_role : target_role;
         const int64_t n_segments    = role ? n_query_role : n_target_role;
+        const uint32_t* sums        = role ? query_role_quality_sums : target_role_quality_sums;
         for (int64_t j = 0; j < n_segments; ++j)
         {
             const gwm_segment& s = segments[j];
@@ -217,6 +234,8 @@ window_selection select_correction_layers(const gwm_segment* target_role, int64_
             const uint32_t owner = (role ? o.query_read_id : o.target_read_id) - first_read_id;
             if (!lies_in_its_window(s, first_window[owner + 1] - first_window[owner], read_lengths[owner], W))
                 throw std::invalid_argument(who + which + " does not lie in its window");
+            if (sums && !passes_quality(sums[j], static_cast<int64_t>(s.query_end) - s.query_begin, min_mean_quality))
+                continue;
             if (spans_its_window(s, read_lengths[owner], W))
                 layers.push_back({first_window[owner] + s.window, s.target_first, s.overlap, role, &s});
         }

@@ -40,9 +40,65 @@ gw_mapper_overlaps* map_batched_guarded(const reads_view& queries, const reads_v
                    static_cast<gw_mapper_overlaps*>(nullptr));
 }
 
-// the windows of a selection into h: their table, and their bases gathered on the device and copied out once
+// The qualities of a weighted call: Phred+33 bytes that share the offsets of the bases, or
+// nullptr for a set that has none. weighted false: a call of the entry points without qualities, which does nothing of
+// what follows.
+struct quality_options
+{
+    bool weighted                = false;
+    const char* query_qualities  = nullptr; // in read correction: of the one set
+    const char* target_qualities = nullptr;
+    int32_t min_mean_quality     = 0;
+};
+
+// every byte in 33..126, before anything is uploaded
+void check_qualities(const std::string& who, const char* qualities, const reads_view& reads)
+{
+    if (!qualities)
+        return;
+    if (reads.n < 0)
+        throw std::invalid_argument(who + ": negative number of reads");
+    const int64_t bytes = reads.offsets[reads.n];
+    for (int64_t i = 0; i < bytes; ++i)
+        if (qualities[i] < 33 || qualities[i] > 126)
+            throw std::invalid_argument(who + ": quality byte " + std::to_string(i) + " lies outside 33..126");
+}
+
+void check_quality_options(const std::string& who, const quality_options& w, const reads_view& queries,
+                           const reads_view& targets)
+{
+    if (w.min_mean_quality < 0)
+        throw std::invalid_argument(who + ": negative min_mean_quality");
+    check_qualities(who, w.query_qualities, queries);
+    check_qualities(who, w.target_qualities, targets);
+}
+
+// a device copy of a set's qualities next to its reads; no qualities, no copy
+void upload_qualities(dbuf<char>& device, const char* qualities, const reads_view& reads)
+{
+    if (qualities)
+        device.upload(qualities, std::max<int64_t>(reads.offsets[reads.n], 1));
+}
+
+// Q1: the quality sums of the records of one role, on the device, and their copy to the host (4 B per record)
+void quality_sums_of(const gwm_segments& s, const gwm_overlap* device_overlaps, int64_t n_overlaps, int32_t query_role,
+                     const char* device_qualities, const reads_view& device_reads, uint32_t first_read_id, void* stream,
+                     std::vector<uint32_t>& sums, float& sums_ms)
+{
+    sums.assign(static_cast<size_t>(s.n_segments), 0u);
+    dbuf<uint32_t> device_sums(s.n_segments);
+    float ms = 0.f;
+    throw_on(gwm_segment_quality_sums(s.segments, s.n_segments, device_overlaps, n_overlaps, query_role,
+                                      device_qualities, device_reads.offsets, device_reads.n, first_read_id,
+                                      device_sums.p, stream, &ms));
+    copy_out(sums.data(), device_sums.p, s.n_segments);
+    sums_ms += ms;
+}
+
+// the windows of a selection into h: their table, and their bases gathered on the device and copied out once; with
+// `qualities` (the device qualities of q and of t, either may be nullptr) their weights as well (Q3), one byte per base
 void gather_windows(gw_mapper_windows& h, window_selection selection, const reads_view& q, const reads_view& t,
-                    void* stream)
+                    void* stream, const char* const* qualities = nullptr)
 {
     h.windows = std::move(selection.windows);
     const std::vector<gwm_gather_entry>& plan = selection.plan;
@@ -62,6 +118,15 @@ void gather_windows(gw_mapper_windows& h, window_selection selection, const read
                                       q.offsets, q.n, t.bases, t.offsets, t.n, device_bases.p, total, stream,
                                       &h.stage_ms[3]));
         copy_out(h.bases.data(), device_bases.p, total);
+        if (qualities)
+        {
+            h.weights.resize(static_cast<size_t>(total));
+            dbuf<int8_t> device_weights(total);
+            throw_on(gwm_gather_weights(device_plan.p, static_cast<int64_t>(plan.size()), device_starts.p, qualities[0],
+                                        q.offsets, q.n, qualities[1], t.offsets, t.n, device_weights.p, total, stream,
+                                        &h.quality_ms[1]));
+            copy_out(h.weights.data(), device_weights.p, total);
+        }
     }
 }
 
@@ -84,7 +149,7 @@ void copy_segments(const gwm_segments& s, int64_t n, std::vector<gwm_segment>& s
 gw_mapper_windows* window_overlaps(const void* overlaps, int64_t n, const reads_view& query_reads,
                                    uint32_t first_query_read_id, const reads_view& target_reads,
                                    uint32_t first_target_read_id, int32_t window_length, int32_t max_depth,
-                                   int64_t max_device_bytes, void* stream)
+                                   int64_t max_device_bytes, void* stream, const quality_options& options = {})
 {
     return guarded([&] {
         std::unique_ptr<gw_mapper_windows> h(new gw_mapper_windows());
@@ -92,7 +157,16 @@ gw_mapper_windows* window_overlaps(const void* overlaps, int64_t n, const reads_
             throw std::invalid_argument("gw_mapper_window_overlaps: negative number of overlaps");
         const gwm_overlap* host_overlaps = static_cast<const gwm_overlap*>(overlaps);
         read_sets reads(query_reads, target_reads);
+        quality_options w = options;
+        if (reads.all_to_all) // the targets are the queries, with the queries' qualities
+            w.target_qualities = nullptr;
+        if (w.weighted)
+            check_quality_options("gw_mapper_window_overlaps_weighted", w, reads.queries, reads.targets);
         reads.upload(); // once: the segments pass and the window gather read the same device copies
+        dbuf<char> query_qualities, target_qualities; // once as well, next to the reads
+        upload_qualities(query_qualities, w.query_qualities, reads.queries);
+        if (!reads.all_to_all)
+            upload_qualities(target_qualities, w.target_qualities, reads.targets);
         dbuf<gwm_overlap> d;
         d.upload(host_overlaps, n);
         const reads_view &q = reads.device_queries, &t = reads.device_targets;
@@ -112,10 +186,25 @@ gw_mapper_windows* window_overlaps(const void* overlaps, int64_t n, const reads_
         std::vector<int64_t> target_lengths(static_cast<size_t>(reads.targets.n));
         for (int32_t r = 0; r < reads.targets.n; ++r)
             target_lengths[r] = reads.targets.offsets[r + 1] - reads.targets.offsets[r];
-        window_selection selection =
-            select_layers(h->segments.data(), s.n_segments, host_overlaps, n, reads.queries.n, first_query_read_id,
-                          target_lengths.data(), reads.targets.n, first_target_read_id, window_length, max_depth);
-        gather_windows(*h, std::move(selection), q, t, stream);
+        if (!w.weighted)
+        {
+            window_selection selection =
+                select_layers(h->segments.data(), s.n_segments, host_overlaps, n, reads.queries.n, first_query_read_id,
+                              target_lengths.data(), reads.targets.n, first_target_read_id, window_length, max_depth);
+            gather_windows(*h, std::move(selection), q, t, stream);
+            return h.release();
+        }
+        // the queries supply every layer: their qualities, where there are any, decide which records are layers (Q2)
+        if (query_qualities.p)
+            quality_sums_of(s, d.p, n, 0, query_qualities.p, q, first_query_read_id, stream, h->quality_sums,
+                            h->quality_ms[0]);
+        window_selection selection = select_layers(
+            h->segments.data(), s.n_segments, host_overlaps, n, reads.queries.n, first_query_read_id,
+            target_lengths.data(), reads.targets.n, first_target_read_id, window_length, max_depth,
+            query_qualities.p ? h->quality_sums.data() : nullptr, w.min_mean_quality);
+        const char* const device_qualities[2] = {query_qualities.p,
+                                                 reads.all_to_all ? query_qualities.p : target_qualities.p};
+        gather_windows(*h, std::move(selection), q, t, stream, device_qualities);
         return h.release();
     }, static_cast<gw_mapper_windows*>(nullptr));
 }
@@ -124,12 +213,14 @@ gw_mapper_windows* window_overlaps(const void* overlaps, int64_t n, const reads_
 // stand and nothing is selected or gathered
 gw_mapper_windows* correction_windows(const void* overlaps, int64_t n, const reads_view& host_reads,
                                       uint32_t first_read_id, int32_t window_length, int32_t max_depth,
-                                      int64_t max_device_bytes, void* stream)
+                                      int64_t max_device_bytes, void* stream, const quality_options& w = {})
 {
     return guarded([&] {
         std::unique_ptr<gw_mapper_windows> h(new gw_mapper_windows());
         if (n < 0)
             throw std::invalid_argument("gw_mapper_correction_windows: negative number of overlaps");
+        if (w.weighted)
+            check_quality_options("gw_mapper_correction_windows_weighted", w, host_reads, host_reads);
         const gwm_overlap* given = static_cast<const gwm_overlap*>(overlaps);
         std::vector<gwm_overlap> pairs;
         if (max_depth < 0)
@@ -147,6 +238,8 @@ gw_mapper_windows* correction_windows(const void* overlaps, int64_t n, const rea
         const int64_t n_pairs = static_cast<int64_t>(pairs.size());
         read_sets reads(host_reads, reads_view{nullptr, nullptr, 0});
         reads.upload(); // once: the segments pass and the window gather read the same device copy
+        dbuf<char> qualities; // once as well, next to the reads
+        upload_qualities(qualities, w.query_qualities, host_reads);
         dbuf<gwm_overlap> d;
         d.upload(pairs.data(), n_pairs);
         const reads_view& r = reads.device_queries;
@@ -164,14 +257,52 @@ gw_mapper_windows* correction_windows(const void* overlaps, int64_t n, const rea
         std::vector<int64_t> lengths(static_cast<size_t>(host_reads.n));
         for (int32_t i = 0; i < host_reads.n; ++i)
             lengths[i] = host_reads.offsets[i + 1] - host_reads.offsets[i];
+        if (!w.weighted)
+        {
+            gather_windows(*h,
+                           select_correction_layers(h->segments.data(), target_role.s.n_segments,
+                                                    h->query_role_segments.data(), query_role.s.n_segments,
+                                                    pairs.data(), n_pairs, lengths.data(), host_reads.n, first_read_id,
+                                                    window_length, max_depth),
+                           r, r, stream);
+            return h.release();
+        }
+        // a target-role record's layer comes from the pair's query read, a query-role record's from its target read
+        if (qualities.p)
+        {
+            quality_sums_of(target_role.s, d.p, n_pairs, 0, qualities.p, r, first_read_id, stream, h->quality_sums,
+                            h->quality_ms[0]);
+            quality_sums_of(query_role.s, d.p, n_pairs, 1, qualities.p, r, first_read_id, stream,
+                            h->query_role_quality_sums, h->quality_ms[0]);
+        }
+        const char* const device_qualities[2] = {qualities.p, qualities.p};
         gather_windows(*h,
                        select_correction_layers(h->segments.data(), target_role.s.n_segments,
                                                 h->query_role_segments.data(), query_role.s.n_segments, pairs.data(),
                                                 n_pairs, lengths.data(), host_reads.n, first_read_id, window_length,
-                                                max_depth),
-                       r, r, stream);
+                                                max_depth, qualities.p ? h->quality_sums.data() : nullptr,
+                                                qualities.p ? h->query_role_quality_sums.data() : nullptr,
+                                                w.min_mean_quality),
+                       r, r, stream, device_qualities);
         return h.release();
     }, static_cast<gw_mapper_windows*>(nullptr));
+}
+
+// what the selection entry points of the C API return and write: the number of sequences; the flat plan and window
+// table where they are asked for and their capacities suffice
+int64_t copy_selection(const window_selection& s, uint32_t* plan, int64_t plan_capacity, int64_t* n_windows,
+                       uint32_t* window_table, int64_t window_capacity)
+{
+    const int64_t sequences = static_cast<int64_t>(s.plan.size()), windows = static_cast<int64_t>(s.windows.size());
+    static_assert(sizeof(gwm_gather_entry) == 5 * sizeof(uint32_t) && sizeof(window_record) == 4 * sizeof(uint32_t),
+                  "the flat layouts of gw_mapper_select_layers");
+    if (plan && sequences <= plan_capacity && sequences > 0)
+        std::memcpy(plan, s.plan.data(), sizeof(gwm_gather_entry) * s.plan.size());
+    if (window_table && windows <= window_capacity && windows > 0)
+        std::memcpy(window_table, s.windows.data(), sizeof(window_record) * s.windows.size());
+    if (n_windows)
+        *n_windows = windows;
+    return sequences;
 }
 
 } // namespace
@@ -504,20 +635,25 @@ int64_t gw_mapper_select_layers(const void* segments, int64_t n_segments, const 
                                 int32_t max_depth, uint32_t* plan, int64_t plan_capacity, int64_t* n_windows,
                                 uint32_t* window_table, int64_t window_capacity)
 {
+    return gw_mapper_select_layers_weighted(segments, n_segments, overlaps, n_overlaps, n_queries, first_query_read_id,
+                                            target_lengths, n_targets, first_target_read_id, window_length, max_depth,
+                                            nullptr, 0, plan, plan_capacity, n_windows, window_table, window_capacity);
+}
+
+int64_t gw_mapper_select_layers_weighted(const void* segments, int64_t n_segments, const void* overlaps,
+                                         int64_t n_overlaps, int32_t n_queries, uint32_t first_query_read_id,
+                                         const int64_t* target_lengths, int32_t n_targets,
+                                         uint32_t first_target_read_id, int32_t window_length, int32_t max_depth,
+                                         const uint32_t* quality_sums, int32_t min_mean_quality, uint32_t* plan,
+                                         int64_t plan_capacity, int64_t* n_windows, uint32_t* window_table,
+                                         int64_t window_capacity)
+{
     return guarded([&] {
-        const window_selection s = select_layers(
-            static_cast<const gwm_segment*>(segments), n_segments, static_cast<const gwm_overlap*>(overlaps), n_overlaps,
-            n_queries, first_query_read_id, target_lengths, n_targets, first_target_read_id, window_length, max_depth);
-        const int64_t sequences = static_cast<int64_t>(s.plan.size()), windows = static_cast<int64_t>(s.windows.size());
-        static_assert(sizeof(gwm_gather_entry) == 5 * sizeof(uint32_t) && sizeof(window_record) == 4 * sizeof(uint32_t),
-                      "the flat layouts of gw_mapper_select_layers");
-        if (plan && sequences <= plan_capacity && sequences > 0)
-            std::memcpy(plan, s.plan.data(), sizeof(gwm_gather_entry) * s.plan.size());
-        if (window_table && windows <= window_capacity && windows > 0)
-            std::memcpy(window_table, s.windows.data(), sizeof(window_record) * s.windows.size());
-        if (n_windows)
-            *n_windows = windows;
-        return sequences;
+        return copy_selection(select_layers(static_cast<const gwm_segment*>(segments), n_segments,
+                                            static_cast<const gwm_overlap*>(overlaps), n_overlaps, n_queries,
+                                            first_query_read_id, target_lengths, n_targets, first_target_read_id,
+                                            window_length, max_depth, quality_sums, min_mean_quality),
+                              plan, plan_capacity, n_windows, window_table, window_capacity);
     }, int64_t(GW_MAPPER_ERROR));
 }
 
@@ -538,19 +674,29 @@ int64_t gw_mapper_select_correction_layers(const void* target_role, int64_t n_ta
                                            int32_t window_length, int32_t max_depth, uint32_t* plan, int64_t plan_capacity,
                                            int64_t* n_windows, uint32_t* window_table, int64_t window_capacity)
 {
+    return gw_mapper_select_correction_layers_weighted(target_role, n_target_role, query_role, n_query_role, pairs,
+                                                       n_pairs, read_lengths, n_reads, first_read_id, window_length,
+                                                       max_depth, nullptr, nullptr, 0, plan, plan_capacity, n_windows,
+                                                       window_table, window_capacity);
+}
+
+int64_t gw_mapper_select_correction_layers_weighted(const void* target_role, int64_t n_target_role,
+                                                    const void* query_role, int64_t n_query_role, const void* pairs,
+                                                    int64_t n_pairs, const int64_t* read_lengths, int32_t n_reads,
+                                                    uint32_t first_read_id, int32_t window_length, int32_t max_depth,
+                                                    const uint32_t* target_role_quality_sums,
+                                                    const uint32_t* query_role_quality_sums, int32_t min_mean_quality,
+                                                    uint32_t* plan, int64_t plan_capacity, int64_t* n_windows,
+                                                    uint32_t* window_table, int64_t window_capacity)
+{
     return guarded([&] {
-        const window_selection s = select_correction_layers(
-            static_cast<const gwm_segment*>(target_role), n_target_role, static_cast<const gwm_segment*>(query_role),
-            n_query_role, static_cast<const gwm_overlap*>(pairs), n_pairs, read_lengths, n_reads, first_read_id,
-            window_length, max_depth);
-        const int64_t sequences = static_cast<int64_t>(s.plan.size()), windows = static_cast<int64_t>(s.windows.size());
-        if (plan && sequences <= plan_capacity && sequences > 0)
-            std::memcpy(plan, s.plan.data(), sizeof(gwm_gather_entry) * s.plan.size());
-        if (window_table && windows <= window_capacity && windows > 0)
-            std::memcpy(window_table, s.windows.data(), sizeof(window_record) * s.windows.size());
-        if (n_windows)
-            *n_windows = windows;
-        return sequences;
+        return copy_selection(
+            select_correction_layers(static_cast<const gwm_segment*>(target_role), n_target_role,
+                                     static_cast<const gwm_segment*>(query_role), n_query_role,
+                                     static_cast<const gwm_overlap*>(pairs), n_pairs, read_lengths, n_reads,
+                                     first_read_id, window_length, max_depth, target_role_quality_sums,
+                                     query_role_quality_sums, min_mean_quality),
+            plan, plan_capacity, n_windows, window_table, window_capacity);
     }, int64_t(GW_MAPPER_ERROR));
 }
 
@@ -593,6 +739,88 @@ int64_t gw_mapper_windows_copy_query_role_segments(const gw_mapper_windows* wind
     if (query_role_ms)
         *query_role_ms = w.query_role_ms;
     return n;
+}
+
+gw_mapper_windows* gw_mapper_window_overlaps_weighted(const void* overlaps, int64_t n, const char* query_bases,
+                                                      const int64_t* query_offsets, int32_t n_queries,
+                                                      uint32_t first_query_read_id, const char* target_bases,
+                                                      const int64_t* target_offsets, int32_t n_targets,
+                                                      uint32_t first_target_read_id, const char* query_qualities,
+                                                      const char* target_qualities, int32_t min_mean_quality,
+                                                      int32_t window_length, int32_t max_depth,
+                                                      int64_t max_device_bytes, void* stream)
+{
+    if (max_depth < 0)
+    {
+        g_capi_error = "gw_mapper_window_overlaps_weighted: negative max_depth";
+        return nullptr;
+    }
+    return window_overlaps(overlaps, n, {query_bases, query_offsets, n_queries}, first_query_read_id,
+                           {target_bases, target_offsets, n_targets}, first_target_read_id, window_length, max_depth,
+                           max_device_bytes, stream, {true, query_qualities, target_qualities, min_mean_quality});
+}
+
+gw_mapper_windows* gw_mapper_correction_windows_weighted(const void* overlaps, int64_t n, const char* bases,
+                                                         const int64_t* offsets, int32_t n_reads,
+                                                         uint32_t first_read_id, const char* qualities,
+                                                         int32_t min_mean_quality, int32_t window_length,
+                                                         int32_t max_depth, int64_t max_device_bytes, void* stream)
+{
+    if (max_depth < 0)
+    {
+        g_capi_error = "gw_mapper_correction_windows_weighted: negative max_depth";
+        return nullptr;
+    }
+    return correction_windows(overlaps, n, {bases, offsets, n_reads}, first_read_id, window_length, max_depth,
+                              max_device_bytes, stream, {true, qualities, nullptr, min_mean_quality});
+}
+
+int gw_mapper_windows_copy_weights(const gw_mapper_windows* windows, int8_t* weights, uint32_t* quality_sums,
+                                   uint32_t* query_role_quality_sums, float* ms)
+{
+    const gw_mapper_windows& w = *windows;
+    if (weights && !w.weights.empty())
+        std::memcpy(weights, w.weights.data(), w.weights.size());
+    if (quality_sums && !w.quality_sums.empty())
+        std::memcpy(quality_sums, w.quality_sums.data(), sizeof(uint32_t) * w.quality_sums.size());
+    if (query_role_quality_sums && !w.query_role_quality_sums.empty())
+        std::memcpy(query_role_quality_sums, w.query_role_quality_sums.data(),
+                    sizeof(uint32_t) * w.query_role_quality_sums.size());
+    if (ms)
+        std::memcpy(ms, w.quality_ms, sizeof(w.quality_ms));
+    return 0;
+}
+
+int gw_mapper_segment_quality_sums(const void* segments, int64_t n_segments, const void* overlaps, int64_t n_overlaps,
+                                   int32_t query_role, const char* qualities, const int64_t* offsets, int32_t n_reads,
+                                   uint32_t first_read_id, uint32_t* sums, void* stream, float* sums_ms)
+{
+    return guarded([&] {
+        if (sums_ms)
+            *sums_ms = 0.f;
+        if (n_segments < 0 || n_overlaps < 0 || n_reads < 0)
+            throw std::invalid_argument("gw_mapper_segment_quality_sums: a negative count");
+        if (!qualities || !offsets)
+            throw std::invalid_argument("gw_mapper_segment_quality_sums: no qualities");
+        const reads_view reads{qualities, offsets, n_reads};
+        check_qualities("gw_mapper_segment_quality_sums", qualities, reads);
+        if (n_segments == 0)
+            return 0;
+        dbuf<char> device_qualities;
+        dbuf<int64_t> device_offsets;
+        dbuf<gwm_segment> device_segments;
+        dbuf<gwm_overlap> device_overlaps;
+        dbuf<uint32_t> device_sums(n_segments);
+        upload_qualities(device_qualities, qualities, reads);
+        device_offsets.upload(offsets, static_cast<int64_t>(n_reads) + 1);
+        device_segments.upload(static_cast<const gwm_segment*>(segments), n_segments);
+        device_overlaps.upload(static_cast<const gwm_overlap*>(overlaps), n_overlaps);
+        throw_on(gwm_segment_quality_sums(device_segments.p, n_segments, device_overlaps.p, n_overlaps, query_role,
+                                          device_qualities.p, device_offsets.p, n_reads, first_read_id, device_sums.p,
+                                          stream, sums_ms));
+        copy_out(sums, device_sums.p, n_segments);
+        return 0;
+    }, GW_MAPPER_ERROR);
 }
 
 gw_mapper_overlaps* gw_mapper_map_batched(const char* query_bases, const int64_t* query_offsets, int32_t n_queries,

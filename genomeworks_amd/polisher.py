@@ -14,7 +14,14 @@ POA does not succeed; nothing is trimmed.
 polish(reads, reads) is not that: rule 1 of section 3j keeps one overlap per query read, the one with the longest
 span, and for a set mapped against itself that is every read's overlap with itself, so the reads come back unchanged.
 correct_reads() drops the self overlaps, keeps one record per pair of reads, aligns it once and cuts the windows of
-both of its reads out of that one alignment."""
+both of its reads out of that one alignment.
+
+    names, reads, qualities = read_fastq("reads.fastq")
+    polished, report = polish(reads, [draft], read_qualities=qualities)      # layers weighted by their Phred scores
+    corrected, report = correct_reads(reads, qualities=qualities)
+
+With qualities every base of a layer enters the POA with its Phred score as its weight, and layers whose mean quality
+is below min_mean_quality are dropped."""
 import time
 
 from . import cudamapper, cudapoa
@@ -29,7 +36,8 @@ def poa_batch_shape(window_length, max_depth, band_width):
 
 
 def polish(reads, targets, overlaps=None, window_length=500, max_depth=30, band_width=256, band_mode="static_band",
-           devices=(0,), timings=None, poa_memory_per_device=4 << 30, **mapping_parameters):
+           devices=(0,), timings=None, poa_memory_per_device=4 << 30, read_qualities=None, target_qualities=None,
+           min_mean_quality=10, **mapping_parameters):
     """`targets` polished by `reads`: (polished_targets, report). polished_targets[i] is a str, the concatenation of
     the results of target i's windows in window order: the consensus of cudapoa (scores 8 / -6 / -8, no weights,
     band_mode with band_width) over the backbone and its layers where at least 2 layers span the window and the POA's
@@ -47,7 +55,15 @@ def polish(reads, targets, overlaps=None, window_length=500, max_depth=30, band_
     memory, which takes seconds to set up on a large device); mapping and windows run on the current device.
     `timings`, if a dict, receives the device times (ms) chain_fuse_filter, fuse, rescue (when mapping), gather, align,
     segments, window_gather, the host times (s) map_seconds, windows_seconds, poa_seconds, stitch_seconds, and
-    bytes_to_host of the windows step."""
+    bytes_to_host of the windows step.
+
+    read_qualities / target_qualities: Phred+33 strings (str / bytes), one per read and of its length, bytes in
+    33..126, or None for a set without qualities, such as a FASTA draft. With either, the
+    windows come from cudamapper.overlap_windows_weighted and every sequence enters the POA with its weights: c - 33
+    per base, or 1 throughout for a set without qualities. With read_qualities a layer must also have a quality sum
+    > 0 and a mean quality >= min_mean_quality (racon's -q). A window whose backbone weights sum to 0 keeps its
+    backbone; its POA is not run and its status is None. `timings` then also receives quality_sums and weight_gather
+    (device ms). With both None this is the call without qualities, and min_mean_quality is not looked at."""
     if window_length < 1:
         raise ValueError("window_length must be >= 1")
     if max_depth < 0:
@@ -66,7 +82,11 @@ def polish(reads, targets, overlaps=None, window_length=500, max_depth=30, band_
     elif mapping_parameters:
         raise TypeError("polish: mapping parameters given together with overlaps")
     t1 = time.perf_counter()
-    windows = cudamapper.overlap_windows(overlaps, reads, targets, window_length, max_depth, timings=times)
+    if read_qualities is None and target_qualities is None:
+        windows = cudamapper.overlap_windows(overlaps, reads, targets, window_length, max_depth, timings=times)
+    else:
+        windows = cudamapper.overlap_windows_weighted(overlaps, reads, targets, read_qualities, target_qualities,
+                                                      window_length, max_depth, min_mean_quality, timings=times)
     t2 = time.perf_counter()
     polished, report, t3 = _consensus_of_windows(windows, len(targets), window_length, max_depth, band_width, band_mode,
                                                  devices, poa_memory_per_device)
@@ -78,21 +98,24 @@ def polish(reads, targets, overlaps=None, window_length=500, max_depth=30, band_
 def _consensus_of_windows(windows, n_reads, window_length, max_depth, band_width, band_mode, devices,
                           poa_memory_per_device):
     """The POA of every window of overlap_windows / correction_windows that at least 2 layers span, and the results
-    stitched per read: (sequences, report, the time the POA was through)."""
-    deep = [i for i, (_, _, seqs) in enumerate(windows) if len(seqs) - 1 >= 2]
+    stitched per read: (sequences, report, the time the POA was through). Windows of the _weighted variants carry
+    their weights as a fourth entry and go through the POA with them, except those whose backbone weights sum to 0."""
+    weighted = bool(windows) and len(windows[0]) == 4
+    deep = [i for i, w in enumerate(windows) if len(w[2]) - 1 >= 2 and (not weighted or int(w[3][0].sum()) > 0)]
     status, consensus = {}, {}
     if deep:
         size, depth, band = poa_batch_shape(window_length, max_depth, band_width)
+        more = dict(weights=[windows[i][3] for i in deep]) if weighted else {}
         out = cudapoa.process_windows_multi_device([windows[i][2] for i in deep], depth, size, devices=tuple(devices),
                                                    memory_per_device=poa_memory_per_device, output_type="consensus",
                                                    band_mode=band_mode, alignment_band_width=band, gap_score=-8,
-                                                   mismatch_score=-6, match_score=8)
+                                                   mismatch_score=-6, match_score=8, **more)
         for j, i in enumerate(deep):
             status[i], consensus[i] = int(out["status"][j]), out["consensus"][j]
     t3 = time.perf_counter()
     pieces = [[] for _ in range(n_reads)]
     report = []
-    for i, (target, window, seqs) in enumerate(windows):
+    for i, (target, window, seqs) in enumerate(w[:3] for w in windows):
         kept = status.get(i) != 0
         pieces[target].append(seqs[0].decode("latin-1") if kept else consensus[i])
         report.append(dict(target_read=target, window=window, layers=len(seqs) - 1, status=status.get(i),
@@ -101,7 +124,8 @@ def _consensus_of_windows(windows, n_reads, window_length, max_depth, band_width
 
 
 def correct_reads(reads, overlaps=None, window_length=500, max_depth=30, band_width=256, band_mode="static_band",
-                  devices=(0,), timings=None, poa_memory_per_device=4 << 30, **mapping_parameters):
+                  devices=(0,), timings=None, poa_memory_per_device=4 << 30, qualities=None, min_mean_quality=10,
+                  **mapping_parameters):
     """`reads` corrected with each other: (corrected_reads, report), both as polish() returns them, with every read in
     the place of a target: corrected_reads[i] is the concatenation of the results of read i's windows, and report has
     one dict per window, by read, then by window, whose target_read is the read that owns the window.
@@ -113,7 +137,10 @@ def correct_reads(reads, overlaps=None, window_length=500, max_depth=30, band_wi
     it (cudamapper.correction_windows; the rules are in INTEGRATION.md section 3k). All windows of all reads are built
     at once, so the host holds up to (1 + max_depth) sequences of up to 2 * window_length bases per window of every
     read; reads are not corrected in batches. The remaining arguments as for polish(). `timings` receives what
-    polish() gives it and pairs, overlaps_in (records aligned, records given) and query_role_segments (device ms)."""
+    polish() gives it and pairs, overlaps_in (records aligned, records given) and query_role_segments (device ms).
+    qualities: the Phred+33 strings of the reads as polish() takes them, or None; with them the windows come from
+    cudamapper.correction_windows_weighted, layers are filtered by min_mean_quality and every sequence, backbones
+    included, is weighted."""
     if window_length < 1:
         raise ValueError("window_length must be >= 1")
     if max_depth < 0:
@@ -132,10 +159,45 @@ def correct_reads(reads, overlaps=None, window_length=500, max_depth=30, band_wi
     elif mapping_parameters:
         raise TypeError("correct_reads: mapping parameters given together with overlaps")
     t1 = time.perf_counter()
-    windows = cudamapper.correction_windows(overlaps, reads, window_length, max_depth, timings=times)
+    if qualities is None:
+        windows = cudamapper.correction_windows(overlaps, reads, window_length, max_depth, timings=times)
+    else:
+        windows = cudamapper.correction_windows_weighted(overlaps, reads, qualities, window_length, max_depth,
+                                                         min_mean_quality, timings=times)
     t2 = time.perf_counter()
     corrected, report, t3 = _consensus_of_windows(windows, len(reads), window_length, max_depth, band_width, band_mode,
                                                   devices, poa_memory_per_device)
     t4 = time.perf_counter()
     times.update(map_seconds=t1 - t0, windows_seconds=t2 - t1, poa_seconds=t3 - t2, stitch_seconds=t4 - t3)
     return corrected, report
+
+
+def read_fastq(path):
+    """(names, sequences, qualities) of a FASTQ file of four-line records: '@' and the name (up to the first blank),
+    the bases, '+' (with or without the name repeated), and as many Phred+33 bytes, 33..126, as there are bases.
+    Sequences and qualities are str. Anything else -- wrapped records, a truncated record, a missing '@' or '+', a
+    length mismatch, a quality byte out of range -- raises ValueError with the line number. Empty lines at the end of
+    the file are allowed. No gzip."""
+    names, sequences, qualities = [], [], []
+    with open(path, "rb") as f:
+        lines = f.read().decode("latin-1").split("\n")
+    while lines and lines[-1].strip() == "" and (len(lines) % 4 or not any(x.strip() for x in lines[-4:])):
+        lines.pop()  # down to whole records: the last record may be one of no bases, whose lines are empty too
+    if len(lines) % 4:
+        raise ValueError("%s: %d lines are not a whole number of four-line records" % (path, len(lines)))
+    for at in range(0, len(lines), 4):
+        header, bases, plus, quality = (line.rstrip("\r") for line in lines[at:at + 4])
+        if not header.startswith("@") or len(header.split()) < 1 or header.split()[0] == "@":
+            raise ValueError("%s, line %d: a record starts with '@' and a name" % (path, at + 1))
+        if not plus.startswith("+"):
+            raise ValueError("%s, line %d: the third line of a record starts with '+'" % (path, at + 3))
+        if len(quality) != len(bases):
+            raise ValueError("%s, line %d: %d qualities for %d bases" % (path, at + 4, len(quality), len(bases)))
+        if any(not 33 <= ord(c) <= 126 for c in quality):
+            raise ValueError("%s, line %d: a quality byte outside 33..126" % (path, at + 4))
+        if any(c.isspace() for c in bases):
+            raise ValueError("%s, line %d: white space among the bases" % (path, at + 2))
+        names.append(header[1:].split()[0])
+        sequences.append(bases)
+        qualities.append(quality)
+    return names, sequences, qualities

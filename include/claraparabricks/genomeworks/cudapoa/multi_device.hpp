@@ -93,6 +93,16 @@ void process_windows_size_classes(MultiDeviceOutput& out, const std::vector<std:
 void process_windows_multi_device(MultiDeviceOutput& out, const std::vector<std::vector<std::string>>& windows,
                                   const BatchConfig& batch_size, const MultiDeviceConfig& config);
 
+/// The same with base weights, as Batch::add_poa_group takes them in Entry::weights: weights[w][r] are the weights of read r
+/// of window w, one per base, or empty for unit weights. Throws std::invalid_argument before any worker starts for weights
+/// that do not match the windows (one entry per window and per read; a read's weights empty or as many as its bases) and
+/// for a negative weight. A window one of whose reads has nothing but zero weights is refused as a whole: it reports
+/// StatusType::zero_weighted_poa_sequence, the status a Batch gives that read, comes back with empty results and takes no
+/// part in any launch, so its neighbours are what they are without it.
+void process_windows_multi_device(MultiDeviceOutput& out, const std::vector<std::vector<std::string>>& windows,
+                                  const std::vector<std::vector<std::vector<int8_t>>>& weights, const BatchConfig& batch_size,
+                                  const MultiDeviceConfig& config);
+
 } // namespace cudapoa
 } // namespace genomeworks
 } // namespace claraparabricks

@@ -137,6 +137,15 @@ gw_poa_multi* gw_poa_multi_device_run(int32_t n_windows, const int32_t* reads_pe
                                       const int32_t* lengths, const gw_poa_batch_config* cfg, const int32_t* devices,
                                       int32_t n_devices, int32_t batches_per_device, int64_t memory_per_device, int8_t output_mask,
                                       int16_t gap_score, int16_t mismatch_score, int16_t match_score);
+/* The same with base weights: weights[i] points to lengths[i] non-negative weights for sequence i (all sequences of all
+   windows back to back, as seqs), or is NULL for unit weights; weights NULL is gw_poa_multi_device_run. A negative weight is an error (NULL is returned). A window
+   one of whose sequences has nothing but zero weights reports status 10 (zero_weighted_poa_sequence), comes back empty and
+   takes part in no launch. */
+gw_poa_multi* gw_poa_multi_device_run_weighted(int32_t n_windows, const int32_t* reads_per_window, const char* const* seqs,
+                                               const int32_t* lengths, const int8_t* const* weights, const gw_poa_batch_config* cfg,
+                                               const int32_t* devices, int32_t n_devices, int32_t batches_per_device,
+                                               int64_t memory_per_device, int8_t output_mask, int16_t gap_score,
+                                               int16_t mismatch_score, int16_t match_score);
 void gw_poa_multi_destroy(gw_poa_multi* h);
 int32_t gw_poa_multi_launches(gw_poa_multi* h);
 double gw_poa_multi_seconds(gw_poa_multi* h); /* workers' wall time: batch creation, filling, kernels, result unpacking */

@@ -208,6 +208,70 @@ int64_t gw_mapper_windows_copy_query_role_segments(const gw_mapper_windows* wind
                                                    int64_t* query_role_offsets, int64_t* pair_positions, int64_t* n_pairs,
                                                    float* query_role_ms);
 
+/* ---- base-quality weights for polishing and read correction ---------------------------------------------------------
+   The rules (Q1 to Q4) are in INTEGRATION.md section 3l. The qualities of a read set are Phred+33 bytes that share the
+   offsets of its bases; every byte must lie in 33..126, which is checked on the host before anything is uploaded, and
+   the weight of byte c is c - 33. A set's qualities are uploaded once, next to its reads, and stay on the device:
+   what reaches the host beyond the unweighted calls is 4 B per segment record (its quality sum) and one weight byte
+   per window base. */
+
+/* gw_mapper_window_overlaps with qualities. Either quality pointer may be NULL: that set has none. Where the queries
+   have qualities, the quality sum of every record is computed on the device (gwm_segment_quality_sums) and a record
+   is a layer only if it also passes Q2 with min_mean_quality (>= 0; racon's -q); where they have none, the layers are
+   those of gw_mapper_window_overlaps. The weights of every window sequence are gathered on the device by the plan of
+   its bases (gwm_gather_weights): c - 33 from a set with qualities, reversed and not complemented on '-' layers, 1
+   throughout from a set without. Without target bases the targets are the queries, with the queries' qualities.
+   Errors as for gw_mapper_window_overlaps, plus a quality byte outside 33..126 and a negative min_mean_quality, both
+   before any device work. */
+gw_mapper_windows* gw_mapper_window_overlaps_weighted(const void* overlaps, int64_t n, const char* query_bases,
+                                                      const int64_t* query_offsets, int32_t n_queries,
+                                                      uint32_t first_query_read_id, const char* target_bases,
+                                                      const int64_t* target_offsets, int32_t n_targets,
+                                                      uint32_t first_target_read_id, const char* query_qualities,
+                                                      const char* target_qualities, int32_t min_mean_quality,
+                                                      int32_t window_length, int32_t max_depth,
+                                                      int64_t max_device_bytes, void* stream);
+/* gw_mapper_correction_windows with the qualities of the one read set (NULL: unit weights and the layers of
+   gw_mapper_correction_windows). The records of both roles get quality sums: a target-role record's layer is supplied
+   by the pair's query read, a query-role record's by its target read. */
+gw_mapper_windows* gw_mapper_correction_windows_weighted(const void* overlaps, int64_t n, const char* bases,
+                                                         const int64_t* offsets, int32_t n_reads,
+                                                         uint32_t first_read_id, const char* qualities,
+                                                         int32_t min_mean_quality, int32_t window_length,
+                                                         int32_t max_depth, int64_t max_device_bytes, void* stream);
+/* What a handle of the two calls above holds beyond the others: weights (one per base of
+   gw_mapper_windows_copy_windows, in the same order), quality_sums (one per record of gw_mapper_windows_copy_segments;
+   none when the supplying set had no qualities), query_role_quality_sums (one per record of
+   gw_mapper_windows_copy_query_role_segments, likewise) and ms[2]: device time of the quality sums and of the weight
+   gather. Any pointer may be NULL. A handle of the unweighted calls holds none of it. */
+int gw_mapper_windows_copy_weights(const gw_mapper_windows* windows, int8_t* weights, uint32_t* quality_sums,
+                                   uint32_t* query_role_quality_sums, float* ms);
+
+/* gw_mapper_select_layers with Q2: quality_sums[n_segments] (NULL: exactly gw_mapper_select_layers) and
+   min_mean_quality (negative: an error). It needs no device. */
+int64_t gw_mapper_select_layers_weighted(const void* segments, int64_t n_segments, const void* overlaps,
+                                         int64_t n_overlaps, int32_t n_queries, uint32_t first_query_read_id,
+                                         const int64_t* target_lengths, int32_t n_targets,
+                                         uint32_t first_target_read_id, int32_t window_length, int32_t max_depth,
+                                         const uint32_t* quality_sums, int32_t min_mean_quality, uint32_t* plan,
+                                         int64_t plan_capacity, int64_t* n_windows, uint32_t* window_table,
+                                         int64_t window_capacity);
+/* gw_mapper_select_correction_layers with Q2: the sums of the records of either role, either may be NULL */
+int64_t gw_mapper_select_correction_layers_weighted(const void* target_role, int64_t n_target_role,
+                                                    const void* query_role, int64_t n_query_role, const void* pairs,
+                                                    int64_t n_pairs, const int64_t* read_lengths, int32_t n_reads,
+                                                    uint32_t first_read_id, int32_t window_length, int32_t max_depth,
+                                                    const uint32_t* target_role_quality_sums,
+                                                    const uint32_t* query_role_quality_sums, int32_t min_mean_quality,
+                                                    uint32_t* plan, int64_t plan_capacity, int64_t* n_windows,
+                                                    uint32_t* window_table, int64_t window_capacity);
+/* Q1 alone, over host arrays: the records (24 B each) and the overlaps they index, the supplying set's qualities and
+   offsets, are uploaded, gwm_segment_quality_sums runs, and sums[n_segments] is copied back. query_role 0: the
+   supplier of a record is its overlap's query read; otherwise its target read. sums_ms (device time) may be NULL. */
+int gw_mapper_segment_quality_sums(const void* segments, int64_t n_segments, const void* overlaps, int64_t n_overlaps,
+                                   int32_t query_role, const char* qualities, const int64_t* offsets, int32_t n_reads,
+                                   uint32_t first_read_id, uint32_t* sums, void* stream, float* sums_ms);
+
 /* group_reads_into_indices: consecutive reads while the running base count stays <= max_basepairs_per_index; a longer
    read gets an index of its own. The reference's loop as it stands: when the very first read is longer than the limit
    a descriptor of zero reads comes first, and no reads at all give the one descriptor {0, 0}. Returns the number of

@@ -299,6 +299,34 @@ int gwm_gather_sequences(const gwm_gather_entry* plan, int64_t n, const int64_t*
                          const int64_t* target_offsets, int32_t n_targets, char* out, int64_t out_bytes, void* stream,
                          float* gather_ms);
 
+/* ---- base qualities: the weights of polishing and read correction ------------------------
+ * The qualities of a read set are Phred+33 bytes that share the offsets of its bases: byte j of read i is the quality
+ * of base j. The weight of byte c is c - 33; the callers of this header refuse bytes outside 33..126 on the host, and
+ * the kernels clamp a weight to 0..93. */
+
+/* Q1: sums[j] = the sum of the weights of the supplier's quality bytes [query_begin, query_end) of record j, saturating
+ * at 2^32 - 1 -- what the layer of the record would weigh. The supplier of a record is its overlap's query read
+ * (query_role 0: the records of gwm_window_segments and the target role of gwm_pair_segments) or its target read
+ * (query_role != 0: the query role of gwm_pair_segments). Device arrays throughout: the records and the overlaps they
+ * index, the supplier set's qualities and offsets (read ids first_read_id .. first_read_id + n_reads - 1), and
+ * sums[n_segments]. One wave64 per record, whose lanes stride the bytes; a record may be of any length. A record that
+ * names an overlap or a read that does not exist, or a range beyond its read, returns -1 before anything is written.
+ * The sums depend on the records alone, not on how the alignment was chunked. sums_ms (device time of the sums
+ * kernel) may be NULL. Synchronous on `stream` when it returns. */
+int gwm_segment_quality_sums(const gwm_segment* segments, int64_t n_segments, const gwm_overlap* overlaps,
+                             int64_t n_overlaps, int32_t query_role, const char* qualities, const int64_t* offsets,
+                             int32_t n_reads, uint32_t first_read_id, uint32_t* sums, void* stream, float* sums_ms);
+
+/* Q3: gwm_gather_sequences with qualities in place of bases: the weights of the n sequences of a device plan into the
+ * device array out[0 .. out_bytes), those of sequence i at out_starts[i], so that weight j of a sequence belongs to
+ * base j of what gwm_gather_sequences writes for the same plan. reversed != 0: back to front, nothing is complemented.
+ * Either quality pointer may be NULL: the entries of that set get weight 1 throughout; its offsets are needed all the
+ * same. Errors and timing as for gwm_gather_sequences. */
+int gwm_gather_weights(const gwm_gather_entry* plan, int64_t n, const int64_t* out_starts, const char* query_qualities,
+                       const int64_t* query_offsets, int32_t n_queries, const char* target_qualities,
+                       const int64_t* target_offsets, int32_t n_targets, int8_t* out, int64_t out_bytes, void* stream,
+                       float* gather_ms);
+
 const char* gwm_last_error(void);
 
 #ifdef __cplusplus

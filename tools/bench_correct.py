@@ -15,7 +15,12 @@ and both directions of every pair. For each of the two mappings, after one warm-
 Device stage times are HIP events summed over the chunks; the others are host wall times. Medians over the repeats.
 No threshold: the record says what was measured.
 
-    python tools/bench_correct.py [--contig-kbp 200] [--coverage 30] [--repeats 3] [--out profiles/correct_bench.json]
+--qualities gives the reads synthetic Phred strings (low Phred at the mutated bases,
+tests/oracle_polish_quality.informative_qualities) and runs correct_reads(..., qualities=...) in the same repeats, next
+to the run without; each mapping's record gains "with_qualities".
+
+    python tools/bench_correct.py [--contig-kbp 200] [--coverage 30] [--repeats 3] [--qualities] [--min-mean-quality 10]
+                                  [--out profiles/correct_bench.json]
 """
 import argparse
 import json
@@ -29,6 +34,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import mapper_cases as MC  # noqa: E402
+import oracle_polish_quality as OQ  # noqa: E402
 from genomeworks_amd import cudamapper, polisher  # noqa: E402
 
 
@@ -36,17 +42,30 @@ def med(rows, key):
     return round(statistics.median(r[key] for r in rows), 4)
 
 
-def measure(reads, overlaps, kw, repeats):
-    """the stage times of correct_reads() over `overlaps` and the align time of all their non-self records"""
+def wall(r):
+    return r["windows_seconds"] + r["poa_seconds"] + r["stitch_seconds"]
+
+
+def measure(reads, overlaps, kw, repeats, qualities=None, min_mean_quality=10):
+    """the stage times of correct_reads() over `overlaps` and the align time of all their non-self records; with
+    qualities, those of correct_reads(..., qualities=...) as well"""
     others = overlaps[overlaps["query_read_id"] != overlaps["target_read_id"]]
     few = overlaps[(overlaps["query_read_id"] < 64) & (overlaps["target_read_id"] < 64)]
     polisher.correct_reads(reads[:64], overlaps=few, **kw)  # code objects, pools
     cudamapper.align_overlaps(others[:64], reads)
-    runs, both = [], []
+    if qualities:
+        polisher.correct_reads(reads[:64], overlaps=few, qualities=qualities[:64], **kw)
+    runs, both, weighted_runs = [], [], []
     for _ in range(repeats):
         t = {}
         _, report = polisher.correct_reads(reads, overlaps=overlaps, timings=t, **kw)
         runs.append(t)
+        if qualities:
+            t = {}
+            _, weighted_report = polisher.correct_reads(reads, overlaps=overlaps, timings=t, qualities=qualities,
+                                                        min_mean_quality=min_mean_quality, **kw)
+            weighted_runs.append(t)
+            print("with qualities", {k: round(v, 3) for k, v in t.items()}, file=sys.stderr, flush=True)
         c = {}
         t0 = time.perf_counter()
         cudamapper.align_overlaps(others, reads, timings=c)
@@ -54,7 +73,21 @@ def measure(reads, overlaps, kw, repeats):
         both.append(c)
         print({k: round(v, 3) for k, v in t.items()}, {k: round(v, 3) for k, v in c.items()}, file=sys.stderr, flush=True)
     pairs_ms, others_ms = med(runs, "align"), med(both, "align")
-    return {"records": int(len(overlaps)), "self_records": int(len(overlaps) - len(others)),
+    more = {}
+    if qualities:
+        more["with_qualities"] = {
+            "min_mean_quality": min_mean_quality,
+            "windows_through_poa": sum(1 for r in weighted_report if r["status"] is not None),
+            "windows_corrected": sum(1 for r in weighted_report if not r["backbone_kept"]),
+            "layers": sum(r["layers"] for r in weighted_report),
+            "windows_step": {"device_ms": {k: med(weighted_runs, k) for k in ("gather", "align", "segments", "query_role_segments",
+                                                                               "quality_sums", "window_gather", "weight_gather")},
+                             "wall_s": med(weighted_runs, "windows_seconds"),
+                             "bytes_to_host": int(weighted_runs[-1]["bytes_to_host"])},
+            "poa": {"wall_s": med(weighted_runs, "poa_seconds")},
+            "end_to_end_s": {"with": round(statistics.median(wall(r) for r in weighted_runs), 4),
+                             "without": round(statistics.median(wall(r) for r in runs), 4)}}
+    return dict(more, **{"records": int(len(overlaps)), "self_records": int(len(overlaps) - len(others)),
             "non_self_records": int(len(others)), "pairs": int(runs[-1]["pairs"]),
             "windows": len(report), "windows_through_poa": sum(1 for r in report if r["status"] is not None),
             "windows_corrected": sum(1 for r in report if not r["backbone_kept"]),
@@ -70,7 +103,7 @@ def measure(reads, overlaps, kw, repeats):
             "align_overlaps_non_self_records": {"device_ms": {k: med(both, k) for k in ("gather", "align", "cigar_text")},
                                                 "wall_s": med(both, "seconds")},
             "pairs_over_non_self_records": {"records": round(runs[-1]["pairs"] / max(len(others), 1), 4),
-                                            "align_ms": round(pairs_ms / others_ms, 4) if others_ms else None}}
+                                            "align_ms": round(pairs_ms / others_ms, 4) if others_ms else None}})
 
 
 def main():
@@ -83,10 +116,16 @@ def main():
     ap.add_argument("--max-depth", type=int, default=30)
     ap.add_argument("--band-width", type=int, default=256)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--qualities", action="store_true", help="also correct with synthetic base qualities")
+    ap.add_argument("--min-mean-quality", type=int, default=10)
     ap.add_argument("--out")
     args = ap.parse_args()
     seed, length = 2025, int(args.contig_kbp * 1000)
     reads = MC.synthetic_reads(seed, length, args.coverage, args.read_length, args.read_error, min_length=200)
+    qualities = None
+    if args.qualities:
+        qualities = OQ.informative_qualities(seed, length, args.coverage, args.read_length, args.read_error, min_length=200)
+        assert [len(q) for q in qualities] == [len(r) for r in reads]
     mapping = dict(k=15, w=10, filtering_parameter=1.0)
     kw = dict(window_length=args.window_length, max_depth=args.max_depth, band_width=args.band_width)
     rec = {"metric": "correction of a read set by itself, stage times", "device": "gpu0", "contig_bases": length,
@@ -104,7 +143,7 @@ def main():
         rec[name] = dict({"map": {"wall_s": round(map_s, 4),
                                   "device_ms": {k: round(float(map_timings[k]), 3)
                                                 for k in ("chain_fuse_filter", "fuse", "rescue")}}},
-                         **measure(reads, overlaps, kw, args.repeats))
+                         **measure(reads, overlaps, kw, args.repeats, qualities, args.min_mean_quality))
     line = json.dumps(rec)
     print(line)
     if args.out:
