@@ -254,6 +254,15 @@ def mapper():
         L.gw_mapper_select_correction_layers_weighted.argtypes = [vp, i64, vp, i64, vp, i64, vp, i32, u32, i32, i32, vp, vp,
                                                                   i32, vp, i64, vp, vp, i64]
         L.gw_mapper_segment_quality_sums.argtypes = [vp, i64, vp, i64, i32, vp, vp, i32, u32, vp, vp, vp]
+        L.gw_mapper_overlap_pileup.restype = vp
+        L.gw_mapper_overlap_pileup.argtypes = [vp, i64, vp, vp, i32, u32, vp, vp, i32, u32, i64, vp]
+        L.gw_mapper_pair_pileup.restype = vp
+        L.gw_mapper_pair_pileup.argtypes = [vp, i64, vp, vp, i32, u32, i64, vp]
+        L.gw_mapper_pileup_bases.restype = i64
+        L.gw_mapper_pileup_bases.argtypes = [vp]
+        L.gw_mapper_pileup_copy.argtypes = [vp, vp, vp]
+        L.gw_mapper_pileup_destroy.restype = None
+        L.gw_mapper_pileup_destroy.argtypes = [vp]
         L.gwm_align_bytes_needed.restype = i64
         L.gwm_align_bytes_needed.argtypes = [i32, i32, i32]
         _mapper = L

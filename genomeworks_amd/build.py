@@ -35,7 +35,8 @@ EXTENDER_HOST_SRCS = ["extender/extender.cpp"]
 SEMIGLOBAL_KERNEL_SRCS = ["semiglobal/gws_ends.hip"]
 # cudamapper likewise
 MAPPER_KERNEL_SRCS = ["mapper/gwm_mapper.hip", "mapper/gwm_postprocess.hip", "mapper/gwm_align.hip",
-                      "mapper/gwm_segments.hip", "mapper/gwm_qualities.hip", "mapper/gwm_index_cache.hip"]
+                      "mapper/gwm_segments.hip", "mapper/gwm_pileup.hip", "mapper/gwm_qualities.hip",
+                      "mapper/gwm_index_cache.hip"]
 MAPPER_HOST_SRCS = ["mapper/mapper.cpp", "mapper/gwm_driver.cpp", "mapper/gwm_index_batcher.cpp",
                     "mapper/gwm_windows.cpp"]
 
@@ -192,7 +193,7 @@ def build_extender(force=False):
 
 def build_mapper(force=False):
     """libcudamapper.so: the sketch / index / matcher / overlapper / post-processing / overlap alignment / window
-    segment kernels with their rocPRIM scans, selects and sorts (hipcc, gfx950), linked against libgwhip.so for the
+    segment / pileup kernels with their rocPRIM scans, selects and sorts (hipcc, gfx950), linked against libgwhip.so for the
     aligner, and the Index / Matcher handles, the index batcher, the batched driver and the host rules of polishing and read correction
     behind the C API (g++);
     then bin/cudamapper, which links it and libgenomeworks_amd.so (built before this)."""

@@ -21,6 +21,8 @@ gfx950), over the flat C API of include/gw_mapper_capi.h.
     windows = correction_windows(overlaps, reads, window_length=500, max_depth=30)   # polisher.correct_reads feeds on it
     windows = overlap_windows_weighted(overlaps, reads, targets, query_qualities=phred33)   # + weights per sequence
     windows = correction_windows_weighted(overlaps, reads, phred33)
+    piles = overlap_pileup(overlaps, reads, targets)               # uint32 (6, len(target)) per target: PILEUP_CHANNELS
+    piles = pair_pileup(pairs, reads)                              # both reads of every pair, one array per read
 
 Index arrays carry the reference's names (representations, read_ids, positions_in_reads, directions_of_reads,
 unique_representations, first_occurrence_of_representations) and come back as numpy arrays."""
@@ -42,6 +44,9 @@ OVERLAP = np.dtype({"names": ["query_read_id", "target_read_id", "query_start_po
 # gwm_segment: what one overlap's alignment covers of one window of its target read
 SEGMENT = np.dtype([("overlap", "<u4"), ("window", "<u4"), ("target_first", "<u4"), ("target_last", "<u4"),
                     ("query_begin", "<u4"), ("query_end", "<u4")])
+
+# the rows of a pileup array: what the aligned overlaps put at a base of the read that owns it
+PILEUP_CHANNELS = ("A", "C", "G", "T", "deletion", "insertion")
 
 FORWARD, REVERSE = 0, 1  # SketchElement::DirectionOfRepresentation
 
@@ -716,6 +721,62 @@ def correction_windows_weighted(overlaps, reads, qualities, window_length=500, m
     _, _, _, (bases, offsets, per_window, owners, index) = _correction_windows(
         overlaps, reads, window_length, max_depth, first_read_id, max_device_bytes, stream, timings, weighted)
     return _split_weighted_windows(bases, weighted["weights"], offsets, per_window, owners, index)
+
+
+def _copy_pileup(L, h, offsets, n_records, timings):
+    """the counters of a pileup handle, copied once and cut per read of the owner set: [uint32 (6, len(read)), ...],
+    views of the one buffer; the handle is destroyed"""
+    if not h:
+        raise _err(L)
+    try:
+        n_bases = int(L.gw_mapper_pileup_bases(h))
+        counts, ms = np.zeros((len(PILEUP_CHANNELS), n_bases), np.uint32), np.zeros(3, np.float32)
+        if L.gw_mapper_pileup_copy(h, _p(counts), _p(ms)) != 0:
+            raise _err(L)
+    finally:
+        L.gw_mapper_pileup_destroy(h)
+    if timings is not None:
+        timings.update(gather=float(ms[0]), align=float(ms[1]), pileup=float(ms[2]),
+                       bytes_to_host=n_records * OVERLAP.itemsize + counts.nbytes)
+    return [counts[:, int(a):int(b)] for a, b in zip(offsets[:-1], offsets[1:])]
+
+
+def overlap_pileup(overlaps, query_reads, target_reads=None, first_query_read_id=0, first_target_read_id=0,
+                   max_device_bytes=0, stream=None, timings=None):
+    """Per-base counts of the aligned overlaps over the target reads, added up on the device from the alignment states
+    (gwm_overlap_pileup): a list with one uint32 array of shape (6, len(target)) per target
+    read, rows as PILEUP_CHANNELS. Every overlap is aligned exactly as align_overlaps aligns it and counted as given
+    -- nothing is selected, a record given twice counts twice --: an aligned column (match or mismatch) adds 1 to the
+    channel of the query's base at its target position (forward target coordinates, the complement channel on '-'), a
+    column with a target base only adds 1 to `deletion` there, and a run of columns with query bases only adds 1 to
+    `insertion` at the smaller target position of its two neighbours, when it has one on both sides within the
+    alignment. Bytes other than ACGT count as the letter the aligner folds them to, (c >> 1) & 3. depth(pile) is the
+    number of records whose target slice covers a position. The arrays are views of one buffer, the only thing copied
+    from the device besides the overlap records that size the chunks. Arguments, chunking and errors as for
+    align_overlaps. `timings`, if a dict, receives gather, align and pileup (device ms) and bytes_to_host."""
+    L = _native.mapper()
+    o = np.ascontiguousarray(overlaps, OVERLAP)
+    q, t = _read_set_args(query_reads, target_reads)
+    _, offsets = pack_reads(query_reads if target_reads is None else target_reads)
+    h = L.gw_mapper_overlap_pileup(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id,
+                                   int(max_device_bytes), _stream(stream))
+    return _copy_pileup(L, h, offsets, len(o), timings)
+
+
+def pair_pileup(pairs, reads, first_read_id=0, max_device_bytes=0, stream=None, timings=None):
+    """Per-base counts over every read of a set from records whose query and target ids both name reads of it
+    (gwm_pair_pileup): each pair is aligned once, as align_overlaps(pairs, reads) aligns it, and counted for both of
+    its reads into one array -- for the target read as overlap_pileup counts it, and for the query read with the roles
+    changed: an aligned column adds 1 to the channel of the target's base at its query position (the complement
+    channel on '-'), a column with a query base only adds 1 to `deletion`, and a run of columns with target bases only
+    adds 1 to `insertion` at the query position before it. Returns one uint32 array of shape (6, len(read)) per read.
+    No pair is selected here: see select_pairs. Arguments, chunking, errors and `timings` as for overlap_pileup."""
+    L = _native.mapper()
+    o = np.ascontiguousarray(pairs, OVERLAP)
+    bases, offsets = pack_reads(reads)
+    h = L.gw_mapper_pair_pileup(_p(o), len(o), _p(bases), _p(offsets), len(reads), first_read_id,
+                                int(max_device_bytes), _stream(stream))
+    return _copy_pileup(L, h, offsets, len(o), timings)
 
 
 def group_reads_into_indices(read_lengths, max_basepairs_per_index):

@@ -1,5 +1,5 @@
-// gwm_align_chunks.hpp -- the chunk loop that gwm_align_overlaps (gwm_align.hip) and gwm_window_segments
-// (gwm_segments.hip) share: validation of the overlap records, sizing on the host, and per chunk of consecutive
+// gwm_align_chunks.hpp -- the chunk loop that gwm_align_overlaps (gwm_align.hip), gwm_window_segments
+// (gwm_segments.hip) and gwm_overlap_pileup (gwm_pileup.hip) share: validation of the overlap records, sizing on the host, and per chunk of consecutive
 // overlaps the gather of the slices, gwhip_hirschberg_myers of libgwhip.so and the per-chunk buffers. What is done with
 // the chunk's alignment states is the caller's: align_chunks() hands them to a consumer while they are on the device.
 // The loop and its kernels are defined once, in gwm_align.hip.
@@ -35,8 +35,8 @@ struct AlignedChunk
 // The budget (max_device_bytes) counts a chunk's working set the same way for every consumer, as
 // gwm_align_bytes_needed states it -- gathered bases, state slots, the aligner's workspace, the small per-overlap
 // arrays and two bytes per column for the consumer's output of the chunk. What a consumer keeps beyond the chunk (the
-// CIGAR text or the segment records of the chunks before, and records beyond two bytes per column, which takes windows
-// of fewer than 12 bases) lies outside it.
+// CIGAR text or the segment records of the chunks before, records beyond two bytes per column, which takes windows
+// of fewer than 12 bases, and the counters of a pileup, 24 B per base of the owner set) lies outside it.
 void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, const char* query_bases,
                   const int64_t* query_offsets, int32_t n_queries, uint32_t first_query_read_id,
                   const char* target_bases, const int64_t* target_offsets, int32_t n_targets,

@@ -146,6 +146,16 @@ struct gw_mapper_cigars
     gw_mapper_cigars& operator=(const gw_mapper_cigars&) = delete;
 };
 
+// The counters of one gwm_overlap_pileup or gwm_pair_pileup call, on the device until they are copied out
+struct gw_mapper_pileup
+{
+    gwm_pileup p{};
+    gw_mapper_pileup() = default;
+    ~gw_mapper_pileup() { gwm_pileup_free(&p); }
+    gw_mapper_pileup(const gw_mapper_pileup&) = delete;
+    gw_mapper_pileup& operator=(const gw_mapper_pileup&) = delete;
+};
+
 // The windows of one gw_mapper_window_overlaps or gw_mapper_correction_windows call, on the host
 struct gw_mapper_windows
 {

@@ -1,0 +1,209 @@
+// gwm_pileup.hip -- cudamapper on gfx950: pileups, the per-base counts of aligned overlaps (include/gwhip_mapper.h,
+// gwm_overlap_pileup and gwm_pair_pileup). A third consumer of the chunk loop of
+// gwm_align_chunks.hpp: where gwm_align_overlaps turns the per-column states into text and gwm_window_segments into
+// records, this adds them into six counters per base of the read that owns the position -- A, C, G, T, deletion,
+// insertion -- and leaves the states where they are. Only the counters cross to the host.
+//
+// One wave64 per alignment over tiles of 64 columns in forward column order, as the segment kernel walks them: state
+// per lane, the query and target positions of a column from ballots of the columns that consume a query / a target
+// base and popcounts over the lower lanes, the running counts and the last column's state carried between tiles in
+// wave-uniform registers. A column that consumes a base of the owner issues one returnless atomic add on its cell; the
+// first column of a run that consumes none issues one on the insertion cell of the owner base before the run. The
+// supplier's base is read from the resident read set. No LDS, no scratch. Integer sums: the result depends neither on
+// the order of the atomics nor on the chunking.
+#include "gwm_align_chunks.hpp"
+
+namespace
+{
+
+constexpr uint32_t kChannels = 6, kDeletion = 4, kInsertion = 5;
+
+// One wave64 per alignment of the chunk (states as AlignedChunk lays them out). counts: channel-major planes of
+// n_bases cells each, counts[c * n_bases + owner.offsets[read] + p] for position p of a read of the owner set.
+// kQueryRole says whose positions are counted: the target read's (`own` = the target position, `other` = the query
+// position, the supplier is the query read) or, in the query role, the query read's, supplied by the target read. A
+// column of state < 2 adds 1 to the channel of the supplier's base at `other`, complemented on '-'; a column that
+// consumes a base of the owner alone (state 2, in the query role 3) adds 1 to the deletion channel; a maximal run of
+// columns that consume none (state 3, in the query role 2) adds 1 to the insertion channel of the smaller owner
+// position of its two neighbours, when it has a neighbour on both sides: 1 <= c <= slice length - 1 with c the owner
+// bases consumed before the run. Every cell lies in the owner's slice and every supplier byte in the supplier's, which
+// align_chunks() has checked against the reads; the counts are compared with the slice lengths all the same.
+template <bool kQueryRole>
+__global__ void __launch_bounds__(kThreads) pileup_kernel(const gwm_overlap* __restrict__ o,
+                                                          const uint8_t* __restrict__ results,
+                                                          const int64_t* __restrict__ starts,
+                                                          const int32_t* __restrict__ result_lengths, int64_t m,
+                                                          ReadSet qset, ReadSet tset, int64_t n_bases,
+                                                          uint32_t* __restrict__ counts)
+{
+    const int64_t i     = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (i >= m)
+        return; // whole waves leave together
+    const gwm_overlap x  = o[i];
+    const int32_t stored = result_lengths[i];
+    const uint32_t len   = static_cast<uint32_t>(stored < 0 ? -stored : stored); // as the host aligner reads it
+    const uint8_t* s     = results + starts[2 * i];
+    const bool reverse   = x.relative_strand == '-';
+    const uint32_t qs = x.query_start_position_in_read, ts = x.target_start_position_in_read,
+                   te = x.target_end_position_in_read;
+    const uint32_t query_length = x.query_end_position_in_read - qs, target_length = te - ts;
+    const uint32_t own_length   = kQueryRole ? query_length : target_length;
+    const int64_t query_at      = qset.offsets[x.query_read_id - qset.first_read_id];
+    const int64_t target_at     = tset.offsets[x.target_read_id - tset.first_read_id];
+    const uint8_t* supplier     = kQueryRole ? tset.bases + target_at : qset.bases + query_at;
+    uint32_t* cells             = counts + (kQueryRole ? query_at : target_at);
+    constexpr uint32_t kSkips   = kQueryRole ? 2u : 3u; // the state that consumes no base of the owner
+    const uint64_t lower        = (1ull << lane) - 1;
+    // wave-uniform: columns walked so far that consume a query / a target base, the state of the last one
+    uint32_t query_run = 0, target_run = 0, last_state = 0;
+    for (uint32_t base = 0; base < len; base += 64)
+    {
+        const bool valid         = lane < min(64u, len - base);
+        const uint32_t state     = valid ? s[len - 1 - base - lane] : 0u;
+        const uint64_t in_query  = __ballot(valid && state != 2);
+        const uint64_t in_target = __ballot(valid && state != 3);
+        const uint32_t a         = query_run + static_cast<uint32_t>(__popcll(in_query & lower));
+        const uint32_t b         = target_run + static_cast<uint32_t>(__popcll(in_target & lower));
+        const uint32_t q         = qs + a;
+        const uint32_t t         = reverse ? te - 1 - b : ts + b;
+        const uint32_t own = kQueryRole ? q : t, other = kQueryRole ? t : q;
+        const uint32_t consumed = kQueryRole ? a : b; // owner bases before this column
+        // the previous column: the next lower lane, or the last column of the tile before
+        uint32_t before = __shfl_up(state, 1, 64);
+        if (lane == 0)
+            before = last_state;
+        if (valid && state != kSkips && consumed < own_length)
+        {
+            uint32_t channel = kDeletion;
+            if (state < 2 && a < query_length && b < target_length)
+            {
+                const uint32_t code = (static_cast<uint32_t>(supplier[other]) >> 1) & 3u; // A, C, T, G = 0, 1, 2, 3
+                channel             = code ^ (code >> 1);                                 // A, C, G, T = 0, 1, 2, 3
+                if (reverse)
+                    channel = 3u - channel;
+            }
+            (void)atomicAdd(cells + static_cast<int64_t>(channel) * n_bases + own, 1u);
+        }
+        else if (valid && state == kSkips && before != kSkips && consumed >= 1 && consumed + 1 <= own_length)
+        {
+            // a run's first column, with owner bases on both sides (a run in column 0 has consumed none)
+            // `own` is the owner position behind the run in column order: the larger neighbour where it ascends
+            const uint32_t p = !kQueryRole && reverse ? own : own - 1;
+            (void)atomicAdd(cells + static_cast<int64_t>(kInsertion) * n_bases + p, 1u);
+        }
+        last_state = __shfl(state, 63, 64);
+        query_run += static_cast<uint32_t>(__popcll(in_query));
+        target_run += static_cast<uint32_t>(__popcll(in_target));
+    }
+}
+
+void check_pileup_arguments(const std::string& who, int32_t n_queries, int32_t n_targets, int64_t max_device_bytes,
+                            int64_t n)
+{
+    if (n_queries < 0 || n_targets < 0)
+        throw std::invalid_argument(who + ": negative number of reads");
+    if (max_device_bytes < 0)
+        throw std::invalid_argument(who + ": negative max_device_bytes");
+    if (n >= (int64_t(1) << 31))
+        throw std::invalid_argument(who + ": 2^31 overlaps or more");
+}
+
+// the zeroed counters of a read set whose offsets are on the device: six planes of offsets[n_reads] cells
+int64_t zeroed_counts(const int64_t* offsets, int32_t n_reads, hipStream_t s, dbuf<uint32_t>& counts)
+{
+    const int64_t n_bases = offsets ? to_host(offsets + n_reads, s) : 0;
+    if (n_bases < 0)
+        throw std::invalid_argument("read offsets that end below 0");
+    counts.resize(kChannels * n_bases);
+    if (n_bases > 0)
+        GWM_CHECK(hipMemsetAsync(counts.p, 0, sizeof(uint32_t) * static_cast<size_t>(kChannels * n_bases), s));
+    return n_bases;
+}
+
+template <bool kQueryRole>
+void add_role(const AlignedChunk& c, const ReadSet& q, const ReadSet& t, int64_t n_bases, uint32_t* counts,
+              hipStream_t s)
+{
+    pileup_kernel<kQueryRole><<<c.m_waves, kThreads, 0, s>>>(c.overlaps, c.results, c.starts, c.result_lengths, c.m, q,
+                                                              t, n_bases, counts);
+    GWM_CHECK(hipGetLastError());
+}
+
+} // namespace
+
+extern "C" {
+
+void gwm_pileup_free(gwm_pileup* pileup)
+{
+    if (!pileup)
+        return;
+    (void)hipFree(pileup->counts);
+    *pileup = gwm_pileup{};
+}
+
+int gwm_overlap_pileup(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                       int32_t n_queries, uint32_t first_query_read_id, const char* target_bases,
+                       const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
+                       int64_t max_device_bytes, void* stream, gwm_pileup* out)
+{
+    *out = gwm_pileup{};
+    try
+    {
+        check_pileup_arguments("gwm_overlap_pileup", n_queries, n_targets, max_device_bytes, n);
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        dbuf<uint32_t> counts;
+        const int64_t n_bases = zeroed_counts(target_offsets, n_targets, s, counts);
+        const ReadSet q{reinterpret_cast<const uint8_t*>(query_bases), query_offsets, static_cast<uint32_t>(n_queries),
+                        first_query_read_id};
+        const ReadSet t{reinterpret_cast<const uint8_t*>(target_bases), target_offsets,
+                        static_cast<uint32_t>(n_targets), first_target_read_id};
+        if (n > 0)
+            gwm::align_chunks("gwm_overlap_pileup", overlaps, n, query_bases, query_offsets, n_queries,
+                              first_query_read_id, target_bases, target_offsets, n_targets, first_target_read_id,
+                              max_device_bytes, s, out->stage_ms,
+                              [&](const AlignedChunk& c) { add_role<false>(c, q, t, n_bases, counts.p, s); });
+        GWM_CHECK(hipStreamSynchronize(s));
+        out->n_bases = n_bases;
+        out->counts  = counts.release();
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        gwm_set_error(e.what());
+        *out = gwm_pileup{};
+        return -1;
+    }
+}
+
+int gwm_pair_pileup(const gwm_overlap* pairs, int64_t n, const char* bases, const int64_t* offsets, int32_t n_reads,
+                    uint32_t first_read_id, int64_t max_device_bytes, void* stream, gwm_pileup* out)
+{
+    *out = gwm_pileup{};
+    try
+    {
+        check_pileup_arguments("gwm_pair_pileup", n_reads, n_reads, max_device_bytes, n);
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        dbuf<uint32_t> counts;
+        const int64_t n_bases = zeroed_counts(offsets, n_reads, s, counts);
+        const ReadSet r{reinterpret_cast<const uint8_t*>(bases), offsets, static_cast<uint32_t>(n_reads), first_read_id};
+        if (n > 0)
+            gwm::align_chunks("gwm_pair_pileup", pairs, n, bases, offsets, n_reads, first_read_id, bases, offsets,
+                              n_reads, first_read_id, max_device_bytes, s, out->stage_ms, [&](const AlignedChunk& c) {
+                                  add_role<false>(c, r, r, n_bases, counts.p, s);
+                                  add_role<true>(c, r, r, n_bases, counts.p, s);
+                              });
+        GWM_CHECK(hipStreamSynchronize(s));
+        out->n_bases = n_bases;
+        out->counts  = counts.release();
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        gwm_set_error(e.what());
+        *out = gwm_pileup{};
+        return -1;
+    }
+}
+
+} // extern "C"

@@ -741,6 +741,59 @@ int64_t gw_mapper_windows_copy_query_role_segments(const gw_mapper_windows* wind
     return n;
 }
 
+gw_mapper_pileup* gw_mapper_overlap_pileup(const void* overlaps, int64_t n, const char* query_bases,
+                                           const int64_t* query_offsets, int32_t n_queries,
+                                           uint32_t first_query_read_id, const char* target_bases,
+                                           const int64_t* target_offsets, int32_t n_targets,
+                                           uint32_t first_target_read_id, int64_t max_device_bytes, void* stream)
+{
+    return guarded([&] {
+        std::unique_ptr<gw_mapper_pileup> h(new gw_mapper_pileup());
+        if (n < 0)
+            throw std::invalid_argument("gw_mapper_overlap_pileup: negative number of overlaps");
+        read_sets reads({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets});
+        reads.upload(); // once; without overlaps too: the counters are those of the target set
+        dbuf<gwm_overlap> d;
+        d.upload(static_cast<const gwm_overlap*>(overlaps), n);
+        const reads_view &q = reads.device_queries, &t = reads.device_targets;
+        throw_on(gwm_overlap_pileup(d.p, n, q.bases, q.offsets, reads.queries.n, first_query_read_id, t.bases, t.offsets,
+                                    reads.targets.n, first_target_read_id, max_device_bytes, stream, &h->p));
+        return h.release();
+    }, static_cast<gw_mapper_pileup*>(nullptr));
+}
+
+gw_mapper_pileup* gw_mapper_pair_pileup(const void* pairs, int64_t n, const char* bases, const int64_t* offsets,
+                                        int32_t n_reads, uint32_t first_read_id, int64_t max_device_bytes, void* stream)
+{
+    return guarded([&] {
+        std::unique_ptr<gw_mapper_pileup> h(new gw_mapper_pileup());
+        if (n < 0)
+            throw std::invalid_argument("gw_mapper_pair_pileup: negative number of pairs");
+        read_sets reads({bases, offsets, n_reads}, reads_view{nullptr, nullptr, 0});
+        reads.upload();
+        dbuf<gwm_overlap> d;
+        d.upload(static_cast<const gwm_overlap*>(pairs), n);
+        const reads_view& r = reads.device_queries;
+        throw_on(gwm_pair_pileup(d.p, n, r.bases, r.offsets, r.n, first_read_id, max_device_bytes, stream, &h->p));
+        return h.release();
+    }, static_cast<gw_mapper_pileup*>(nullptr));
+}
+
+int64_t gw_mapper_pileup_bases(const gw_mapper_pileup* pileup) { return pileup->p.n_bases; }
+
+int gw_mapper_pileup_copy(const gw_mapper_pileup* pileup, uint32_t* counts, float* stage_ms)
+{
+    return guarded([&] {
+        const gwm_pileup& p = pileup->p;
+        copy_out(counts, p.counts, 6 * p.n_bases);
+        if (stage_ms)
+            std::memcpy(stage_ms, p.stage_ms, sizeof(p.stage_ms));
+        return 0;
+    }, GW_MAPPER_ERROR);
+}
+
+void gw_mapper_pileup_destroy(gw_mapper_pileup* pileup) { delete pileup; }
+
 gw_mapper_windows* gw_mapper_window_overlaps_weighted(const void* overlaps, int64_t n, const char* query_bases,
                                                       const int64_t* query_offsets, int32_t n_queries,
                                                       uint32_t first_query_read_id, const char* target_bases,

@@ -21,8 +21,17 @@ both of its reads out of that one alignment.
     corrected, report = correct_reads(reads, qualities=qualities)
 
 With qualities every base of a layer enters the POA with its Phred score as its weight, and layers whose mean quality
-is below min_mean_quality are dropped."""
+is below min_mean_quality are dropped.
+
+    piles = pileup(reads, [draft])                                 # uint32 (6, len(draft)): A, C, G, T, deletion, insertion
+    piles = read_pileup(reads); coverage = depth(piles[0])
+
+How every base of the draft, or of a read, is supported by the alignments polish() / correct_reads() use: per base the
+number of aligned reads that put an A, C, G or T there, that delete it, and that insert after it, counted on the
+device from the alignment states."""
 import time
+
+import numpy as np
 
 from . import cudamapper, cudapoa
 
@@ -170,6 +179,60 @@ def correct_reads(reads, overlaps=None, window_length=500, max_depth=30, band_wi
     t4 = time.perf_counter()
     times.update(map_seconds=t1 - t0, windows_seconds=t2 - t1, poa_seconds=t3 - t2, stitch_seconds=t4 - t3)
     return corrected, report
+
+
+def _mapped(who, reads, targets, overlaps, mapping_parameters):
+    """the overlaps of a pileup call: those given, or the mapping polish() / correct_reads() run, with their refusals"""
+    if overlaps is not None:
+        if mapping_parameters:
+            raise TypeError("%s: mapping parameters given together with overlaps" % who)
+        return overlaps
+    shortest = mapping_parameters.get("k", 15) + mapping_parameters.get("w", 10) - 1
+    if any(len(r) < shortest for r in list(reads) + list(targets or [])):
+        raise ValueError("%s: a read shorter than k + w - 1 = %d bases cannot be mapped" % (who, shortest))
+    if mapping_parameters.get("align"):
+        raise ValueError("%s: the overlaps are aligned by the pileup step" % who)
+    parameters = dict(dict(post_process=True, rescue_overlap_ends=True, filtering_parameter=1.0), **mapping_parameters)
+    return cudamapper.map_reads_batched(reads, targets, **parameters)
+
+
+def one_overlap_per_read(overlaps):
+    """Rule 1 of INTEGRATION.md section 3j: the positions (ascending) of the overlaps polish() aligns, one per query
+    read -- the one with the greatest query span, the first on ties."""
+    best = {}
+    for i, o in enumerate(overlaps):
+        span = int(o["query_end_position_in_read"]) - int(o["query_start_position_in_read"])
+        q = int(o["query_read_id"])
+        if q not in best or span > best[q][0]:
+            best[q] = (span, i)
+    return sorted(i for _, i in best.values())
+
+
+def pileup(reads, targets, overlaps=None, timings=None, **mapping_parameters):
+    """How every base of `targets` is supported by the alignments polish() uses: a list with one uint32 array of shape
+    (6, len(target)) per target, rows as cudamapper.PILEUP_CHANNELS -- how many aligned reads put an A, C, G or T at
+    the base, how many delete it and how many insert after it. overlaps as for polish():
+    None maps first, with the same defaults and the same refusals. One overlap per query read is kept (rule 1 of
+    section 3j) and counted by cudamapper.overlap_pileup, which `timings` is passed to; depth(pile) is the coverage."""
+    overlaps = _mapped("pileup", reads, targets, overlaps, mapping_parameters)
+    kept = np.ascontiguousarray(overlaps, cudamapper.OVERLAP)
+    kept = kept[one_overlap_per_read(kept)]
+    return cudamapper.overlap_pileup(kept, reads, targets, timings=timings)
+
+
+def read_pileup(reads, overlaps=None, timings=None, **mapping_parameters):
+    """pileup() for the reads of a set mapped against itself, over the alignments correct_reads() uses: one array per
+    read. overlaps as for correct_reads(): None maps first. One record per pair of reads is kept
+    (cudamapper.select_pairs, rule C1 of section 3k), aligned once and counted for both of its reads
+    (cudamapper.pair_pileup); self overlaps count nowhere."""
+    overlaps = _mapped("read_pileup", reads, None, overlaps, mapping_parameters)
+    overlaps = np.ascontiguousarray(overlaps, cudamapper.OVERLAP)
+    return cudamapper.pair_pileup(overlaps[cudamapper.select_pairs(overlaps)], reads, timings=timings)
+
+
+def depth(pile):
+    """the coverage of every base of a pileup array: the overlaps that put a base there or delete it"""
+    return pile[:5].sum(0)
 
 
 def read_fastq(path):

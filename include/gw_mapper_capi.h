@@ -2,7 +2,7 @@
  * gw_mapper_capi.h -- flat C API of cudamapper (libcudamapper.so), for foreign-function bindings
  * (genomeworks_amd/cudamapper.py): index creation from host reads, the anchor matcher, the triggered overlapper, one
  * call for a whole mapping of one index pair, overlap post-processing, end rescue and alignment of overlaps into
- * CIGARs, their cutting into POA windows for polishing, packed host copies of indices, the index batcher and the cached batched driver behind the cudamapper tool.
+ * CIGARs, their cutting into POA windows for polishing, their pileups, packed host copies of indices, the index batcher and the cached batched driver behind the cudamapper tool.
  * Functions returning int give 0 on success; those returning a count give it, or GW_MAPPER_ERROR; creators return NULL.
  * On an error the exception text is in gw_mapper_last_error().
  *
@@ -271,6 +271,35 @@ int64_t gw_mapper_select_correction_layers_weighted(const void* target_role, int
 int gw_mapper_segment_quality_sums(const void* segments, int64_t n_segments, const void* overlaps, int64_t n_overlaps,
                                    int32_t query_role, const char* qualities, const int64_t* offsets, int32_t n_reads,
                                    uint32_t first_read_id, uint32_t* sums, void* stream, float* sums_ms);
+
+/* ---- pileups: per-base counts of aligned overlaps --------------------------------------------------------------------
+   Six uint32 counters per base of the read that owns the position -- channels 0..5 = A, C, G, T, deletion, insertion --,
+   added up on the device from the alignment states (gwm_overlap_pileup and gwm_pair_pileup of gwhip_mapper.h; the rules
+   are in INTEGRATION.md section 3m). Neither the states nor any CIGAR text reach the host: the counters do, once. */
+
+/* The pileup of the target set under n host overlaps over host reads (target_bases NULL: the target set is the query
+   set). The reads are uploaded once, the overlaps are aligned as gw_mapper_align_overlaps aligns them and counted on
+   the device as they stand: no overlap is selected here. The handle keeps the counters on the device until they are
+   copied. Without overlaps every counter is 0. Errors as for gw_mapper_align_overlaps (NULL). */
+typedef struct gw_mapper_pileup gw_mapper_pileup;
+gw_mapper_pileup* gw_mapper_overlap_pileup(const void* overlaps, int64_t n, const char* query_bases,
+                                           const int64_t* query_offsets, int32_t n_queries,
+                                           uint32_t first_query_read_id, const char* target_bases,
+                                           const int64_t* target_offsets, int32_t n_targets,
+                                           uint32_t first_target_read_id, int64_t max_device_bytes, void* stream);
+/* The pileup of one read set under records that are taken for pairs as they stand (no pair selection): every pair is
+   aligned once and counted for both of its reads, the target read in the target role and the query read in the query
+   role, into the one array. */
+gw_mapper_pileup* gw_mapper_pair_pileup(const void* pairs, int64_t n, const char* bases, const int64_t* offsets,
+                                        int32_t n_reads, uint32_t first_read_id, int64_t max_device_bytes,
+                                        void* stream);
+/* bases of the owner set: offsets[n_reads] */
+int64_t gw_mapper_pileup_bases(const gw_mapper_pileup* pileup);
+/* counts[6 * bases], channel-major planes: counts[c * bases + offsets[read] + p] is channel c of position p of read
+   `read` (position in its set) -- one copy from the device --, and stage_ms[3]: device time of gather, align and
+   pileup. Either pointer may be NULL. */
+int gw_mapper_pileup_copy(const gw_mapper_pileup* pileup, uint32_t* counts, float* stage_ms);
+void gw_mapper_pileup_destroy(gw_mapper_pileup* pileup);
 
 /* group_reads_into_indices: consecutive reads while the running base count stays <= max_basepairs_per_index; a longer
    read gets an index of its own. The reference's loop as it stands: when the very first read is longer than the limit

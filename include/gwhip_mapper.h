@@ -278,6 +278,55 @@ int gwm_pair_segments(const gwm_overlap* pairs, int64_t n, const char* bases, co
                       uint32_t first_read_id, int32_t window_length, int64_t max_device_bytes, void* stream,
                       gwm_segments* target_role, gwm_segments* query_role);
 
+/* ---- pileups: per-base counts of aligned overlaps ----------------------------------------
+ * Six counters per base of the read that owns the position, channels 0..5 = A, C, G, T, deletion, insertion. */
+
+/* The pileup of a read set of n_bases bases (offsets[n_reads]). Device array, owned by the struct; free it with
+ * gwm_pileup_free. */
+typedef struct gwm_pileup
+{
+    int64_t n_bases;   /* bases of the owner set */
+    uint32_t* counts;  /* device [6 * n_bases], channel-major planes: counts[c * n_bases + offsets[read] + p] is channel c
+                          of position p of read `read` (position in its set); NULL when n_bases is 0 */
+    float stage_ms[3]; /* HIP events, summed over the chunks: gather, align, pileup */
+} gwm_pileup;
+
+/* gwm_window_segments with a third consumer of the alignment states: the same arguments without window_length, the
+ * same slices, strand, aligner, chunking (and its independence of max_device_bytes) and errors; instead of records it
+ * leaves the pileup of the target set on the device, zeroed by the call and then added to. With the states, a(j), b(j),
+ * q and t of a column as for gwm_window_segments, A and B those counts over the whole alignment (the slice lengths of
+ * an alignment that has a result), and the owner the target read, positions in forward target coordinates:
+ *   state < 2: +1 at (t, channel of Q[q]), the complement channel on '-';
+ *   state 2:   +1 at (t, deletion);
+ *   a maximal run of state 3 that starts at column j with 1 <= b(j) <= B - 1: +1 at (p, insertion), p the smaller
+ *   target position of its two neighbours, target start + b(j) - 1 on '+' and target end - 1 - b(j) on '-'. A run at
+ *   either end of the alignment, which has no neighbour on one side, is not counted.
+ * The channel of a base byte c is (0, 1, 3, 2)[(c >> 1) & 3], the aligner's folding read as A, C, G, T, and the
+ * complement of channel k is 3 - k; a byte other than ACGT (and their lower-case forms) counts as the letter the
+ * aligner folds it to, N as G. An alignment without columns (no result, or two empty slices) adds nothing; a record
+ * given twice counts twice. For every position the channels 0..4 sum to the number of records with a result whose
+ * target slice covers it.
+ * One wave64 per alignment over tiles of 64 columns, one returnless atomic add per counted column or run; the
+ * supplier's base is read from the resident read set. The states are not copied anywhere. max_device_bytes bounds a
+ * chunk's working set exactly as for gwm_align_overlaps; the counters, 24 B per base of the target set, are the
+ * result and lie outside that budget, as the segment records do. n == 0 launches no kernel and gives zeroed counters.
+ * On an error the call returns -1, sets gwm_last_error() and leaves *out zeroed. */
+int gwm_overlap_pileup(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                       int32_t n_queries, uint32_t first_query_read_id, const char* target_bases,
+                       const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
+                       int64_t max_device_bytes, void* stream, gwm_pileup* out);
+void gwm_pileup_free(gwm_pileup* pileup);
+
+/* Read correction's pileup: one read set, as for gwm_pair_segments, and one array of counters into which both roles of
+ * every pair are added out of one alignment, by the same chunk consumer. The target role is that of gwm_overlap_pileup.
+ * In the query role the owner is the query read and positions are query positions, ascending on both strands:
+ *   state < 2: +1 at (q, channel of T[t]), the complement channel on '-';
+ *   state 3:   +1 at (q, deletion);
+ *   a maximal run of state 2 that starts at column j with 1 <= a(j) <= A - 1: +1 at (query start + a(j) - 1, insertion).
+ * Memory and errors as for gwm_overlap_pileup. */
+int gwm_pair_pileup(const gwm_overlap* pairs, int64_t n, const char* bases, const int64_t* offsets, int32_t n_reads,
+                    uint32_t first_read_id, int64_t max_device_bytes, void* stream, gwm_pileup* out);
+
 /* One sequence of a gather plan (20 B): bases [begin, end) of read `read` (position in its set) of the query set
  * (set 0) or the target set (set 1); reversed != 0: back to front, every byte through "TGAC"[(c >> 1) & 3]. */
 typedef struct gwm_gather_entry
