@@ -7,14 +7,13 @@
 // the bases nor the states cross to the host; the overlap records (36 B each) are read there to size the chunks.
 //
 // CIGAR text: one wave64 per alignment over
-// tiles of 64 columns -- symbol per lane, run heads by comparison with the neighbouring lane, a 64-bit ballot, run
-// lengths from the distance to the next lower set bit, the open run carried between tiles in wave-uniform registers;
-// a counting pass, an exclusive scan of the byte counts, a writing pass. No LDS, no scratch.
-#include "gwm_align_chunks.hpp"
+// tiles of 64 columns (the states as WaveStates of gwm_column_walk.hpp reads them) -- symbol per lane, run heads by
+// comparison with the neighbouring lane, a 64-bit ballot, run lengths from the distance to the next lower set bit, the
+// open run carried between tiles in wave-uniform registers; a counting pass, an exclusive scan of the byte counts, a
+// writing pass (ChunkedOutput of gwm_align_chunks.hpp). No LDS, no scratch.
+#include "gwm_column_walk.hpp"
 
 #include "gwhip.h"
-
-#include <deque>
 
 namespace
 {
@@ -68,8 +67,7 @@ __global__ void __launch_bounds__(kThreads) slice_lengths_kernel(const gwm_overl
 
 // Block b writes slice b of the chunk (even: the query slice of overlap b / 2, odd: its target slice, forward target
 // coordinates) to sequences[starts[b] .. starts[b + 1]). A '-' target slice is written back to front through the
-// aligner's complement table, "TGAC"[(c >> 1) & 3] for every byte. Lane L of a pass takes output byte L: ascending
-// addresses on both sides, or descending ones on the read side when reversed -- one segment per wave either way.
+// aligner's complement table, "TGAC"[(c >> 1) & 3] for every byte (copy_slice of gwm_device_utils.hpp).
 __global__ void __launch_bounds__(kThreads) gather_kernel(const gwm_overlap* __restrict__ o, ReadSet qs, ReadSet ts,
                                                           const int64_t* __restrict__ starts,
                                                           uint8_t* __restrict__ sequences)
@@ -82,18 +80,7 @@ __global__ void __launch_bounds__(kThreads) gather_kernel(const gwm_overlap* __r
     const uint32_t from = target ? x.target_start_position_in_read : x.query_start_position_in_read;
     const uint8_t* src  = set.bases + set.offsets[read] + from;
     const int64_t at    = starts[b];
-    const int64_t len   = starts[b + 1] - at;
-    uint8_t* dst        = sequences + at;
-    if (target && x.relative_strand == '-')
-    {
-        for (int64_t j = threadIdx.x; j < len; j += kThreads)
-            dst[j] = static_cast<uint8_t>("TGAC"[(src[len - 1 - j] >> 1) & 3]);
-    }
-    else
-    {
-        for (int64_t j = threadIdx.x; j < len; j += kThreads)
-            dst[j] = src[j];
-    }
+    copy_slice(sequences + at, src, starts[b + 1] - at, target && x.relative_strand == '-', AsItIs{}, Complement{});
 }
 
 __device__ inline uint32_t decimal_digits(uint32_t v)
@@ -128,19 +115,16 @@ __global__ void __launch_bounds__(kThreads) cigar_kernel(const uint8_t* __restri
     const uint32_t lane = threadIdx.x & 63u;
     if (i >= m)
         return; // whole waves leave together
-    const int64_t slot   = starts[2 * i];
-    const int32_t stored = result_lengths[i];
-    const uint32_t len   = static_cast<uint32_t>(stored < 0 ? -stored : stored); // as the host aligner reads it
-    const uint8_t* s     = results + slot;
-    char* out            = kWrite ? text + text_offsets[i] : nullptr;
+    const WaveStates w(results, starts, result_lengths, i);
+    char* out = kWrite ? text + text_offsets[i] : nullptr;
     uint32_t open_op = 0xffu, open_len = 0; // the run that is still open behind the tiles walked so far (wave-uniform)
     uint32_t written = 0, edits = 0;        // wave-uniform
     uint32_t bytes   = 0;                   // per lane
-    for (uint32_t base = 0; base < len; base += 64)
+    for (uint32_t base = 0; base < w.len; base += 64)
     {
-        const uint32_t columns = min(64u, len - base);
+        const uint32_t columns = min(64u, w.len - base);
         const bool valid       = lane < columns;
-        const uint32_t state   = valid ? s[len - 1 - base - lane] : 0u;
+        const uint32_t state   = w.state(base, lane, valid);
         const uint32_t op      = state < 2 ? 0u : state;
         uint32_t before        = __shfl_up(op, 1, 64);
         if (lane == 0)
@@ -193,7 +177,7 @@ __global__ void __launch_bounds__(kThreads) cigar_kernel(const uint8_t* __restri
         if (lane == 0)
         {
             text_bytes[i]     = bytes + (open_len ? decimal_digits(open_len) + 1 : 0u);
-            edit_distances[i] = len ? static_cast<int32_t>(edits) : (starts[2 * i + 2] == slot ? 0 : -1);
+            edit_distances[i] = w.edit_distance(edits, starts, i);
         }
     }
 }
@@ -211,17 +195,11 @@ inline int64_t chunk_bytes(int64_t m, int64_t bases, size_t workspace)
 namespace gwm
 {
 
-void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, const char* query_bases,
-                  const int64_t* query_offsets, int32_t n_queries, uint32_t first_query_read_id,
-                  const char* target_bases, const int64_t* target_offsets, int32_t n_targets,
-                  uint32_t first_target_read_id, int64_t max_device_bytes, hipStream_t s, float* stage_ms,
+void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, const ReadSet& q, const ReadSet& t,
+                  int64_t max_device_bytes, hipStream_t s, float* stage_ms,
                   const std::function<void(const AlignedChunk&)>& consume)
 {
     const std::string who = std::string(name) + ": ";
-    const ReadSet q{reinterpret_cast<const uint8_t*>(query_bases), query_offsets, static_cast<uint32_t>(n_queries),
-                    first_query_read_id};
-    const ReadSet t{reinterpret_cast<const uint8_t*>(target_bases), target_offsets, static_cast<uint32_t>(n_targets),
-                    first_target_read_id};
     {
         dbuf<uint32_t> bad(1);
         GWM_CHECK(hipMemsetAsync(bad.p, 0, sizeof(uint32_t), s));
@@ -339,7 +317,6 @@ void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, cons
     }
 }
 
-
 } // namespace gwm
 
 extern "C" {
@@ -368,58 +345,34 @@ int gwm_align_overlaps(const gwm_overlap* overlaps, int64_t n, const char* query
     *out = gwm_cigars{};
     try
     {
-        if (n_queries < 0 || n_targets < 0)
-            throw std::invalid_argument("gwm_align_overlaps: negative number of reads");
-        if (max_device_bytes < 0)
-            throw std::invalid_argument("gwm_align_overlaps: negative max_device_bytes");
+        check_chunk_arguments("gwm_align_overlaps", n_queries, n_targets, max_device_bytes, n);
         if (n <= 0)
             return 0;
-        if (n >= (int64_t(1) << 31))
-            throw std::invalid_argument("gwm_align_overlaps: 2^31 overlaps or more");
         hipStream_t s = static_cast<hipStream_t>(stream);
-        dbuf<int64_t> counts(n + 1), offsets(n + 1), local_offsets;
         dbuf<int32_t> edit_distances(n);
-        GWM_CHECK(hipMemsetAsync(counts.p, 0, sizeof(int64_t) * static_cast<size_t>(n + 1), s));
-        std::deque<dbuf<char>> texts; // one per chunk
-        std::vector<int64_t> text_sizes;
-        // the CIGAR writer: byte counts, their scan, the text of the chunk
+        ChunkedOutput<char> cigars(n, s);
         Temp temp;
+        // the CIGAR writer: byte counts, then the text of the chunk
         auto write_cigars = [&](const AlignedChunk& c) {
-            grow(local_offsets, c.m + 1);
-            cigar_kernel<false><<<c.m_waves, kThreads, 0, s>>>(c.results, c.starts, c.result_lengths, c.m,
-                                                              counts.p + c.first, edit_distances.p + c.first, nullptr,
-                                                              nullptr);
-            GWM_CHECK(hipGetLastError());
-            exclusive_sum(counts.p + c.first, local_offsets.p, c.m + 1, temp, s); // entry m of the input is not summed
-            const int64_t text_bytes = to_host(local_offsets.p + c.m, s);
-            texts.emplace_back(text_bytes);
-            text_sizes.push_back(text_bytes);
-            if (text_bytes > 0)
-            {
-                cigar_kernel<true><<<c.m_waves, kThreads, 0, s>>>(c.results, c.starts, c.result_lengths, c.m, nullptr,
-                                                                 nullptr, local_offsets.p, texts.back().p);
-                GWM_CHECK(hipGetLastError());
-            }
+            cigars.add(
+                c, temp, s,
+                [&](int64_t* text_bytes) {
+                    cigar_kernel<false><<<c.m_waves, kThreads, 0, s>>>(c.results, c.starts, c.result_lengths, c.m,
+                                                                      text_bytes, edit_distances.p + c.first, nullptr,
+                                                                      nullptr);
+                },
+                [&](const int64_t* text_offsets, char* text) {
+                    cigar_kernel<true><<<c.m_waves, kThreads, 0, s>>>(c.results, c.starts, c.result_lengths, c.m, nullptr,
+                                                                     nullptr, text_offsets, text);
+                });
         };
-        gwm::align_chunks("gwm_align_overlaps", overlaps, n, query_bases, query_offsets, n_queries, first_query_read_id,
-                     target_bases, target_offsets, n_targets, first_target_read_id, max_device_bytes, s, out->stage_ms,
-                     write_cigars);
-        exclusive_sum(counts.p, offsets.p, n + 1, temp, s);
-        int64_t total = 0;
-        for (int64_t b : text_sizes)
-            total += b;
+        gwm::align_chunks("gwm_align_overlaps", overlaps, n,
+                          read_set(query_bases, query_offsets, n_queries, first_query_read_id),
+                          read_set(target_bases, target_offsets, n_targets, first_target_read_id), max_device_bytes, s,
+                          out->stage_ms, write_cigars);
+        dbuf<int64_t> offsets;
         dbuf<char> text;
-        if (texts.size() == 1)
-            text.p = texts[0].release();
-        else
-        {
-            text.resize(total);
-            int64_t at = 0;
-            for (size_t c = 0; c < texts.size(); at += text_sizes[c], ++c)
-                if (text_sizes[c] > 0)
-                    GWM_CHECK(hipMemcpyAsync(text.p + at, texts[c].p, static_cast<size_t>(text_sizes[c]),
-                                             hipMemcpyDeviceToDevice, s));
-        }
+        const int64_t total = cigars.finish(n, temp, s, offsets, text);
         GWM_CHECK(hipStreamSynchronize(s));
         out->n              = n;
         out->text_bytes     = total;

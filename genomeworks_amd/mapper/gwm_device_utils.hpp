@@ -1,6 +1,7 @@
 // gwm_device_utils.hpp -- helpers shared by the cudamapper translation units (gwm_mapper.hip, gwm_postprocess.hip,
 // gwm_align.hip, gwm_index_cache.hip): what gwm_host_utils.hpp holds (checked HIP calls, owning device buffers,
-// HIP-event stage timers, the device read set) and, on top of it, the rocPRIM scan / select / sort wrappers.
+// HIP-event stage timers, the device read set) and, on top of it, the rocPRIM scan / select / sort wrappers, the timer
+// around a single launch and the slice copy of the gather kernels.
 // Everything here has internal linkage; the one shared object is the error text behind gwm_last_error().
 #ifndef GWM_DEVICE_UTILS_HPP
 #define GWM_DEVICE_UTILS_HPP
@@ -43,6 +44,55 @@ T to_host(const T* d, hipStream_t s)
     GWM_CHECK(hipMemcpyAsync(&h, d, sizeof(T), hipMemcpyDeviceToHost, s));
     GWM_CHECK(hipStreamSynchronize(s));
     return h;
+}
+
+// a device read set from the four arguments the stage functions take it as
+inline ReadSet read_set(const char* bases, const int64_t* offsets, int32_t n_reads, uint32_t first_read_id)
+{
+    return {reinterpret_cast<const uint8_t*>(bases), offsets, static_cast<uint32_t>(n_reads), first_read_id};
+}
+
+// One launch (or several) on s between two HIP events: waits for it, and *ms_out = its device time where asked for.
+template <typename F>
+void timed_launch(hipStream_t s, float* ms_out, F&& launch)
+{
+    Events ev(2);
+    ev.record(0, s);
+    launch();
+    GWM_CHECK(hipGetLastError());
+    ev.record(1, s);
+    const float ms = ev.ms(0, 1); // waits
+    if (ms_out)
+        *ms_out = ms;
+}
+
+// The byte maps of copy_slice: a base as it is, and through the aligner's complement table.
+struct AsItIs
+{
+    __device__ __forceinline__ uint8_t operator()(uint8_t c) const { return c; }
+};
+struct Complement
+{
+    __device__ __forceinline__ uint8_t operator()(uint8_t c) const { return static_cast<uint8_t>("TGAC"[(c >> 1) & 3]); }
+};
+
+// A block copies the slice src[0 .. len) to dst: forward through `forward`, or with `reversed` back to front through
+// `backward`. Thread L of a pass takes output byte L: ascending addresses on both sides, or descending ones on the
+// read side when reversed -- one segment per wave either way.
+template <typename Out, typename Length, typename Forward, typename Backward>
+__device__ __forceinline__ void copy_slice(Out* dst, const uint8_t* src, Length len, bool reversed, Forward forward,
+                                           Backward backward)
+{
+    if (reversed)
+    {
+        for (Length j = threadIdx.x; j < len; j += kThreads)
+            dst[j] = static_cast<Out>(backward(src[len - 1 - j]));
+    }
+    else
+    {
+        for (Length j = threadIdx.x; j < len; j += kThreads)
+            dst[j] = static_cast<Out>(forward(src[j]));
+    }
 }
 
 template <typename In, typename Out>

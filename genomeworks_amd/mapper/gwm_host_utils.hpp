@@ -1,7 +1,8 @@
 // gwm_host_utils.hpp -- the part of the cudamapper helpers that needs nothing but hip_runtime.h, so the host sources
 // (mapper.cpp, gwm_driver.cpp) share it with the .hip translation units, which get it through gwm_device_utils.hpp:
 // checked HIP calls, the owning device buffer, HIP-event timers and the device read set.
-// Everything here has internal linkage; what a translation unit does not use is `inline` and so warns nowhere.
+// Everything here but the read set has internal linkage; what a translation unit does not use is `inline` and so
+// warns nowhere.
 #ifndef GWM_HOST_UTILS_HPP
 #define GWM_HOST_UTILS_HPP
 
@@ -11,8 +12,25 @@
 #include <stdexcept>
 #include <string>
 
+namespace gwm
+{
+
+// A read set on the device: bases[offsets[i] .. offsets[i + 1]) is read first_read_id + i. Not in the unnamed
+// namespace below: align_chunks() (gwm_align_chunks.hpp) takes it across translation units.
+struct ReadSet
+{
+    const uint8_t* bases;
+    const int64_t* offsets;
+    uint32_t n_reads;
+    uint32_t first_read_id;
+};
+
+} // namespace gwm
+
 namespace
 {
+
+using gwm::ReadSet;
 
 inline void check(hipError_t e, const char* what)
 {
@@ -60,15 +78,6 @@ struct dbuf
         n    = 0;
         return r;
     }
-};
-
-// A read set on the device: bases[offsets[i] .. offsets[i + 1]) is read first_read_id + i.
-struct ReadSet
-{
-    const uint8_t* bases;
-    const int64_t* offsets;
-    uint32_t n_reads;
-    uint32_t first_read_id;
 };
 
 struct Events

@@ -4,14 +4,13 @@
 // records, this adds them into six counters per base of the read that owns the position -- A, C, G, T, deletion,
 // insertion -- and leaves the states where they are. Only the counters cross to the host.
 //
-// One wave64 per alignment over tiles of 64 columns in forward column order, as the segment kernel walks them: state
-// per lane, the query and target positions of a column from ballots of the columns that consume a query / a target
-// base and popcounts over the lower lanes, the running counts and the last column's state carried between tiles in
-// wave-uniform registers. A column that consumes a base of the owner issues one returnless atomic add on its cell; the
-// first column of a run that consumes none issues one on the insertion cell of the owner base before the run. The
-// supplier's base is read from the resident read set. No LDS, no scratch. Integer sums: the result depends neither on
-// the order of the atomics nor on the chunking.
-#include "gwm_align_chunks.hpp"
+// One wave64 per alignment over tiles of 64 columns in forward column order, by the walk of gwm_column_walk.hpp that
+// the segment kernel shares, which gives every lane the query and target position of its column; the last column's
+// state is carried between tiles in a wave-uniform register. A column that consumes a base of the owner issues one
+// returnless atomic add on its cell; the first column of a run that consumes none issues one on the insertion cell of
+// the owner base before the run. The supplier's base is read from the resident read set. No LDS, no scratch. Integer
+// sums: the result depends neither on the order of the atomics nor on the chunking.
+#include "gwm_column_walk.hpp"
 
 namespace
 {
@@ -40,14 +39,9 @@ __global__ void __launch_bounds__(kThreads) pileup_kernel(const gwm_overlap* __r
     const uint32_t lane = threadIdx.x & 63u;
     if (i >= m)
         return; // whole waves leave together
-    const gwm_overlap x  = o[i];
-    const int32_t stored = result_lengths[i];
-    const uint32_t len   = static_cast<uint32_t>(stored < 0 ? -stored : stored); // as the host aligner reads it
-    const uint8_t* s     = results + starts[2 * i];
-    const bool reverse   = x.relative_strand == '-';
-    const uint32_t qs = x.query_start_position_in_read, ts = x.target_start_position_in_read,
-                   te = x.target_end_position_in_read;
-    const uint32_t query_length = x.query_end_position_in_read - qs, target_length = te - ts;
+    const WaveAlignment w(o, results, starts, result_lengths, i);
+    const gwm_overlap& x        = w.x;
+    const uint32_t query_length = x.query_end_position_in_read - w.qs, target_length = w.te - w.ts;
     const uint32_t own_length   = kQueryRole ? query_length : target_length;
     const int64_t query_at      = qset.offsets[x.query_read_id - qset.first_read_id];
     const int64_t target_at     = tset.offsets[x.target_read_id - tset.first_read_id];
@@ -57,18 +51,14 @@ __global__ void __launch_bounds__(kThreads) pileup_kernel(const gwm_overlap* __r
     const uint64_t lower        = (1ull << lane) - 1;
     // wave-uniform: columns walked so far that consume a query / a target base, the state of the last one
     uint32_t query_run = 0, target_run = 0, last_state = 0;
-    for (uint32_t base = 0; base < len; base += 64)
+    for (uint32_t base = 0; base < w.len; base += 64)
     {
-        const bool valid         = lane < min(64u, len - base);
-        const uint32_t state     = valid ? s[len - 1 - base - lane] : 0u;
-        const uint64_t in_query  = __ballot(valid && state != 2);
-        const uint64_t in_target = __ballot(valid && state != 3);
-        const uint32_t a         = query_run + static_cast<uint32_t>(__popcll(in_query & lower));
-        const uint32_t b         = target_run + static_cast<uint32_t>(__popcll(in_target & lower));
-        const uint32_t q         = qs + a;
-        const uint32_t t         = reverse ? te - 1 - b : ts + b;
-        const uint32_t own = kQueryRole ? q : t, other = kQueryRole ? t : q;
-        const uint32_t consumed = kQueryRole ? a : b; // owner bases before this column
+        const TileColumn c(w, base, lane, lower, query_run, target_run);
+        query_run = c.query_run, target_run = c.target_run;
+        const bool valid     = c.valid;
+        const uint32_t state = c.state;
+        const uint32_t own = kQueryRole ? c.q : c.t, other = kQueryRole ? c.t : c.q;
+        const uint32_t consumed = kQueryRole ? c.a : c.b; // owner bases before this column
         // the previous column: the next lower lane, or the last column of the tile before
         uint32_t before = __shfl_up(state, 1, 64);
         if (lane == 0)
@@ -76,11 +66,11 @@ __global__ void __launch_bounds__(kThreads) pileup_kernel(const gwm_overlap* __r
         if (valid && state != kSkips && consumed < own_length)
         {
             uint32_t channel = kDeletion;
-            if (state < 2 && a < query_length && b < target_length)
+            if (state < 2 && c.a < query_length && c.b < target_length)
             {
                 const uint32_t code = (static_cast<uint32_t>(supplier[other]) >> 1) & 3u; // A, C, T, G = 0, 1, 2, 3
                 channel             = code ^ (code >> 1);                                 // A, C, G, T = 0, 1, 2, 3
-                if (reverse)
+                if (w.reverse)
                     channel = 3u - channel;
             }
             (void)atomicAdd(cells + static_cast<int64_t>(channel) * n_bases + own, 1u);
@@ -89,24 +79,11 @@ __global__ void __launch_bounds__(kThreads) pileup_kernel(const gwm_overlap* __r
         {
             // a run's first column, with owner bases on both sides (a run in column 0 has consumed none)
             // `own` is the owner position behind the run in column order: the larger neighbour where it ascends
-            const uint32_t p = !kQueryRole && reverse ? own : own - 1;
+            const uint32_t p = !kQueryRole && w.reverse ? own : own - 1;
             (void)atomicAdd(cells + static_cast<int64_t>(kInsertion) * n_bases + p, 1u);
         }
         last_state = __shfl(state, 63, 64);
-        query_run += static_cast<uint32_t>(__popcll(in_query));
-        target_run += static_cast<uint32_t>(__popcll(in_target));
     }
-}
-
-void check_pileup_arguments(const std::string& who, int32_t n_queries, int32_t n_targets, int64_t max_device_bytes,
-                            int64_t n)
-{
-    if (n_queries < 0 || n_targets < 0)
-        throw std::invalid_argument(who + ": negative number of reads");
-    if (max_device_bytes < 0)
-        throw std::invalid_argument(who + ": negative max_device_bytes");
-    if (n >= (int64_t(1) << 31))
-        throw std::invalid_argument(who + ": 2^31 overlaps or more");
 }
 
 // the zeroed counters of a read set whose offsets are on the device: six planes of offsets[n_reads] cells
@@ -150,18 +127,14 @@ int gwm_overlap_pileup(const gwm_overlap* overlaps, int64_t n, const char* query
     *out = gwm_pileup{};
     try
     {
-        check_pileup_arguments("gwm_overlap_pileup", n_queries, n_targets, max_device_bytes, n);
+        check_chunk_arguments("gwm_overlap_pileup", n_queries, n_targets, max_device_bytes, n);
         hipStream_t s = static_cast<hipStream_t>(stream);
         dbuf<uint32_t> counts;
         const int64_t n_bases = zeroed_counts(target_offsets, n_targets, s, counts);
-        const ReadSet q{reinterpret_cast<const uint8_t*>(query_bases), query_offsets, static_cast<uint32_t>(n_queries),
-                        first_query_read_id};
-        const ReadSet t{reinterpret_cast<const uint8_t*>(target_bases), target_offsets,
-                        static_cast<uint32_t>(n_targets), first_target_read_id};
+        const ReadSet q = read_set(query_bases, query_offsets, n_queries, first_query_read_id);
+        const ReadSet t = read_set(target_bases, target_offsets, n_targets, first_target_read_id);
         if (n > 0)
-            gwm::align_chunks("gwm_overlap_pileup", overlaps, n, query_bases, query_offsets, n_queries,
-                              first_query_read_id, target_bases, target_offsets, n_targets, first_target_read_id,
-                              max_device_bytes, s, out->stage_ms,
+            gwm::align_chunks("gwm_overlap_pileup", overlaps, n, q, t, max_device_bytes, s, out->stage_ms,
                               [&](const AlignedChunk& c) { add_role<false>(c, q, t, n_bases, counts.p, s); });
         GWM_CHECK(hipStreamSynchronize(s));
         out->n_bases = n_bases;
@@ -182,14 +155,14 @@ int gwm_pair_pileup(const gwm_overlap* pairs, int64_t n, const char* bases, cons
     *out = gwm_pileup{};
     try
     {
-        check_pileup_arguments("gwm_pair_pileup", n_reads, n_reads, max_device_bytes, n);
+        check_chunk_arguments("gwm_pair_pileup", n_reads, n_reads, max_device_bytes, n);
         hipStream_t s = static_cast<hipStream_t>(stream);
         dbuf<uint32_t> counts;
         const int64_t n_bases = zeroed_counts(offsets, n_reads, s, counts);
-        const ReadSet r{reinterpret_cast<const uint8_t*>(bases), offsets, static_cast<uint32_t>(n_reads), first_read_id};
+        const ReadSet r = read_set(bases, offsets, n_reads, first_read_id);
         if (n > 0)
-            gwm::align_chunks("gwm_pair_pileup", pairs, n, bases, offsets, n_reads, first_read_id, bases, offsets,
-                              n_reads, first_read_id, max_device_bytes, s, out->stage_ms, [&](const AlignedChunk& c) {
+            gwm::align_chunks("gwm_pair_pileup", pairs, n, r, r, max_device_bytes, s, out->stage_ms,
+                              [&](const AlignedChunk& c) {
                                   add_role<false>(c, r, r, n_bases, counts.p, s);
                                   add_role<true>(c, r, r, n_bases, counts.p, s);
                               });

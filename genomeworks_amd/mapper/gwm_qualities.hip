@@ -95,17 +95,8 @@ __global__ void __launch_bounds__(kThreads) gather_weights_kernel(const gwm_gath
             dst[j] = 1;
         return;
     }
-    const uint8_t* src = set.bases + set.offsets[e.read] + e.begin;
-    if (e.reversed)
-    {
-        for (uint32_t j = threadIdx.x; j < len; j += kThreads)
-            dst[j] = static_cast<int8_t>(weight_of(src[len - 1 - j]));
-    }
-    else
-    {
-        for (uint32_t j = threadIdx.x; j < len; j += kThreads)
-            dst[j] = static_cast<int8_t>(weight_of(src[j]));
-    }
+    const auto weight = [](uint8_t c) { return weight_of(c); };
+    copy_slice(dst, set.bases + set.offsets[e.read] + e.begin, len, e.reversed != 0, weight, weight);
 }
 
 template <bool kQueryRole>
@@ -123,15 +114,10 @@ void quality_sums(const gwm_segment* segments, int64_t n, const gwm_overlap* ove
         throw std::invalid_argument("gwm_segment_quality_sums: a record's overlap names a read outside the read set");
     if (what & 4u)
         throw std::invalid_argument("gwm_segment_quality_sums: a record lies beyond the end of its read");
-    Events ev(2);
-    ev.record(0, s);
     const unsigned blocks = static_cast<unsigned>((n + kWavesPerBlock - 1) / kWavesPerBlock);
-    quality_sums_kernel<kQueryRole><<<blocks, kThreads, 0, s>>>(segments, n, overlaps, set, sums);
-    GWM_CHECK(hipGetLastError());
-    ev.record(1, s);
-    const float ms = ev.ms(0, 1); // waits
-    if (sums_ms)
-        *sums_ms = ms;
+    timed_launch(s, sums_ms, [&] {
+        quality_sums_kernel<kQueryRole><<<blocks, kThreads, 0, s>>>(segments, n, overlaps, set, sums);
+    });
 }
 
 } // namespace
@@ -155,8 +141,7 @@ int gwm_segment_quality_sums(const gwm_segment* segments, int64_t n_segments, co
         if (!qualities || !offsets || !sums)
             throw std::invalid_argument("gwm_segment_quality_sums: a null array");
         hipStream_t s = static_cast<hipStream_t>(stream);
-        const ReadSet set{reinterpret_cast<const uint8_t*>(qualities), offsets, static_cast<uint32_t>(n_reads),
-                          first_read_id};
+        const ReadSet set = read_set(qualities, offsets, n_reads, first_read_id);
         if (query_role)
             quality_sums<true>(segments, n_segments, overlaps, n_overlaps, set, sums, s, sums_ms);
         else
@@ -188,17 +173,12 @@ int gwm_gather_weights(const gwm_gather_entry* plan, int64_t n, const int64_t* o
         if (n >= (int64_t(1) << 31))
             throw std::invalid_argument("gwm_gather_weights: 2^31 sequences or more");
         hipStream_t s = static_cast<hipStream_t>(stream);
-        const ReadSet q{reinterpret_cast<const uint8_t*>(query_qualities), query_offsets, static_cast<uint32_t>(n_queries), 0};
-        const ReadSet t{reinterpret_cast<const uint8_t*>(target_qualities), target_offsets, static_cast<uint32_t>(n_targets), 0};
+        const ReadSet q = read_set(query_qualities, query_offsets, n_queries, 0);
+        const ReadSet t = read_set(target_qualities, target_offsets, n_targets, 0);
         validate_plan("gwm_gather_weights", plan, n, out_starts, q, t, out_bytes, s);
-        Events ev(2);
-        ev.record(0, s);
-        gather_weights_kernel<<<static_cast<unsigned>(n), kThreads, 0, s>>>(plan, out_starts, q, t, out);
-        GWM_CHECK(hipGetLastError());
-        ev.record(1, s);
-        const float ms = ev.ms(0, 1); // waits
-        if (gather_ms)
-            *gather_ms = ms;
+        timed_launch(s, gather_ms, [&] {
+            gather_weights_kernel<<<static_cast<unsigned>(n), kThreads, 0, s>>>(plan, out_starts, q, t, out);
+        });
         return 0;
     }
     catch (const std::exception& e)

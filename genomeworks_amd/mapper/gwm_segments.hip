@@ -5,22 +5,20 @@
 // records cross to the host, where the layers of every window are chosen (gwm_windows.cpp); gwm_gather_sequences then
 // cuts backbones and layers out of the resident read sets.
 //
-// Segments: one wave64 per alignment over tiles of 64 columns in forward column order -- state per lane, the query and
-// target positions of a column from ballots of the columns that consume a query / a target base and popcounts over the
-// lower lanes, the running counts and the last aligned column's (window, target position, query position) carried
-// between tiles in wave-uniform registers. An aligned column whose window differs from the previous aligned column's
+// Segments: one wave64 per alignment over tiles of 64 columns in forward column order, by the walk of
+// gwm_column_walk.hpp, which gives every lane the query and target position of its column; the last aligned column's
+// (window, target position, query position) is carried between tiles in wave-uniform registers. An aligned column whose window differs from the previous aligned column's
 // is a head: it opens a record and closes the one before it; lane 0 closes the last one behind the tiles. A counting
 // pass, an exclusive scan of the record counts, a writing pass. Forward column order is ascending target order on '+'
 // and descending on '-', where the record of the r-th head goes to the r-th place from the end: records come out
-// window-ascending on both strands. No LDS, no scratch.
+// window-ascending on both strands. No LDS, no scratch. The count / scan / write bookkeeping of the two passes is
+// ChunkedOutput of gwm_align_chunks.hpp.
 //
 // gwm_pair_segments (read correction, both reads of a pair out of one alignment) runs the same kernel a second time per
 // chunk in its query role: the windows are those of the query read, whose positions ascend in forward column order on
 // both strands, and the ranges of the record are those of the target positions.
-#include "gwm_align_chunks.hpp"
+#include "gwm_column_walk.hpp"
 #include "gwm_gather_plan.hpp"
-
-#include <deque>
 
 namespace
 {
@@ -51,38 +49,26 @@ __global__ void __launch_bounds__(kThreads) segment_kernel(const gwm_overlap* __
     const uint32_t lane = threadIdx.x & 63u;
     if (i >= m)
         return; // whole waves leave together
-    const gwm_overlap x  = o[i];
-    const int64_t slot   = starts[2 * i];
-    const int32_t stored = result_lengths[i];
-    const uint32_t len   = static_cast<uint32_t>(stored < 0 ? -stored : stored); // as the host aligner reads it
-    const uint8_t* s     = results + slot;
-    const bool reverse   = x.relative_strand == '-';
-    const bool own_down = !kQueryRole && reverse, other_down = kQueryRole && reverse;
-    const uint32_t qs = x.query_start_position_in_read, ts = x.target_start_position_in_read,
-                   te      = x.target_end_position_in_read;
-    const uint32_t total   = kWrite ? static_cast<uint32_t>(offsets[i + 1] - offsets[i]) : 0u;
-    gwm_segment* out       = kWrite ? segments + offsets[i] : nullptr;
-    const uint64_t lower   = (1ull << lane) - 1;
+    const WaveAlignment w(o, results, starts, result_lengths, i);
+    const bool own_down  = !kQueryRole && w.reverse, other_down = kQueryRole && w.reverse;
+    const uint32_t total = kWrite ? static_cast<uint32_t>(offsets[i + 1] - offsets[i]) : 0u;
+    gwm_segment* out     = kWrite ? segments + offsets[i] : nullptr;
+    const uint64_t lower = (1ull << lane) - 1;
     // wave-uniform: columns walked so far that consume a query / a target base, the last aligned column, records opened
     uint32_t query_run = 0, target_run = 0;
     bool has_last   = false;
     uint32_t last_k = 0, last_own = 0, last_other = 0;
     uint32_t records = 0, edits = 0;
-    for (uint32_t base = 0; base < len; base += 64)
+    for (uint32_t base = 0; base < w.len; base += 64)
     {
-        const bool valid          = lane < min(64u, len - base);
-        const uint32_t state      = valid ? s[len - 1 - base - lane] : 0u;
-        const uint64_t in_query   = __ballot(valid && state != 2);
-        const uint64_t in_target  = __ballot(valid && state != 3);
-        const bool aligned        = valid && state < 2;
+        const TileColumn c(w, base, lane, lower, query_run, target_run);
+        query_run = c.query_run, target_run = c.target_run;
+        const bool aligned        = c.valid && c.state < 2;
         const uint64_t aligned_at = __ballot(aligned);
         if (!kWrite)
-            edits += static_cast<uint32_t>(__popcll(__ballot(valid && state != 0)));
-        const uint32_t q     = qs + query_run + static_cast<uint32_t>(__popcll(in_query & lower));
-        const uint32_t b     = target_run + static_cast<uint32_t>(__popcll(in_target & lower));
-        const uint32_t t     = reverse ? te - 1 - b : ts + b;
-        const uint32_t own   = kQueryRole ? q : t;
-        const uint32_t other = kQueryRole ? t : q;
+            edits += static_cast<uint32_t>(__popcll(__ballot(c.valid && c.state != 0)));
+        const uint32_t own   = kQueryRole ? c.q : c.t;
+        const uint32_t other = kQueryRole ? c.t : c.q;
         const uint32_t k     = aligned ? own / window_length : 0u;
         // the previous aligned column: the next lower aligned lane of the tile, or the one carried in
         const uint64_t below = aligned_at & lower;
@@ -127,8 +113,6 @@ __global__ void __launch_bounds__(kThreads) segment_kernel(const gwm_overlap* __
             last_k = __shfl(k, last, 64), last_own = __shfl(own, last, 64), last_other = __shfl(other, last, 64);
             has_last = true;
         }
-        query_run += static_cast<uint32_t>(__popcll(in_query));
-        target_run += static_cast<uint32_t>(__popcll(in_target));
     }
     if (lane != 0)
         return;
@@ -148,7 +132,7 @@ __global__ void __launch_bounds__(kThreads) segment_kernel(const gwm_overlap* __
     {
         counts[i] = records;
         if (edit_distances)
-            edit_distances[i] = len ? static_cast<int32_t>(edits) : (starts[2 * i + 2] == slot ? 0 : -1);
+            edit_distances[i] = w.edit_distance(edits, starts, i);
     }
 }
 
@@ -161,95 +145,42 @@ __global__ void __launch_bounds__(kThreads) gather_sequences_kernel(const gwm_ga
     const gwm_gather_entry e = plan[blockIdx.x];
     const ReadSet& set       = e.set ? ts : qs;
     const uint8_t* src       = set.bases + set.offsets[e.read] + e.begin;
-    const uint32_t len       = e.end - e.begin;
-    uint8_t* dst             = out + out_starts[blockIdx.x];
-    if (e.reversed)
-    {
-        for (uint32_t j = threadIdx.x; j < len; j += kThreads)
-            dst[j] = static_cast<uint8_t>("TGAC"[(src[len - 1 - j] >> 1) & 3]);
-    }
-    else
-    {
-        for (uint32_t j = threadIdx.x; j < len; j += kThreads)
-            dst[j] = src[j];
-    }
+    copy_slice(out + out_starts[blockIdx.x], src, e.end - e.begin, e.reversed != 0, AsItIs{}, Complement{});
 }
 
 // The records of one role over the chunks of a call: the segment writer (record counts, their scan, the records of the
 // chunk) as a consumer of align_chunks(), and what is left of it when the chunks are through.
-struct RoleRecords
+struct RoleRecords : ChunkedOutput<gwm_segment>
 {
-    dbuf<int64_t> counts, local_offsets;
-    std::deque<dbuf<gwm_segment>> parts; // one per chunk
-    std::vector<int64_t> part_sizes;
-    RoleRecords(int64_t n, hipStream_t s)
-        : counts(n + 1)
-    {
-        GWM_CHECK(hipMemsetAsync(counts.p, 0, sizeof(int64_t) * static_cast<size_t>(n + 1), s));
-    }
+    using ChunkedOutput::ChunkedOutput;
     // edit_distances: of the call, or nullptr to leave them alone
     template <bool kQueryRole>
     void write(const AlignedChunk& c, int32_t window_length, int32_t* edit_distances, Temp& temp, hipStream_t s)
     {
-        grow(local_offsets, c.m + 1);
-        segment_kernel<false, kQueryRole><<<c.m_waves, kThreads, 0, s>>>(
-            c.overlaps, c.results, c.starts, c.result_lengths, c.m, static_cast<uint32_t>(c.first),
-            static_cast<uint32_t>(window_length), counts.p + c.first,
-            edit_distances ? edit_distances + c.first : nullptr, nullptr, nullptr);
-        GWM_CHECK(hipGetLastError());
-        exclusive_sum(counts.p + c.first, local_offsets.p, c.m + 1, temp, s); // entry m of the input is not summed
-        const int64_t records = to_host(local_offsets.p + c.m, s);
-        parts.emplace_back(records);
-        part_sizes.push_back(records);
-        if (records > 0)
-        {
-            segment_kernel<true, kQueryRole><<<c.m_waves, kThreads, 0, s>>>(
-                c.overlaps, c.results, c.starts, c.result_lengths, c.m, static_cast<uint32_t>(c.first),
-                static_cast<uint32_t>(window_length), nullptr, nullptr, local_offsets.p, parts.back().p);
-            GWM_CHECK(hipGetLastError());
-        }
+        const uint32_t first = static_cast<uint32_t>(c.first), w = static_cast<uint32_t>(window_length);
+        add(
+            c, temp, s,
+            [&](int64_t* counts) {
+                segment_kernel<false, kQueryRole><<<c.m_waves, kThreads, 0, s>>>(
+                    c.overlaps, c.results, c.starts, c.result_lengths, c.m, first, w, counts,
+                    edit_distances ? edit_distances + c.first : nullptr, nullptr, nullptr);
+            },
+            [&](const int64_t* offsets, gwm_segment* records) {
+                segment_kernel<true, kQueryRole><<<c.m_waves, kThreads, 0, s>>>(
+                    c.overlaps, c.results, c.starts, c.result_lengths, c.m, first, w, nullptr, nullptr, offsets, records);
+            });
     }
-    // the offsets of the call and the records of its chunks in one array, into *out; queued on s, so this object
-    // outlives the caller's wait for s
+    // into *out, queued on s
     void finish(int64_t n, Temp& temp, hipStream_t s, gwm_segments* out)
     {
-        dbuf<int64_t> offsets(n + 1);
-        exclusive_sum(counts.p, offsets.p, n + 1, temp, s);
-        int64_t total = 0;
-        for (int64_t b : part_sizes)
-            total += b;
+        dbuf<int64_t> offsets;
         dbuf<gwm_segment> segments;
-        if (parts.size() == 1)
-            segments.p = parts[0].release();
-        else
-        {
-            segments.resize(total);
-            int64_t at = 0;
-            for (size_t c = 0; c < parts.size(); at += part_sizes[c], ++c)
-                if (part_sizes[c] > 0)
-                    GWM_CHECK(hipMemcpyAsync(segments.p + at, parts[c].p,
-                                             sizeof(gwm_segment) * static_cast<size_t>(part_sizes[c]),
-                                             hipMemcpyDeviceToDevice, s));
-        }
+        out->n_segments      = ChunkedOutput::finish(n, temp, s, offsets, segments);
         out->n               = n;
-        out->n_segments      = total;
         out->segments        = segments.release();
         out->segment_offsets = offsets.release();
     }
 };
-
-void check_segment_arguments(const std::string& who, int32_t n_queries, int32_t n_targets, int64_t max_device_bytes,
-                             int32_t window_length, int64_t n)
-{
-    if (n_queries < 0 || n_targets < 0)
-        throw std::invalid_argument(who + ": negative number of reads");
-    if (max_device_bytes < 0)
-        throw std::invalid_argument(who + ": negative max_device_bytes");
-    if (window_length < 1)
-        throw std::invalid_argument(who + ": window_length below 1");
-    if (n >= (int64_t(1) << 31))
-        throw std::invalid_argument(who + ": 2^31 overlaps or more");
-}
 
 } // namespace
 
@@ -273,18 +204,21 @@ int gwm_window_segments(const gwm_overlap* overlaps, int64_t n, const char* quer
     *out = gwm_segments{};
     try
     {
-        check_segment_arguments("gwm_window_segments", n_queries, n_targets, max_device_bytes, window_length, n);
+        check_chunk_arguments("gwm_window_segments", n_queries, n_targets, max_device_bytes, n);
+        if (window_length < 1)
+            throw std::invalid_argument("gwm_window_segments: window_length below 1");
         if (n <= 0)
             return 0;
         hipStream_t s = static_cast<hipStream_t>(stream);
         dbuf<int32_t> edit_distances(n);
         RoleRecords records(n, s);
         Temp temp;
-        gwm::align_chunks("gwm_window_segments", overlaps, n, query_bases, query_offsets, n_queries, first_query_read_id,
-                     target_bases, target_offsets, n_targets, first_target_read_id, max_device_bytes, s, out->stage_ms,
-                     [&](const AlignedChunk& c) {
-                         records.write<false>(c, window_length, edit_distances.p, temp, s);
-                     });
+        gwm::align_chunks("gwm_window_segments", overlaps, n,
+                          read_set(query_bases, query_offsets, n_queries, first_query_read_id),
+                          read_set(target_bases, target_offsets, n_targets, first_target_read_id), max_device_bytes, s,
+                          out->stage_ms, [&](const AlignedChunk& c) {
+                              records.write<false>(c, window_length, edit_distances.p, temp, s);
+                          });
         records.finish(n, temp, s, out);
         GWM_CHECK(hipStreamSynchronize(s));
         out->edit_distances = edit_distances.release();
@@ -305,7 +239,9 @@ int gwm_pair_segments(const gwm_overlap* pairs, int64_t n, const char* bases, co
     *target_role = *query_role = gwm_segments{};
     try
     {
-        check_segment_arguments("gwm_pair_segments", n_reads, n_reads, max_device_bytes, window_length, n);
+        check_chunk_arguments("gwm_pair_segments", n_reads, n_reads, max_device_bytes, n);
+        if (window_length < 1)
+            throw std::invalid_argument("gwm_pair_segments: window_length below 1");
         if (n <= 0)
             return 0;
         hipStream_t s = static_cast<hipStream_t>(stream);
@@ -314,8 +250,9 @@ int gwm_pair_segments(const gwm_overlap* pairs, int64_t n, const char* bases, co
         Temp temp;
         Events ev(3);
         float role_ms[2] = {0.f, 0.f}; // the consumer's time, which align_chunks() sums for both, apart for each role
-        gwm::align_chunks("gwm_pair_segments", pairs, n, bases, offsets, n_reads, first_read_id, bases, offsets, n_reads,
-                          first_read_id, max_device_bytes, s, target_role->stage_ms, [&](const AlignedChunk& c) {
+        const ReadSet r = read_set(bases, offsets, n_reads, first_read_id);
+        gwm::align_chunks("gwm_pair_segments", pairs, n, r, r, max_device_bytes, s, target_role->stage_ms,
+                          [&](const AlignedChunk& c) {
                               ev.record(0, s);
                               of_target.write<false>(c, window_length, edit_distances.p, temp, s);
                               ev.record(1, s);
@@ -360,18 +297,13 @@ int gwm_gather_sequences(const gwm_gather_entry* plan, int64_t n, const int64_t*
         if (n >= (int64_t(1) << 31))
             throw std::invalid_argument("gwm_gather_sequences: 2^31 sequences or more");
         hipStream_t s = static_cast<hipStream_t>(stream);
-        const ReadSet q{reinterpret_cast<const uint8_t*>(query_bases), query_offsets, static_cast<uint32_t>(n_queries), 0};
-        const ReadSet t{reinterpret_cast<const uint8_t*>(target_bases), target_offsets, static_cast<uint32_t>(n_targets), 0};
+        const ReadSet q = read_set(query_bases, query_offsets, n_queries, 0);
+        const ReadSet t = read_set(target_bases, target_offsets, n_targets, 0);
         validate_plan("gwm_gather_sequences", plan, n, out_starts, q, t, out_bytes, s);
-        Events ev(2);
-        ev.record(0, s);
-        gather_sequences_kernel<<<static_cast<unsigned>(n), kThreads, 0, s>>>(plan, out_starts, q, t,
-                                                                             reinterpret_cast<uint8_t*>(out));
-        GWM_CHECK(hipGetLastError());
-        ev.record(1, s);
-        const float ms = ev.ms(0, 1); // waits
-        if (gather_ms)
-            *gather_ms = ms;
+        timed_launch(s, gather_ms, [&] {
+            gather_sequences_kernel<<<static_cast<unsigned>(n), kThreads, 0, s>>>(plan, out_starts, q, t,
+                                                                                 reinterpret_cast<uint8_t*>(out));
+        });
         return 0;
     }
     catch (const std::exception& e)

@@ -32,17 +32,36 @@ auto guarded(F&& f, decltype(f()) on_error) -> decltype(f())
     return on_error;
 }
 
-// the three batched entry points: the driver behind the C API's error convention
-gw_mapper_overlaps* map_batched_guarded(const reads_view& queries, const reads_view& targets, const map_options& options,
-                                        void* stream)
+// The read sets and the overlap records of one call on the device, uploaded once: q and t are the device copies of
+// the queries and the targets. even_without_overlaps false: with n <= 0 nothing is uploaded and q, t and d are empty.
+struct device_call
 {
-    return guarded([&] { return map_batched(queries, targets, options, static_cast<hipStream_t>(stream)); },
-                   static_cast<gw_mapper_overlaps*>(nullptr));
+    read_sets reads;
+    dbuf<gwm_overlap> d;
+    const reads_view &q, &t;
+    device_call(const reads_view& queries, const reads_view& targets, const void* overlaps, int64_t n,
+                bool even_without_overlaps)
+        : reads(queries, targets), q(reads.device_queries), t(reads.device_targets)
+    {
+        if (even_without_overlaps || n > 0)
+        {
+            reads.upload();
+            d.upload(static_cast<const gwm_overlap*>(overlaps), n);
+        }
+    }
+};
+
+// the entry points that select layers refuse a negative max_depth, which their helpers take for "segments only"
+bool refuse_negative_depth(const char* who, int32_t max_depth)
+{
+    if (max_depth < 0)
+        g_capi_error = std::string(who) + ": negative max_depth";
+    return max_depth < 0;
 }
 
 // The qualities of a weighted call: Phred+33 bytes that share the offsets of the bases, or
-// nullptr for a set that has none. weighted false: a call of the entry points without qualities, which does nothing of
-// what follows.
+// nullptr for a set that has none. weighted false: a call of the entry points without qualities, which has none, is
+// not validated and gathers no weights; everything else is one path, on which absent qualities filter nothing.
 struct quality_options
 {
     bool weighted                = false;
@@ -156,25 +175,23 @@ gw_mapper_windows* window_overlaps(const void* overlaps, int64_t n, const reads_
         if (n < 0)
             throw std::invalid_argument("gw_mapper_window_overlaps: negative number of overlaps");
         const gwm_overlap* host_overlaps = static_cast<const gwm_overlap*>(overlaps);
-        read_sets reads(query_reads, target_reads);
-        quality_options w = options;
-        if (reads.all_to_all) // the targets are the queries, with the queries' qualities
+        const bool all_to_all            = target_reads.bases == nullptr;
+        quality_options w                = options;
+        if (all_to_all) // the targets are the queries, with the queries' qualities
             w.target_qualities = nullptr;
         if (w.weighted)
-            check_quality_options("gw_mapper_window_overlaps_weighted", w, reads.queries, reads.targets);
-        reads.upload(); // once: the segments pass and the window gather read the same device copies
-        dbuf<char> query_qualities, target_qualities; // once as well, next to the reads
+            check_quality_options("gw_mapper_window_overlaps_weighted", w, query_reads, target_reads);
+        // once: the segments pass and the window gather read the same device copies
+        device_call c(query_reads, target_reads, overlaps, n, true);
+        const read_sets& reads = c.reads;
+        dbuf<char> query_qualities, target_qualities; // once as well, next to the reads; none without qualities
         upload_qualities(query_qualities, w.query_qualities, reads.queries);
-        if (!reads.all_to_all)
-            upload_qualities(target_qualities, w.target_qualities, reads.targets);
-        dbuf<gwm_overlap> d;
-        d.upload(host_overlaps, n);
-        const reads_view &q = reads.device_queries, &t = reads.device_targets;
+        upload_qualities(target_qualities, w.target_qualities, reads.targets);
         // segments on the device, their records (24 B each) to the host
         owned_segments device;
-        throw_on(gwm_window_segments(d.p, n, q.bases, q.offsets, reads.queries.n, first_query_read_id, t.bases, t.offsets,
-                                     reads.targets.n, first_target_read_id, window_length, max_device_bytes, stream,
-                                     &device.s));
+        throw_on(gwm_window_segments(c.d.p, n, c.q.bases, c.q.offsets, reads.queries.n, first_query_read_id, c.t.bases,
+                                     c.t.offsets, reads.targets.n, first_target_read_id, window_length, max_device_bytes,
+                                     stream, &device.s));
         const gwm_segments& s = device.s;
         copy_segments(s, n, h->segments, h->segment_offsets);
         h->edit_distances.resize(static_cast<size_t>(n));
@@ -186,25 +203,16 @@ gw_mapper_windows* window_overlaps(const void* overlaps, int64_t n, const reads_
         std::vector<int64_t> target_lengths(static_cast<size_t>(reads.targets.n));
         for (int32_t r = 0; r < reads.targets.n; ++r)
             target_lengths[r] = reads.targets.offsets[r + 1] - reads.targets.offsets[r];
-        if (!w.weighted)
-        {
-            window_selection selection =
-                select_layers(h->segments.data(), s.n_segments, host_overlaps, n, reads.queries.n, first_query_read_id,
-                              target_lengths.data(), reads.targets.n, first_target_read_id, window_length, max_depth);
-            gather_windows(*h, std::move(selection), q, t, stream);
-            return h.release();
-        }
         // the queries supply every layer: their qualities, where there are any, decide which records are layers (Q2)
         if (query_qualities.p)
-            quality_sums_of(s, d.p, n, 0, query_qualities.p, q, first_query_read_id, stream, h->quality_sums,
+            quality_sums_of(s, c.d.p, n, 0, query_qualities.p, c.q, first_query_read_id, stream, h->quality_sums,
                             h->quality_ms[0]);
         window_selection selection = select_layers(
             h->segments.data(), s.n_segments, host_overlaps, n, reads.queries.n, first_query_read_id,
             target_lengths.data(), reads.targets.n, first_target_read_id, window_length, max_depth,
             query_qualities.p ? h->quality_sums.data() : nullptr, w.min_mean_quality);
-        const char* const device_qualities[2] = {query_qualities.p,
-                                                 reads.all_to_all ? query_qualities.p : target_qualities.p};
-        gather_windows(*h, std::move(selection), q, t, stream, device_qualities);
+        const char* const device_qualities[2] = {query_qualities.p, all_to_all ? query_qualities.p : target_qualities.p};
+        gather_windows(*h, std::move(selection), c.q, c.t, stream, w.weighted ? device_qualities : nullptr);
         return h.release();
     }, static_cast<gw_mapper_windows*>(nullptr));
 }
@@ -236,16 +244,14 @@ gw_mapper_windows* correction_windows(const void* overlaps, int64_t n, const rea
                 pairs.push_back(given[i]);
         }
         const int64_t n_pairs = static_cast<int64_t>(pairs.size());
-        read_sets reads(host_reads, reads_view{nullptr, nullptr, 0});
-        reads.upload(); // once: the segments pass and the window gather read the same device copy
-        dbuf<char> qualities; // once as well, next to the reads
+        // once: the segments pass and the window gather read the same device copy
+        device_call c(host_reads, reads_view{nullptr, nullptr, 0}, pairs.data(), n_pairs, true);
+        dbuf<char> qualities; // once as well, next to the reads; none without qualities
         upload_qualities(qualities, w.query_qualities, host_reads);
-        dbuf<gwm_overlap> d;
-        d.upload(pairs.data(), n_pairs);
-        const reads_view& r = reads.device_queries;
+        const reads_view& r = c.q;
         owned_segments target_role, query_role;
-        throw_on(gwm_pair_segments(d.p, n_pairs, r.bases, r.offsets, r.n, first_read_id, window_length, max_device_bytes,
-                                   stream, &target_role.s, &query_role.s));
+        throw_on(gwm_pair_segments(c.d.p, n_pairs, r.bases, r.offsets, r.n, first_read_id, window_length,
+                                   max_device_bytes, stream, &target_role.s, &query_role.s));
         copy_segments(target_role.s, n_pairs, h->segments, h->segment_offsets);
         copy_segments(query_role.s, n_pairs, h->query_role_segments, h->query_role_offsets);
         h->edit_distances.resize(static_cast<size_t>(n_pairs));
@@ -257,22 +263,12 @@ gw_mapper_windows* correction_windows(const void* overlaps, int64_t n, const rea
         std::vector<int64_t> lengths(static_cast<size_t>(host_reads.n));
         for (int32_t i = 0; i < host_reads.n; ++i)
             lengths[i] = host_reads.offsets[i + 1] - host_reads.offsets[i];
-        if (!w.weighted)
-        {
-            gather_windows(*h,
-                           select_correction_layers(h->segments.data(), target_role.s.n_segments,
-                                                    h->query_role_segments.data(), query_role.s.n_segments,
-                                                    pairs.data(), n_pairs, lengths.data(), host_reads.n, first_read_id,
-                                                    window_length, max_depth),
-                           r, r, stream);
-            return h.release();
-        }
         // a target-role record's layer comes from the pair's query read, a query-role record's from its target read
         if (qualities.p)
         {
-            quality_sums_of(target_role.s, d.p, n_pairs, 0, qualities.p, r, first_read_id, stream, h->quality_sums,
+            quality_sums_of(target_role.s, c.d.p, n_pairs, 0, qualities.p, r, first_read_id, stream, h->quality_sums,
                             h->quality_ms[0]);
-            quality_sums_of(query_role.s, d.p, n_pairs, 1, qualities.p, r, first_read_id, stream,
+            quality_sums_of(query_role.s, c.d.p, n_pairs, 1, qualities.p, r, first_read_id, stream,
                             h->query_role_quality_sums, h->quality_ms[0]);
         }
         const char* const device_qualities[2] = {qualities.p, qualities.p};
@@ -283,7 +279,7 @@ gw_mapper_windows* correction_windows(const void* overlaps, int64_t n, const rea
                                                 max_depth, qualities.p ? h->quality_sums.data() : nullptr,
                                                 qualities.p ? h->query_role_quality_sums.data() : nullptr,
                                                 w.min_mean_quality),
-                       r, r, stream, device_qualities);
+                       r, r, stream, w.weighted ? device_qualities : nullptr);
         return h.release();
     }, static_cast<gw_mapper_windows*>(nullptr));
 }
@@ -477,18 +473,13 @@ int gw_mapper_rescue_overlap_ends(void* overlaps, int64_t n, const char* query_b
     return guarded([&] {
         if (rescue_ms)
             *rescue_ms = 0.f;
-        read_sets reads({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets});
-        dbuf<gwm_overlap> d;
-        if (n > 0) // without overlaps nothing is uploaded, and the argument checks still apply
-        {
-            reads.upload();
-            d.upload(static_cast<const gwm_overlap*>(overlaps), n);
-        }
-        const reads_view &q = reads.device_queries, &t = reads.device_targets;
-        throw_on(gwm_rescue_overlap_ends(d.p, n, q.bases, q.offsets, reads.queries.n, first_query_read_id, t.bases,
-                                         t.offsets, reads.targets.n, first_target_read_id, extension,
+        // without overlaps nothing is uploaded, and the argument checks still apply
+        device_call c({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets}, overlaps, n,
+                      false);
+        throw_on(gwm_rescue_overlap_ends(c.d.p, n, c.q.bases, c.q.offsets, c.reads.queries.n, first_query_read_id,
+                                         c.t.bases, c.t.offsets, c.reads.targets.n, first_target_read_id, extension,
                                          required_similarity, stream, rescue_ms));
-        copy_out(static_cast<gwm_overlap*>(overlaps), d.p, n);
+        copy_out(static_cast<gwm_overlap*>(overlaps), c.d.p, n);
         return 0;
     }, GW_MAPPER_ERROR);
 }
@@ -518,16 +509,12 @@ gw_mapper_cigars* gw_mapper_align_overlaps(const void* overlaps, int64_t n, cons
 {
     return guarded([&] {
         std::unique_ptr<gw_mapper_cigars> h(new gw_mapper_cigars());
-        read_sets reads({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets});
-        dbuf<gwm_overlap> d;
-        if (n > 0) // without overlaps nothing is uploaded, and the argument checks still apply
-        {
-            reads.upload();
-            d.upload(static_cast<const gwm_overlap*>(overlaps), n);
-        }
-        const reads_view &q = reads.device_queries, &t = reads.device_targets;
-        throw_on(gwm_align_overlaps(d.p, n, q.bases, q.offsets, reads.queries.n, first_query_read_id, t.bases,
-                                    t.offsets, reads.targets.n, first_target_read_id, max_device_bytes, stream, &h->c));
+        // without overlaps nothing is uploaded, and the argument checks still apply
+        device_call c({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets}, overlaps, n,
+                      false);
+        throw_on(gwm_align_overlaps(c.d.p, n, c.q.bases, c.q.offsets, c.reads.queries.n, first_query_read_id, c.t.bases,
+                                    c.t.offsets, c.reads.targets.n, first_target_read_id, max_device_bytes, stream,
+                                    &h->c));
         return h.release();
     }, static_cast<gw_mapper_cigars*>(nullptr));
 }
@@ -561,11 +548,8 @@ gw_mapper_windows* gw_mapper_window_overlaps(const void* overlaps, int64_t n, co
                                              uint32_t first_target_read_id, int32_t window_length, int32_t max_depth,
                                              int64_t max_device_bytes, void* stream)
 {
-    if (max_depth < 0)
-    {
-        g_capi_error = "gw_mapper_window_overlaps: negative max_depth";
+    if (refuse_negative_depth("gw_mapper_window_overlaps", max_depth))
         return nullptr;
-    }
     return window_overlaps(overlaps, n, {query_bases, query_offsets, n_queries}, first_query_read_id,
                            {target_bases, target_offsets, n_targets}, first_target_read_id, window_length, max_depth,
                            max_device_bytes, stream);
@@ -705,11 +689,8 @@ gw_mapper_windows* gw_mapper_correction_windows(const void* overlaps, int64_t n,
                                                 int32_t window_length, int32_t max_depth, int64_t max_device_bytes,
                                                 void* stream)
 {
-    if (max_depth < 0)
-    {
-        g_capi_error = "gw_mapper_correction_windows: negative max_depth";
+    if (refuse_negative_depth("gw_mapper_correction_windows", max_depth))
         return nullptr;
-    }
     return correction_windows(overlaps, n, {bases, offsets, n_reads}, first_read_id, window_length, max_depth,
                               max_device_bytes, stream);
 }
@@ -751,13 +732,12 @@ gw_mapper_pileup* gw_mapper_overlap_pileup(const void* overlaps, int64_t n, cons
         std::unique_ptr<gw_mapper_pileup> h(new gw_mapper_pileup());
         if (n < 0)
             throw std::invalid_argument("gw_mapper_overlap_pileup: negative number of overlaps");
-        read_sets reads({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets});
-        reads.upload(); // once; without overlaps too: the counters are those of the target set
-        dbuf<gwm_overlap> d;
-        d.upload(static_cast<const gwm_overlap*>(overlaps), n);
-        const reads_view &q = reads.device_queries, &t = reads.device_targets;
-        throw_on(gwm_overlap_pileup(d.p, n, q.bases, q.offsets, reads.queries.n, first_query_read_id, t.bases, t.offsets,
-                                    reads.targets.n, first_target_read_id, max_device_bytes, stream, &h->p));
+        // without overlaps too: the counters are those of the target set
+        device_call c({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets}, overlaps, n,
+                      true);
+        throw_on(gwm_overlap_pileup(c.d.p, n, c.q.bases, c.q.offsets, c.reads.queries.n, first_query_read_id, c.t.bases,
+                                    c.t.offsets, c.reads.targets.n, first_target_read_id, max_device_bytes, stream,
+                                    &h->p));
         return h.release();
     }, static_cast<gw_mapper_pileup*>(nullptr));
 }
@@ -769,12 +749,8 @@ gw_mapper_pileup* gw_mapper_pair_pileup(const void* pairs, int64_t n, const char
         std::unique_ptr<gw_mapper_pileup> h(new gw_mapper_pileup());
         if (n < 0)
             throw std::invalid_argument("gw_mapper_pair_pileup: negative number of pairs");
-        read_sets reads({bases, offsets, n_reads}, reads_view{nullptr, nullptr, 0});
-        reads.upload();
-        dbuf<gwm_overlap> d;
-        d.upload(static_cast<const gwm_overlap*>(pairs), n);
-        const reads_view& r = reads.device_queries;
-        throw_on(gwm_pair_pileup(d.p, n, r.bases, r.offsets, r.n, first_read_id, max_device_bytes, stream, &h->p));
+        device_call c({bases, offsets, n_reads}, reads_view{nullptr, nullptr, 0}, pairs, n, true);
+        throw_on(gwm_pair_pileup(c.d.p, n, c.q.bases, c.q.offsets, c.q.n, first_read_id, max_device_bytes, stream, &h->p));
         return h.release();
     }, static_cast<gw_mapper_pileup*>(nullptr));
 }
@@ -803,11 +779,8 @@ gw_mapper_windows* gw_mapper_window_overlaps_weighted(const void* overlaps, int6
                                                       int32_t window_length, int32_t max_depth,
                                                       int64_t max_device_bytes, void* stream)
 {
-    if (max_depth < 0)
-    {
-        g_capi_error = "gw_mapper_window_overlaps_weighted: negative max_depth";
+    if (refuse_negative_depth("gw_mapper_window_overlaps_weighted", max_depth))
         return nullptr;
-    }
     return window_overlaps(overlaps, n, {query_bases, query_offsets, n_queries}, first_query_read_id,
                            {target_bases, target_offsets, n_targets}, first_target_read_id, window_length, max_depth,
                            max_device_bytes, stream, {true, query_qualities, target_qualities, min_mean_quality});
@@ -819,11 +792,8 @@ gw_mapper_windows* gw_mapper_correction_windows_weighted(const void* overlaps, i
                                                          int32_t min_mean_quality, int32_t window_length,
                                                          int32_t max_depth, int64_t max_device_bytes, void* stream)
 {
-    if (max_depth < 0)
-    {
-        g_capi_error = "gw_mapper_correction_windows_weighted: negative max_depth";
+    if (refuse_negative_depth("gw_mapper_correction_windows_weighted", max_depth))
         return nullptr;
-    }
     return correction_windows(overlaps, n, {bases, offsets, n_reads}, first_read_id, window_length, max_depth,
                               max_device_bytes, stream, {true, qualities, nullptr, min_mean_quality});
 }
@@ -884,12 +854,11 @@ gw_mapper_overlaps* gw_mapper_map_batched(const char* query_bases, const int64_t
                                           int64_t max_basepairs_per_target_index, int32_t post_process,
                                           int32_t drop_fused_overlaps, int32_t rescue_overlap_ends, void* stream)
 {
-    return map_batched_guarded({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets},
-                               {kmer_size, window_size, filtering_parameter, min_residues, min_overlap_len,
-                                min_bases_per_residue, min_overlap_fraction, max_basepairs_per_query_index,
-                                max_basepairs_per_target_index, post_process, drop_fused_overlaps, rescue_overlap_ends,
-                                0, 0, 1, 1, 1, 1},
-                               stream);
+    return gw_mapper_map_batched_cached(query_bases, query_offsets, n_queries, target_bases, target_offsets, n_targets,
+                                        kmer_size, window_size, filtering_parameter, min_residues, min_overlap_len,
+                                        min_bases_per_residue, min_overlap_fraction, max_basepairs_per_query_index,
+                                        max_basepairs_per_target_index, post_process, drop_fused_overlaps,
+                                        rescue_overlap_ends, 0, 0, 1, 1, 1, 1, stream);
 }
 
 gw_mapper_overlaps* gw_mapper_map_batched_aligned(
@@ -900,12 +869,11 @@ gw_mapper_overlaps* gw_mapper_map_batched_aligned(
     int32_t drop_fused_overlaps, int32_t rescue_overlap_ends, int32_t align_overlaps, int64_t max_device_bytes,
     void* stream)
 {
-    return map_batched_guarded({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets},
-                               {kmer_size, window_size, filtering_parameter, min_residues, min_overlap_len,
-                                min_bases_per_residue, min_overlap_fraction, max_basepairs_per_query_index,
-                                max_basepairs_per_target_index, post_process, drop_fused_overlaps, rescue_overlap_ends,
-                                align_overlaps, max_device_bytes, 1, 1, 1, 1},
-                               stream);
+    return gw_mapper_map_batched_cached(query_bases, query_offsets, n_queries, target_bases, target_offsets, n_targets,
+                                        kmer_size, window_size, filtering_parameter, min_residues, min_overlap_len,
+                                        min_bases_per_residue, min_overlap_fraction, max_basepairs_per_query_index,
+                                        max_basepairs_per_target_index, post_process, drop_fused_overlaps,
+                                        rescue_overlap_ends, align_overlaps, max_device_bytes, 1, 1, 1, 1, stream);
 }
 
 gw_mapper_overlaps* gw_mapper_map_batched_cached(
@@ -917,14 +885,16 @@ gw_mapper_overlaps* gw_mapper_map_batched_cached(
     int32_t query_indices_in_host_memory, int32_t query_indices_in_device_memory, int32_t target_indices_in_host_memory,
     int32_t target_indices_in_device_memory, void* stream)
 {
-    return map_batched_guarded({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets},
-                               {kmer_size, window_size, filtering_parameter, min_residues, min_overlap_len,
-                                min_bases_per_residue, min_overlap_fraction, max_basepairs_per_query_index,
-                                max_basepairs_per_target_index, post_process, drop_fused_overlaps, rescue_overlap_ends,
-                                align_overlaps, max_device_bytes, query_indices_in_host_memory,
-                                query_indices_in_device_memory, target_indices_in_host_memory,
-                                target_indices_in_device_memory},
-                               stream);
+    return guarded([&] {
+        const map_options options{kmer_size, window_size, filtering_parameter, min_residues, min_overlap_len,
+                                  min_bases_per_residue, min_overlap_fraction, max_basepairs_per_query_index,
+                                  max_basepairs_per_target_index, post_process, drop_fused_overlaps, rescue_overlap_ends,
+                                  align_overlaps, max_device_bytes, query_indices_in_host_memory,
+                                  query_indices_in_device_memory, target_indices_in_host_memory,
+                                  target_indices_in_device_memory};
+        return map_batched({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets}, options,
+                           static_cast<hipStream_t>(stream));
+    }, static_cast<gw_mapper_overlaps*>(nullptr));
 }
 
 int gw_mapper_overlaps_cache_counts(const gw_mapper_overlaps* result, int64_t* index_builds, int64_t* index_restores,

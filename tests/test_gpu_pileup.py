@@ -187,6 +187,18 @@ def test_insertion_runs_across_a_tile_boundary(cm):
     # mirrored: the query's positions ascend on both strands
     assert insertions(8 + 1, 0, "query") == [63] and insertions(8 + 2, 0, "query") == [62]
     assert insertions(12 + 1, 1, "query") == [63] and insertions(12 + 3, 1, "query") == [61, 125]
+    # the segment kernel walks the same columns: the records of both roles of the same 16 alignments, against the
+    # CIGAR formulations of the two oracles on the device's own CIGARs, with a window cut at every lane (1), at odd
+    # lanes (7) and at the tile boundary itself (64)
+    for W in (1, 7, 64):
+        (target_role, target_offsets, _), (query_role, query_offsets) = cm.pair_segments(o, reads, W)
+        for got, offsets, from_cigar in ((target_role, target_offsets, OPo.segments_from_cigar),
+                                         (query_role, query_offsets, OC.query_role_from_cigar)):
+            rows = [from_cigar(i, o[i], cigars[i], W) for i in range(len(o))]
+            want = np.array([r for per_record in rows for r in per_record], OC.SEGMENT).reshape(-1)
+            assert got.dtype == cm.SEGMENT and got.tolist() == want.tolist(), (W, from_cigar.__name__)
+            assert offsets.tolist() == np.cumsum([0] + [len(r) for r in rows]).tolist()
+            assert len(got) >= len(o) * (140 // W)  # every window of a read holds an aligned column, a few of W = 1 aside
 
 
 def test_every_cell_of_the_polishing_case(cm, polishing):
