@@ -136,6 +136,22 @@ def extender():
     return _extender
 
 
+_poa_hooks = None
+
+
+def poa_hooks():
+    """libgwhip_poa_hooks.so: test-only hook of the production POA merge (include/gwhip_poa_hooks.h)."""
+    global _poa_hooks
+    if _poa_hooks is None:
+        L = _load("libgwhip_poa_hooks.so")
+        vp, i32 = C.c_void_p, C.c_int32
+        L.gwhip_poa_test_add_alignment_parallel_scratch_bytes.restype = C.c_size_t
+        L.gwhip_poa_test_add_alignment_parallel_scratch_bytes.argtypes = [i32, i32, i32]
+        L.gwhip_poa_test_add_alignment_parallel.argtypes = [vp] * 9 + [i32] + [vp] * 5 + [i32, i32, i32, vp, vp, vp]
+        _poa_hooks = L
+    return _poa_hooks
+
+
 def gwhip_error():
     buf = C.create_string_buffer(512)
     gwhip().gwhip_last_error_string(buf, 512)

@@ -3,6 +3,7 @@
   genomeworks_amd/lib/libgwhip.so            hand-written HIP kernels + the thin C-ABI (include/gwhip.h)
   genomeworks_amd/lib/libgwsemiglobal.so     cudaaligner's infix / prefix types: the ends scan and the slice gather
                                              (include/gwhip_semiglobal.h), linked against libgwhip.so
+  genomeworks_amd/lib/libgwhip_poa_hooks.so  test-only hook of the production POA merge (include/gwhip_poa_hooks.h)
   genomeworks_amd/lib/libgenomeworks_amd.so  host C++ (Batch / Aligner, allocator, C API include/gw_capi.h)
   genomeworks_amd/lib/libcudaextender.so     cudaextender: HIP kernels (include/gwhip_extender.h) + Extender
                                              (cudaextender/extender.hpp, C API include/gw_extender_capi.h)
@@ -33,6 +34,8 @@ EXTENDER_KERNEL_SRCS = ["extender/gwx_ungapped_xdrop.hip"]
 EXTENDER_HOST_SRCS = ["extender/extender.cpp"]
 # the infix / prefix alignment types of cudaaligner likewise (the host class is in host/)
 SEMIGLOBAL_KERNEL_SRCS = ["semiglobal/gws_ends.hip"]
+# the test-only hook of the production POA merge likewise (include/gwhip_poa_hooks.h)
+POA_HOOKS_KERNEL_SRCS = ["poa_hooks/gwhip_poa_merge_hook.hip"]
 # cudamapper likewise
 MAPPER_KERNEL_SRCS = ["mapper/gwm_mapper.hip", "mapper/gwm_postprocess.hip", "mapper/gwm_align.hip",
                       "mapper/gwm_segments.hip", "mapper/gwm_pileup.hip", "mapper/gwm_qualities.hip",
@@ -180,6 +183,14 @@ def build_semiglobal(force=False):
     return _build_library("libgwsemiglobal.so", jobs, ["-L", LIB, "-lgwhip", "-Wl,-rpath,$ORIGIN"], force)[0]
 
 
+def build_poa_hooks(force=False):
+    """libgwhip_poa_hooks.so: test-only entry points onto device routines of csrc/ (hipcc, gfx950); nothing links it."""
+    header = os.path.join(ROOT, "include", "gwhip_poa_hooks.h")
+    jobs = [(HIPCC_OBJECT, src, _digest([src, header] + _local_includes(src), KERNEL_FLAGS))
+            for src in (os.path.join(PKG, s) for s in POA_HOOKS_KERNEL_SRCS)]
+    return _build_library("libgwhip_poa_hooks.so", jobs, [], force)[0]
+
+
 def build_extender(force=False):
     """libcudaextender.so: the extension kernel + rocPRIM compaction / sort (hipcc, gfx950) and the Extender host
     classes (g++), linked against libgenomeworks_amd.so for the allocator and logging."""
@@ -262,6 +273,7 @@ def _run_in(cwd, cmd):
 def build_all(force=False):
     k = build_kernels(force)
     build_semiglobal(force)
+    build_poa_hooks(force)
     h = build_host(force)
     build_extender(force)
     build_mapper(force)
