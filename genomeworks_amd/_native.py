@@ -279,6 +279,14 @@ def mapper():
         L.gw_mapper_pileup_copy.argtypes = [vp, vp, vp]
         L.gw_mapper_pileup_destroy.restype = None
         L.gw_mapper_pileup_destroy.argtypes = [vp]
+        L.gw_mapper_overlap_variants.restype = vp
+        L.gw_mapper_overlap_variants.argtypes = [vp, i64, vp, vp, i32, u32, vp, vp, i32, u32, i32, i32, i64, vp]
+        L.gw_mapper_variants_count.restype = i64
+        L.gw_mapper_variants_count.argtypes = [vp]
+        L.gw_mapper_variants_copy.argtypes = [vp, vp, vp]
+        L.gw_mapper_variants_pileup_copy.argtypes = [vp, vp]
+        L.gw_mapper_variants_destroy.restype = None
+        L.gw_mapper_variants_destroy.argtypes = [vp]
         L.gwm_align_bytes_needed.restype = i64
         L.gwm_align_bytes_needed.argtypes = [i32, i32, i32]
         _mapper = L

@@ -38,8 +38,8 @@ SEMIGLOBAL_KERNEL_SRCS = ["semiglobal/gws_ends.hip"]
 POA_HOOKS_KERNEL_SRCS = ["poa_hooks/gwhip_poa_merge_hook.hip"]
 # cudamapper likewise
 MAPPER_KERNEL_SRCS = ["mapper/gwm_mapper.hip", "mapper/gwm_postprocess.hip", "mapper/gwm_align.hip",
-                      "mapper/gwm_segments.hip", "mapper/gwm_pileup.hip", "mapper/gwm_qualities.hip",
-                      "mapper/gwm_index_cache.hip"]
+                      "mapper/gwm_segments.hip", "mapper/gwm_pileup.hip", "mapper/gwm_variants.hip",
+                      "mapper/gwm_qualities.hip", "mapper/gwm_index_cache.hip"]
 MAPPER_HOST_SRCS = ["mapper/mapper.cpp", "mapper/gwm_driver.cpp", "mapper/gwm_index_batcher.cpp",
                     "mapper/gwm_windows.cpp"]
 
@@ -204,7 +204,7 @@ def build_extender(force=False):
 
 def build_mapper(force=False):
     """libcudamapper.so: the sketch / index / matcher / overlapper / post-processing / overlap alignment / window
-    segment / pileup kernels with their rocPRIM scans, selects and sorts (hipcc, gfx950), linked against libgwhip.so for the
+    segment / pileup / variant kernels with their rocPRIM scans, selects and sorts (hipcc, gfx950), linked against libgwhip.so for the
     aligner, and the Index / Matcher handles, the index batcher, the batched driver and the host rules of polishing and read correction
     behind the C API (g++);
     then bin/cudamapper, which links it and libgenomeworks_amd.so (built before this)."""

@@ -23,6 +23,7 @@ gfx950), over the flat C API of include/gw_mapper_capi.h.
     windows = correction_windows_weighted(overlaps, reads, phred33)
     piles = overlap_pileup(overlaps, reads, targets)               # uint32 (6, len(target)) per target: PILEUP_CHANNELS
     piles = pair_pileup(pairs, reads)                              # both reads of every pair, one array per read
+    records = overlap_variants(overlaps, reads, targets)           # VARIANT records: SNVs, deletions, insertion alleles
 
 Index arrays carry the reference's names (representations, read_ids, positions_in_reads, directions_of_reads,
 unique_representations, first_occurrence_of_representations) and come back as numpy arrays."""
@@ -47,6 +48,12 @@ SEGMENT = np.dtype([("overlap", "<u4"), ("window", "<u4"), ("target_first", "<u4
 
 # the rows of a pileup array: what the aligned overlaps put at a base of the read that owns it
 PILEUP_CHANNELS = ("A", "C", "G", "T", "deletion", "insertion")
+
+# gwm_variant: one called variant of a target read; 32 B
+VARIANT = np.dtype({"names": ["target_read", "position", "count", "depth", "kind", "ref", "alt", "length", "key"],
+                    "formats": ["<u4", "<u4", "<u4", "<u4", "u1", "u1", "u1", "u1", "<u8"],
+                    "offsets": [0, 4, 8, 12, 16, 17, 18, 19, 24], "itemsize": 32})
+VARIANT_KINDS = ("snv", "deletion", "insertion")  # the values of VARIANT's kind
 
 FORWARD, REVERSE = 0, 1  # SketchElement::DirectionOfRepresentation
 
@@ -777,6 +784,63 @@ def pair_pileup(pairs, reads, first_read_id=0, max_device_bytes=0, stream=None, 
     h = L.gw_mapper_pair_pileup(_p(o), len(o), _p(bases), _p(offsets), len(reads), first_read_id,
                                 int(max_device_bytes), _stream(stream))
     return _copy_pileup(L, h, offsets, len(o), timings)
+
+
+def overlap_variants(overlaps, query_reads, target_reads=None, min_count=3, min_percent=30, first_query_read_id=0,
+                     first_target_read_id=0, max_device_bytes=0, stream=None, timings=None, return_pileup=False):
+    """The variants of the target reads under their aligned overlaps, called on the device from one alignment pass
+    (gwm_overlap_variants): a numpy array of VARIANT records, ascending by target read and
+    position, within a position SNV, deletion, insertion. With n[0..5] the counters of overlap_pileup at a base, r the
+    channel of the target's own base and d = n[0] + ... + n[4], a count k passes when k >= min_count and 100 * k >=
+    min_percent * d. An SNV (kind 0) is the channel other than r with the greatest count, the smallest on a tie, when
+    that count passes; a deletion (kind 1) is called per base when n[4] passes; an insertion (kind 2) after a base
+    is the allele most of the insertion runs there spell -- on a tie the shorter, then the alphabetically smaller --
+    when the number of runs that spell it passes: `length` and `key` hold it, insertion_allele(length, key) is its
+    text, in forward target coordinates. Runs of more than 32 bases are counted in the pileup and never called.
+    The defaults min_count = 3 and min_percent = 30 are conventions and are not tuned on any data. With return_pileup:
+    (records, piles), piles what overlap_pileup returns for the same input, out of the same pass. Nothing but the
+    records (and the counters when asked for) is copied from the device, besides the overlap records that size the
+    chunks. min_count < 1 or min_percent outside 0..100 raise ValueError before anything is launched; other
+    arguments, chunking and errors as for overlap_pileup. `timings`, if a dict, receives gather, align, pileup (with
+    the insertion-run records) and call (device ms) and bytes_to_host."""
+    if int(min_count) < 1:
+        raise ValueError("min_count must be >= 1")
+    if not 0 <= int(min_percent) <= 100:
+        raise ValueError("min_percent must be within 0..100")
+    L = _native.mapper()
+    o = np.ascontiguousarray(overlaps, OVERLAP)
+    q, t = _read_set_args(query_reads, target_reads)
+    _, offsets = pack_reads(query_reads if target_reads is None else target_reads)
+    h = L.gw_mapper_overlap_variants(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id, int(min_count),
+                                     int(min_percent), int(max_device_bytes), _stream(stream))
+    if not h:
+        raise _err(L)
+    try:
+        records, ms = np.zeros(int(L.gw_mapper_variants_count(h)), VARIANT), np.zeros(4, np.float32)
+        if L.gw_mapper_variants_copy(h, _p(records), _p(ms)) != 0:
+            raise _err(L)
+        counts = None
+        if return_pileup:
+            counts = np.zeros((len(PILEUP_CHANNELS), int(offsets[-1])), np.uint32)
+            if L.gw_mapper_variants_pileup_copy(h, _p(counts)) != 0:
+                raise _err(L)
+    finally:
+        L.gw_mapper_variants_destroy(h)
+    if timings is not None:
+        timings.update(gather=float(ms[0]), align=float(ms[1]), pileup=float(ms[2]), call=float(ms[3]),
+                       bytes_to_host=len(o) * OVERLAP.itemsize + records.nbytes + (counts.nbytes if return_pileup else 0))
+    if not return_pileup:
+        return records
+    return records, [counts[:, int(a):int(b)] for a, b in zip(offsets[:-1], offsets[1:])]
+
+
+def insertion_allele(length, key):
+    """the text of an insertion allele of VARIANT records: `length` bases, two bits each from the top of the
+    2 * length low bits of `key`, A, C, G, T = 0..3"""
+    length, key = int(length), int(key)
+    if not 0 <= length <= 32 or key >> (2 * length):
+        raise ValueError("an allele of %d bases with key %d" % (length, key))
+    return "".join("ACGT"[(key >> (2 * (length - 1 - i))) & 3] for i in range(length))
 
 
 def group_reads_into_indices(read_lengths, max_basepairs_per_index):

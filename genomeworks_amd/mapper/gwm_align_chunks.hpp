@@ -1,11 +1,11 @@
 // gwm_align_chunks.hpp -- the chunk loop that gwm_align_overlaps (gwm_align.hip), gwm_window_segments
-// (gwm_segments.hip) and gwm_overlap_pileup (gwm_pileup.hip) share: validation of the overlap records, sizing on the
-// host, and per chunk of consecutive overlaps the gather of the slices, gwhip_hirschberg_myers of libgwhip.so and the
-// per-chunk buffers. What is done with the chunk's alignment states is the caller's: align_chunks() hands them to a
-// consumer while they are on the device. The loop and its kernels are defined once, in gwm_align.hip. Here as well:
-// the check of the arguments every such entry point takes, and ChunkedOutput, the bookkeeping of a consumer that
-// writes a variable number of items per alignment (CIGAR bytes, segment records). How a consumer's kernel reads the
-// states is in gwm_column_walk.hpp.
+// (gwm_segments.hip), gwm_overlap_pileup (gwm_pileup.hip) and gwm_overlap_variants (gwm_variants.hip) share:
+// validation of the overlap records, sizing on the host, and per chunk of consecutive overlaps the gather of the
+// slices, gwhip_hirschberg_myers of libgwhip.so and the per-chunk buffers. What is done with the chunk's alignment
+// states is the caller's: align_chunks() hands them to a consumer while they are on the device. The loop and its
+// kernels are defined once, in gwm_align.hip. Here as well: the check of the arguments every such entry point takes,
+// and ChunkedOutput, the bookkeeping of a consumer that writes a variable number of items per alignment (CIGAR bytes,
+// segment records, insertion-run records). How a consumer's kernel reads the states is in gwm_column_walk.hpp.
 #ifndef GWM_ALIGN_CHUNKS_HPP
 #define GWM_ALIGN_CHUNKS_HPP
 
@@ -41,7 +41,8 @@ struct AlignedChunk
 // gwm_align_bytes_needed states it -- gathered bases, state slots, the aligner's workspace, the small per-overlap
 // arrays and two bytes per column for the consumer's output of the chunk. What a consumer keeps beyond the chunk (the
 // CIGAR text or the segment records of the chunks before, records beyond two bytes per column, which takes windows
-// of fewer than 12 bases, and the counters of a pileup, 24 B per base of the owner set) lies outside it.
+// of fewer than 12 bases, the counters of a pileup, 24 B per base of the owner set, and the insertion-run records of the
+// variant caller, 24 B each) lies outside it.
 void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, const ReadSet& q, const ReadSet& t,
                   int64_t max_device_bytes, hipStream_t s, float* stage_ms,
                   const std::function<void(const AlignedChunk&)>& consume);

@@ -156,6 +156,16 @@ struct gw_mapper_pileup
     gw_mapper_pileup& operator=(const gw_mapper_pileup&) = delete;
 };
 
+// The records and the counters of one gwm_overlap_variants call, on the device until they are copied out
+struct gw_mapper_variants
+{
+    gwm_variants v{};
+    gw_mapper_variants() = default;
+    ~gw_mapper_variants() { gwm_variants_free(&v); }
+    gw_mapper_variants(const gw_mapper_variants&) = delete;
+    gw_mapper_variants& operator=(const gw_mapper_variants&) = delete;
+};
+
 // The windows of one gw_mapper_window_overlaps or gw_mapper_correction_windows call, on the host
 struct gw_mapper_windows
 {

@@ -770,6 +770,56 @@ int gw_mapper_pileup_copy(const gw_mapper_pileup* pileup, uint32_t* counts, floa
 
 void gw_mapper_pileup_destroy(gw_mapper_pileup* pileup) { delete pileup; }
 
+gw_mapper_variants* gw_mapper_overlap_variants(const void* overlaps, int64_t n, const char* query_bases,
+                                               const int64_t* query_offsets, int32_t n_queries,
+                                               uint32_t first_query_read_id, const char* target_bases,
+                                               const int64_t* target_offsets, int32_t n_targets,
+                                               uint32_t first_target_read_id, int32_t min_count, int32_t min_percent,
+                                               int64_t max_device_bytes, void* stream)
+{
+    return guarded([&] {
+        std::unique_ptr<gw_mapper_variants> h(new gw_mapper_variants());
+        if (n < 0)
+            throw std::invalid_argument("gw_mapper_overlap_variants: negative number of overlaps");
+        // refused before the reads are uploaded: nothing reaches the device
+        if (min_count < 1)
+            throw std::invalid_argument("gw_mapper_overlap_variants: min_count below 1");
+        if (min_percent < 0 || min_percent > 100)
+            throw std::invalid_argument("gw_mapper_overlap_variants: min_percent outside 0..100");
+        // without overlaps too: the counters are those of the target set
+        device_call c({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets}, overlaps, n,
+                      true);
+        throw_on(gwm_overlap_variants(c.d.p, n, c.q.bases, c.q.offsets, c.reads.queries.n, first_query_read_id,
+                                      c.t.bases, c.t.offsets, c.reads.targets.n, first_target_read_id, min_count,
+                                      min_percent, max_device_bytes, stream, &h->v));
+        return h.release();
+    }, static_cast<gw_mapper_variants*>(nullptr));
+}
+
+int64_t gw_mapper_variants_count(const gw_mapper_variants* variants) { return variants->v.n_variants; }
+
+int gw_mapper_variants_copy(const gw_mapper_variants* variants, void* records, float* stage_ms)
+{
+    return guarded([&] {
+        const gwm_variants& v = variants->v;
+        copy_out(static_cast<gwm_variant*>(records), v.variants, v.n_variants);
+        if (stage_ms)
+            std::memcpy(stage_ms, v.stage_ms, sizeof(v.stage_ms));
+        return 0;
+    }, GW_MAPPER_ERROR);
+}
+
+int gw_mapper_variants_pileup_copy(const gw_mapper_variants* variants, uint32_t* counts)
+{
+    return guarded([&] {
+        const gwm_pileup& p = variants->v.pileup;
+        copy_out(counts, p.counts, 6 * p.n_bases);
+        return 0;
+    }, GW_MAPPER_ERROR);
+}
+
+void gw_mapper_variants_destroy(gw_mapper_variants* variants) { delete variants; }
+
 gw_mapper_windows* gw_mapper_window_overlaps_weighted(const void* overlaps, int64_t n, const char* query_bases,
                                                       const int64_t* query_offsets, int32_t n_queries,
                                                       uint32_t first_query_read_id, const char* target_bases,

@@ -28,7 +28,13 @@ is below min_mean_quality are dropped.
 
 How every base of the draft, or of a read, is supported by the alignments polish() / correct_reads() use: per base the
 number of aligned reads that put an A, C, G or T there, that delete it, and that insert after it, counted on the
-device from the alignment states."""
+device from the alignment states.
+
+    variants = call_variants(reads, [draft])                       # SNVs, deletions, insertion alleles: a list of dicts
+    text = format_vcf(variants, ["draft"], [draft])                # VCF 4.2
+
+Where the reads disagree with the draft and what they say instead, called on the device by counting, out of the same
+alignment pass as the pileup."""
 import time
 
 import numpy as np
@@ -233,6 +239,84 @@ def read_pileup(reads, overlaps=None, timings=None, **mapping_parameters):
 def depth(pile):
     """the coverage of every base of a pileup array: the overlaps that put a base there or delete it"""
     return pile[:5].sum(0)
+
+
+def call_variants(reads, targets, overlaps=None, min_count=3, min_percent=30, timings=None, **mapping_parameters):
+    """Where the alignments polish() uses disagree with `targets`, and what they say instead: a list of dicts with
+    target (position in `targets`), position (0-based), kind ("snv", "deletion", "insertion"), ref, alt, count and
+    depth, by target, then by position, within a position SNV, deletion, insertion.
+    overlaps as for pileup(): None maps first, with the same defaults and the same refusals; one overlap per query read
+    is kept and cudamapper.overlap_variants, which `timings` is passed to, calls on the device: a count passes when it
+    is >= min_count and at least min_percent per cent of the depth (both defaults are conventions, not tuned on any
+    data). An SNV has the target's base as ref and the called base as alt. An insertion follows `position`; its ref is
+    "" and its alt the inserted bases. Called deletions of neighbouring bases of one target are joined into one
+    variant at the first of them: ref is the deleted bases, alt "", count the smallest of their counts and depth that
+    of the first base."""
+    overlaps = _mapped("call_variants", reads, targets, overlaps, mapping_parameters)
+    kept = np.ascontiguousarray(overlaps, cudamapper.OVERLAP)
+    kept = kept[one_overlap_per_read(kept)]
+    records = cudamapper.overlap_variants(kept, reads, targets, min_count, min_percent, timings=timings)
+    return join_deletions(records, targets)
+
+
+def join_deletions(records, targets):
+    """the dicts call_variants() returns, from VARIANT records in their order and the targets they speak of"""
+    out = []
+    last, last_at = None, -1  # the deletion a next deleted base would extend: (target, the position behind it), out[]
+    for v in records:
+        target, p, kind = int(v["target_read"]), int(v["position"]), cudamapper.VARIANT_KINDS[int(v["kind"])]
+        own = targets[target][p:p + 1]
+        own = own.decode("latin-1") if isinstance(own, bytes) else own
+        if kind == "deletion" and last == (target, p):
+            joined = out[last_at]
+            joined["ref"] += own
+            joined["count"] = min(joined["count"], int(v["count"]))
+            last = (target, p + 1)
+            continue
+        alt = ""
+        if kind == "snv":
+            alt = "ACGT"[int(v["alt"])]
+        elif kind == "insertion":
+            alt = cudamapper.insertion_allele(v["length"], v["key"])
+        out.append(dict(target=target, position=p, kind=kind, ref="" if kind == "insertion" else own, alt=alt,
+                        count=int(v["count"]), depth=int(v["depth"])))
+        if kind == "deletion":
+            last, last_at = (target, p + 1), len(out) - 1
+    return out
+
+
+def format_vcf(variants, target_names, targets):
+    """The variants of call_variants() as VCF 4.2 text: ##fileformat, one ##contig line per target, the ##INFO lines
+    of DP (depth), AD (count) and TYPE (kind), the column line, and one line per variant in target order, then by POS;
+    QUAL is ".", FILTER "PASS", and there are no sample columns. An SNV stands at POS position + 1. An insertion after
+    `position` stands there too, with REF the target's base and ALT that base and the inserted ones. A deletion of
+    [p, p + k) with p > 0 stands at POS p with REF target[p - 1 : p + k] and ALT target[p - 1]; one of [0, k) at POS 1
+    with REF target[0 : k + 1] and ALT target[k]. REF letters are as the target has them."""
+    if len(target_names) != len(targets):
+        raise ValueError("%d names for %d targets" % (len(target_names), len(targets)))
+    texts = [t.decode("latin-1") if isinstance(t, bytes) else t for t in targets]
+    lines = ["##fileformat=VCFv4.2"]
+    lines += ["##contig=<ID=%s,length=%d>" % (name, len(t)) for name, t in zip(target_names, texts)]
+    lines += ['##INFO=<ID=DP,Number=1,Type=Integer,Description="Aligned reads that put a base at the position or delete it">',
+              '##INFO=<ID=AD,Number=1,Type=Integer,Description="Aligned reads that support the alternative allele">',
+              '##INFO=<ID=TYPE,Number=1,Type=String,Description="snv, deletion or insertion">',
+              "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO"]
+    rows = []
+    for v in variants:
+        t, p, kind = texts[v["target"]], v["position"], v["kind"]
+        if kind == "snv":
+            pos, ref, alt = p + 1, t[p], v["alt"]
+        elif kind == "insertion":
+            pos, ref, alt = p + 1, t[p], t[p] + v["alt"]
+        else:
+            k = len(v["ref"])
+            if p + k > len(t) or (p == 0 and k >= len(t)):
+                raise ValueError("a deletion of [%d, %d) of a target of %d bases has no base to stand at" % (p, p + k, len(t)))
+            pos, ref, alt = (p, t[p - 1:p + k], t[p - 1]) if p > 0 else (1, t[:k + 1], t[k])
+        rows.append((v["target"], pos, "%s\t%d\t.\t%s\t%s\t.\tPASS\tDP=%d;AD=%d;TYPE=%s"
+                     % (target_names[v["target"]], pos, ref, alt, v["depth"], v["count"], kind)))
+    rows.sort(key=lambda r: r[:2])  # stable: the order of call_variants() within a POS
+    return "\n".join(lines + [r[2] for r in rows]) + "\n"
 
 
 def read_fastq(path):

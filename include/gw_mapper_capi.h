@@ -301,6 +301,32 @@ int64_t gw_mapper_pileup_bases(const gw_mapper_pileup* pileup);
 int gw_mapper_pileup_copy(const gw_mapper_pileup* pileup, uint32_t* counts, float* stage_ms);
 void gw_mapper_pileup_destroy(gw_mapper_pileup* pileup);
 
+/* ---- variant calling: SNVs, deletions and insertion alleles of the target set ---------------------------------------
+   gwm_overlap_variants of gwhip_mapper.h over host arrays; the rules are in INTEGRATION.md section 3n. One alignment
+   pass leaves the pileup of the target set and the variants called from it on the device; the records (gwm_variant,
+   32 B each) reach the host, and the counters if they are asked for. */
+
+/* The variants of the target set under n host overlaps over host reads (target_bases NULL: the target set is the query
+   set), aligned and counted as gw_mapper_overlap_pileup does it and called with min_count >= 1 and 0 <= min_percent
+   <= 100, which are refused out of range before anything reaches the device. Without overlaps there are no records
+   and every counter is 0. Errors as for gw_mapper_overlap_pileup (NULL). */
+typedef struct gw_mapper_variants gw_mapper_variants;
+gw_mapper_variants* gw_mapper_overlap_variants(const void* overlaps, int64_t n, const char* query_bases,
+                                               const int64_t* query_offsets, int32_t n_queries,
+                                               uint32_t first_query_read_id, const char* target_bases,
+                                               const int64_t* target_offsets, int32_t n_targets,
+                                               uint32_t first_target_read_id, int32_t min_count, int32_t min_percent,
+                                               int64_t max_device_bytes, void* stream);
+/* the number of called records */
+int64_t gw_mapper_variants_count(const gw_mapper_variants* variants);
+/* records[count] (gwm_variant), ascending by cell, within a cell SNV, deletion, insertion -- one copy from the
+   device --, and stage_ms[4]: device time of gather, align, pileup + insertion runs, vote + call. Either pointer may
+   be NULL. */
+int gw_mapper_variants_copy(const gw_mapper_variants* variants, void* records, float* stage_ms);
+/* counts[6 * bases of the target set], as gw_mapper_pileup_copy gives them for the same input */
+int gw_mapper_variants_pileup_copy(const gw_mapper_variants* variants, uint32_t* counts);
+void gw_mapper_variants_destroy(gw_mapper_variants* variants);
+
 /* group_reads_into_indices: consecutive reads while the running base count stays <= max_basepairs_per_index; a longer
    read gets an index of its own. The reference's loop as it stands: when the very first read is longer than the limit
    a descriptor of zero reads comes first, and no reads at all give the one descriptor {0, 0}. Returns the number of

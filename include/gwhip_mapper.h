@@ -327,6 +327,71 @@ void gwm_pileup_free(gwm_pileup* pileup);
 int gwm_pair_pileup(const gwm_overlap* pairs, int64_t n, const char* bases, const int64_t* offsets, int32_t n_reads,
                     uint32_t first_read_id, int64_t max_device_bytes, void* stream, gwm_pileup* out);
 
+/* ---- variant calling: SNVs, deletions and insertion alleles of the target set -------------
+ * A small-variant caller by counting: no genotypes, no likelihoods, no base qualities. */
+
+/* One called variant (32 B). Channels are those of the pileup: A, C, G, T = 0..3. */
+typedef struct gwm_variant
+{
+    uint32_t target_read; /* position of the target read in its set */
+    uint32_t position;    /* p, forward target coordinates: the base an SNV replaces, the deleted base, the base an
+                             insertion follows */
+    uint32_t count;       /* SNV: n[alt]; deletion: n[deletion]; insertion: the run records of the called allele */
+    uint32_t depth;       /* d(p) = n[A] + n[C] + n[G] + n[T] + n[deletion] */
+    uint8_t kind;         /* 0 SNV, 1 deletion, 2 insertion */
+    uint8_t ref;          /* r: the channel of the target's own byte at p */
+    uint8_t alt;          /* SNV: the called channel; 0 otherwise */
+    uint8_t length;       /* insertion: L, 1..32 bases; 0 otherwise */
+    uint32_t reserved;    /* 0 */
+    uint64_t key;         /* insertion: the allele, sum of code(allele[i]) << 2 (L - 1 - i); 0 otherwise */
+} gwm_variant;
+
+/* The called variants of a target set and its pileup. Device arrays, owned by the struct; free them with
+ * gwm_variants_free. */
+typedef struct gwm_variants
+{
+    int64_t n_variants;
+    gwm_variant* variants; /* device: ascending by cell (offsets[read] + p), within a cell SNV, deletion, insertion; NULL
+                              when there are none */
+    gwm_pileup pileup;     /* what gwm_overlap_pileup gives for the same arguments, its stage_ms included */
+    float stage_ms[4];     /* HIP events: gather, align, pileup + insertion runs (summed over the chunks), vote + call */
+} gwm_variants;
+
+/* gwm_overlap_pileup with a fourth consumer of the alignment states in the same chunk callback, and a calling stage
+ * behind the chunks: the same arguments, slices, strand, aligner, chunking and errors, and every overlap is aligned
+ * once. It leaves the pileup of the target set and the variants called from it on the device. With n[0..5] the
+ * counters of base p of a target read as gwm_overlap_pileup defines them, r the channel of the target's own byte at p
+ * and d = n[0] + ... + n[4], a count k passes at depth d when k >= min_count and 100 k >= min_percent d (64-bit
+ * integers; min_count >= 1, 0 <= min_percent <= 100, anything else is an error before anything is launched):
+ *   SNV: alt is the channel other than r with the greatest count, the smallest such channel on a tie; called when
+ *   n[alt] passes at d.
+ *   Deletion of base p: called when n[4] passes at d. One record per base; neighbours are not joined.
+ *   Insertion after base p: every maximal run of state 3 that the pileup counts at cell p (it starts at column j with
+ *   1 <= b(j) <= B - 1) and whose length L is 1..32 gives one run record (cell, L, key). Its allele is the run's query
+ *   bases in forward target coordinates: Q[q .. q + L) on '+', their reverse complement on '-'; key = the sum of
+ *   code(allele[i]) << 2 (L - 1 - i), codes A, C, G, T = 0..3 after the aligner's folding, so that among alleles of
+ *   one length key order is alphabetical order. Runs of more than 32 bases stay counted in n[5] and give no record.
+ *   Records are equal when (L, key) are; the best allele of a cell is the one with the most records, on a tie the
+ *   shorter, then the one with the smaller key. The insertion is called when the record count of the best allele --
+ *   not n[5] -- passes at d(p).
+ * A cell yields at most one record of each kind. The records are a function of the multiset of alignments: they depend
+ * neither on the order of the atomics, nor on the chunking, nor on the order of the overlaps.
+ * Device: one wave64 per alignment finds the heads of the runs as the pileup kernel does; a head lane reads its run's
+ * length from the up to 32 state bytes behind it and packs the query bytes itself, so a run that crosses a 64-column
+ * tile is no special case. A counting pass, a scan, a writing pass; the run records are sorted by (cell, L, key) with
+ * rocPRIM, run-length encoded and reduced per cell to the best allele. One thread per base flags SNV and deletion, one
+ * per best allele applies the threshold; rocPRIM selects compact the three kinds and two merges give the order.
+ * max_device_bytes bounds a chunk's working set exactly as for gwm_align_overlaps; the counters (24 B per base of the
+ * target set), one flag byte per base, the run records (24 B each, kept for all chunks until the vote) and the variant
+ * records lie outside that budget, as the segment records do. n == 0 launches no kernel and gives zeroed counters and
+ * no records. On an error the call returns -1, sets gwm_last_error() and leaves *out zeroed. */
+int gwm_overlap_variants(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                         int32_t n_queries, uint32_t first_query_read_id, const char* target_bases,
+                         const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
+                         int32_t min_count, int32_t min_percent, int64_t max_device_bytes, void* stream,
+                         gwm_variants* out);
+void gwm_variants_free(gwm_variants* variants);
+
 /* One sequence of a gather plan (20 B): bases [begin, end) of read `read` (position in its set) of the query set
  * (set 0) or the target set (set 1); reversed != 0: back to front, every byte through "TGAC"[(c >> 1) & 3]. */
 typedef struct gwm_gather_entry
