@@ -210,6 +210,8 @@ def mapper():
         L.gw_mapper_overlaps_destroy.argtypes = [vp]
         L.gw_mapper_align_overlaps.restype = vp
         L.gw_mapper_align_overlaps.argtypes = [vp, i64, vp, vp, i32, u32, vp, vp, i32, u32, i64, vp]
+        L.gw_mapper_align_overlaps_scored.restype = vp
+        L.gw_mapper_align_overlaps_scored.argtypes = [vp, i64, vp, vp, i32, u32, vp, vp, i32, u32, vp, i64, vp]
         L.gw_mapper_cigars_count.restype = i64
         L.gw_mapper_cigars_count.argtypes = [vp]
         L.gw_mapper_cigars_text_bytes.restype = i64
@@ -281,6 +283,8 @@ def mapper():
         L.gw_mapper_pileup_destroy.argtypes = [vp]
         L.gw_mapper_overlap_variants.restype = vp
         L.gw_mapper_overlap_variants.argtypes = [vp, i64, vp, vp, i32, u32, vp, vp, i32, u32, i32, i32, i64, vp]
+        L.gw_mapper_overlap_variants_scored.restype = vp
+        L.gw_mapper_overlap_variants_scored.argtypes = [vp, i64, vp, vp, i32, u32, vp, vp, i32, u32, i32, i32, vp, i64, vp]
         L.gw_mapper_variants_count.restype = i64
         L.gw_mapper_variants_count.argtypes = [vp]
         L.gw_mapper_variants_copy.argtypes = [vp, vp, vp]
@@ -289,5 +293,7 @@ def mapper():
         L.gw_mapper_variants_destroy.argtypes = [vp]
         L.gwm_align_bytes_needed.restype = i64
         L.gwm_align_bytes_needed.argtypes = [i32, i32, i32]
+        L.gwm_align_bytes_needed_scored.restype = i64
+        L.gwm_align_bytes_needed_scored.argtypes = [i32, i32, i32]
         _mapper = L
     return _mapper

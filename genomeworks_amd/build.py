@@ -3,6 +3,8 @@
   genomeworks_amd/lib/libgwhip.so            hand-written HIP kernels + the thin C-ABI (include/gwhip.h)
   genomeworks_amd/lib/libgwsemiglobal.so     cudaaligner's infix / prefix types: the ends scan and the slice gather
                                              (include/gwhip_semiglobal.h), linked against libgwhip.so
+  genomeworks_amd/lib/libgwaffine.so         the affine-gap global aligner: forward pass and traceback inside a diagonal band
+                                             (include/gwhip_affine.h), on its own
   genomeworks_amd/lib/libgwhip_poa_hooks.so  test-only hook of the production POA merge (include/gwhip_poa_hooks.h)
   genomeworks_amd/lib/libgenomeworks_amd.so  host C++ (Batch / Aligner, allocator, C API include/gw_capi.h)
   genomeworks_amd/lib/libcudaextender.so     cudaextender: HIP kernels (include/gwhip_extender.h) + Extender
@@ -27,13 +29,15 @@ HIPCC = os.path.join(ROCM, "bin", "hipcc")
 KERNEL_SRCS = ["csrc/gwhip_poa.hip", "csrc/gwhip_poa_part0.hip", "csrc/gwhip_poa_part1.hip", "csrc/gwhip_poa_part2.hip",
                "csrc/gwhip_poa_part3.hip", "csrc/gwhip_poa_part4.hip", "csrc/gwhip_poa_part5.hip", "csrc/gwhip_poa_part6.hip", "csrc/gwhip_poa_part7.hip", "csrc/gwhip_poa_hooks.hip", "csrc/gwhip_myers.hip", "csrc/gwhip_ukkonen.hip"]
 HOST_SRCS = ["host/capi.cpp", "host/cudapoa_batch.cpp", "host/cudapoa_utils.cpp", "host/cudaaligner.cpp", "host/aligner_global.cpp", "host/device_pool.cpp",
-             "host/aligner_semiglobal.cpp", "host/alignment_impl.cpp", "host/runtime.cpp", "host/logging.cpp", "host/overlap_alignment.cpp", "host/multi_device.cpp",
+             "host/aligner_semiglobal.cpp", "host/aligner_affine.cpp", "host/alignment_impl.cpp", "host/runtime.cpp", "host/logging.cpp", "host/overlap_alignment.cpp", "host/multi_device.cpp",
              "host/fasta_parser.cpp"]
 # cudaextender lives apart from csrc/ so that kernel_source_digest() (the stamped POA / aligner kernel set) ignores it
 EXTENDER_KERNEL_SRCS = ["extender/gwx_ungapped_xdrop.hip"]
 EXTENDER_HOST_SRCS = ["extender/extender.cpp"]
 # the infix / prefix alignment types of cudaaligner likewise (the host class is in host/)
 SEMIGLOBAL_KERNEL_SRCS = ["semiglobal/gws_ends.hip"]
+# the affine-gap global aligner likewise (the host class is in host/)
+AFFINE_KERNEL_SRCS = ["affine/gwaffine.hip"]
 # the test-only hook of the production POA merge likewise (include/gwhip_poa_hooks.h)
 POA_HOOKS_KERNEL_SRCS = ["poa_hooks/gwhip_poa_merge_hook.hip"]
 # cudamapper likewise
@@ -157,17 +161,20 @@ def build_host(force=False):
     os.makedirs(LIB, exist_ok=True)
     target = os.path.join(LIB, "libgenomeworks_amd.so")
     srcs = [os.path.join(PKG, s) for s in HOST_SRCS if os.path.exists(os.path.join(PKG, s))]
-    # the host library links libgwhip.so and libgwsemiglobal.so. Called alone in a fresh tree, this builds the first;
-    # the second is brought up to date every time (one small translation unit, incremental), and a relink follows it
+    # the host library links libgwhip.so, libgwsemiglobal.so and libgwaffine.so. Called alone in a fresh tree, this builds
+    # the first; the other two are brought up to date every time (one small translation unit each, incremental), and a
+    # relink follows them
     if not os.path.exists(os.path.join(LIB, "libgwhip.so")):
         build_kernels()
     with open(build_semiglobal() + ".stamp") as f:
         semiglobal_sig = f.read().strip()
-    sig = _digest(_deps("host", (".cpp", ".h", ".hpp")), [HOST_FLAGS, semiglobal_sig])
+    with open(build_affine() + ".stamp") as f:
+        affine_sig = f.read().strip()
+    sig = _digest(_deps("host", (".cpp", ".h", ".hpp")), [HOST_FLAGS, semiglobal_sig, affine_sig])
     if force or _stale(target, sig):
         cmd = ["g++"] + HOST_FLAGS + ["-shared", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROCM, "include"),
                                      "-o", target] + srcs + [
-            "-L", LIB, "-lgwsemiglobal", "-lgwhip", "-L", os.path.join(ROCM, "lib"), "-lamdhip64",
+            "-L", LIB, "-lgwaffine", "-lgwsemiglobal", "-lgwhip", "-L", os.path.join(ROCM, "lib"), "-lamdhip64",
             "-Wl,-rpath,$ORIGIN", "-Wl,-rpath," + os.path.join(ROCM, "lib")]
         _run(cmd)
         _mark(target, sig)
@@ -181,6 +188,14 @@ def build_semiglobal(force=False):
     jobs = [(HIPCC_OBJECT, src, _digest([src, header], KERNEL_FLAGS))
             for src in (os.path.join(PKG, s) for s in SEMIGLOBAL_KERNEL_SRCS)]
     return _build_library("libgwsemiglobal.so", jobs, ["-L", LIB, "-lgwhip", "-Wl,-rpath,$ORIGIN"], force)[0]
+
+
+def build_affine(force=False):
+    """libgwaffine.so: the affine-gap global aligner (hipcc, gfx950); it links nothing of the project."""
+    header = os.path.join(ROOT, "include", "gwhip_affine.h")
+    jobs = [(HIPCC_OBJECT, src, _digest([src, header] + _local_includes(src), KERNEL_FLAGS))
+            for src in (os.path.join(PKG, s) for s in AFFINE_KERNEL_SRCS)]
+    return _build_library("libgwaffine.so", jobs, [], force)[0]
 
 
 def build_poa_hooks(force=False):
@@ -208,13 +223,14 @@ def build_mapper(force=False):
     aligner, and the Index / Matcher handles, the index batcher, the batched driver and the host rules of polishing and read correction
     behind the C API (g++);
     then bin/cudamapper, which links it and libgenomeworks_amd.so (built before this)."""
-    headers = [os.path.join(ROOT, "include", "gwhip_mapper.h"), os.path.join(ROOT, "include", "gwhip.h")]
+    headers = [os.path.join(ROOT, "include", "gwhip_mapper.h"), os.path.join(ROOT, "include", "gwhip.h"),
+               os.path.join(ROOT, "include", "gwhip_affine.h")]
     host_sig = _digest(_deps("mapper", (".cpp", ".h", ".hpp")), HOST_FLAGS)
     jobs = [(HIPCC_OBJECT, src, _digest([src] + headers + _local_includes(src), KERNEL_FLAGS))
             for src in (os.path.join(PKG, s) for s in MAPPER_KERNEL_SRCS)]
     jobs += [(GXX_OBJECT, os.path.join(PKG, s), host_sig) for s in MAPPER_HOST_SRCS]
-    # gwm_align.hip calls the default aligner of libgwhip.so (built before this)
-    target, link_sig = _build_library("libcudamapper.so", jobs, ["-L", LIB, "-lgwhip", "-Wl,-rpath,$ORIGIN"], force)
+    # gwm_align.hip calls the default aligner of libgwhip.so and the affine-gap aligner of libgwaffine.so (built before this)
+    target, link_sig = _build_library("libcudamapper.so", jobs, ["-L", LIB, "-lgwaffine", "-lgwhip", "-Wl,-rpath,$ORIGIN"], force)
     # the cudamapper tool: a thin main over the C API, the FASTA reader and PAF writer of libgenomeworks_amd.so
     _build_tool("cudamapper", os.path.join(PKG, "mapper", "cudamapper_main.cpp"), ["-lcudamapper"],
                 _digest(_deps("host", (".hpp",)), [host_sig, link_sig]), force)
@@ -229,7 +245,7 @@ def _build_tool(name, src, more_libs, sig, force):
     if force or _stale(target, sig):
         _run(["g++"] + [f for f in HOST_FLAGS if f != "-fPIC"] + INCLUDE +
              ["-I", os.path.join(ROCM, "include"), "-o", target, src, "-L", LIB] + more_libs +
-             ["-lgenomeworks_amd", "-lgwsemiglobal", "-lgwhip", "-L", os.path.join(ROCM, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN/../lib",
+             ["-lgenomeworks_amd", "-lgwaffine", "-lgwsemiglobal", "-lgwhip", "-L", os.path.join(ROCM, "lib"), "-lamdhip64", "-Wl,-rpath,$ORIGIN/../lib",
               "-Wl,-rpath," + os.path.join(ROCM, "lib")])
         _mark(target, sig)
     return target
@@ -273,6 +289,7 @@ def _run_in(cwd, cmd):
 def build_all(force=False):
     k = build_kernels(force)
     build_semiglobal(force)
+    build_affine(force)
     build_poa_hooks(force)
     h = build_host(force)
     build_extender(force)

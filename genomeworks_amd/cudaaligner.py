@@ -3,7 +3,9 @@
 CudaAlignerBatch keeps the reference's constructor (the default, fixed-stride factory); `max_bandwidth=` selects the
 banded Myers aligner (create_aligner(global_alignment, max_bandwidth, ...)), which is what the benchmarks use.
 `alignment_type="infix"` / `"prefix"` (not in pygenomeworks) place the whole query on the best slice / the best prefix of
-its target: CudaAlignment.target_begin / .target_end name the slice that the states, the CIGARs and the distance describe."""
+its target: CudaAlignment.target_begin / .target_end name the slice that the states, the CIGARs and the distance describe.
+`algorithm="affine"` (not in pygenomeworks) aligns globally under gap-open / gap-extend costs inside a diagonal band
+(include/gwhip_affine.h states the rules): its alignments carry `.cost`."""
 import ctypes as C
 
 import numpy as np
@@ -44,6 +46,9 @@ def _bind(L):
     L.gw_aligner_create_typed.argtypes = [i32, i32, i32, i32, vp, i32, C.c_int64]
     L.gw_alignment_target_range.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.gw_aligner_stage_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.gw_aligner_create_affine.restype = vp
+    L.gw_aligner_create_affine.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, i32, C.c_int64]
+    L.gw_alignment_cost.argtypes = [vp, i32]
     L.gw_aligner_create_algorithm.restype = vp
     L.gw_aligner_create_algorithm.argtypes = [C.c_char_p, i32, i32, i32, vp, i32, C.c_int64]
     L.gw_aligner_destroy.argtypes = [vp]
@@ -70,7 +75,7 @@ class CudaAlignment:
     """One alignment result (pygenomeworks CudaAlignment): query, target, cigar, status, alignment states."""
 
     def __init__(self, query, target, cigar, cigar_extended, status, is_optimal, edit_distance, states,
-                 target_begin=0, target_end=None):
+                 target_begin=0, target_end=None, cost=-1):
         self.query = query
         self.target = target
         self.cigar = cigar
@@ -82,6 +87,8 @@ class CudaAlignment:
         # the slice of the target that the alignment covers: all of it unless the batch is "infix" or "prefix"
         self.target_begin = target_begin
         self.target_end = len(target) if target_end is None else target_end
+        # algorithm="affine": the alignment's cost under the batch's scoring; -1 for every other aligner
+        self.cost = cost
 
     def format_alignment(self):
         """(query line, pairing line, target line) like Alignment::format_alignment, over target[target_begin:target_end]."""
@@ -101,10 +108,15 @@ class CudaAlignerBatch:
 
     def __init__(self, max_query_length=None, max_target_length=None, max_alignments=None, alignment_type="global",
                  stream=None, device_id=0, max_device_memory_allocator_caching_size=-1, max_bandwidth=None,
-                 algorithm=None):
+                 algorithm=None, mismatch=None, gap_open=None, gap_extend=None, band_width=None):
         """algorithm (not in pygenomeworks): one of the reference's non-public aligner classes that its C++ tests and
-        benchmarks construct directly -- "hirschberg_myers" (the default), "ukkonen", "myers"."""
+        benchmarks construct directly -- "hirschberg_myers" (the default), "ukkonen", "myers" -- or "affine": global
+        alignment under the costs mismatch (4), gap_open (6), gap_extend (2) -- minimised, a gap run of L columns costs
+        gap_open + L * gap_extend -- within band_width (128) diagonals on either side of the corners' diagonals."""
         self._L = _bind(_native.host())
+        scoring = dict(mismatch=mismatch, gap_open=gap_open, gap_extend=gap_extend, band_width=band_width)
+        if algorithm != "affine" and any(v is not None for v in scoring.values()):
+            raise RuntimeError("%s: only algorithm=\"affine\" takes these" % ", ".join(k for k, v in scoring.items() if v is not None))
         if alignment_type not in _ALIGNMENT_TYPES:
             raise RuntimeError("Unknown alignment_type provided. Must be global, infix or prefix.")
         if alignment_type != "global" and (max_bandwidth is not None or algorithm is not None):
@@ -120,6 +132,11 @@ class CudaAlignerBatch:
                                                       int(max_device_memory_allocator_caching_size))
         elif max_bandwidth is not None:
             self._h = self._L.gw_aligner_create_banded(int(max_bandwidth), st, device_id,
+                                                       int(max_device_memory_allocator_caching_size))
+        elif algorithm == "affine":
+            x, o, e, b = (d if v is None else int(v) for v, d in zip(scoring.values(), (4, 6, 2, 128)))
+            self._h = self._L.gw_aligner_create_affine(int(max_query_length), int(max_target_length), int(max_alignments),
+                                                       x, o, e, b, st, device_id,
                                                        int(max_device_memory_allocator_caching_size))
         elif algorithm is not None:
             self._h = self._L.gw_aligner_create_algorithm(algorithm.encode(), int(max_query_length), int(max_target_length),
@@ -177,7 +194,8 @@ class CudaAlignerBatch:
         return n.value, total.value
 
     def stage_ms(self):
-        """Measurement aid for "infix" / "prefix" batches: (ends scan ms, gather + traceback ms) of the last align_all()."""
+        """Measurement aid for "infix" / "prefix" batches: (ends scan ms, gather + traceback ms) of the last align_all();
+        for algorithm="affine": (forward pass ms, traceback ms)."""
         ends, tb = C.c_float(0), C.c_float(0)
         if self._L.gw_aligner_stage_ms(self._h, C.byref(ends), C.byref(tb)) != 0:
             raise RuntimeError(self._L.gw_last_error().decode())
@@ -252,7 +270,8 @@ class CudaAlignerBatch:
                 rng = self._L.gw_alignment_target_range(self._h, i, C.byref(tb), C.byref(te))
             if ns < 0 or st < 0 or opt < 0 or ed < 0 or rng < 0:  # the C ABI reports a bad index / a thrown accessor as -1 + error string
                 raise RuntimeError("alignment %d: %s" % (i, self._L.gw_last_error().decode()))
-            out.append(CudaAlignment(q, t, cigar, cigar_x, st, bool(opt), ed, [int(x) for x in states[:ns]], tb.value, te.value))
+            out.append(CudaAlignment(q, t, cigar, cigar_x, st, bool(opt), ed, [int(x) for x in states[:ns]], tb.value, te.value,
+                                     self._L.gw_alignment_cost(self._h, i)))
         return out
 
     def reset(self):

@@ -370,8 +370,34 @@ def align_bytes_needed(query_length, target_length, max_query_length):
     return int(_native.mapper().gwm_align_bytes_needed(int(query_length), int(target_length), int(max_query_length)))
 
 
+def align_bytes_needed_scored(query_length, target_length, band):
+    """align_bytes_needed for a call of align_overlaps with a scoring of this band (gwm_align_bytes_needed_scored)."""
+    return int(_native.mapper().gwm_align_bytes_needed_scored(int(query_length), int(target_length), int(band)))
+
+
+def _scoring_args(scoring):
+    """scoring of align_overlaps / overlap_variants as the C API takes it: None, or four int32 (mismatch, gap_open,
+    gap_extend, band) from a 4-tuple or a dict with these keys (a dict may leave out any: 4, 6, 2, 128)."""
+    if scoring is None:
+        return None
+    if isinstance(scoring, dict):
+        unknown = set(scoring) - {"mismatch", "gap_open", "gap_extend", "band"}
+        if unknown:
+            raise ValueError("scoring: unknown keys %s" % sorted(unknown))
+        values = [scoring.get("mismatch", 4), scoring.get("gap_open", 6), scoring.get("gap_extend", 2), scoring.get("band", 128)]
+    else:
+        values = list(scoring)
+        if len(values) != 4:
+            raise ValueError("scoring: a dict or (mismatch, gap_open, gap_extend, band)")
+    x, o, e, b = (int(v) for v in values)
+    if not (1 <= x <= 255 and 0 <= o <= 255 and 1 <= e <= 255 and 0 <= b < 2 ** 31):
+        raise ValueError("scoring (mismatch %d, gap_open %d, gap_extend %d, band %d) outside 1..255, 0..255, 1..255, >= 0"
+                         % (x, o, e, b))
+    return np.array([x, o, e, b], np.int32)
+
+
 def align_overlaps(overlaps, query_reads, target_reads=None, first_query_read_id=0, first_target_read_id=0,
-                   max_device_bytes=0, stream=None, timings=None):
+                   max_device_bytes=0, stream=None, timings=None, scoring=None):
     """Global alignment of every overlap over its own slices, on the device from the reads to the CIGAR text: query
     slice [query start, query end) against target slice [target start, target end), on '-' against that target
     slice's reverse complement as cudaaligner takes it ("TGAC"[(c >> 1) & 3] for every byte), with the default aligner
@@ -381,12 +407,21 @@ def align_overlaps(overlaps, query_reads, target_reads=None, first_query_read_id
     r is query_reads[r - first_query_read_id] / target_reads[r - first_target_read_id]; target_reads None means the
     query reads. Overlaps are aligned in chunks that keep within max_device_bytes (0: half of the free device memory);
     the result does not depend on it, and an overlap that does not fit alone raises, as do a read id outside its set,
-    start > end and an end beyond its read. `timings`, if a dict, receives gather, align and cigar_text (device ms)."""
+    start > end and an end beyond its read. `timings`, if a dict, receives gather, align and cigar_text (device ms).
+    scoring: None, or (mismatch, gap_open, gap_extend, band) as a 4-tuple or a dict -- the slices are then aligned under
+    affine gap costs inside a diagonal band (include/gwhip_affine.h) instead; the edit
+    distances stay the columns that are not a match, an overlap whose band |m - n| + 2 band + 1 exceeds 2048 diagonals has
+    an empty CIGAR and -1, and values out of range raise ValueError before anything is launched."""
+    sc = _scoring_args(scoring)
     L = _native.mapper()
     o = np.ascontiguousarray(overlaps, OVERLAP)
     q, t = _read_set_args(query_reads, target_reads)
-    h = L.gw_mapper_align_overlaps(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id,
-                                   int(max_device_bytes), _stream(stream))
+    if sc is None:
+        h = L.gw_mapper_align_overlaps(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id,
+                                       int(max_device_bytes), _stream(stream))
+    else:
+        h = L.gw_mapper_align_overlaps_scored(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id, _p(sc),
+                                              int(max_device_bytes), _stream(stream))
     if not h:
         raise _err(L)
     try:
@@ -787,7 +822,8 @@ def pair_pileup(pairs, reads, first_read_id=0, max_device_bytes=0, stream=None, 
 
 
 def overlap_variants(overlaps, query_reads, target_reads=None, min_count=3, min_percent=30, first_query_read_id=0,
-                     first_target_read_id=0, max_device_bytes=0, stream=None, timings=None, return_pileup=False):
+                     first_target_read_id=0, max_device_bytes=0, stream=None, timings=None, return_pileup=False,
+                     scoring=None):
     """The variants of the target reads under their aligned overlaps, called on the device from one alignment pass
     (gwm_overlap_variants): a numpy array of VARIANT records, ascending by target read and
     position, within a position SNV, deletion, insertion. With n[0..5] the counters of overlap_pileup at a base, r the
@@ -802,7 +838,9 @@ def overlap_variants(overlaps, query_reads, target_reads=None, min_count=3, min_
     records (and the counters when asked for) is copied from the device, besides the overlap records that size the
     chunks. min_count < 1 or min_percent outside 0..100 raise ValueError before anything is launched; other
     arguments, chunking and errors as for overlap_pileup. `timings`, if a dict, receives gather, align, pileup (with
-    the insertion-run records) and call (device ms) and bytes_to_host."""
+    the insertion-run records) and call (device ms) and bytes_to_host. scoring as for align_overlaps: the alignments
+    that are counted are then the affine-gap ones."""
+    sc = _scoring_args(scoring)
     if int(min_count) < 1:
         raise ValueError("min_count must be >= 1")
     if not 0 <= int(min_percent) <= 100:
@@ -811,8 +849,13 @@ def overlap_variants(overlaps, query_reads, target_reads=None, min_count=3, min_
     o = np.ascontiguousarray(overlaps, OVERLAP)
     q, t = _read_set_args(query_reads, target_reads)
     _, offsets = pack_reads(query_reads if target_reads is None else target_reads)
-    h = L.gw_mapper_overlap_variants(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id, int(min_count),
-                                     int(min_percent), int(max_device_bytes), _stream(stream))
+    if sc is None:
+        h = L.gw_mapper_overlap_variants(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id, int(min_count),
+                                         int(min_percent), int(max_device_bytes), _stream(stream))
+    else:
+        h = L.gw_mapper_overlap_variants_scored(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id,
+                                                int(min_count), int(min_percent), _p(sc), int(max_device_bytes),
+                                                _stream(stream))
     if not h:
         raise _err(L)
     try:

@@ -14,6 +14,7 @@
 #include "poa_batch_impl.hpp"
 #include "aligner_impl.hpp"
 #include "aligner_global.hpp"
+#include "aligner_affine.hpp"
 #include "aligner_semiglobal.hpp"
 #include "alignment_impl.hpp"
 #include <claraparabricks/genomeworks/cudapoa/multi_device.hpp>
@@ -427,6 +428,18 @@ gw_aligner* gw_aligner_create_typed(int32_t alignment_type, int32_t max_query_le
     GW_CATCH(nullptr)
 }
 
+gw_aligner* gw_aligner_create_affine(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments, int32_t mismatch,
+                                     int32_t gap_open, int32_t gap_extend, int32_t band_width, void* stream, int32_t device_id,
+                                     int64_t max_device_memory)
+{
+    GW_TRY
+    auto h     = std::make_unique<gw_aligner>();
+    h->aligner = aln::create_aligner_affine(max_query_length, max_target_length, max_alignments, aln::AffineScoring{mismatch, gap_open, gap_extend},
+                                            band_width, static_cast<cudaStream_t>(stream), device_id, max_device_memory);
+    return h.release();
+    GW_CATCH(nullptr)
+}
+
 gw_aligner* gw_aligner_create_algorithm(const char* algorithm, int32_t max_query_length, int32_t max_target_length,
                                         int32_t max_alignments, void* stream, int32_t device_id, int64_t max_device_memory)
 {
@@ -523,11 +536,28 @@ int gw_alignment_target_range(gw_aligner* a, int32_t i, int32_t* begin, int32_t*
     return 0;
     GW_CATCH(-1)
 }
+int32_t gw_alignment_cost(gw_aligner* a, int32_t i)
+{
+    GW_TRY
+    return aln::get_alignment_cost(*a->aligner->get_alignments().at(static_cast<size_t>(i)));
+    GW_CATCH(-1)
+}
 int gw_aligner_stage_ms(gw_aligner* a, float* ends_ms, float* traceback_ms)
 {
     GW_TRY
     auto* semiglobal = dynamic_cast<aln::AlignerSemiglobal*>(a->aligner.get());
     float ends = 0.f, traceback = 0.f;
+    if (auto* affine = dynamic_cast<aln::AlignerGlobalAffine*>(a->aligner.get())) // its forward pass and its traceback
+    {
+        if (!affine->last_stage_ms(&ends, &traceback))
+        {
+            gwhost::set_last_error("gw_aligner_stage_ms: no align_all() to report");
+            return -1;
+        }
+        if (ends_ms) *ends_ms = ends;
+        if (traceback_ms) *traceback_ms = traceback;
+        return 0;
+    }
     if (semiglobal == nullptr || !semiglobal->last_stage_ms(&ends, &traceback))
     {
         gwhost::set_last_error(semiglobal ? "gw_aligner_stage_ms: no align_all() to report" : "gw_aligner_stage_ms: not an infix / prefix aligner");

@@ -2,7 +2,8 @@
 // (include/gwhip_mapper.h, gwm_align_overlaps). Per chunk of consecutive overlaps (the loop of gwm_align_chunks.hpp): a
 // gather kernel cuts the query and target slices out of the resident read sets into the layout the default aligner
 // takes (the target slice reverse-complemented with the aligner's table on '-'), gwhip_hirschberg_myers of libgwhip.so
-// aligns them as it stands, and the CIGAR writer here, the loop's consumer, turns the per-column states into the text
+// aligns them as it stands (or, for a call with a scoring, gwhip_affine_align of libgwaffine.so, into the same
+// buffers), and the CIGAR writer here, the loop's consumer, turns the per-column states into the text
 // of Alignment::convert_to_cigar() and the edit distance. Neither
 // the bases nor the states cross to the host; the overlap records (36 B each) are read there to size the chunks.
 //
@@ -14,6 +15,7 @@
 #include "gwm_column_walk.hpp"
 
 #include "gwhip.h"
+#include "gwhip_affine.h"
 
 namespace
 {
@@ -196,10 +198,11 @@ namespace gwm
 {
 
 void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, const ReadSet& q, const ReadSet& t,
-                  int64_t max_device_bytes, hipStream_t s, float* stage_ms,
+                  int64_t max_device_bytes, const gwm_scoring* scoring, hipStream_t s, float* stage_ms,
                   const std::function<void(const AlignedChunk&)>& consume)
 {
     const std::string who = std::string(name) + ": ";
+    check_scoring(who, scoring);
     {
         dbuf<uint32_t> bad(1);
         GWM_CHECK(hipMemsetAsync(bad.p, 0, sizeof(uint32_t), s));
@@ -237,10 +240,16 @@ void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, cons
         GWM_CHECK(hipMemGetInfo(&free_bytes, &total_bytes));
         budget = static_cast<int64_t>(free_bytes / 2);
     }
+    // the aligner's workspace for overlaps [first, first + m); the affine aligner's costs and flags are counted with it
+    auto workspace_bytes = [&](int64_t first, int64_t m) -> size_t {
+        const int64_t* hs = host_starts.data() + 2 * first;
+        if (scoring == nullptr)
+            return gwhip_hirschberg_myers_workspace_bytes(static_cast<int32_t>(m), hs, capacity);
+        return gwhip_affine_workspace_bytes(static_cast<int32_t>(m), hs, scoring->band) + static_cast<size_t>(m) * 5 + 256;
+    };
     auto cost = [&](int64_t first, int64_t m) {
         const int64_t* hs = host_starts.data() + 2 * first;
-        return chunk_bytes(m, hs[2 * m] - hs[0],
-                           gwhip_hirschberg_myers_workspace_bytes(static_cast<int32_t>(m), hs, capacity));
+        return chunk_bytes(m, hs[2 * m] - hs[0], workspace_bytes(first, m));
     };
 
     Temp temp;
@@ -276,7 +285,7 @@ void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, cons
         }
         const int64_t* hs     = host_starts.data() + 2 * first;
         const int64_t bases   = hs[2 * m] - hs[0];
-        const size_t ws_bytes = gwhip_hirschberg_myers_workspace_bytes(static_cast<int32_t>(m), hs, capacity);
+        const size_t ws_bytes = workspace_bytes(first, m);
         const gwm_overlap* o  = overlaps + first;
         grow(sequences, bases + kPad);
         grow(results, bases + kPad);
@@ -292,20 +301,45 @@ void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, cons
         gather_kernel<<<static_cast<unsigned>(2 * m), kThreads, 0, s>>>(o, q, t, starts.p, sequences.p);
         GWM_CHECK(hipGetLastError());
         ev.record(1, s);
-        gwhip_hirschberg_args a{};
-        a.n_alignments     = static_cast<int32_t>(m);
-        a.sequences        = reinterpret_cast<const char*>(sequences.p);
-        a.sequence_starts  = starts.p;
-        a.max_query_length = capacity;
-        a.results          = reinterpret_cast<int8_t*>(results.p);
-        a.result_lengths   = result_lengths.p;
-        a.workspace        = workspace.p;
-        a.workspace_bytes  = ws_bytes;
-        if (gwhip_hirschberg_myers(&a, s) != 0)
+        if (scoring == nullptr)
         {
-            char text[512] = "";
-            gwhip_last_error_string(text, sizeof(text));
-            throw std::runtime_error(who + text);
+            gwhip_hirschberg_args a{};
+            a.n_alignments     = static_cast<int32_t>(m);
+            a.sequences        = reinterpret_cast<const char*>(sequences.p);
+            a.sequence_starts  = starts.p;
+            a.max_query_length = capacity;
+            a.results          = reinterpret_cast<int8_t*>(results.p);
+            a.result_lengths   = result_lengths.p;
+            a.workspace        = workspace.p;
+            a.workspace_bytes  = ws_bytes;
+            if (gwhip_hirschberg_myers(&a, s) != 0)
+            {
+                char text[512] = "";
+                gwhip_last_error_string(text, sizeof(text));
+                throw std::runtime_error(who + text);
+            }
+        }
+        else
+        {
+            // costs and flags, which no consumer reads, lie behind the aligner's own workspace
+            const size_t own = gwhip_affine_workspace_bytes(static_cast<int32_t>(m), hs, scoring->band);
+            gwhip_affine_args a{};
+            a.n_alignments         = static_cast<int32_t>(m);
+            a.sequences            = reinterpret_cast<const char*>(sequences.p);
+            a.sequence_starts      = starts.p;
+            a.sequence_starts_host = hs;
+            a.mismatch             = scoring->mismatch;
+            a.gap_open             = scoring->gap_open;
+            a.gap_extend           = scoring->gap_extend;
+            a.band                 = scoring->band;
+            a.results              = reinterpret_cast<int8_t*>(results.p);
+            a.result_lengths       = result_lengths.p;
+            a.costs                = reinterpret_cast<int32_t*>(workspace.p + ((own + 255) & ~size_t(255)));
+            a.optimal              = reinterpret_cast<uint8_t*>(a.costs + m);
+            a.workspace            = workspace.p;
+            a.workspace_bytes      = own;
+            if (gwhip_affine_align(&a, s) != 0)
+                throw std::runtime_error(who + gwhip_affine_last_error());
         }
         ev.record(2, s);
         consume(AlignedChunk{first, m, static_cast<unsigned>((m + kWavesPerBlock - 1) / kWavesPerBlock), o, results.p,
@@ -327,6 +361,12 @@ int64_t gwm_align_bytes_needed(int32_t query_length, int32_t target_length, int3
     return chunk_bytes(1, starts[2], gwhip_hirschberg_myers_workspace_bytes(1, starts, max_query_length));
 }
 
+int64_t gwm_align_bytes_needed_scored(int32_t query_length, int32_t target_length, int32_t band)
+{
+    const int64_t starts[3] = {0, query_length, static_cast<int64_t>(query_length) + target_length};
+    return chunk_bytes(1, starts[2], gwhip_affine_workspace_bytes(1, starts, band) + 5 + 256);
+}
+
 void gwm_cigars_free(gwm_cigars* cigars)
 {
     if (!cigars)
@@ -342,10 +382,20 @@ int gwm_align_overlaps(const gwm_overlap* overlaps, int64_t n, const char* query
                        const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
                        int64_t max_device_bytes, void* stream, gwm_cigars* out)
 {
+    return gwm_align_overlaps_scored(overlaps, n, query_bases, query_offsets, n_queries, first_query_read_id, target_bases,
+                                     target_offsets, n_targets, first_target_read_id, nullptr, max_device_bytes, stream, out);
+}
+
+int gwm_align_overlaps_scored(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                              int32_t n_queries, uint32_t first_query_read_id, const char* target_bases,
+                              const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
+                              const gwm_scoring* scoring, int64_t max_device_bytes, void* stream, gwm_cigars* out)
+{
     *out = gwm_cigars{};
     try
     {
         check_chunk_arguments("gwm_align_overlaps", n_queries, n_targets, max_device_bytes, n);
+        check_scoring("gwm_align_overlaps: ", scoring);
         if (n <= 0)
             return 0;
         hipStream_t s = static_cast<hipStream_t>(stream);
@@ -368,8 +418,8 @@ int gwm_align_overlaps(const gwm_overlap* overlaps, int64_t n, const char* query
         };
         gwm::align_chunks("gwm_align_overlaps", overlaps, n,
                           read_set(query_bases, query_offsets, n_queries, first_query_read_id),
-                          read_set(target_bases, target_offsets, n_targets, first_target_read_id), max_device_bytes, s,
-                          out->stage_ms, write_cigars);
+                          read_set(target_bases, target_offsets, n_targets, first_target_read_id), max_device_bytes,
+                          scoring, s, out->stage_ms, write_cigars);
         dbuf<int64_t> offsets;
         dbuf<char> text;
         const int64_t total = cigars.finish(n, temp, s, offsets, text);

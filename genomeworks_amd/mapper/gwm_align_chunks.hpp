@@ -1,7 +1,8 @@
 // gwm_align_chunks.hpp -- the chunk loop that gwm_align_overlaps (gwm_align.hip), gwm_window_segments
 // (gwm_segments.hip), gwm_overlap_pileup (gwm_pileup.hip) and gwm_overlap_variants (gwm_variants.hip) share:
 // validation of the overlap records, sizing on the host, and per chunk of consecutive overlaps the gather of the
-// slices, gwhip_hirschberg_myers of libgwhip.so and the per-chunk buffers. What is done with the chunk's alignment
+// slices, the aligner (gwhip_hirschberg_myers of libgwhip.so, or gwhip_affine_align of libgwaffine.so when the call
+// names a scoring) and the per-chunk buffers. What is done with the chunk's alignment
 // states is the caller's: align_chunks() hands them to a consumer while they are on the device. The loop and its
 // kernels are defined once, in gwm_align.hip. Here as well: the check of the arguments every such entry point takes,
 // and ChunkedOutput, the bookkeeping of a consumer that writes a variable number of items per alignment (CIGAR bytes,
@@ -43,8 +44,11 @@ struct AlignedChunk
 // CIGAR text or the segment records of the chunks before, records beyond two bytes per column, which takes windows
 // of fewer than 12 bases, the counters of a pileup, 24 B per base of the owner set, and the insertion-run records of the
 // variant caller, 24 B each) lies outside it.
+// scoring == nullptr: unit costs, the default aligner. Otherwise the affine-gap aligner (include/gwhip_affine.h) under
+// these costs and this band writes the same results / result_lengths buffers, and its workspace is what the budget
+// counts; a scoring out of range is refused before anything is launched.
 void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, const ReadSet& q, const ReadSet& t,
-                  int64_t max_device_bytes, hipStream_t s, float* stage_ms,
+                  int64_t max_device_bytes, const gwm_scoring* scoring, hipStream_t s, float* stage_ms,
                   const std::function<void(const AlignedChunk&)>& consume);
 
 } // namespace gwm
@@ -66,6 +70,19 @@ inline void check_chunk_arguments(const std::string& who, int32_t n_queries, int
         throw std::invalid_argument(who + ": negative max_device_bytes");
     if (n >= (int64_t(1) << 31))
         throw std::invalid_argument(who + ": 2^31 overlaps or more");
+}
+
+// a scoring (nullptr: unit costs) outside the ranges of include/gwhip_affine.h; `who` opens the text
+inline void check_scoring(const std::string& who, const gwm_scoring* scoring)
+{
+    if (scoring == nullptr)
+        return;
+    if (scoring->mismatch < 1 || scoring->mismatch > 255 || scoring->gap_open < 0 || scoring->gap_open > 255 ||
+        scoring->gap_extend < 1 || scoring->gap_extend > 255 || scoring->band < 0)
+        throw std::invalid_argument(who + "scoring (mismatch " + std::to_string(scoring->mismatch) + ", gap_open " +
+                                    std::to_string(scoring->gap_open) + ", gap_extend " +
+                                    std::to_string(scoring->gap_extend) + ", band " + std::to_string(scoring->band) +
+                                    ") outside 1..255, 0..255, 1..255, >= 0");
 }
 
 inline void exclusive_sum(const int64_t* in, int64_t* out, int64_t n, Temp& t, hipStream_t s)

@@ -444,10 +444,22 @@ int gwm_overlap_variants(const gwm_overlap* overlaps, int64_t n, const char* que
                          int32_t min_count, int32_t min_percent, int64_t max_device_bytes, void* stream,
                          gwm_variants* out)
 {
+    return gwm_overlap_variants_scored(overlaps, n, query_bases, query_offsets, n_queries, first_query_read_id, target_bases,
+                                       target_offsets, n_targets, first_target_read_id, min_count, min_percent, nullptr,
+                                       max_device_bytes, stream, out);
+}
+
+int gwm_overlap_variants_scored(const gwm_overlap* overlaps, int64_t n, const char* query_bases,
+                                const int64_t* query_offsets, int32_t n_queries, uint32_t first_query_read_id,
+                                const char* target_bases, const int64_t* target_offsets, int32_t n_targets,
+                                uint32_t first_target_read_id, int32_t min_count, int32_t min_percent,
+                                const gwm_scoring* scoring, int64_t max_device_bytes, void* stream, gwm_variants* out)
+{
     *out = gwm_variants{};
     try
     {
         check_chunk_arguments("gwm_overlap_variants", n_queries, n_targets, max_device_bytes, n);
+        check_scoring("gwm_overlap_variants: ", scoring);
         if (min_count < 1)
             throw std::invalid_argument("gwm_overlap_variants: min_count below 1");
         if (min_percent < 0 || min_percent > 100)
@@ -463,7 +475,7 @@ int gwm_overlap_variants(const gwm_overlap* overlaps, int64_t n, const char* que
         {
             ChunkedOutput<gwm_insertion_run> records(n, s);
             Temp temp;
-            gwm::align_chunks("gwm_overlap_variants", overlaps, n, q, t, max_device_bytes, s, out->stage_ms,
+            gwm::align_chunks("gwm_overlap_variants", overlaps, n, q, t, max_device_bytes, scoring, s, out->stage_ms,
                               [&](const AlignedChunk& c) {
                                   add_role<false>(c, q, t, n_bases, counts.p, s);
                                   records.add(

@@ -507,14 +507,46 @@ gw_mapper_cigars* gw_mapper_align_overlaps(const void* overlaps, int64_t n, cons
                                            const int64_t* target_offsets, int32_t n_targets,
                                            uint32_t first_target_read_id, int64_t max_device_bytes, void* stream)
 {
+    return gw_mapper_align_overlaps_scored(overlaps, n, query_bases, query_offsets, n_queries, first_query_read_id,
+                                           target_bases, target_offsets, n_targets, first_target_read_id, nullptr,
+                                           max_device_bytes, stream);
+}
+
+namespace
+{
+// scoring[0..3] = mismatch, gap_open, gap_extend, band of the C API as the kernel level takes it; refused here when
+// out of range, before anything is uploaded
+const gwm_scoring* checked_scoring(const char* who, const int32_t* scoring, gwm_scoring* storage)
+{
+    if (scoring == nullptr)
+        return nullptr;
+    *storage = gwm_scoring{scoring[0], scoring[1], scoring[2], scoring[3]};
+    if (scoring[0] < 1 || scoring[0] > 255 || scoring[1] < 0 || scoring[1] > 255 || scoring[2] < 1 || scoring[2] > 255 ||
+        scoring[3] < 0)
+        throw std::invalid_argument(std::string(who) + ": scoring (mismatch " + std::to_string(scoring[0]) + ", gap_open " +
+                                    std::to_string(scoring[1]) + ", gap_extend " + std::to_string(scoring[2]) + ", band " +
+                                    std::to_string(scoring[3]) + ") outside 1..255, 0..255, 1..255, >= 0");
+    return storage;
+}
+} // namespace
+
+gw_mapper_cigars* gw_mapper_align_overlaps_scored(const void* overlaps, int64_t n, const char* query_bases,
+                                                  const int64_t* query_offsets, int32_t n_queries,
+                                                  uint32_t first_query_read_id, const char* target_bases,
+                                                  const int64_t* target_offsets, int32_t n_targets,
+                                                  uint32_t first_target_read_id, const int32_t* scoring,
+                                                  int64_t max_device_bytes, void* stream)
+{
     return guarded([&] {
         std::unique_ptr<gw_mapper_cigars> h(new gw_mapper_cigars());
+        gwm_scoring storage{};
+        const gwm_scoring* sc = checked_scoring("gw_mapper_align_overlaps_scored", scoring, &storage);
         // without overlaps nothing is uploaded, and the argument checks still apply
         device_call c({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets}, overlaps, n,
                       false);
-        throw_on(gwm_align_overlaps(c.d.p, n, c.q.bases, c.q.offsets, c.reads.queries.n, first_query_read_id, c.t.bases,
-                                    c.t.offsets, c.reads.targets.n, first_target_read_id, max_device_bytes, stream,
-                                    &h->c));
+        throw_on(gwm_align_overlaps_scored(c.d.p, n, c.q.bases, c.q.offsets, c.reads.queries.n, first_query_read_id,
+                                           c.t.bases, c.t.offsets, c.reads.targets.n, first_target_read_id, sc,
+                                           max_device_bytes, stream, &h->c));
         return h.release();
     }, static_cast<gw_mapper_cigars*>(nullptr));
 }
@@ -777,8 +809,23 @@ gw_mapper_variants* gw_mapper_overlap_variants(const void* overlaps, int64_t n, 
                                                uint32_t first_target_read_id, int32_t min_count, int32_t min_percent,
                                                int64_t max_device_bytes, void* stream)
 {
+    return gw_mapper_overlap_variants_scored(overlaps, n, query_bases, query_offsets, n_queries, first_query_read_id,
+                                             target_bases, target_offsets, n_targets, first_target_read_id, min_count,
+                                             min_percent, nullptr, max_device_bytes, stream);
+}
+
+gw_mapper_variants* gw_mapper_overlap_variants_scored(const void* overlaps, int64_t n, const char* query_bases,
+                                                      const int64_t* query_offsets, int32_t n_queries,
+                                                      uint32_t first_query_read_id, const char* target_bases,
+                                                      const int64_t* target_offsets, int32_t n_targets,
+                                                      uint32_t first_target_read_id, int32_t min_count,
+                                                      int32_t min_percent, const int32_t* scoring,
+                                                      int64_t max_device_bytes, void* stream)
+{
     return guarded([&] {
         std::unique_ptr<gw_mapper_variants> h(new gw_mapper_variants());
+        gwm_scoring storage{};
+        const gwm_scoring* sc = checked_scoring("gw_mapper_overlap_variants_scored", scoring, &storage);
         if (n < 0)
             throw std::invalid_argument("gw_mapper_overlap_variants: negative number of overlaps");
         // refused before the reads are uploaded: nothing reaches the device
@@ -789,9 +836,9 @@ gw_mapper_variants* gw_mapper_overlap_variants(const void* overlaps, int64_t n, 
         // without overlaps too: the counters are those of the target set
         device_call c({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets}, overlaps, n,
                       true);
-        throw_on(gwm_overlap_variants(c.d.p, n, c.q.bases, c.q.offsets, c.reads.queries.n, first_query_read_id,
-                                      c.t.bases, c.t.offsets, c.reads.targets.n, first_target_read_id, min_count,
-                                      min_percent, max_device_bytes, stream, &h->v));
+        throw_on(gwm_overlap_variants_scored(c.d.p, n, c.q.bases, c.q.offsets, c.reads.queries.n, first_query_read_id,
+                                             c.t.bases, c.t.offsets, c.reads.targets.n, first_target_read_id, min_count,
+                                             min_percent, sc, max_device_bytes, stream, &h->v));
         return h.release();
     }, static_cast<gw_mapper_variants*>(nullptr));
 }

@@ -241,7 +241,8 @@ def depth(pile):
     return pile[:5].sum(0)
 
 
-def call_variants(reads, targets, overlaps=None, min_count=3, min_percent=30, timings=None, **mapping_parameters):
+def call_variants(reads, targets, overlaps=None, min_count=3, min_percent=30, timings=None, scoring=None,
+                  **mapping_parameters):
     """Where the alignments polish() uses disagree with `targets`, and what they say instead: a list of dicts with
     target (position in `targets`), position (0-based), kind ("snv", "deletion", "insertion"), ref, alt, count and
     depth, by target, then by position, within a position SNV, deletion, insertion.
@@ -251,11 +252,12 @@ def call_variants(reads, targets, overlaps=None, min_count=3, min_percent=30, ti
     data). An SNV has the target's base as ref and the called base as alt. An insertion follows `position`; its ref is
     "" and its alt the inserted bases. Called deletions of neighbouring bases of one target are joined into one
     variant at the first of them: ref is the deleted bases, alt "", count the smallest of their counts and depth that
-    of the first base."""
+    of the first base. scoring, as cudamapper.overlap_variants takes it, aligns under affine gap costs instead of unit
+    costs: one indel event is then one gap run in every read that carries it."""
     overlaps = _mapped("call_variants", reads, targets, overlaps, mapping_parameters)
     kept = np.ascontiguousarray(overlaps, cudamapper.OVERLAP)
     kept = kept[one_overlap_per_read(kept)]
-    records = cudamapper.overlap_variants(kept, reads, targets, min_count, min_percent, timings=timings)
+    records = cudamapper.overlap_variants(kept, reads, targets, min_count, min_percent, timings=timings, scoring=scoring)
     return join_deletions(records, targets)
 
 

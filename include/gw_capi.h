@@ -193,6 +193,16 @@ gw_aligner* gw_aligner_create_algorithm(const char* algorithm, int32_t max_query
    gw_last_error() saying so. NULL on error. */
 gw_aligner* gw_aligner_create_typed(int32_t alignment_type, int32_t max_query_length, int32_t max_target_length,
                                     int32_t max_alignments, void* stream, int32_t device_id, int64_t max_device_memory);
+/* create_aligner_affine (cudaaligner/aligner_affine.hpp): global alignment under affine gap costs (minimised; match 0,
+   mismatch 1..255, a gap run of L columns gap_open + L * gap_extend with gap_open 0..255 and gap_extend 1..255) inside the
+   diagonals [min(0, m - n) - band_width, max(0, m - n) + band_width] of every pair; include/gwhip_affine.h states the rules.
+   gw_alignment_is_optimal says that the cost is the full-matrix optimum; a pair whose band has more than 2048 diagonals keeps
+   the status uninitialized. Like the infix / prefix aligners it has no device-resident results: gw_aligner_get_runs works;
+   gw_aligner_device_alignments returns 1; gw_aligner_relaunch, _relaunch_timed and _band_cells return -1 with gw_last_error()
+   saying so. gw_aligner_stage_ms reports its forward pass and its traceback. NULL on error (parameters out of range). */
+gw_aligner* gw_aligner_create_affine(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments, int32_t mismatch,
+                                     int32_t gap_open, int32_t gap_extend, int32_t band_width, void* stream, int32_t device_id,
+                                     int64_t max_device_memory);
 void gw_aligner_destroy(gw_aligner* a);
 int gw_aligner_add_alignment(gw_aligner* a, const char* query, int32_t query_length, const char* target,
                              int32_t target_length, int reverse_complement_query, int reverse_complement_target);
@@ -205,6 +215,8 @@ int32_t gw_alignment_status(gw_aligner* a, int32_t i);
 int32_t gw_alignment_is_optimal(gw_aligner* a, int32_t i);
 int32_t gw_alignment_edit_distance(gw_aligner* a, int32_t i);
 int32_t gw_alignment_type(gw_aligner* a, int32_t i); /* Alignment::get_alignment_type() */
+/* get_alignment_cost(): the cost of an affine aligner's alignment; -1 without a result, for other aligners and on error */
+int32_t gw_alignment_cost(gw_aligner* a, int32_t i);
 /* Alignment::get_target_begin() / get_target_end(): 0 and the target's length for a global alignment. 0, or -1 on error. */
 int gw_alignment_target_range(gw_aligner* a, int32_t i, int32_t* begin, int32_t* end);
 /* infix / prefix aligners, measurement aid: HIP-event times (ms) of the last align_all() -- the ends scan, and the gather of

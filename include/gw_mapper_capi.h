@@ -107,6 +107,16 @@ gw_mapper_cigars* gw_mapper_align_overlaps(const void* overlaps, int64_t n, cons
                                            uint32_t first_query_read_id, const char* target_bases,
                                            const int64_t* target_offsets, int32_t n_targets,
                                            uint32_t first_target_read_id, int64_t max_device_bytes, void* stream);
+/* The same under affine gap costs (gwm_align_overlaps_scored of gwhip_mapper.h): scoring[0..3] = mismatch (1..255),
+   gap_open (0..255), gap_extend (1..255), band (>= 0); NULL is gw_mapper_align_overlaps itself. A scoring out of range is
+   refused before anything reaches the device (NULL). An overlap whose band has more than 2048 diagonals has an empty
+   CIGAR and edit distance -1. */
+gw_mapper_cigars* gw_mapper_align_overlaps_scored(const void* overlaps, int64_t n, const char* query_bases,
+                                                  const int64_t* query_offsets, int32_t n_queries,
+                                                  uint32_t first_query_read_id, const char* target_bases,
+                                                  const int64_t* target_offsets, int32_t n_targets,
+                                                  uint32_t first_target_read_id, const int32_t* scoring,
+                                                  int64_t max_device_bytes, void* stream);
 int64_t gw_mapper_cigars_count(const gw_mapper_cigars* cigars);
 int64_t gw_mapper_cigars_text_bytes(const gw_mapper_cigars* cigars);
 int gw_mapper_cigars_copy(const gw_mapper_cigars* cigars, char* text, int64_t* offsets, int32_t* edit_distances,
@@ -317,6 +327,14 @@ gw_mapper_variants* gw_mapper_overlap_variants(const void* overlaps, int64_t n, 
                                                const int64_t* target_offsets, int32_t n_targets,
                                                uint32_t first_target_read_id, int32_t min_count, int32_t min_percent,
                                                int64_t max_device_bytes, void* stream);
+/* The same over the alignments of gw_mapper_align_overlaps_scored; scoring as there, NULL is gw_mapper_overlap_variants. */
+gw_mapper_variants* gw_mapper_overlap_variants_scored(const void* overlaps, int64_t n, const char* query_bases,
+                                                      const int64_t* query_offsets, int32_t n_queries,
+                                                      uint32_t first_query_read_id, const char* target_bases,
+                                                      const int64_t* target_offsets, int32_t n_targets,
+                                                      uint32_t first_target_read_id, int32_t min_count,
+                                                      int32_t min_percent, const int32_t* scoring,
+                                                      int64_t max_device_bytes, void* stream);
 /* the number of called records */
 int64_t gw_mapper_variants_count(const gw_mapper_variants* variants);
 /* records[count] (gwm_variant), ascending by cell, within a cell SNV, deletion, insertion -- one copy from the

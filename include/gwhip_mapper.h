@@ -218,6 +218,31 @@ void gwm_cigars_free(gwm_cigars* cigars);
  * Host arithmetic only. */
 int64_t gwm_align_bytes_needed(int32_t query_length, int32_t target_length, int32_t max_query_length);
 
+/* Affine gap costs for the alignments of a call (include/gwhip_affine.h states the rules): costs are minimised, a match
+ * costs 0, a gap run of L columns gap_open + L * gap_extend; 1 <= mismatch <= 255, 0 <= gap_open <= 255,
+ * 1 <= gap_extend <= 255; band >= 0 diagonals on either side of the corners' diagonals. */
+typedef struct gwm_scoring
+{
+    int32_t mismatch;
+    int32_t gap_open;
+    int32_t gap_extend;
+    int32_t band;
+} gwm_scoring;
+
+/* gwm_align_overlaps with the aligner chosen by `scoring`: NULL is gwm_align_overlaps itself; otherwise the slices,
+ * gathered as there, are aligned by gwhip_affine_align under these costs inside this band, and the CIGARs and
+ * edit_distances (still the columns that are not a match) describe those alignments. An overlap whose band has more
+ * than GWHIP_AFFINE_MAX_DIAGONALS diagonals (|m - n| + 2 band + 1) is the aligner's "no result": an empty CIGAR and -1.
+ * The budget counts gwhip_affine_workspace_bytes in place of the default aligner's workspace
+ * (gwm_align_bytes_needed_scored); the result does not depend on it. A scoring out of range is an error before anything
+ * is launched. */
+int gwm_align_overlaps_scored(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                              int32_t n_queries, uint32_t first_query_read_id, const char* target_bases,
+                              const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
+                              const gwm_scoring* scoring, int64_t max_device_bytes, void* stream, gwm_cigars* out);
+/* gwm_align_bytes_needed for a call with a scoring of this band. Host arithmetic only. */
+int64_t gwm_align_bytes_needed_scored(int32_t query_length, int32_t target_length, int32_t band);
+
 /* ---- polishing: from aligned overlaps to POA windows ----------------------------------------------------------------
  * The target reads are cut into windows of window_length bases: window k of a read is its bases [k W, (k + 1) W). */
 
@@ -390,6 +415,12 @@ int gwm_overlap_variants(const gwm_overlap* overlaps, int64_t n, const char* que
                          const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
                          int32_t min_count, int32_t min_percent, int64_t max_device_bytes, void* stream,
                          gwm_variants* out);
+/* gwm_overlap_variants over the alignments of gwm_align_overlaps_scored: NULL is gwm_overlap_variants itself. */
+int gwm_overlap_variants_scored(const gwm_overlap* overlaps, int64_t n, const char* query_bases,
+                                const int64_t* query_offsets, int32_t n_queries, uint32_t first_query_read_id,
+                                const char* target_bases, const int64_t* target_offsets, int32_t n_targets,
+                                uint32_t first_target_read_id, int32_t min_count, int32_t min_percent,
+                                const gwm_scoring* scoring, int64_t max_device_bytes, void* stream, gwm_variants* out);
 void gwm_variants_free(gwm_variants* variants);
 
 /* One sequence of a gather plan (20 B): bases [begin, end) of read `read` (position in its set) of the query set
