@@ -19,13 +19,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <climits>
 #include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "../../include/gwhip.h"
+#include "gwhip_device_facts.h"
+#include "gwhip_switches.h"
 
 namespace gwhip
 {
@@ -3583,6 +3584,7 @@ int gwhip_myers_banded(const gwhip_myers_args* args, gwhip_stream_t stream_)
         g_last_error = "gwhip_myers_banded: invalid arguments";
         return (int)hipErrorInvalidValue;
     }
+    const MyersSwitches sw = read_myers_switches();
     const int32_t n = args->n_alignments;
     if (n == 0) return 0;
     if (!args->workspace || ((uintptr_t)args->workspace & 255) != 0)
@@ -3690,12 +3692,8 @@ int gwhip_myers_banded(const gwhip_myers_args* args, gwhip_stream_t stream_)
             ka.lds_band_words    = bwords;
         }
     }
-    {
-        const char* sk = std::getenv("GWHIP_MYERS_SKIP");
-        ka.debug_skip  = sk ? std::atoi(sk) : 0;
-    }
-    const char* myers_dbg = std::getenv("GWHIP_MYERS_HBM_STATE"); // debugging: force the HBM-state kernel
-    if (myers_dbg && myers_dbg[0] == '1') use_lds = false;
+    ka.debug_skip = sw.skip;
+    if (sw.hbm_state) use_lds = false; // debugging: force the HBM-state kernel
     // Small batches of long pairs: G lanes per pair (myers_banded_group_kernel). Worth it while the one-lane kernel
     // would leave SIMDs empty (fewer wavefronts than SIMDs) and a pair is a long chain (queries of 256 bases and more).
     // G = 6 / 8 for batches that then fill the SIMDs (BASELINE configs[1]); G = 16 / 32 / 64 (round 6) while the batch still
@@ -3705,11 +3703,7 @@ int gwhip_myers_banded(const gwhip_myers_args* args, gwhip_stream_t stream_)
     // 15.7 ms: every column of a 13-word attempt was 13 dependent word steps of one lane.
     int group_lanes = 0; // 0: not the group kernel
     {
-        const char* gdbg = std::getenv("GWHIP_MYERS_GROUP"); // debugging: 0 = never, 1 = whenever the LDS tables fit
-        int cus = 0, dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        const int32_t simds  = 4 * cus;
+        const int32_t simds  = 4 * device_facts().cus;
         const int32_t qwords = args->max_query_length > 0 ? (args->max_query_length + kWord - 1) / kWord : 0;
         // LDS of a block of four wavefronts with G lanes per pair: per pair the pattern table (+ 1: odd stride) and 17 words of
         // target characters, plus the backtrace's column window (224 words for each of the 64 slots of a workspace region)
@@ -3728,8 +3722,7 @@ int gwhip_myers_banded(const gwhip_myers_args* args, gwhip_stream_t stream_)
         };
         auto fits = [&](int G) { return tile_of(G) >= 0; };
         bool use_group = (n + 63) / 64 < simds && args->max_query_length >= 256;
-        if (gdbg && gdbg[0] == '0') use_group = false;
-        if (gdbg && gdbg[0] == '1') use_group = true;
+        if (sw.group >= 0) use_group = sw.group == 1; // debugging: 0 = never, 1 = whenever the LDS tables fit
         if (use_group)
         {
             // (four lanes per pair with two words per lane -- half the wavefronts for 10 000 pairs -- was measured and is no
@@ -3740,11 +3733,7 @@ int gwhip_myers_banded(const gwhip_myers_args* args, gwhip_stream_t stream_)
             const int32_t bw_cap      = args->max_bandwidth_hint > 0 ? std::min(args->max_bandwidth_hint, args->max_query_length) : args->max_query_length;
             const int32_t worst_words = (bw_cap + kWord - 1) / kWord;
             while (G >= 8 && G < 64 && G < worst_words && (int64_t)n * (2 * G) / 64 <= simds) G *= 2;
-            if (const char* gl = std::getenv("GWHIP_MYERS_GROUP_LANES")) // forces the choice (6, 8, 16, 32, 64)
-            {
-                const int v = std::atoi(gl);
-                if (v == 6 || v == 8 || v == 16 || v == 32 || v == 64) G = v;
-            }
+            if (sw.group_lanes != 0) G = sw.group_lanes; // forces the choice (6, 8, 16, 32, 64)
             // tables that do not fit: fewer pairs per block (more lanes per pair) until they do, if the batch allows it
             for (int g = G; g <= 64 && group_lanes == 0; g = g == 6 ? 8 : 2 * g)
                 if (fits(g) && (g == G || (int64_t)n * g / 64 <= 2 * simds)) group_lanes = g;
@@ -3789,9 +3778,8 @@ int gwhip_myers_banded(const gwhip_myers_args* args, gwhip_stream_t stream_)
     {
         const bool runs = args->results_host && args->result_counts_host && args->results_host_capacity > 0;
         // (a small grid: the link needs few stores in flight, and a wide one slows the alignment kernel it runs beside)
-        static const int mirror_blocks = [] { const char* e = std::getenv("GWHIP_MIRROR_BLOCKS"); return e ? std::max(1, std::atoi(e)) : 16; }();
         if (runs || args->result_starts_host)
-            hipLaunchKernelGGL(mirror_runs_kernel, dim3(std::max(1, std::min((n + 63) / 64, mirror_blocks))), dim3(256), 0, stream, args->results, args->result_counts,
+            hipLaunchKernelGGL(mirror_runs_kernel, dim3(std::max(1, std::min((n + 63) / 64, sw.mirror_blocks))), dim3(256), 0, stream, args->results, args->result_counts,
                                args->result_starts, n, runs ? args->results_host : nullptr, args->result_counts_host, args->results_host_capacity,
                                args->result_metadata, args->result_starts_host, args->result_metadata_host);
     }
@@ -3870,6 +3858,7 @@ int gwhip_hirschberg_myers(const gwhip_hirschberg_args* args, gwhip_stream_t str
         g_last_error = "gwhip_hirschberg_myers: invalid arguments";
         return (int)hipErrorInvalidValue;
     }
+    const HirschbergSwitches sw = read_hirschberg_switches();
     const int32_t n = args->n_alignments;
     if (n == 0) return 0;
     const int32_t n_waves = (n + 63) / 64;
@@ -3901,22 +3890,10 @@ int gwhip_hirschberg_myers(const gwhip_hirschberg_args* args, gwhip_stream_t str
     const size_t wave_lds     = (size_t)(4 * kHbStackEntries + 6 * 64 * part_chunks + 3 * kHwLeafElems) * sizeof(uint32_t);
     // LDS a block may ask for on this device (queried once per device: 160 KB on gfx950) minus a margin for the kernels' static
     // LDS; a launch that would not fit falls through to the kernels below instead of failing
-    static std::atomic<int> lds_limit_of_device[64]; // zero-initialised; filled by whichever host thread asks first (same value)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev >= 0 && dev < 64 && lds_limit_of_device[dev].load(std::memory_order_relaxed) == 0)
-    {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0) v = 64 * 1024;
-        lds_limit_of_device[dev].store(v, std::memory_order_relaxed);
-    }
-    const size_t lds_limit    = (size_t)((dev >= 0 && dev < 64) ? lds_limit_of_device[dev].load(std::memory_order_relaxed) : 64 * 1024) - 10 * 1024;
-    bool use_wave             = n <= 262144 && wave_lds <= lds_limit;
-    {
-        const char* hw = std::getenv("GWHIP_HIRSCHBERG_WAVE");
-        if (hw && hw[0] == '0') use_wave = false;
-        if (hw && hw[0] == '1') use_wave = wave_lds <= lds_limit;
-    }
+    const size_t lds_limit = (size_t)device_facts().max_lds_per_block - 10 * 1024;
+    bool use_wave          = n <= 262144 && wave_lds <= lds_limit;
+    if (sw.wave == 0) use_wave = false;
+    if (sw.wave == 1) use_wave = wave_lds <= lds_limit;
     if (use_wave && wave_lds > 48 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(&hirschberg_wave_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wave_lds) != hipSuccess)
     {
@@ -3930,8 +3907,7 @@ int gwhip_hirschberg_myers(const gwhip_hirschberg_args* args, gwhip_stream_t str
         // queries of up to 2 048 bases: the level-by-level kernel first (GWHIP_HIRSCHBERG_LEVELS=0: depth-first only), the
         // depth-first kernel behind it for what that one leaves (targets beyond its LDS rows, list overflows)
         {
-            const char* lv = std::getenv("GWHIP_HIRSCHBERG_LEVELS");
-            if (args->max_query_length <= kLvMaxQuery && !(lv && lv[0] == '0'))
+            if (args->max_query_length <= kLvMaxQuery && sw.levels)
             {
                 const size_t lv_lds = (size_t)lv_layout(std::max(args->max_query_length, 1)).total;
                 bool lv_ok          = lv_lds <= lds_limit;
@@ -3950,10 +3926,7 @@ int gwhip_hirschberg_myers(const gwhip_hirschberg_args* args, gwhip_stream_t str
         }
         // long single pairs (queries beyond kSpanPartQuery in a batch of at most kSpanMaxPairs pairs): the top of the tree level by
         // level across blocks, then one wavefront per part (GWHIP_HIRSCHBERG_SPAN=0: the depth-first kernel alone)
-        {
-            const char* sp = std::getenv("GWHIP_HIRSCHBERG_SPAN");
-            ka.span_levels = (n <= kSpanMaxPairs && !(sp && sp[0] == '0')) ? hb_span_levels(args->max_query_length) : 0;
-        }
+        ka.span_levels = (n <= kSpanMaxPairs && sw.span) ? hb_span_levels(args->max_query_length) : 0;
         if (lds_request > 48 * 1024)
         {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&hirschberg_wave_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_request);
@@ -3970,8 +3943,7 @@ int gwhip_hirschberg_myers(const gwhip_hirschberg_args* args, gwhip_stream_t str
                 // several) -- GWHIP_HIRSCHBERG_SPAN=1: one wavefront per half, chunk after chunk (A/B)
                 const int32_t half   = ((args->max_query_length >> level) + 1) / 2 + 1;
                 const int32_t chunks = (((half + kWord - 1) / kWord) + 63) / 64;
-                const char* sp       = std::getenv("GWHIP_HIRSCHBERG_SPAN");
-                if (chunks > kMwMaxChunks || (sp && sp[0] == '1'))
+                if (chunks > kMwMaxChunks || sw.span_single_wave)
                     hipLaunchKernelGGL(hb_span_rows_kernel, dim3(2u << level, n), dim3(64), lds_request, stream, ka, level);
                 else
                     hipLaunchKernelGGL(hb_span_rows_mw_kernel, dim3(2u << level, n), dim3(64 * std::max(1, std::min(chunks, kMwMaxWaves))), 0, stream, ka, level);

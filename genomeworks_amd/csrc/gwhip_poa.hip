@@ -8,6 +8,8 @@
 #include <cstring>
 #include <string>
 
+#include "gwhip_device_facts.h"
+#include "gwhip_switches.h"
 #include "poa_device.h"
 #include "poa_full_device.h"
 #include "poa_graph_device.h"
@@ -463,20 +465,20 @@ __global__ __launch_bounds__(kWave * NW) void poa_window_kernel(KernelArgs a)
             // incremental order (replay of the previous run in blocks) when the ids fit its 17-bit fields and the score
             // matrix holds its working set (24 bytes per node); GWHIP_DEBUG bit 17 selects the cached full re-sort instead
             // (A/B: the choice must be the same for every read of a window, the two keep different things in local_cnt)
-            const bool incr_ok = c.max_nodes_per_graph <= 131071 && !(debug_flags & (1 << 17)) &&
+            const bool incr_ok = c.max_nodes_per_graph <= 131071 && !(debug_flags & kDbgTopsortCachedFull) &&
                                  (int64_t)a.L.scores_elems * (int64_t)sizeof(ScoreT) >= (int64_t)c.max_nodes_per_graph * 24 + 2048;
-            if (status_and_count >= 0 && !c.spoa_accurate && !(debug_flags & (1 << 21)) && incr_ok)
+            if (status_and_count >= 0 && !c.spoa_accurate && !(debug_flags & kDbgTopsortFullResort) && incr_ok)
             {
                 wave_sync();
                 // hot state in LDS (the idle score ring) when the graph's counters fit beside the window of the previous
                 // order; GWHIP_DEBUG bit 16: the HBM routine only (A/B)
                 bool done = false;
-                if (!(debug_flags & (1 << 16)) && topsort_incr_cnt8_lds_bytes(status_and_count) <= ring_bytes)
+                if (!(debug_flags & kDbgTopsortIncrHbmOnly) && topsort_incr_cnt8_lds_bytes(status_and_count) <= ring_bytes)
                     done = topsort_kahn_incr_cnt8<IdT>(g, node_count, status_and_count, smem, reinterpret_cast<int32_t*>(scores), lane);
                 if (!done) topsort_kahn_incr_hbm<IdT>(g, node_count, status_and_count, reinterpret_cast<int32_t*>(scores), lane);
                 sorted_here = true;
             }
-            else if (status_and_count >= 0 && !c.spoa_accurate && !(debug_flags & (1 << 21)) &&
+            else if (status_and_count >= 0 && !c.spoa_accurate && !(debug_flags & kDbgTopsortFullResort) &&
                      (int64_t)a.L.scores_elems * (int64_t)sizeof(ScoreT) >= (int64_t)(2 * ((node_count + 63) & ~63)) * 4)
             {
                 wave_sync();
@@ -498,7 +500,7 @@ __global__ __launch_bounds__(kWave * NW) void poa_window_kernel(KernelArgs a)
         {
             if constexpr (LDS_TABLES)
             {
-                if (!(debug_flags & (1 << 21))) // GWHIP_DEBUG bit 21: full re-sort after every read (A/B switch)
+                if (!(debug_flags & kDbgTopsortFullResort)) // GWHIP_DEBUG bit 21: full re-sort after every read (A/B switch)
                     topsort_kahn_incr_lds<IdT>(g, node_count, status_and_count, lds_rowinfo_region, smem, lds_read_buf, lane,
                                                debug_flags, pc.acc ? &pc.acc[kPhOther] : nullptr);
                 else
@@ -576,7 +578,7 @@ __global__ __launch_bounds__(kWave) void poa_consensus_lds_kernel(KernelArgs a)
     if (n <= a.cons_lds_nodes)
         generate_consensus_lds<int16_t>(g, n, cons_smem, a.cons_lds_nodes, consensus, a.coverage + (size_t)w * c.max_consensus_size,
                                         c.max_consensus_size, threadIdx.x & (kWave - 1),
-                                        (a.debug_flags & 16) != 0); // GWHIP_DEBUG bit 4: the first bundle pass node by node (A/B)
+                                        (a.debug_flags & kDbgConsensusNodeByNode) != 0); // GWHIP_DEBUG bit 4: the first bundle pass node by node (A/B)
     else if (threadIdx.x == 0) // a graph beyond the LDS tables of this launch: the serial HBM routine
         generate_consensus<int16_t>(g, n, g.cons_pred, g.cons_scores, consensus, a.coverage + (size_t)w * c.max_consensus_size,
                                     c.max_consensus_size);
@@ -739,12 +741,7 @@ static hipError_t launch_window_kernel(const KernelArgs& ka_in, hipStream_t stre
     // more windows than one wavefront per SIMD (LDS-table kernels: 39 KB of LDS = four one-wave blocks per CU): a persistent grid
     if (LDS_TABLES && ka.work_counters != nullptr)
     {
-        static const int simds = [] {
-            int cus = 0, dev = 0;
-            (void)hipGetDevice(&dev);
-            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-            return 4 * cus;
-        }();
+        const int simds = 4 * device_facts().cus; // (what gwhip_poa_resident_windows() tells the host)
         if (ka.total_windows > simds) grid = dim3(simds);
     }
     if (grid.x >= (unsigned)ka.total_windows) ka.work_counters = nullptr;
@@ -860,7 +857,7 @@ extern template hipError_t launch_trace_split<int32_t, int16_t>(const KernelArgs
 extern template hipError_t launch_trace_split<int16_t, int32_t>(const KernelArgs&, hipStream_t);
 extern template hipError_t launch_trace_split<int16_t, int16_t>(const KernelArgs&, hipStream_t);
 
-static KernelArgs make_kernel_args(const gwhip_poa_args* args)
+static KernelArgs make_kernel_args(const gwhip_poa_args* args, const PoaSwitches& sw)
 {
     KernelArgs ka{};
     ka.cfg             = args->cfg;
@@ -877,13 +874,8 @@ static KernelArgs make_kernel_args(const gwhip_poa_args* args)
     ka.full_scores     = ka.workspace + (size_t)args->total_windows * ka.L.per_window;
     ka.cells           = args->cells;
     ka.phase_cycles    = args->phase_cycles;
-    ka.work_counters   = args->work_counters;
-    if (const char* pg = std::getenv("GWHIP_POA_PERSISTENT")) // A/B: 0 = always one block per window
-        if (pg[0] == '0') ka.work_counters = nullptr;
-    {
-        const char* dbg = std::getenv("GWHIP_DEBUG");
-        ka.debug_flags  = dbg ? std::atoi(dbg) : 0;
-    }
+    ka.work_counters   = sw.persistent_grid ? args->work_counters : nullptr; // (A/B: always one block per window)
+    ka.debug_flags     = sw.debug_flags;
     return ka;
 }
 #endif // GWHIP_POA_PART
@@ -932,13 +924,7 @@ int32_t gwhip_poa_resident_windows(const gwhip_poa_config* cfg)
     // the condition of launch_msa_split() for the LDS-table kernels (one 64-lane block per window, 39 KB of LDS: four per CU)
     const bool lds = !cfg->size32 && cfg->max_nodes_per_graph + 2 <= kRowInfoLds && cfg->max_sequence_size + 16 <= kReadLds;
     if (!lds) return 0;
-    int cus = 0, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    {
-        (void)hipGetLastError();
-        cus = 256;
-    }
-    return 4 * cus;
+    return 4 * device_facts().cus;
 }
 
 int32_t gwhip_poa_reads_host_sequences(const gwhip_poa_config* cfg)
@@ -955,7 +941,8 @@ int gwhip_poa_generate(const gwhip_poa_args* args, gwhip_stream_t stream_)
     hipStream_t stream = (hipStream_t)stream_;
     if (!args || !validate(args)) return fail_msg((int)hipErrorInvalidValue, "gwhip_poa_generate: invalid arguments");
     if (args->total_windows == 0) return 0;
-    KernelArgs ka = make_kernel_args(args);
+    const PoaSwitches sw = read_poa_switches();
+    KernelArgs ka        = make_kernel_args(args, sw);
     if (!args->workspace || ((uintptr_t)args->workspace & 255) != 0)
         return fail_msg((int)hipErrorInvalidValue, "gwhip_poa_generate: workspace must be 256-byte aligned");
     if (args->workspace_bytes < gwhip_poa_workspace_bytes(&args->cfg, args->total_windows, 0))
@@ -977,8 +964,7 @@ int gwhip_poa_generate(const gwhip_poa_args* args, gwhip_stream_t stream_)
     {
         // wave-wide racon order with its marks in LDS when a byte per node fits (long-read graphs: one block per CU)
         const size_t msa_lds = (size_t)kMsaStackEntries * 4 + (((size_t)args->cfg.max_nodes_per_graph + 15) & ~size_t(15));
-        const char* msa_dbg  = std::getenv("GWHIP_MSA_SERIAL"); // debugging: the serial HBM routine
-        const bool msa_wave  = msa_lds <= 150 * 1024 && !(msa_dbg && msa_dbg[0] == '1');
+        const bool msa_wave  = msa_lds <= 150 * 1024 && !sw.msa_serial; // (debugging: the serial HBM routine)
         ka.cons_lds_nodes    = msa_wave ? args->cfg.max_nodes_per_graph : 0;
         if (args->cfg.size32)
         {
@@ -993,17 +979,14 @@ int gwhip_poa_generate(const gwhip_poa_args* args, gwhip_stream_t stream_)
     }
     else
     {
-        const char* cons_dbg = std::getenv("GWHIP_CONSENSUS_SERIAL"); // debugging: force the HBM-only kernel
         if (args->cfg.size32) hipLaunchKernelGGL(poa_consensus_kernel<int32_t>, grid, block, 0, stream, ka);
-        else if (args->cfg.max_nodes_per_graph <= kConsLdsNodes && !(cons_dbg && cons_dbg[0] == '1'))
+        else if (args->cfg.max_nodes_per_graph <= kConsLdsNodes && !sw.consensus_hbm_only) // (debugging: force the HBM-only kernel)
         {
             // 55 KB of LDS for the largest graph lets two blocks share a CU; with more windows than that holds at once
             // the tables are sized for 2176 nodes (39 KB, four blocks per CU) and larger graphs take the HBM routine
-            int cus = 0, dev = 0;
-            (void)hipGetDevice(&dev);
-            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+            const int cus     = device_facts().cus;
             const int32_t cap = (args->cfg.max_nodes_per_graph > kConsLdsNodesSmall && (args->total_windows > 2 * cus || args->shared_device != 0) &&
-                                 !(cons_dbg && cons_dbg[0] == '2'))
+                                 !sw.consensus_full_tables)
                                     ? kConsLdsNodesSmall
                                     : std::min<int32_t>(args->cfg.max_nodes_per_graph, kConsLdsNodes);
             ka.cons_lds_nodes = cap;
@@ -1026,7 +1009,7 @@ int gwhip_poa_export_graphs_range(const gwhip_poa_args* args, int32_t first_wind
     if (n_windows == 0) return 0;
     if (args->workspace_bytes < gwhip_poa_workspace_bytes(&args->cfg, args->total_windows, 0))
         return fail_msg((int)hipErrorInvalidValue, "gwhip_poa_export_graphs: workspace_bytes is smaller than gwhip_poa_workspace_bytes(cfg, total_windows, 0)");
-    KernelArgs ka = make_kernel_args(args);
+    KernelArgs ka = make_kernel_args(args, read_poa_switches());
     dim3 grid(n_windows), block(256);
     if (args->cfg.size32)
         hipLaunchKernelGGL(poa_export_graph_kernel<int32_t>, grid, block, 0, stream, ka, first_window, nodes, incoming_edges,

@@ -17,6 +17,7 @@
 
 #include <type_traits>
 
+#include "poa_debug_flags.h"
 #include "poa_layout.h"
 #include "poa_pred_rows.h"
 
@@ -632,7 +633,7 @@ __device__ __forceinline__ int32_t traceback_banded_lanes(const BandedCtx<ScoreT
     uint32_t* stage  = reinterpret_cast<uint32_t*>(tile + kTileRows * kTileStride);
     // profiling (GWHIP_DEBUG bits 22-24): 4 cycles in the steps (incl. their tile loads), 5 their number (x 1000), 6 cycles of
     // the post-pass; arrives in the "other" accumulator
-    const int32_t psel = prof_acc ? (dbg >> 22) & 7 : 0;
+    const int32_t psel = prof_acc ? (dbg >> kDbgTbShift) & kDbgTbMask : 0;
     uint64_t pacc      = 0;
 
     auto window_lo = [&](int32_t t) -> int32_t { return ((tile_col - kLead - t) & ~3) + 1; };
@@ -704,8 +705,8 @@ __device__ __forceinline__ int32_t traceback_banded_lanes(const BandedCtx<ScoreT
     // (every step appends one entry, so the reference's loop counter is aligned_nodes)
     while (!(i == 0 && j == 0) && aligned_nodes < bound)
     {
-        const uint64_t t_rc = psel == 4 ? clock64() : 0;
-        if (psel == 5) pacc += 1000;
+        const uint64_t t_rc = psel == kDbgTbStepCycles ? clock64() : 0;
+        if (psel == kDbgTbSteps) pacc += 1000;
         // keep the current cell and its near predecessors inside the tile
         if (use_tile)
         {
@@ -822,12 +823,12 @@ __device__ __forceinline__ int32_t traceback_banded_lanes(const BandedCtx<ScoreT
         ri_hi     = next_hi;
         rch       = next_rch;
         have      = found;
-        if (psel == 4) pacc += clock64() - t_rc;
+        if (psel == kDbgTbStepCycles) pacc += clock64() - t_rc;
     }
-    const uint64_t t_pp = psel == 6 ? clock64() : 0;
+    const uint64_t t_pp = psel == kDbgTbPostPassCycles ? clock64() : 0;
     if (aligned_nodes > 0 && (aligned_nodes & (kStage - 1)) != 0)
         flush_stage(aligned_nodes & ~(kStage - 1), aligned_nodes & (kStage - 1));
-    if ((dbg & 2) && prof_acc && lane == 0) *prof_acc += (uint64_t)max(aligned_nodes, 0); // profiling: all steps
+    if ((dbg & kDbgTbCountAllSteps) && prof_acc && lane == 0) *prof_acc += (uint64_t)max(aligned_nodes, 0); // profiling: all steps
     if (aligned_nodes >= bound) aligned_nodes = kNwLoopFailed;
     wave_sync();
     for (int32_t k0 = lane; k0 < aligned_nodes; k0 += 4 * kWave) // 4 independent load chains per lane in flight
@@ -842,7 +843,7 @@ __device__ __forceinline__ int32_t traceback_banded_lanes(const BandedCtx<ScoreT
             if (pos[u] >= 0) alignment_graph[k0 + u * kWave] = node[u];
     }
     wave_sync();
-    if (psel == 6) pacc += clock64() - t_pp;
+    if (psel == kDbgTbPostPassCycles) pacc += clock64() - t_pp;
     if (psel && lane == 0) *prof_acc += pacc;
     return aligned_nodes;
 }
@@ -990,12 +991,12 @@ __device__ __forceinline__ void banded_forward_1pass(const GraphView<IdT>& g, co
         out.v[2] = (ScoreT)narrow_chk<ScoreT>(P2, wrapped); out.v[3] = (ScoreT)narrow_chk<ScoreT>(P3, wrapped);
         if (full_wave)
         {
-            if (!(dbg & 1)) *reinterpret_cast<Quad<ScoreT>*>(row_out + lane4 + 1 + kRelShift) = out;
+            if (!(dbg & kDbgNoScoreStores)) *reinterpret_cast<Quad<ScoreT>*>(row_out + lane4 + 1 + kRelShift) = out;
             *reinterpret_cast<Quad<ScoreT>*>(ring_out + lane4 + 1 + kRelShift) = out;
         }
         else if (active)
         {
-            if (!(dbg & 1)) *reinterpret_cast<Quad<ScoreT>*>(row_out + lane4 + 1 + kRelShift) = out;
+            if (!(dbg & kDbgNoScoreStores)) *reinterpret_cast<Quad<ScoreT>*>(row_out + lane4 + 1 + kRelShift) = out;
             *reinterpret_cast<Quad<ScoreT>*>(ring_out + lane4 + 1 + kRelShift) = out;
         }
         if (bs == 0) // only rows whose band starts at column 0 have a real left-boundary value
@@ -1056,7 +1057,7 @@ __device__ __forceinline__ void banded_forward_1pass(const GraphView<IdT>& g, co
 
         // ================= general row =================
         {
-            const uint64_t t_general = (dbg & 4) ? clock64() : 0;
+            const uint64_t t_general = (dbg & kDbgTimeGeneralRows) ? clock64() : 0;
             const int32_t pred_count = ri.cnt();
             const int32_t bs         = ri.bs();
             const uint32_t base      = (uint32_t)ri.base();
@@ -1189,10 +1190,10 @@ __device__ __forceinline__ void banded_forward_1pass(const GraphView<IdT>& g, co
                 ri       = uniform_row(raw_next);
                 raw_next = rowinfo[min(r + 1, graph_count)];
             }
-            if (dbg & 4) general_acc += (dbg & 8) ? 1 : clock64() - t_general;
+            if (dbg & kDbgTimeGeneralRows) general_acc += (dbg & kDbgCountGeneralRows) ? 1 : clock64() - t_general;
         }
     }
-    if ((dbg & 4) && general_row_acc) *general_row_acc += general_acc;
+    if ((dbg & kDbgTimeGeneralRows) && general_row_acc) *general_row_acc += general_acc;
 }
 
 } // namespace gwhip
@@ -1295,9 +1296,9 @@ __device__ __forceinline__ void generic_forward_skew(const MwArgs<ScoreT>& A, co
     // in the row-table batches, 14 cycles in the block barriers of far rows
     // (PROF = false: the helper wavefronts of a production kernel, whose copy of the arguments comes out of LDS and could
     // not be folded: no counter code in their row loop. Wave 0 passes a compile-time 0 in production kernels.)
-    const int32_t sksel = PROF ? (A.dbg >> 12) & 15 : 0;
+    const int32_t sksel = PROF ? (A.dbg >> kDbgSkewShift) & kDbgSkewMask : 0;
     uint64_t skacc      = 0;
-    const uint64_t t_pass = sksel == 4 ? clock64() : 0;
+    const uint64_t t_pass = sksel == kDbgSkewPassCycles ? clock64() : 0;
     static_assert(sizeof(RowT) == 24, "the register copy of the row table holds six dwords per row");
     const int32_t graph_count = A.graph_count, read_length = A.read_length, band_width = A.band_width;
     const int32_t max_column = A.max_column, gap_score = A.gap_score;
@@ -1425,11 +1426,11 @@ __device__ __forceinline__ void generic_forward_skew(const MwArgs<ScoreT>& A, co
         asm volatile("s_mov_b64 exec, 1\n\tds_write_b32 %0, %1\n\ts_mov_b64 exec, -1" ::"v"(my_skipped), "v"(row) : "memory");
     };
     auto wait_left = [&](int32_t row) {
-        const uint64_t t_w = sksel == 5 ? clock64() : 0;
+        const uint64_t t_w = sksel == kDbgSkewLeftWaitCycles ? clock64() : 0;
         int32_t spins = 0;
         while (left_done < row)
         {
-            if (sksel == 9) skacc++;
+            if (sksel == kDbgSkewPolls) skacc++;
             const uint2 e    = hand_load(left_hand, row);
             const int32_t sk = *left_skipped;
             left_done        = max(left_done, max(wave_first((int32_t)e.y), wave_first(sk)));
@@ -1439,14 +1440,14 @@ __device__ __forceinline__ void generic_forward_skew(const MwArgs<ScoreT>& A, co
                 if (++spins > (1 << 22)) give_up();
             }
         }
-        if (sksel == 5) skacc += clock64() - t_w;
+        if (sksel == kDbgSkewLeftWaitCycles) skacc += clock64() - t_w;
     };
     auto wait_right = [&](int32_t row) {
-        const uint64_t t_w = sksel == 6 ? clock64() : 0;
+        const uint64_t t_w = sksel == kDbgSkewRingWaitCycles ? clock64() : 0;
         int32_t spins = 0;
         while (right_done < row)
         {
-            if (sksel == 9) skacc++;
+            if (sksel == kDbgSkewPolls) skacc++;
             const uint2 e    = hand_load(right_hand, row);
             const int32_t sk = *right_skipped;
             right_done       = max(right_done, max(wave_first((int32_t)e.y), wave_first(sk)));
@@ -1456,7 +1457,7 @@ __device__ __forceinline__ void generic_forward_skew(const MwArgs<ScoreT>& A, co
                 if (++spins > (1 << 22)) give_up();
             }
         }
-        if (sksel == 6) skacc += clock64() - t_w;
+        if (sksel == kDbgSkewRingWaitCycles) skacc += clock64() - t_w;
     };
     auto left_carry = [&](int32_t row) -> int32_t { // of a row the left neighbour has finished
         const uint2 e = hand_load(left_hand, row);
@@ -1482,10 +1483,10 @@ __device__ __forceinline__ void generic_forward_skew(const MwArgs<ScoreT>& A, co
     {
     if (r0 > 1)
     {
-        const uint64_t t_b = sksel == 13 ? clock64() : 0;
+        const uint64_t t_b = sksel == kDbgSkewRowTableCycles ? clock64() : 0;
         adopt_batch(r0);
         load_batch(r0 + 64, nxt);
-        if (sksel == 13) skacc += clock64() - t_b;
+        if (sksel == kDbgSkewRowTableCycles) skacc += clock64() - t_b;
     }
     const int32_t r_last = min(r0 + 63, graph_count);
     for (int32_t r = r0; r <= r_last; r++, next_row())
@@ -1524,10 +1525,10 @@ __device__ __forceinline__ void generic_forward_skew(const MwArgs<ScoreT>& A, co
                     far                = far || (r - prow >= near_rows);
                 }
             }
-            const uint64_t t_bar = (far && sksel == 14) ? clock64() : 0;
+            const uint64_t t_bar = (far && sksel == kDbgSkewFarBarrierCycles) ? clock64() : 0;
             if (far) block_barrier();
-            if (far && sksel == 3) skacc += 1000;
-            if (far && sksel == 14) skacc += clock64() - t_bar;
+            if (far && sksel == kDbgSkewBlockBarriers) skacc += 1000;
+            if (far && sksel == kDbgSkewFarBarrierCycles) skacc += clock64() - t_bar;
         }
 
         if ((int32_t)(kb >> 19) != blk) // the band has passed this wave's block: on to the next one
@@ -1538,18 +1539,18 @@ __device__ __forceinline__ void generic_forward_skew(const MwArgs<ScoreT>& A, co
         if (kind == 7) // the band has not reached this block yet, or has passed it
         {
             publish_skip(r); // (not an entry of MwShared::hand: see there)
-            if (sksel == 2) skacc++;
+            if (sksel == kDbgSkewRowsSkipped) skacc++;
             continue;
         }
         const bool first_block = (bs >> 8) == blk;
         const int32_t tg       = cvec - bs; // index of the lane's first cell in the band
         // cells of column 256 blk of the predecessor rows are the left neighbour's: it must be past row r - 1
-        const uint64_t t_ws = sksel == 10 ? clock64() : 0;
+        const uint64_t t_ws = sksel == kDbgSkewRowStartWaitCycles ? clock64() : 0;
         if (left_done < r - 1) wait_left(r - 1);
-        if (sksel == 10) skacc += clock64() - t_ws;
-        if (sksel == 1) skacc++;
-        if (sksel == 12 && first_block) skacc++;
-        const uint64_t t_rb = (sksel == 8 || (sksel == 11 && first_block)) ? clock64() : 0;
+        if (sksel == kDbgSkewRowStartWaitCycles) skacc += clock64() - t_ws;
+        if (sksel == kDbgSkewRowsWorked) skacc++;
+        if (sksel == kDbgSkewFirstBlockRows && first_block) skacc++;
+        const uint64_t t_rb = (sksel == kDbgSkewBodyCycles || (sksel == kDbgSkewFirstBlockCycles && first_block)) ? clock64() : 0;
 
         // what the two row bodies leave behind
         int32_t H0, H1, H2, H3;
@@ -1784,13 +1785,13 @@ __device__ __forceinline__ void generic_forward_skew(const MwArgs<ScoreT>& A, co
             else if (kind == 4) fast_row(std::integral_constant<int, 2>{}, std::true_type{});
             else if (kind == 2) fast_row(std::integral_constant<int, 3>{}, std::false_type{});
             else fast_row(std::integral_constant<int, 3>{}, std::true_type{});
-            if (sksel == 8 || (sksel == 11 && first_block)) skacc += clock64() - t_rb;
+            if (sksel == kDbgSkewBodyCycles || (sksel == kDbgSkewFirstBlockCycles && first_block)) skacc += clock64() - t_rb;
             continue;
         }
         else
         {
             // ================= general row: any number of predecessors, far ones from the HBM matrix =================
-            if (sksel == 7) skacc++;
+            if (sksel == kDbgSkewGeneralRows) skacc++;
             const bool many       = pred_count > 3;
             const int32_t node_id = many ? wave_first((int32_t)g.sorted_poa[r - 1]) : 0;
             auto pred_row = [&](int32_t p) -> int32_t {
@@ -1918,10 +1919,10 @@ __device__ __forceinline__ void generic_forward_skew(const MwArgs<ScoreT>& A, co
             scores[(int64_t)r * stride + kRelShift]                                          = (ScoreT)rel0_val;
         }
         publish(r, __builtin_amdgcn_readlane(H3, kWave - 1));
-        if (sksel == 8 || (sksel == 11 && first_block)) skacc += clock64() - t_rb;
+        if (sksel == kDbgSkewBodyCycles || (sksel == kDbgSkewFirstBlockCycles && first_block)) skacc += clock64() - t_rb;
     }
     }
-    if (sksel == 4) skacc += clock64() - t_pass;
+    if (sksel == kDbgSkewPassCycles) skacc += clock64() - t_pass;
     if (sksel && lane == 0) __hip_atomic_fetch_add(&shared->prof, (unsigned long long)skacc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     block_barrier(); // the score and code matrices are complete in HBM (wave 0's traceback reads them)
     if (sksel && prof_out && lane == 0) *prof_out += shared->prof;
@@ -2052,7 +2053,7 @@ __device__ __forceinline__ int32_t nw_banded(const GraphView<IdT>& g, RowT* rowi
         const int32_t u_span = max(band_width, 256) * abs(gap_score); // u-space offset of the last band cell
         const bool packed_ok = width_ok && max_column >= band_width && ring_bytes >= kPkSlots * kPkSlotBytes &&
                                abs(gap_score) <= 30 && abs(match_score) <= 100 && abs(mismatch_score) <= 100 &&
-                               codes != nullptr && !(dbg & 256) && ring_bytes >= kMtBytes &&
+                               codes != nullptr && !(dbg & kDbgNoPackedPasses) && ring_bytes >= kMtBytes &&
                                // no packed operation can leave int16: the largest score (all matches) plus the u-space offset of
                                // the last band cell, and the smallest (every step at the worst penalty; min_score-derived cells)
                                max(match_score, 0) * min(read_length, graph_count) + u_span + abs(match_score) <= 32767 &&
@@ -2075,15 +2076,15 @@ __device__ __forceinline__ int32_t nw_banded(const GraphView<IdT>& g, RowT* rowi
             {
                 banded_forward_moves<IdT, 256>(g, rowinfo, graph_count, lds_read, scores, codes, reinterpret_cast<uint8_t*>(ring_base),
                                                reinterpret_cast<const uint64_t*>(code_tile), max_column, gap_score, mismatch_score, match_score,
-                                               dbg, pc.acc ? &pc.acc[kPhOther] : nullptr, (dbg & (1 << 25)) != 0);
-                packed_selective = !(dbg & (1 << 25));
+                                               dbg, pc.acc ? &pc.acc[kPhOther] : nullptr, (dbg & kDbgEveryRowStoresScores) != 0);
+                packed_selective = !(dbg & kDbgEveryRowStoresScores);
             }
             else if constexpr (PV == 1)
             {
                 banded_forward_moves<IdT, 128>(g, rowinfo, graph_count, lds_read, scores, codes, reinterpret_cast<uint8_t*>(ring_base),
                                                reinterpret_cast<const uint64_t*>(code_tile), max_column, gap_score, mismatch_score, match_score,
-                                               dbg, pc.acc ? &pc.acc[kPhOther] : nullptr, (dbg & (1 << 25)) != 0);
-                packed_selective = !(dbg & (1 << 25));
+                                               dbg, pc.acc ? &pc.acc[kPhOther] : nullptr, (dbg & kDbgEveryRowStoresScores) != 0);
+                packed_selective = !(dbg & kDbgEveryRowStoresScores);
             }
             fast_done   = true;
             moves_valid = true;
@@ -2105,7 +2106,7 @@ __device__ __forceinline__ int32_t nw_banded(const GraphView<IdT>& g, RowT* rowi
         // rows the ring may hold there: the band start must move less than one block between a row and the row that
         // reuses its slot (see the function's header)
         const int32_t sk_rows = min(b.ring_rows, (int32_t)(200.0f / (gradient + 1.0f)));
-        if (!fast_done && mw_args != nullptr && npass >= 2 && sk_rows >= kSkLead + 3 && !(dbg & (1 << 18)))
+        if (!fast_done && mw_args != nullptr && npass >= 2 && sk_rows >= kSkLead + 3 && !(dbg & kDbgSingleWaveForward))
         {
             MwArgs<ScoreT> A;
             A.op = 1;
@@ -2295,15 +2296,15 @@ __device__ __forceinline__ int32_t nw_banded(const GraphView<IdT>& g, RowT* rowi
                 Quad<ScoreT> out;
                 out.v[0] = (ScoreT)N0; out.v[1] = (ScoreT)N1; out.v[2] = (ScoreT)N2; out.v[3] = (ScoreT)N3;
                 const int32_t rel = pass * 256 + 4 * lane + 1;
-                if (!(dbg & 1)) *reinterpret_cast<Quad<ScoreT>*>(scores + (int64_t)r * stride + rel + kRelShift) = out;
-                if (b.ring_rows && !(dbg & 2))
+                if (!(dbg & kDbgNoScoreStores)) *reinterpret_cast<Quad<ScoreT>*>(scores + (int64_t)r * stride + rel + kRelShift) = out;
+                if (b.ring_rows && !(dbg & kDbgNoRingStores))
                     *reinterpret_cast<Quad<ScoreT>*>(b.ring + slot_r * stride + rel + kRelShift) = out;
             }
         }
         if (lane == 0)
         {
-            if (!(dbg & 1)) scores[(int64_t)r * stride + kRelShift] = (ScoreT)rel0_val;
-            if (b.ring_rows && !(dbg & 2)) b.ring[slot_r * stride + kRelShift] = (ScoreT)rel0_val;
+            if (!(dbg & kDbgNoScoreStores)) scores[(int64_t)r * stride + kRelShift] = (ScoreT)rel0_val;
+            if (b.ring_rows && !(dbg & kDbgNoRingStores)) b.ring[slot_r * stride + kRelShift] = (ScoreT)rel0_val;
             if (bs_ring && b.ring_rows) bs_ring[slot_r] = bs;
         }
         hbm_dirty = true;
@@ -2328,7 +2329,7 @@ __device__ __forceinline__ int32_t nw_banded(const GraphView<IdT>& g, RowT* rowi
                 const int32_t np = max(ri.cnt(), 1);
                 for (int32_t p = 0; p < np; p++) all_in_ring = all_in_ring && (r - (ri.cnt() ? ri.pred(p) : 0) < b.ring_rows);
             }
-            if ((dbg & (1 << 20)) && pc.acc) pc.acc[kPhOther] += all_in_ring ? 1 : (1 << 20); // profiling: rows per path
+            if ((dbg & kDbgRowsPerPath) && pc.acc) pc.acc[kPhOther] += all_in_ring ? 1 : (1 << 20); // profiling: rows per path
             if (wave_first((int32_t)all_in_ring))
                 row_body(std::true_type{}, r, slot_r, ri);
             else
@@ -2341,7 +2342,7 @@ __device__ __forceinline__ int32_t nw_banded(const GraphView<IdT>& g, RowT* rowi
     if (__ballot(wrapped) != 0) return kNwScoreWrapped; // enforced precondition, see narrow_chk
 
     // ---- sink selection (:410-426): first row with the strictly greatest H(row, L) among sink rows ----
-    const uint64_t t_sink = (pc.acc && ((dbg >> 22) & 7) == 1) ? clock64() : 0;
+    const uint64_t t_sink = (pc.acc && ((dbg >> kDbgTbShift) & kDbgTbMask) == kDbgTbSinkCycles) ? clock64() : 0;
     int32_t best = min_score, best_i = 0;
     if constexpr (std::is_same<RowT, RowInfo<false>>::value)
     {
@@ -2381,7 +2382,7 @@ __device__ __forceinline__ int32_t nw_banded(const GraphView<IdT>& g, RowT* rowi
         if (ob > best || (ob == best && oi != 0 && (best_i == 0 || oi < best_i))) { best = ob; best_i = oi; }
     }
 
-    if (pc.acc && ((dbg >> 22) & 7) == 1) pc.acc[kPhOther] += clock64() - t_sink;
+    if (pc.acc && ((dbg >> kDbgTbShift) & kDbgTbMask) == kDbgTbSinkCycles) pc.acc[kPhOther] += clock64() - t_sink;
     int32_t aligned_nodes = 0;
     const bool tile_fits = (int32_t)(64 * 64 * sizeof(ScoreT) + 64 * sizeof(int32_t)) <= ring_bytes; // also covers the 60 x 68 + 64-word layout
     constexpr bool kLanesOk = std::is_same<RowT, RowInfo<true>>::value && LDS_READ;
@@ -2393,7 +2394,7 @@ __device__ __forceinline__ int32_t nw_banded(const GraphView<IdT>& g, RowT* rowi
             aligned_nodes = traceback_moves<int16_t, IdT, RowInfo<true>, ADAPTIVE>(b, g, rowinfo, graph_count, lds_read, read_length, wave_first(best_i),
                                                            alignment_graph, alignment_read, gap_score, mismatch_score, match_score,
                                                            rerun, reinterpret_cast<uint8_t*>(ring_base), codes, nullptr,
-                                                           packed_selective ? ((dbg & (1 << 23)) ? 2 : 0) : 1,
+                                                           packed_selective ? ((dbg & kDbgRerunEveryStep) ? 2 : 0) : 1,
                                                            reinterpret_cast<const uint64_t*>(code_tile));
             if (aligned_nodes == kNwNeedScoreRows)
             {
@@ -2402,7 +2403,7 @@ __device__ __forceinline__ int32_t nw_banded(const GraphView<IdT>& g, RowT* rowi
                 // (GWHIP_DEBUG, debug instantiation: bit 24 counts these reruns into the "other" phase accumulator, bit 23 makes
                 // every recomputed step below row 0 take this path, bit 25 stores every row in the first place; with bit 13 a
                 // rerun adds 2^40, which keeps the count exact above the phase's ticks -- without a row-kind selector of bits 28-30)
-                if (pc.acc && (dbg & (1 << 24))) pc.acc[kPhOther] += (dbg & (1 << 13)) ? (1ull << 40) : 1ull;
+                if (pc.acc && (dbg & kDbgCountReruns)) pc.acc[kPhOther] += (dbg & kDbgKindFine) ? (1ull << 40) : 1ull;
                 if (band_width == 256)
                     banded_forward_moves<IdT, 256>(g, rowinfo, graph_count, lds_read, scores, codes, reinterpret_cast<uint8_t*>(ring_base),
                                                    reinterpret_cast<const uint64_t*>(code_tile), max_column, gap_score, mismatch_score, match_score,
@@ -2422,7 +2423,7 @@ __device__ __forceinline__ int32_t nw_banded(const GraphView<IdT>& g, RowT* rowi
     }
     if constexpr (kLanesOk)
     {
-        if (!tb_done && tile_fits && b.stride >= 64 && !(dbg & 32))
+        if (!tb_done && tile_fits && b.stride >= 64 && !(dbg & kDbgTbNoLanes))
         {
             aligned_nodes = traceback_banded_lanes<ScoreT, IdT, ADAPTIVE>(b, g, rowinfo, graph_count, lds_read, read_length,
                                                                           wave_first(best_i), alignment_graph, alignment_read, gap_score,
@@ -2435,7 +2436,7 @@ __device__ __forceinline__ int32_t nw_banded(const GraphView<IdT>& g, RowT* rowi
     const bool staged_fits   = (int32_t)(64 * 64 * sizeof(ScoreT) + 64 * 4 + 64 * sizeof(RowT) + 256 + 64 * 8) <= ring_bytes;
     if constexpr (kStagedOk)
     {
-        if (codes_valid && codes != nullptr && ring_bytes >= kMtBytesWide && b.stride >= 80 && !(dbg & 64))
+        if (codes_valid && codes != nullptr && ring_bytes >= kMtBytesWide && b.stride >= 80 && !(dbg & kDbgTbNoWideMoves))
         {
             // wide bands, graphs beyond the LDS tables: the pipelined forward pass left move bytes
             aligned_nodes = traceback_moves<ScoreT, IdT, RowT, ADAPTIVE>(b, g, rowinfo, graph_count, read, read_length, wave_first(best_i),
@@ -2445,7 +2446,7 @@ __device__ __forceinline__ int32_t nw_banded(const GraphView<IdT>& g, RowT* rowi
         }
     }
     if (tb_done) {}
-    else if (kStagedOk && staged_fits && b.stride >= 64 && !(dbg & 128))
+    else if (kStagedOk && staged_fits && b.stride >= 64 && !(dbg & kDbgTbNoStaged))
     {
         // graphs beyond the LDS tables: score tile, row records, read window and output all staged in the dead ring
         aligned_nodes = traceback_banded_tiled_staged<ScoreT, IdT, RowT, ADAPTIVE>(b, g, rowinfo, graph_count, read, read_length,

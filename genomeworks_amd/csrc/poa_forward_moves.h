@@ -77,7 +77,7 @@ __device__ __forceinline__ int32_t classify_kinds(RowInfo<true>* rowinfo, int32_
     int32_t first_moved = graph_count + 1;
     // (bit 30 is also the top bit of the row loop's profiling selector: with bit 13, which makes that selector name a
     // descriptor kind, it demotes nothing)
-    const bool demote_many = (dbg & (1 << 30)) != 0 && (dbg & (1 << 13)) == 0;
+    const bool demote_many = (dbg & kDbgManyPredsToGeneral) != 0 && (dbg & kDbgKindFine) == 0;
     for (int32_t r = 1 + lane; r <= graph_count; r += kWave)
     {
         RowInfo<true> ri  = rowinfo[r];
@@ -105,10 +105,10 @@ __device__ __forceinline__ int32_t classify_kinds(RowInfo<true>* rowinfo, int32_
         // A/B selectors (GWHIP_DEBUG, debug instantiation): demote kinds so that the routines can be checked against each
         // other -- bit 10: registers -> ring (kinds 0, 1 -> 2), bit 15: kind 1 -> 2, bit 9: ring -> general (2, 3 -> 4),
         // bit 11: registers -> general (0, 1 -> 4), bit 30 without bit 13 (above): rows with 4..6 predecessors -> general
-        if ((dbg & 1024) && kind <= 1) kind = 2;
-        if ((dbg & 32768) && kind == 1) kind = 2;
-        if ((dbg & 512) && (kind == 2 || kind == 3)) kind = 4;
-        if ((dbg & 2048) && kind <= 1) kind = 4;
+        if ((dbg & kDbgRegistersToRing) && kind <= 1) kind = 2;
+        if ((dbg & kDbgMovedToRing) && kind == 1) kind = 2;
+        if ((dbg & kDbgRingToGeneral) && (kind == 2 || kind == 3)) kind = 4;
+        if ((dbg & kDbgRegistersToGeneral) && kind <= 1) kind = 4;
         ri.w       = (ri.w & ~(7ull << kKindShift)) | (kind << kKindShift);
         rowinfo[r] = ri;
         if (bs > 0) first_moved = min(first_moved, r);
@@ -220,18 +220,18 @@ __device__ __forceinline__ void banded_forward_moves(const GraphView<IdT>& g, Ro
     // 17 no move bytes, 16 no rows at all)
     // (all of them only with bit 14 set: the same bits are the merge / topsort profiling selectors of the window kernel, 16-18 and
     // 25-27 -- tools/profile_subphases.sh's topsort selectors 2, 3 and 6 switched the row stores off until round 6)
-    const bool abl       = (dbg & (1 << 14)) != 0;
-    const bool st_scores = !(abl && (dbg & (1 << 26))), st_moves = !(abl && (dbg & (1 << 27)));
-    const bool ab_ring = !(abl && (dbg & (1 << 20))), ab_guard = !(abl && (dbg & (1 << 19))), ab_scan = !(abl && (dbg & (1 << 18))),
-               ab_moves = !(abl && (dbg & (1 << 17))), ab_rows = !(abl && (dbg & (1 << 16)));
+    const bool abl       = (dbg & kDbgAblationsOn) != 0;
+    const bool st_scores = !(abl && (dbg & kDbgAblNoScoreRowStores)), st_moves = !(abl && (dbg & kDbgAblNoMoveRowStores));
+    const bool ab_ring = !(abl && (dbg & kDbgAblNoRingWrite)), ab_guard = !(abl && (dbg & kDbgAblNoGuard)), ab_scan = !(abl && (dbg & kDbgAblNoScan)),
+               ab_moves = !(abl && (dbg & kDbgAblNoMoveBytes)), ab_rows = !(abl && (dbg & kDbgAblNoRows));
     // profiling (GWHIP_DEBUG bits 28-30 = row kind + 1): cycles spent in rows of that kind, or with bit 12 their number;
     // arrives in the "other" phase accumulator. The kind is a TABLE kind (3 = every multi-predecessor ring row), or with bit 13
     // a DESCRIPTOR kind (poa_forward_row_operands.h: 3 two, 5 three, 6 four to six predecessors); with bit 13 a counted row
     // adds 2^32 in the phase of band start 0 and 2^48 in the moved phase, which keeps both counts exact above the phase's ticks
     // (up to 65 535 rows per window, phase and launch).
-    const int32_t ksel = prof_acc ? ((dbg >> 28) & 7) - 1 : -1;
-    const bool kfine   = (dbg & (1 << 13)) != 0;
-    const bool kcount  = (dbg & (1 << 12)) != 0;
+    const int32_t ksel = prof_acc ? ((dbg >> kDbgRowKindShift) & kDbgRowKindMask) - 1 : -1;
+    const bool kfine   = (dbg & kDbgKindFine) != 0;
+    const bool kcount  = (dbg & kDbgKindCount) != 0;
     uint64_t kacc      = 0;
     auto kselected = [&](uint32_t dk) -> bool { return ksel == (int32_t)((kfine || dk < kDkRingThree) ? dk : (uint32_t)kDkRingTwo); };
     const bool ksel_prev = kselected(kDkPrev), ksel_moved = kselected(kDkPrevMoved), ksel_one = kselected(kDkRingOne),

@@ -45,7 +45,7 @@ __device__ __forceinline__ void full_forward_moves(const GraphView<IdT>& g, RowI
     // 0). GWHIP_DEBUG bit 25 (debug instantiation): every row stores its scores (A/B).
     // (the list of rows whose predecessors are not all in LDS goes into the ring region, which is idle until row 0 is stored)
     static_assert(kWdSlots * kWdSlotBytes >= 4096 * (int)sizeof(uint16_t), "the ring region holds the list of left-over rows (rows <= 4095)");
-    mark_score_rows<IdT>(g, rowinfo, graph_count, lane, (dbg & (1 << 25)) != 0, reinterpret_cast<uint16_t*>(ring), xpred);
+    mark_score_rows<IdT>(g, rowinfo, graph_count, lane, (dbg & kDbgEveryRowStoresScores) != 0, reinterpret_cast<uint16_t*>(ring), xpred);
 
     const uint32_t GAP2   = pin_vgpr(pk_dup(gap_score));
     const uint32_t MAT2   = pin_vgpr(pk_dup(match_score));
@@ -129,8 +129,8 @@ __device__ __forceinline__ void full_forward_moves(const GraphView<IdT>& g, RowI
     auto pack_moves = [&](uint32_t m01, uint32_t m23) -> uint32_t { return __builtin_amdgcn_perm(m23, m01, 0x06040200u); };
     // timing ablations (GWHIP_DEBUG, debug instantiation only; results are garbage): bit 26 no score-row stores, bit 27 no
     // move-row stores
-    const bool abl       = (dbg & (1 << 14)) != 0; // (the store ablations only with bit 14: bits 26 / 27 are topsort selectors too)
-    const bool st_scores = !(abl && (dbg & (1 << 26))), st_moves = !(abl && (dbg & (1 << 27)));
+    const bool abl       = (dbg & kDbgAblationsOn) != 0; // (the store ablations only with it: their bits are topsort selectors too)
+    const bool st_scores = !(abl && (dbg & kDbgAblNoScoreRowStores)), st_moves = !(abl && (dbg & kDbgAblNoMoveRowStores));
     // the finished row (P*) of row r with H[r][0] = c0: HBM score row, ring slot r & 3, move bytes. Both HBM stores are
     // streaming stores (round 5, same-box A/B on the 1024 windows: 59.0 -> 55.2 ms; the matrices of a full-band batch are 10 GB,
     // far beyond every cache level, and the walk reads a sliver of the move rows)
@@ -427,7 +427,7 @@ __device__ __forceinline__ int32_t nw_full_packed(const GraphView<IdT>& g, RowIn
     handled        = false;
     const int32_t u_span = 1024 * abs(gap_score); // u-space offset of the last column
     const bool ok = read_length >= 1 && read_length <= 1023 && scores_width >= read_length + 1 + kCellsPerLane && moves != nullptr &&
-                    xpred != nullptr && ring_bytes >= kWdSlots * kWdSlotBytes && ring_bytes >= kMtBytes && !(dbg & 256) && gap_score < 0 &&
+                    xpred != nullptr && ring_bytes >= kWdSlots * kWdSlotBytes && ring_bytes >= kMtBytes && !(dbg & kDbgNoPackedPasses) && gap_score < 0 &&
                     abs(gap_score) <= 30 && abs(match_score) <= 100 && abs(mismatch_score) <= 100 &&
                     // no packed operation can leave int16: the largest score (all matches) plus the u-space offset of the last
                     // column, and the smallest (every step at the worst penalty)

@@ -161,7 +161,7 @@ __device__ __forceinline__ int32_t add_alignment_parallel(int32_t& new_node_coun
                                                           int32_t dbg = 0, uint64_t* prof_acc = nullptr)
 {
     const int32_t L = read_length;
-    const int32_t prof_sel = (dbg >> 16) & 7; // profiling (GWHIP_DEBUG bits 16-18): 1 = load, 2 = classify, 3 = create, 4 = edges
+    const int32_t prof_sel = (dbg >> kDbgMergeShift) & kDbgMergeMask; // profiling (GWHIP_DEBUG bits 16-18): 1 = load, 2 = classify, 3 = create, 4 = edges
     uint64_t prof_t = prof_sel ? clock64() : 0;
     auto prof_mark = [&](int32_t which) {
         if (prof_sel)
@@ -200,7 +200,7 @@ __device__ __forceinline__ int32_t add_alignment_parallel(int32_t& new_node_coun
     // The map over read positions needs a complete alignment (every read position exactly once); a degenerate
     // traceback result (reference quirk: a walk that finds no predecessor at its first step) goes the serial way.
     if (covered != L) return -1;
-    prof_mark(1);
+    prof_mark(kDbgMergeLoad);
 
     // ---- A + B: classify, detect conflicts, number new nodes in rp order ----
     int32_t running   = 0;
@@ -269,7 +269,7 @@ __device__ __forceinline__ int32_t add_alignment_parallel(int32_t& new_node_coun
     for (int off = 32; off > 0; off >>= 1) rp_nodeerr = min(rp_nodeerr, __shfl_xor(rp_nodeerr, off));
     wave_sync();
 
-    prof_mark(2);
+    prof_mark(kDbgMergeClassify);
     const int32_t first_new = node_count;
     auto in_count_of  = [&](int32_t n) -> int32_t { return n >= first_new ? 0 : (int32_t)g.incoming_edge_count[n]; };
     auto out_count_of = [&](int32_t n) -> int32_t { return n >= first_new ? 0 : (int32_t)g.outgoing_edge_count[n]; };
@@ -321,7 +321,7 @@ __device__ __forceinline__ int32_t add_alignment_parallel(int32_t& new_node_coun
         g.node_alignment_count[cur] = (uint16_t)na_new;
     }
     wave_sync();
-    prof_mark(3);
+    prof_mark(kDbgMergeCreate);
 
     // ---- D: edges and coverage ----
     // Read positions are independent here (a node is the current node of one position and the head of one
@@ -415,7 +415,7 @@ __device__ __forceinline__ int32_t add_alignment_parallel(int32_t& new_node_coun
     }
     for (int off = 32; off > 0; off >>= 1) rp_edgeerr = min(rp_edgeerr, __shfl_xor(rp_edgeerr, off));
     wave_sync();
-    prof_mark(4);
+    prof_mark(kDbgMergeEdges);
     if (rp_edgeerr != INT32_MAX) return (int32_t)kEdgeCountExceeded;
     new_node_count = node_count + running;
     return 0;
@@ -755,9 +755,9 @@ __device__ __forceinline__ void topsort_kahn_incr_lds(const GraphView<IdT>& g, i
 {
     // profiling (GWHIP_DEBUG bits 25-27): cycles of 1 phase 1, 2 replayed blocks, 3 ordinary steps, 4 phase 3;
     // 5 number of blocks x 1000, 6 number of ordinary steps x 1000
-    const int32_t tsel = prof_acc ? (dbg >> 25) & 7 : 0;
+    const int32_t tsel = prof_acc ? (dbg >> kDbgTopsortShift) & kDbgTopsortMask : 0;
     uint64_t tacc      = 0;
-    const uint64_t t_p1 = tsel == 1 ? clock64() : 0;
+    const uint64_t t_p1 = tsel == kDbgTopsortPhase1Cycles ? clock64() : 0;
     constexpr int32_t kDummy = 3073; // spare word of the 3074-entry region
     constexpr int32_t kQClip = 15;
     uint64_t* ent   = reinterpret_cast<uint64_t*>(lds);
@@ -823,7 +823,7 @@ __device__ __forceinline__ void topsort_kahn_incr_lds(const GraphView<IdT>& g, i
         }
     }
     wave_sync();
-    if (tsel == 1) tacc += clock64() - t_p1;
+    if (tsel == kDbgTopsortPhase1Cycles) tacc += clock64() - t_p1;
     // phase 2: wave-uniform control; k = new nodes output so far, M = highest previous position output so far.
     // The queue's front lives in registers: lane l holds the id and the node word of queue[head + l] for l < wcnt
     // (wcnt <= min(tail - head, 64); always a prefix of the queue). A queued node's word does not change any more: its
@@ -852,7 +852,7 @@ __device__ __forceinline__ void topsort_kahn_incr_lds(const GraphView<IdT>& g, i
     asm volatile("" : "+v"(sh012), "+v"(sh345), "+v"(m345), "+v"(m63));
     while (head < tail)
     {
-        const uint64_t t_it = (tsel == 2 || tsel == 3) ? clock64() : 0;
+        const uint64_t t_it = (tsel == kDbgTopsortBlockCycles || tsel == kDbgTopsortStepCycles) ? clock64() : 0;
         if (wcnt == 0) refill();
         const int32_t u   = wave_first(wn);
         const uint32_t lo = (uint32_t)wave_first((int32_t)wlo), hi = (uint32_t)wave_first((int32_t)whi);
@@ -964,8 +964,8 @@ __device__ __forceinline__ void topsort_kahn_incr_lds(const GraphView<IdT>& g, i
                 asm volatile("" ::: "memory"); // LDS executes one wavefront's operations in order: no wait, no barrier
                 wcnt = 0;
                 if (head < tail) refill(); // the register window restarts behind the block
-                if (tsel == 2) tacc += clock64() - t_it;
-                if (tsel == 5) tacc += 1000;
+                if (tsel == kDbgTopsortBlockCycles) tacc += clock64() - t_it;
+                if (tsel == kDbgTopsortBlocks) tacc += 1000;
                 continue;
             }
         }
@@ -1024,11 +1024,11 @@ __device__ __forceinline__ void topsort_kahn_incr_lds(const GraphView<IdT>& g, i
             wcnt = 0;
         }
         asm volatile("" ::: "memory");
-        if (tsel == 3) tacc += clock64() - t_it;
-        if (tsel == 6) tacc += 1000;
+        if (tsel == kDbgTopsortStepCycles) tacc += clock64() - t_it;
+        if (tsel == kDbgTopsortSteps) tacc += 1000;
     }
     wave_sync();
-    const uint64_t t_p3 = tsel == 4 ? clock64() : 0;
+    const uint64_t t_p3 = tsel == kDbgTopsortPhase3Cycles ? clock64() : 0;
     // phase 3 (all lanes): publish order, inverse map and the per-node record for the next read
     for (int32_t i0 = lane; i0 < node_count; i0 += 4 * kWave) // four chunks per HBM round trip
     {
@@ -1054,7 +1054,7 @@ __device__ __forceinline__ void topsort_kahn_incr_lds(const GraphView<IdT>& g, i
             }
         }
     }
-    if (tsel == 4)
+    if (tsel == kDbgTopsortPhase3Cycles)
     {
         wave_sync();
         tacc += clock64() - t_p3;

@@ -333,7 +333,7 @@ __device__ __forceinline__ int32_t nw_banded_tb_packed(const GraphView<IdT>& g, 
     }
     const int32_t u_span = max(band_width, 256) * abs(gap_score); // u-space offset of the last band cell
     const bool packed_ok = (band_width == 256 || band_width == 128 || band_width == 384 || band_width == 512) && max_column >= band_width && ring_bytes >= kPkSlots * kPkSlotBytes &&
-                           ring_bytes >= kMtBytes && xpred != nullptr && H >= 16 && !(dbg & 256) &&
+                           ring_bytes >= kMtBytes && xpred != nullptr && H >= 16 && !(dbg & kDbgNoPackedPasses) &&
                            abs(gap_score) <= 30 && abs(match_score) <= 100 && abs(mismatch_score) <= 100 &&
                            // no packed operation can leave int16 (the bounds of nw_banded's packed pass)
                            max(match_score, 0) * min(read_length, graph_count) + u_span + abs(match_score) <= 32767 &&

@@ -18,6 +18,7 @@ import random
 import pytest
 
 import oracle_poa as O
+from genomeworks_amd import debug_flags as D
 from test_gpu_poa import config3, oracle_cfg, run_gpu
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +28,8 @@ SEEDS = tuple(range(9100, 9136))
 SHAPE_SEED = 63
 CONFIG3_FIRST, CONFIG3_COUNT = 1000, 4
 CONFIGS = tuple((mode, width) for width in (256, 128) for mode in ("static_band", "adaptive_band"))
-ARMS = (("ring_through_general", str(1 << 9)), ("everything_general", str((1 << 9) | (1 << 11) | (1 << 30))))
+ARMS = (("ring_through_general", D.env_value(D.kDbgRingToGeneral)),
+        ("everything_general", D.env_value(D.kDbgRingToGeneral, D.kDbgRegistersToGeneral, D.kDbgManyPredsToGeneral)))
 # descriptor kinds (poa_forward_row_operands.h)
 KINDS = {0: "previous row", 1: "previous row, band moved", 2: "one from the ring", 3: "two from the ring", 4: "general",
          5: "three from the ring", 6: "four to six from the ring"}
@@ -93,7 +95,7 @@ def test_every_descriptor_kind_runs_in_both_phases(monkeypatch, windows):
     b = run_gpu(windows, "static_band", band_width=256, mem=2 << 30)
     rows = {}
     for kind in KINDS:
-        monkeypatch.setenv("GWHIP_DEBUG", str(((kind + 1) << 28) | (1 << 13) | (1 << 12)))
+        monkeypatch.setenv("GWHIP_DEBUG", D.env_value(D.kDbgKindFine, D.kDbgKindCount, row_kind=kind))
         per_window = [w["other"] for w in b.profile_phases_per_window()]
         rows[kind] = (sum((v >> 32) & 0xffff for v in per_window), sum(v >> 48 for v in per_window))
     monkeypatch.delenv("GWHIP_DEBUG")

@@ -3,10 +3,46 @@ import numpy as np
 import pytest
 
 import oracle_poa as O
+from genomeworks_amd import debug_flags as D
 
 pytestmark = pytest.mark.gpu
 
 BAND = {"full_band": 0, "static_band": 1, "adaptive_band": 2, "static_band_traceback": 3, "adaptive_band_traceback": 4}
+
+# The A/B arms of the debug instantiation, by name: the value of GWHIP_DEBUG (None: unset, the production instantiation).
+# Every arm must give what the production arm gives; each test picks the arms that reach its kernels (pick_arms).
+ARMS = {
+    "production": None, "default": None,
+    # the forward pass switched off in favour of the generic routine (one name per test that has such an arm)
+    "generic_passes": D.env_value(D.kDbgNoPackedPasses),
+    "memory_faithful_routine": D.env_value(D.kDbgNoPackedPasses),
+    "generic_nw_full": D.env_value(D.kDbgNoPackedPasses),
+    # the row kinds of the packed passes demoted into each other
+    "ring_through_general": D.env_value(D.kDbgRingToGeneral),
+    "registers_through_ring": D.env_value(D.kDbgRegistersToRing),
+    "registers_through_general": D.env_value(D.kDbgRegistersToGeneral),
+    "moved_band_through_ring": D.env_value(D.kDbgMovedToRing),
+    "many_predecessors_general": D.env_value(D.kDbgManyPredsToGeneral),
+    "everything_general": D.env_value(D.kDbgRingToGeneral, D.kDbgRegistersToGeneral, D.kDbgManyPredsToGeneral),
+    # score rows kept out of HBM, and the rerun of a read whose walk needs one after all
+    "every_row_stores_scores": D.env_value(D.kDbgEveryRowStoresScores),
+    "every_row_stores_scores_registers_through_ring": D.env_value(D.kDbgEveryRowStoresScores, D.kDbgRegistersToRing),
+    "every_row_stores_scores_ring_through_general": D.env_value(D.kDbgEveryRowStoresScores, D.kDbgRingToGeneral),
+    "score_row_rerun_on_every_read": D.env_value(D.kDbgRerunEveryStep),
+    # topological order
+    "full_resort": D.env_value(D.kDbgTopsortFullResort), "serial_full_resort": D.env_value(D.kDbgTopsortFullResort),
+    "cached_full_resort": D.env_value(D.kDbgTopsortCachedFull),
+    "incremental_in_hbm": D.env_value(D.kDbgTopsortIncrHbmOnly),
+    "plain": D.env_value(D.kDbgTopsortFullResort, D.kDbgManyPredsToGeneral),
+    # long reads, consensus
+    "recomputed_traceback": D.env_value(D.kDbgTbNoWideMoves),
+    "single_wave": D.env_value(D.kDbgSingleWaveForward),
+    "consensus_node_by_node": D.env_value(D.kDbgConsensusNodeByNode),
+}
+
+
+def pick_arms(*names):
+    return tuple((name, ARMS[name]) for name in names)
 
 
 def run_gpu(windows, band_mode, max_seq=1024, max_seqs=32, band_width=256, output_type="consensus", nodes=None, mem=8 << 30, **kw):
@@ -325,9 +361,8 @@ def test_long_read_forward_and_traceback_variants_agree(monkeypatch):
     windows.append([r.decode() for r in synthetic.generate_window(9200, 6000, 10, 900, 40, 40)])   # four predecessors and more
     windows.append([r.decode() for r in synthetic.generate_window(9201, 3000, 5, 20, 900, 20)])    # reads much longer than the backbone
     out = {}
-    for name, flag in (("default", None), ("recomputed_traceback", str(1 << 6)), ("single_wave", str(1 << 18)),
-                       ("cached_full_resort", str(1 << 17)), ("serial_full_resort", str(1 << 21)),
-                       ("incremental_in_hbm", str(1 << 16))):
+    for name, flag in pick_arms("default", "recomputed_traceback", "single_wave", "cached_full_resort", "serial_full_resort",
+                                "incremental_in_hbm"):
         if flag is None:
             monkeypatch.delenv("GWHIP_DEBUG", raising=False)
         else:
@@ -438,15 +473,14 @@ def test_kernel_shortcuts_equal_the_plain_schedule(monkeypatch):
             w = [("GATTACA"[: rng.randrange(8)] + r)[rng.randrange(5):] for r in w]
         windows.append([r for r in w if 0 < len(r) < 1024])
     out = {}
-    arms = (("production", None), ("full_resort", str(1 << 21)), ("many_predecessors_general", str(1 << 30)),
-            ("plain", str((1 << 21) | (1 << 30))), ("registers_through_ring", str(1 << 10)), ("moved_band_through_ring", str(1 << 15)),
-            ("ring_through_general", str(1 << 9)), ("registers_through_general", str(1 << 11)),
-            ("everything_general", str((1 << 9) | (1 << 11) | (1 << 30))), ("consensus_node_by_node", str(1 << 4)),
-            # round 5: the production pass keeps the score rows nobody reads out of HBM and reruns a read whose walk needs one
-            # after all (kNwNeedScoreRows); bit 25 stores every row as rounds 1-4 did
-            ("every_row_stores_scores", str(1 << 25)), ("every_row_stores_scores_registers_through_ring", str((1 << 25) | (1 << 10))),
-            # ... and bit 23 sends EVERY read through that rerun (any recomputed step below row 0 ends the first walk)
-            ("score_row_rerun_on_every_read", str(1 << 23)))
+    arms = pick_arms("production", "full_resort", "many_predecessors_general", "plain", "registers_through_ring",
+                     "moved_band_through_ring", "ring_through_general", "registers_through_general", "everything_general",
+                     "consensus_node_by_node",
+                     # round 5: the production pass keeps the score rows nobody reads out of HBM and reruns a read whose walk
+                     # needs one after all (kNwNeedScoreRows); bit 25 stores every row as rounds 1-4 did
+                     "every_row_stores_scores", "every_row_stores_scores_registers_through_ring",
+                     # ... and bit 23 sends EVERY read through that rerun (any recomputed step below row 0 ends the first walk)
+                     "score_row_rerun_on_every_read")
     for name, flag in arms:
         if flag is None:
             monkeypatch.delenv("GWHIP_DEBUG", raising=False)
@@ -481,10 +515,8 @@ def test_two_pass_kernel_shortcuts_equal_the_plain_schedule(monkeypatch, band_wi
             w = [("GATTACA"[: rng.randrange(8)] + r)[rng.randrange(5):] for r in w]
         windows.append([r for r in w if 0 < len(r) < 1024])
     out = {}
-    arms = (("production", None), ("registers_through_ring", str(1 << 10)), ("moved_band_through_ring", str(1 << 15)),
-            ("ring_through_general", str(1 << 9)), ("registers_through_general", str(1 << 11)),
-            ("many_predecessors_general", str(1 << 30)), ("everything_general", str((1 << 9) | (1 << 11) | (1 << 30))),
-            ("generic_passes", str(1 << 8)))
+    arms = pick_arms("production", "registers_through_ring", "moved_band_through_ring", "ring_through_general",
+                     "registers_through_general", "many_predecessors_general", "everything_general", "generic_passes")
     for name, flag in arms:
         if flag is None:
             monkeypatch.delenv("GWHIP_DEBUG", raising=False)
@@ -528,10 +560,8 @@ def test_traceback_buffer_packed_pass_equals_the_memory_faithful_routine(monkeyp
             w = [("GATTACA"[: rng.randrange(8)] + r)[rng.randrange(5):] for r in w]
         windows.append([r for r in w if 0 < len(r) < 1024])
     out = {}
-    arms = (("production", None), ("memory_faithful_routine", str(1 << 8)), ("registers_through_ring", str(1 << 10)),
-            ("moved_band_through_ring", str(1 << 15)), ("ring_through_general", str(1 << 9)),
-            ("registers_through_general", str(1 << 11)), ("many_predecessors_general", str(1 << 30)),
-            ("everything_general", str((1 << 9) | (1 << 11) | (1 << 30))))
+    arms = pick_arms("production", "memory_faithful_routine", "registers_through_ring", "moved_band_through_ring",
+                     "ring_through_general", "registers_through_general", "many_predecessors_general", "everything_general")
     modes = ("static_band_traceback", "adaptive_band_traceback")
     for name, flag in arms:
         if flag is None:
@@ -736,12 +766,11 @@ def test_full_band_packed_pass_equals_the_generic_routine_and_the_oracle(monkeyp
             w.append((w[-1] * (1023 // max(1, len(w[-1])) + 1))[:1023])
         windows.append([r for r in w if 0 < len(r) <= 1024][:32])
     out = {}
-    arms = (("production", None), ("registers_through_ring", str(1 << 10)), ("ring_through_general", str(1 << 9)),
-            ("registers_through_general", str(1 << 11)), ("many_predecessors_general", str(1 << 30)),
-            ("everything_general", str((1 << 9) | (1 << 11) | (1 << 30))), ("generic_nw_full", str(1 << 8)),
-            # the production pass writes a score row to HBM only when somebody will read it back (general rows' predecessors,
-            # rows with undecided cells and their predecessors, sinks): bit 25 stores every row
-            ("every_row_stores_scores", str(1 << 25)), ("every_row_stores_scores_ring_through_general", str((1 << 25) | (1 << 9))))
+    arms = pick_arms("production", "registers_through_ring", "ring_through_general", "registers_through_general",
+                     "many_predecessors_general", "everything_general", "generic_nw_full",
+                     # the production pass writes a score row to HBM only when somebody will read it back (general rows'
+                     # predecessors, rows with undecided cells and their predecessors, sinks): bit 25 stores every row
+                     "every_row_stores_scores", "every_row_stores_scores_ring_through_general")
     for name, flag in arms:
         if flag is None:
             monkeypatch.delenv("GWHIP_DEBUG", raising=False)

@@ -17,11 +17,12 @@ import time
 import pytest
 
 import poa_int16_edge_cases as E
+from genomeworks_amd import debug_flags as D
 
 pytestmark = pytest.mark.gpu
 
 SCORE_CASES, WEIGHT_CASES = E.all_cases()
-GENERAL = str(1 << 8)  # GWHIP_DEBUG: packed passes off
+GENERAL = D.env_value(D.kDbgNoPackedPasses)  # GWHIP_DEBUG: packed passes off
 _GPU = {}
 
 
@@ -110,7 +111,7 @@ def test_msa_output_at_the_edges(case):
 
 # bit 4: the first bundle pass of the LDS consensus routine node by node instead of in chunks of 64 nodes;
 # GWHIP_CONSENSUS_SERIAL=1: the HBM consensus routine (generate_consensus) instead of the LDS one
-WEIGHT_ARMS = SCORE_ARMS + (("bundle_pass_node_by_node", {"GWHIP_DEBUG": str(1 << 4)}), ("hbm_consensus_routine", {"GWHIP_CONSENSUS_SERIAL": "1"}))
+WEIGHT_ARMS = SCORE_ARMS + (("bundle_pass_node_by_node", {"GWHIP_DEBUG": D.env_value(D.kDbgConsensusNodeByNode)}), ("hbm_consensus_routine", {"GWHIP_CONSENSUS_SERIAL": "1"}))
 
 
 @pytest.mark.parametrize("case", WEIGHT_CASES, ids=ids(WEIGHT_CASES))
@@ -157,7 +158,7 @@ def test_both_sides_of_the_upper_edge_are_hit(mode, width, max_seq, match):
     rows = [0, 0]
     try:
         for kind in DESCRIPTOR_KINDS:
-            os.environ["GWHIP_DEBUG"] = str(((kind + 1) << 28) | (1 << 13) | (1 << 12))
+            os.environ["GWHIP_DEBUG"] = D.env_value(D.kDbgKindFine, D.kDbgKindCount, row_kind=kind)
             for w, counters in enumerate(b.profile_phases_per_window()):
                 rows[w] += ((counters["other"] >> 32) & 0xffff) + (counters["other"] >> 48)
     finally:

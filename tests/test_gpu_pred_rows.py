@@ -15,6 +15,7 @@ import pytest
 
 import oracle_poa as O
 import pred_rows_windows as P
+from genomeworks_amd import debug_flags as D
 from test_gpu_poa import oracle_cfg, run_gpu
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +23,7 @@ pytestmark = pytest.mark.gpu
 CONFIGS = tuple((mode, width) for width in (256, 128) for mode in ("static_band", "adaptive_band"))
 # GWHIP_DEBUG (debug instantiation): bit 25 every score row is stored, bit 23 every recomputed step of the walk reruns the
 # forward pass with every row stored -- a predecessor that lost its mark would show as a walk over a row that was never written
-ARMS = (("every_score_row_stored", str(1 << 25)), ("every_recomputed_step_reruns", str(1 << 23)))
+ARMS = (("every_score_row_stored", D.env_value(D.kDbgEveryRowStoresScores)), ("every_recomputed_step_reruns", D.env_value(D.kDbgRerunEveryStep)))
 
 
 @pytest.fixture(scope="module")
@@ -86,7 +87,7 @@ def test_reruns_of_the_forward_pass_equal_the_parents(monkeypatch, windows):
     """GWHIP_DEBUG bit 24 with bit 13 adds 2^40 per rerun (a walk that met a cell it must recompute in a row kept out of HBM) to
     a window's "other" counter, above the clock ticks it otherwise holds: the exact number of reruns over the set, printed and
     equal to the parent's."""
-    monkeypatch.setenv("GWHIP_DEBUG", str((1 << 24) | (1 << 13)))
+    monkeypatch.setenv("GWHIP_DEBUG", D.env_value(D.kDbgCountReruns, D.kDbgKindFine))
     reruns = {}
     for mode, width in CONFIGS:
         b = run_gpu(windows, mode, band_width=width, mem=2 << 30)

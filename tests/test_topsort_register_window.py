@@ -11,6 +11,7 @@ import random
 import pytest
 
 import oracle_poa as O
+from genomeworks_amd import debug_flags as D
 
 BAND = {"full_band": 0, "static_band": 1, "adaptive_band": 2, "static_band_traceback": 3}
 BASES = "ACGT"
@@ -173,7 +174,7 @@ def test_kernel_equals_full_resort_and_oracle(monkeypatch, band_mode, which):
     _, max_seqs, mem = SETS[which]
     monkeypatch.delenv("GWHIP_DEBUG", raising=False)
     prod = _run_gpu(windows, band_mode, max_seqs, mem, min_sources=65 if which == "many_reads" else 0)
-    monkeypatch.setenv("GWHIP_DEBUG", str(1 << 21))
+    monkeypatch.setenv("GWHIP_DEBUG", D.env_value(D.kDbgTopsortFullResort))
     full = _run_gpu(windows, band_mode, max_seqs, mem)
     monkeypatch.delenv("GWHIP_DEBUG", raising=False)
     assert prod == full

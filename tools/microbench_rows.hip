@@ -112,17 +112,17 @@ int main(int argc, char** argv)
                                   "kind 3, four predecessors (rows r-1 .. r-4 from the ring, 255-row passes)"};
     struct Abl { const char* name; int bits; };
     const Abl abl[] = {{"full row", 0},
-                       {"no score-row store", 1 << 26},
-                       {"no move-row store", 1 << 27},
-                       {"no HBM stores", (1 << 26) | (1 << 27)},
-                       {"no ring write", 1 << 20},
-                       {"no guard write", 1 << 19},
-                       {"no LDS writes", (1 << 20) | (1 << 19)},
-                       {"no stores at all", (1 << 26) | (1 << 27) | (1 << 20) | (1 << 19)},
-                       {"no cross-lane scan", 1 << 18},
-                       {"no move bytes", 1 << 17},
-                       {"no stores, no scan, no move bytes", (1 << 26) | (1 << 27) | (1 << 20) | (1 << 19) | (1 << 18) | (1 << 17)},
-                       {"no rows (classification + setup only)", 1 << 16}};
+                       {"no score-row store", kDbgAblNoScoreRowStores},
+                       {"no move-row store", kDbgAblNoMoveRowStores},
+                       {"no HBM stores", kDbgAblNoScoreRowStores | kDbgAblNoMoveRowStores},
+                       {"no ring write", kDbgAblNoRingWrite},
+                       {"no guard write", kDbgAblNoGuard},
+                       {"no LDS writes", kDbgAblNoRingWrite | kDbgAblNoGuard},
+                       {"no stores at all", kDbgAblNoScoreRowStores | kDbgAblNoMoveRowStores | kDbgAblNoRingWrite | kDbgAblNoGuard},
+                       {"no cross-lane scan", kDbgAblNoScan},
+                       {"no move bytes", kDbgAblNoMoveBytes},
+                       {"no stores, no scan, no move bytes", kDbgAblNoScoreRowStores | kDbgAblNoMoveRowStores | kDbgAblNoRingWrite | kDbgAblNoGuard | kDbgAblNoScan | kDbgAblNoMoveBytes},
+                       {"no rows (classification + setup only)", kDbgAblNoRows}};
     std::vector<unsigned long long> h(blocks);
     hipEvent_t e0, e1;
     hipEventCreate(&e0);
@@ -134,9 +134,9 @@ int main(int argc, char** argv)
         {
             // the side table of predecessors 3..5 has one entry per row & 255: a pass of the four-predecessor pattern is 255 rows
             a.graph_count = p == 7 ? 255 : 1400;
-            if (p != 0 && p != 5 && ab.bits != 0 && ab.bits != ((1 << 26) | (1 << 27)) && ab.bits != (1 << 16)) continue; // full ablation table for kind 0 and the mix
+            if (p != 0 && p != 5 && ab.bits != 0 && ab.bits != (kDbgAblNoScoreRowStores | kDbgAblNoMoveRowStores) && ab.bits != kDbgAblNoRows) continue; // full ablation table for kind 0 and the mix
             a.pattern = p;
-            a.dbg     = ab.bits ? (ab.bits | (1 << 14)) : 0; // (bit 14 enables the ablation bits, poa_forward_moves.h)
+            a.dbg     = ab.bits ? (ab.bits | kDbgAblationsOn) : 0; // (the ablations are honoured only with it, poa_forward_moves.h)
             double best_ms = 1e30, cyc = 0;
             for (int it = 0; it < 3; it++)
             {
