@@ -212,6 +212,8 @@ def mapper():
         L.gw_mapper_align_overlaps.argtypes = [vp, i64, vp, vp, i32, u32, vp, vp, i32, u32, i64, vp]
         L.gw_mapper_align_overlaps_scored.restype = vp
         L.gw_mapper_align_overlaps_scored.argtypes = [vp, i64, vp, vp, i32, u32, vp, vp, i32, u32, vp, i64, vp]
+        L.gw_mapper_align_overlaps_scored2.restype = vp
+        L.gw_mapper_align_overlaps_scored2.argtypes = [vp, i64, vp, vp, i32, u32, vp, vp, i32, u32, vp, i64, vp]
         L.gw_mapper_cigars_count.restype = i64
         L.gw_mapper_cigars_count.argtypes = [vp]
         L.gw_mapper_cigars_text_bytes.restype = i64
@@ -285,6 +287,8 @@ def mapper():
         L.gw_mapper_overlap_variants.argtypes = [vp, i64, vp, vp, i32, u32, vp, vp, i32, u32, i32, i32, i64, vp]
         L.gw_mapper_overlap_variants_scored.restype = vp
         L.gw_mapper_overlap_variants_scored.argtypes = [vp, i64, vp, vp, i32, u32, vp, vp, i32, u32, i32, i32, vp, i64, vp]
+        L.gw_mapper_overlap_variants_scored2.restype = vp
+        L.gw_mapper_overlap_variants_scored2.argtypes = [vp, i64, vp, vp, i32, u32, vp, vp, i32, u32, i32, i32, vp, i64, vp]
         L.gw_mapper_variants_count.restype = i64
         L.gw_mapper_variants_count.argtypes = [vp]
         L.gw_mapper_variants_copy.argtypes = [vp, vp, vp]

@@ -48,6 +48,8 @@ def _bind(L):
     L.gw_aligner_stage_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.gw_aligner_create_affine.restype = vp
     L.gw_aligner_create_affine.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, i32, C.c_int64]
+    L.gw_aligner_create_affine2.restype = vp
+    L.gw_aligner_create_affine2.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, C.c_int64]
     L.gw_alignment_cost.argtypes = [vp, i32]
     L.gw_aligner_create_algorithm.restype = vp
     L.gw_aligner_create_algorithm.argtypes = [C.c_char_p, i32, i32, i32, vp, i32, C.c_int64]
@@ -108,13 +110,23 @@ class CudaAlignerBatch:
 
     def __init__(self, max_query_length=None, max_target_length=None, max_alignments=None, alignment_type="global",
                  stream=None, device_id=0, max_device_memory_allocator_caching_size=-1, max_bandwidth=None,
-                 algorithm=None, mismatch=None, gap_open=None, gap_extend=None, band_width=None):
+                 algorithm=None, mismatch=None, gap_open=None, gap_extend=None, band_width=None, gap_open2=None,
+                 gap_extend2=None):
         """algorithm (not in pygenomeworks): one of the reference's non-public aligner classes that its C++ tests and
         benchmarks construct directly -- "hirschberg_myers" (the default), "ukkonen", "myers" -- or "affine": global
         alignment under the costs mismatch (4), gap_open (6), gap_extend (2) -- minimised, a gap run of L columns costs
-        gap_open + L * gap_extend -- within band_width (128) diagonals on either side of the corners' diagonals."""
+        gap_open + L * gap_extend -- within band_width (128) diagonals on either side of the corners' diagonals. With
+        gap_open2 and gap_extend2 (both, or neither) the gap costs are two-piece, min(gap_open + L * gap_extend,
+        gap_open2 + L * gap_extend2), and what is left out of (mismatch, gap_open, gap_extend, gap_open2, gap_extend2)
+        is taken from (6, 4, 3, 24, 2)."""
         self._L = _bind(_native.host())
         scoring = dict(mismatch=mismatch, gap_open=gap_open, gap_extend=gap_extend, band_width=band_width)
+        second = dict(gap_open2=gap_open2, gap_extend2=gap_extend2)
+        given = [k for k, v in second.items() if v is not None]
+        if algorithm != "affine" and given:
+            raise RuntimeError("%s: only algorithm=\"affine\" takes these" % ", ".join(given))
+        if len(given) == 1:
+            raise RuntimeError("%s without %s: two-piece gap costs take both" % (given[0], (set(second) - set(given)).pop()))
         if algorithm != "affine" and any(v is not None for v in scoring.values()):
             raise RuntimeError("%s: only algorithm=\"affine\" takes these" % ", ".join(k for k, v in scoring.items() if v is not None))
         if alignment_type not in _ALIGNMENT_TYPES:
@@ -133,6 +145,11 @@ class CudaAlignerBatch:
         elif max_bandwidth is not None:
             self._h = self._L.gw_aligner_create_banded(int(max_bandwidth), st, device_id,
                                                        int(max_device_memory_allocator_caching_size))
+        elif algorithm == "affine" and given:
+            x, o, e, b = (d if v is None else int(v) for v, d in zip(scoring.values(), (6, 4, 3, 128)))
+            self._h = self._L.gw_aligner_create_affine2(int(max_query_length), int(max_target_length), int(max_alignments),
+                                                        x, o, e, int(gap_open2), int(gap_extend2), b, st, device_id,
+                                                        int(max_device_memory_allocator_caching_size))
         elif algorithm == "affine":
             x, o, e, b = (d if v is None else int(v) for v, d in zip(scoring.values(), (4, 6, 2, 128)))
             self._h = self._L.gw_aligner_create_affine(int(max_query_length), int(max_target_length), int(max_alignments),

@@ -377,23 +377,35 @@ def align_bytes_needed_scored(query_length, target_length, band):
 
 def _scoring_args(scoring):
     """scoring of align_overlaps / overlap_variants as the C API takes it: None, or four int32 (mismatch, gap_open,
-    gap_extend, band) from a 4-tuple or a dict with these keys (a dict may leave out any: 4, 6, 2, 128)."""
+    gap_extend, band) from a 4-tuple or a dict with these keys (a dict may leave out any: 4, 6, 2, 128), or, for
+    two-piece gap costs, six int32 (mismatch, gap_open, gap_extend, gap_open2, gap_extend2, band) from a 6-tuple or a
+    dict that has both gap_open2 and gap_extend2 (what such a dict leaves out: 6, 4, 3, 24, 2, 128)."""
     if scoring is None:
         return None
     if isinstance(scoring, dict):
-        unknown = set(scoring) - {"mismatch", "gap_open", "gap_extend", "band"}
+        unknown = set(scoring) - {"mismatch", "gap_open", "gap_extend", "gap_open2", "gap_extend2", "band"}
         if unknown:
             raise ValueError("scoring: unknown keys %s" % sorted(unknown))
-        values = [scoring.get("mismatch", 4), scoring.get("gap_open", 6), scoring.get("gap_extend", 2), scoring.get("band", 128)]
+        if ("gap_open2" in scoring) != ("gap_extend2" in scoring):
+            raise ValueError("scoring: gap_open2 and gap_extend2 go together")
+        if "gap_open2" in scoring:
+            values = [scoring.get("mismatch", 6), scoring.get("gap_open", 4), scoring.get("gap_extend", 3),
+                      scoring["gap_open2"], scoring["gap_extend2"], scoring.get("band", 128)]
+        else:
+            values = [scoring.get("mismatch", 4), scoring.get("gap_open", 6), scoring.get("gap_extend", 2), scoring.get("band", 128)]
     else:
         values = list(scoring)
-        if len(values) != 4:
-            raise ValueError("scoring: a dict or (mismatch, gap_open, gap_extend, band)")
-    x, o, e, b = (int(v) for v in values)
+        if len(values) not in (4, 6):
+            raise ValueError("scoring: a dict, (mismatch, gap_open, gap_extend, band) or "
+                             "(mismatch, gap_open, gap_extend, gap_open2, gap_extend2, band)")
+    values = [int(v) for v in values]
+    x, o, e, b = values[0], values[1], values[2], values[-1]
     if not (1 <= x <= 255 and 0 <= o <= 255 and 1 <= e <= 255 and 0 <= b < 2 ** 31):
         raise ValueError("scoring (mismatch %d, gap_open %d, gap_extend %d, band %d) outside 1..255, 0..255, 1..255, >= 0"
                          % (x, o, e, b))
-    return np.array([x, o, e, b], np.int32)
+    if len(values) == 6 and not (0 <= values[3] <= 255 and 1 <= values[4] <= 255):
+        raise ValueError("scoring (gap_open2 %d, gap_extend2 %d) outside 0..255, 1..255" % (values[3], values[4]))
+    return np.array(values, np.int32)
 
 
 def align_overlaps(overlaps, query_reads, target_reads=None, first_query_read_id=0, first_target_read_id=0,
@@ -411,7 +423,10 @@ def align_overlaps(overlaps, query_reads, target_reads=None, first_query_read_id
     scoring: None, or (mismatch, gap_open, gap_extend, band) as a 4-tuple or a dict -- the slices are then aligned under
     affine gap costs inside a diagonal band (include/gwhip_affine.h) instead; the edit
     distances stay the columns that are not a match, an overlap whose band |m - n| + 2 band + 1 exceeds 2048 diagonals has
-    an empty CIGAR and -1, and values out of range raise ValueError before anything is launched."""
+    an empty CIGAR and -1, and values out of range raise ValueError before anything is launched. A 6-tuple (mismatch,
+    gap_open, gap_extend, gap_open2, gap_extend2, band), or a dict with gap_open2 and gap_extend2, asks for two-piece gap
+    costs, min(gap_open + L gap_extend, gap_open2 + L gap_extend2) for a run of L columns (INTEGRATION.md section 3p);
+    the capacity is then 1024 diagonals."""
     sc = _scoring_args(scoring)
     L = _native.mapper()
     o = np.ascontiguousarray(overlaps, OVERLAP)
@@ -420,8 +435,9 @@ def align_overlaps(overlaps, query_reads, target_reads=None, first_query_read_id
         h = L.gw_mapper_align_overlaps(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id,
                                        int(max_device_bytes), _stream(stream))
     else:
-        h = L.gw_mapper_align_overlaps_scored(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id, _p(sc),
-                                              int(max_device_bytes), _stream(stream))
+        scored = L.gw_mapper_align_overlaps_scored if len(sc) == 4 else L.gw_mapper_align_overlaps_scored2
+        h = scored(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id, _p(sc), int(max_device_bytes),
+                   _stream(stream))
     if not h:
         raise _err(L)
     try:
@@ -853,9 +869,9 @@ def overlap_variants(overlaps, query_reads, target_reads=None, min_count=3, min_
         h = L.gw_mapper_overlap_variants(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id, int(min_count),
                                          int(min_percent), int(max_device_bytes), _stream(stream))
     else:
-        h = L.gw_mapper_overlap_variants_scored(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id,
-                                                int(min_count), int(min_percent), _p(sc), int(max_device_bytes),
-                                                _stream(stream))
+        scored = L.gw_mapper_overlap_variants_scored if len(sc) == 4 else L.gw_mapper_overlap_variants_scored2
+        h = scored(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id, int(min_count), int(min_percent),
+                   _p(sc), int(max_device_bytes), _stream(stream))
     if not h:
         raise _err(L)
     try:

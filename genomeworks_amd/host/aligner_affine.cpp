@@ -29,16 +29,54 @@ AffineScoring checked(AffineScoring s, int32_t band_width)
     if (band_width < 0) throw std::invalid_argument("band_width must be non-negative.");
     return s;
 }
+
+TwoPieceScoring checked(TwoPieceScoring s, int32_t band_width)
+{
+    checked(AffineScoring{s.mismatch, s.gap_open, s.gap_extend}, band_width);
+    if (s.gap_open2 < 0 || s.gap_open2 > 255 || s.gap_extend2 < 1 || s.gap_extend2 > 255)
+        throw std::invalid_argument("affine scoring (gap_open2 " + std::to_string(s.gap_open2) + ", gap_extend2 " +
+                                    std::to_string(s.gap_extend2) + ") outside 0..255, 1..255");
+    return s;
+}
+
+// the allocator of max_device_memory bytes (-1: the largest free section of the device, written back)
+DefaultDeviceAllocator caching_allocator(cudaStream_t stream, int64_t* max_device_memory)
+{
+    if (*max_device_memory < -1) throw std::invalid_argument("max_device_memory has to be either -1 (=all available GPU memory) or greater or equal than 0.");
+    if (*max_device_memory == -1)
+    {
+        *max_device_memory = cudautils::find_largest_contiguous_device_memory_section();
+        if (*max_device_memory == 0) throw std::runtime_error("No memory available for caching");
+    }
+    return DefaultDeviceAllocator(static_cast<size_t>(*max_device_memory), stream);
+}
 } // namespace
 
 AlignerGlobalAffine::AlignerGlobalAffine(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments,
                                          AffineScoring scoring, int32_t band_width, int64_t max_device_memory,
                                          DefaultDeviceAllocator allocator, cudaStream_t stream, int32_t device_id)
     : FixedLimitAligner(AlignmentType::global_alignment, max_query_length, max_target_length, max_alignments, allocator, stream, device_id)
-    , scoring_(checked(scoring, band_width))
+    , scoring_{checked(scoring, band_width).mismatch, scoring.gap_open, scoring.gap_extend, 0, 0}
+    , two_piece_(false)
     , band_width_(band_width)
     , max_device_memory_(max_device_memory < 0 ? get_size_of_largest_free_memory_block(allocator) : max_device_memory)
 {
+}
+
+AlignerGlobalAffine::AlignerGlobalAffine(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments,
+                                         TwoPieceScoring scoring, int32_t band_width, int64_t max_device_memory,
+                                         DefaultDeviceAllocator allocator, cudaStream_t stream, int32_t device_id)
+    : FixedLimitAligner(AlignmentType::global_alignment, max_query_length, max_target_length, max_alignments, allocator, stream, device_id)
+    , scoring_(checked(scoring, band_width))
+    , two_piece_(true)
+    , band_width_(band_width)
+    , max_device_memory_(max_device_memory < 0 ? get_size_of_largest_free_memory_block(allocator) : max_device_memory)
+{
+}
+
+size_t AlignerGlobalAffine::workspace_bytes(int32_t pairs, const int64_t* starts) const
+{
+    return two_piece_ ? gwhip_affine2_workspace_bytes(pairs, starts, band_width_) : gwhip_affine_workspace_bytes(pairs, starts, band_width_);
 }
 
 AlignerGlobalAffine::~AlignerGlobalAffine()
@@ -77,7 +115,7 @@ StatusType AlignerGlobalAffine::add_alignment(const char* query, int32_t query_l
         num_alignments() < max_alignments_)
     {
         const int64_t starts[3] = {0, query_length, static_cast<int64_t>(query_length) + target_length};
-        pair_bits               = static_cast<int64_t>(gwhip_affine_workspace_bytes(1, starts, band_width_)) - 256; // without the offsets
+        pair_bits               = static_cast<int64_t>(workspace_bytes(1, starts)) - 256; // without the offsets
         if (device_bytes(num_alignments() + 1, seq_starts_h_.back() + starts[2], bit_bytes_ + pair_bits) > max_device_memory_)
         {
             GW_LOG_DEBUG("The batch's device buffers would exceed the memory given to the aligner.");
@@ -110,7 +148,7 @@ StatusType AlignerGlobalAffine::align_all()
     free_device();
     const size_t un      = static_cast<size_t>(n);
     const int64_t total  = seq_starts_h_.back();
-    const size_t ws_size = gwhip_affine_workspace_bytes(n, seq_starts_h_.data(), band_width_);
+    const size_t ws_size = workspace_bytes(n, seq_starts_h_.data());
     gwhost::BlockLayout layout;
     const auto seq       = layout.take<char>(static_cast<size_t>(total) + 16);
     const auto starts    = layout.take<int64_t>(2 * un + 1);
@@ -140,7 +178,29 @@ StatusType AlignerGlobalAffine::align_all()
     a.workspace            = workspace.in(device_block_);
     a.workspace_bytes      = ws_size;
     void* const events[3]  = {events_[0], events_[1], events_[2]};
-    if (gwhip_affine_align_events(&a, stream_, events) != 0) throw std::runtime_error(gwhip_affine_last_error());
+    if (two_piece_)
+    {
+        gwhip_affine2_args b{};
+        b.n_alignments         = n;
+        b.sequences            = a.sequences;
+        b.sequence_starts      = a.sequence_starts;
+        b.sequence_starts_host = a.sequence_starts_host;
+        b.mismatch             = scoring_.mismatch;
+        b.gap_open             = scoring_.gap_open;
+        b.gap_extend           = scoring_.gap_extend;
+        b.gap_open2            = scoring_.gap_open2;
+        b.gap_extend2          = scoring_.gap_extend2;
+        b.band                 = band_width_;
+        b.results              = a.results;
+        b.result_lengths       = a.result_lengths;
+        b.costs                = a.costs;
+        b.optimal              = a.optimal;
+        b.workspace            = a.workspace;
+        b.workspace_bytes      = ws_size;
+        if (gwhip_affine2_align_events(&b, stream_, events) != 0) throw std::runtime_error(gwhip_affine_last_error());
+    }
+    else if (gwhip_affine_align_events(&a, stream_, events) != 0)
+        throw std::runtime_error(gwhip_affine_last_error());
     results_h_.resize(static_cast<size_t>(total) + 16);
     result_lengths_h_.resize(un);
     costs_h_.resize(un);
@@ -164,7 +224,7 @@ StatusType AlignerGlobalAffine::sync_alignments()
     {
         const int64_t slot = seq_starts_h_[2 * i + 2] - seq_starts_h_[2 * i];
         const int32_t len  = result_lengths_h_[i];
-        if (costs_h_[i] < 0) continue; // no result (a band of more than 2048 diagonals): the status stays uninitialized
+        if (costs_h_[i] < 0) continue; // no result (a band of more diagonals than the kernels take): the status stays uninitialized
         if (len < 0 || len > slot)
             throw std::runtime_error("affine alignment " + std::to_string(i) + ": the kernels report " + std::to_string(len) +
                                      " columns for a slot of " + std::to_string(slot));
@@ -200,13 +260,26 @@ std::unique_ptr<Aligner> create_aligner_affine(int32_t max_query_length, int32_t
 {
     checked(scoring, band_width); // before the device is touched
     scoped_device_switch device(device_id);
-    if (max_device_memory < -1) throw std::invalid_argument("max_device_memory has to be either -1 (=all available GPU memory) or greater or equal than 0.");
-    if (max_device_memory == -1)
-    {
-        max_device_memory = cudautils::find_largest_contiguous_device_memory_section();
-        if (max_device_memory == 0) throw std::runtime_error("No memory available for caching");
-    }
-    DefaultDeviceAllocator allocator(static_cast<size_t>(max_device_memory), stream);
+    const DefaultDeviceAllocator allocator = caching_allocator(stream, &max_device_memory);
+    return std::make_unique<AlignerGlobalAffine>(max_query_length, max_target_length, max_alignments, scoring, band_width, max_device_memory,
+                                                 allocator, stream, device_id);
+}
+
+std::unique_ptr<Aligner> create_aligner_affine(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments,
+                                               TwoPieceScoring scoring, int32_t band_width, DefaultDeviceAllocator allocator,
+                                               cudaStream_t stream, int32_t device_id)
+{
+    return std::make_unique<AlignerGlobalAffine>(max_query_length, max_target_length, max_alignments, scoring, band_width, int64_t(-1), allocator,
+                                                 stream, device_id);
+}
+
+std::unique_ptr<Aligner> create_aligner_affine(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments,
+                                               TwoPieceScoring scoring, int32_t band_width, cudaStream_t stream, int32_t device_id,
+                                               int64_t max_device_memory)
+{
+    checked(scoring, band_width); // before the device is touched
+    scoped_device_switch device(device_id);
+    const DefaultDeviceAllocator allocator = caching_allocator(stream, &max_device_memory);
     return std::make_unique<AlignerGlobalAffine>(max_query_length, max_target_length, max_alignments, scoring, band_width, max_device_memory,
                                                  allocator, stream, device_id);
 }

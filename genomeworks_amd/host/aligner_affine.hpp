@@ -33,6 +33,10 @@ public:
     AlignerGlobalAffine(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments, AffineScoring scoring,
                         int32_t band_width, int64_t max_device_memory, DefaultDeviceAllocator allocator, cudaStream_t stream,
                         int32_t device_id);
+    /// the same under two-piece gap costs (gwhip_affine2_align)
+    AlignerGlobalAffine(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments, TwoPieceScoring scoring,
+                        int32_t band_width, int64_t max_device_memory, DefaultDeviceAllocator allocator, cudaStream_t stream,
+                        int32_t device_id);
     ~AlignerGlobalAffine() override;
 
     StatusType add_alignment(const char* query, int32_t query_length, const char* target, int32_t target_length,
@@ -48,7 +52,10 @@ private:
     void free_device() override;
     int64_t device_bytes(int64_t pairs, int64_t bases, int64_t bit_bytes) const;
 
-    AffineScoring scoring_;
+    size_t workspace_bytes(int32_t pairs, const int64_t* starts) const;
+
+    TwoPieceScoring scoring_; ///< the second piece is read only when two_piece_
+    bool two_piece_;
     int32_t band_width_;
     int64_t max_device_memory_;
     int64_t bit_bytes_ = 0; ///< of the queued pairs' bit matrices

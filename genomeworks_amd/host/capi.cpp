@@ -440,6 +440,19 @@ gw_aligner* gw_aligner_create_affine(int32_t max_query_length, int32_t max_targe
     GW_CATCH(nullptr)
 }
 
+gw_aligner* gw_aligner_create_affine2(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments, int32_t mismatch,
+                                      int32_t gap_open, int32_t gap_extend, int32_t gap_open2, int32_t gap_extend2, int32_t band_width,
+                                      void* stream, int32_t device_id, int64_t max_device_memory)
+{
+    GW_TRY
+    auto h     = std::make_unique<gw_aligner>();
+    h->aligner = aln::create_aligner_affine(max_query_length, max_target_length, max_alignments,
+                                            aln::TwoPieceScoring{mismatch, gap_open, gap_extend, gap_open2, gap_extend2}, band_width,
+                                            static_cast<cudaStream_t>(stream), device_id, max_device_memory);
+    return h.release();
+    GW_CATCH(nullptr)
+}
+
 gw_aligner* gw_aligner_create_algorithm(const char* algorithm, int32_t max_query_length, int32_t max_target_length,
                                         int32_t max_alignments, void* stream, int32_t device_id, int64_t max_device_memory)
 {

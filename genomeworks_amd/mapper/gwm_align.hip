@@ -2,8 +2,8 @@
 // (include/gwhip_mapper.h, gwm_align_overlaps). Per chunk of consecutive overlaps (the loop of gwm_align_chunks.hpp): a
 // gather kernel cuts the query and target slices out of the resident read sets into the layout the default aligner
 // takes (the target slice reverse-complemented with the aligner's table on '-'), gwhip_hirschberg_myers of libgwhip.so
-// aligns them as it stands (or, for a call with a scoring, gwhip_affine_align of libgwaffine.so, into the same
-// buffers), and the CIGAR writer here, the loop's consumer, turns the per-column states into the text
+// aligns them as it stands (or, for a call with a scoring, gwhip_affine_align or gwhip_affine2_align of libgwaffine.so,
+// into the same buffers), and the CIGAR writer here, the loop's consumer, turns the per-column states into the text
 // of Alignment::convert_to_cigar() and the edit distance. Neither
 // the bases nor the states cross to the host; the overlap records (36 B each) are read there to size the chunks.
 //
@@ -198,9 +198,10 @@ namespace gwm
 {
 
 void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, const ReadSet& q, const ReadSet& t,
-                  int64_t max_device_bytes, const gwm_scoring* scoring, hipStream_t s, float* stage_ms,
+                  int64_t max_device_bytes, const Scoring& scoring, hipStream_t s, float* stage_ms,
                   const std::function<void(const AlignedChunk&)>& consume)
 {
+    const gwm_scoring2& sc = scoring.costs;
     const std::string who = std::string(name) + ": ";
     check_scoring(who, scoring);
     {
@@ -243,9 +244,9 @@ void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, cons
     // the aligner's workspace for overlaps [first, first + m); the affine aligner's costs and flags are counted with it
     auto workspace_bytes = [&](int64_t first, int64_t m) -> size_t {
         const int64_t* hs = host_starts.data() + 2 * first;
-        if (scoring == nullptr)
+        if (scoring.pieces == 0)
             return gwhip_hirschberg_myers_workspace_bytes(static_cast<int32_t>(m), hs, capacity);
-        return gwhip_affine_workspace_bytes(static_cast<int32_t>(m), hs, scoring->band) + static_cast<size_t>(m) * 5 + 256;
+        return gwhip_affine_workspace_bytes(static_cast<int32_t>(m), hs, sc.band) + static_cast<size_t>(m) * 5 + 256;
     };
     auto cost = [&](int64_t first, int64_t m) {
         const int64_t* hs = host_starts.data() + 2 * first;
@@ -301,7 +302,7 @@ void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, cons
         gather_kernel<<<static_cast<unsigned>(2 * m), kThreads, 0, s>>>(o, q, t, starts.p, sequences.p);
         GWM_CHECK(hipGetLastError());
         ev.record(1, s);
-        if (scoring == nullptr)
+        if (scoring.pieces == 0)
         {
             gwhip_hirschberg_args a{};
             a.n_alignments     = static_cast<int32_t>(m);
@@ -322,23 +323,40 @@ void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, cons
         else
         {
             // costs and flags, which no consumer reads, lie behind the aligner's own workspace
-            const size_t own = gwhip_affine_workspace_bytes(static_cast<int32_t>(m), hs, scoring->band);
-            gwhip_affine_args a{};
-            a.n_alignments         = static_cast<int32_t>(m);
-            a.sequences            = reinterpret_cast<const char*>(sequences.p);
-            a.sequence_starts      = starts.p;
-            a.sequence_starts_host = hs;
-            a.mismatch             = scoring->mismatch;
-            a.gap_open             = scoring->gap_open;
-            a.gap_extend           = scoring->gap_extend;
-            a.band                 = scoring->band;
-            a.results              = reinterpret_cast<int8_t*>(results.p);
-            a.result_lengths       = result_lengths.p;
-            a.costs                = reinterpret_cast<int32_t*>(workspace.p + ((own + 255) & ~size_t(255)));
-            a.optimal              = reinterpret_cast<uint8_t*>(a.costs + m);
-            a.workspace            = workspace.p;
-            a.workspace_bytes      = own;
-            if (gwhip_affine_align(&a, s) != 0)
+            const size_t own = gwhip_affine_workspace_bytes(static_cast<int32_t>(m), hs, sc.band);
+            // both argument structs, field by field
+            auto fill = [&](auto& a) {
+                a.n_alignments         = static_cast<int32_t>(m);
+                a.sequences            = reinterpret_cast<const char*>(sequences.p);
+                a.sequence_starts      = starts.p;
+                a.sequence_starts_host = hs;
+                a.mismatch             = sc.mismatch;
+                a.gap_open             = sc.gap_open;
+                a.gap_extend           = sc.gap_extend;
+                a.band                 = sc.band;
+                a.results              = reinterpret_cast<int8_t*>(results.p);
+                a.result_lengths       = result_lengths.p;
+                a.costs                = reinterpret_cast<int32_t*>(workspace.p + ((own + 255) & ~size_t(255)));
+                a.optimal              = reinterpret_cast<uint8_t*>(a.costs + m);
+                a.workspace            = workspace.p;
+                a.workspace_bytes      = own;
+            };
+            int status = 0;
+            if (scoring.pieces == 1)
+            {
+                gwhip_affine_args a{};
+                fill(a);
+                status = gwhip_affine_align(&a, s);
+            }
+            else
+            {
+                gwhip_affine2_args a{};
+                fill(a);
+                a.gap_open2   = sc.gap_open2;
+                a.gap_extend2 = sc.gap_extend2;
+                status        = gwhip_affine2_align(&a, s);
+            }
+            if (status != 0)
                 throw std::runtime_error(who + gwhip_affine_last_error());
         }
         ev.record(2, s);
@@ -352,6 +370,16 @@ void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, cons
 }
 
 } // namespace gwm
+
+namespace
+{
+
+int align_overlaps(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                   int32_t n_queries, uint32_t first_query_read_id, const char* target_bases, const int64_t* target_offsets,
+                   int32_t n_targets, uint32_t first_target_read_id, const gwm::Scoring& scoring, int64_t max_device_bytes,
+                   void* stream, gwm_cigars* out);
+
+} // namespace
 
 extern "C" {
 
@@ -386,10 +414,33 @@ int gwm_align_overlaps(const gwm_overlap* overlaps, int64_t n, const char* query
                                      target_offsets, n_targets, first_target_read_id, nullptr, max_device_bytes, stream, out);
 }
 
+int gwm_align_overlaps_scored2(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                               int32_t n_queries, uint32_t first_query_read_id, const char* target_bases,
+                               const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
+                               const gwm_scoring2* scoring, int64_t max_device_bytes, void* stream, gwm_cigars* out)
+{
+    return align_overlaps(overlaps, n, query_bases, query_offsets, n_queries, first_query_read_id, target_bases, target_offsets,
+                          n_targets, first_target_read_id, gwm::scoring_of(scoring), max_device_bytes, stream, out);
+}
+
 int gwm_align_overlaps_scored(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
                               int32_t n_queries, uint32_t first_query_read_id, const char* target_bases,
                               const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
                               const gwm_scoring* scoring, int64_t max_device_bytes, void* stream, gwm_cigars* out)
+{
+    return align_overlaps(overlaps, n, query_bases, query_offsets, n_queries, first_query_read_id, target_bases, target_offsets,
+                          n_targets, first_target_read_id, gwm::scoring_of(scoring), max_device_bytes, stream, out);
+}
+
+} // extern "C"
+
+namespace
+{
+
+int align_overlaps(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                   int32_t n_queries, uint32_t first_query_read_id, const char* target_bases, const int64_t* target_offsets,
+                   int32_t n_targets, uint32_t first_target_read_id, const gwm::Scoring& scoring, int64_t max_device_bytes,
+                   void* stream, gwm_cigars* out)
 {
     *out = gwm_cigars{};
     try
@@ -439,4 +490,4 @@ int gwm_align_overlaps_scored(const gwm_overlap* overlaps, int64_t n, const char
     }
 }
 
-} // extern "C"
+} // namespace

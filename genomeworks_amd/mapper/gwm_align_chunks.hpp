@@ -1,8 +1,8 @@
 // gwm_align_chunks.hpp -- the chunk loop that gwm_align_overlaps (gwm_align.hip), gwm_window_segments
 // (gwm_segments.hip), gwm_overlap_pileup (gwm_pileup.hip) and gwm_overlap_variants (gwm_variants.hip) share:
 // validation of the overlap records, sizing on the host, and per chunk of consecutive overlaps the gather of the
-// slices, the aligner (gwhip_hirschberg_myers of libgwhip.so, or gwhip_affine_align of libgwaffine.so when the call
-// names a scoring) and the per-chunk buffers. What is done with the chunk's alignment
+// slices, the aligner (gwhip_hirschberg_myers of libgwhip.so, or gwhip_affine_align / gwhip_affine2_align of
+// libgwaffine.so when the call names a scoring) and the per-chunk buffers. What is done with the chunk's alignment
 // states is the caller's: align_chunks() hands them to a consumer while they are on the device. The loop and its
 // kernels are defined once, in gwm_align.hip. Here as well: the check of the arguments every such entry point takes,
 // and ChunkedOutput, the bookkeeping of a consumer that writes a variable number of items per alignment (CIGAR bytes,
@@ -34,6 +34,22 @@ struct AlignedChunk
     const int32_t* result_lengths;
 };
 
+// How a call's slices are aligned. pieces 0: unit costs, the default aligner. pieces 1 / 2: the affine-gap aligner
+// (include/gwhip_affine.h) under one-piece / two-piece gap costs inside `costs.band`; with one piece gap_open2 and
+// gap_extend2 are not read.
+struct Scoring
+{
+    int32_t pieces = 0;
+    gwm_scoring2 costs{};
+};
+
+inline Scoring scoring_of(const gwm_scoring* s)
+{
+    return s == nullptr ? Scoring{} : Scoring{1, gwm_scoring2{s->mismatch, s->gap_open, s->gap_extend, 0, 0, s->band}};
+}
+
+inline Scoring scoring_of(const gwm_scoring2* s) { return s == nullptr ? Scoring{} : Scoring{2, *s}; }
+
 // Aligns device overlaps[0..n) of the device read sets q and t chunk by chunk, as include/gwhip_mapper.h states it for
 // gwm_align_overlaps, and calls consume(chunk) for every chunk while its states are on the device. stage_ms[0..2] +=
 // the device time (HIP events) of gather, align and the consumer, summed over the chunks. `name` opens the error
@@ -44,11 +60,11 @@ struct AlignedChunk
 // CIGAR text or the segment records of the chunks before, records beyond two bytes per column, which takes windows
 // of fewer than 12 bases, the counters of a pileup, 24 B per base of the owner set, and the insertion-run records of the
 // variant caller, 24 B each) lies outside it.
-// scoring == nullptr: unit costs, the default aligner. Otherwise the affine-gap aligner (include/gwhip_affine.h) under
-// these costs and this band writes the same results / result_lengths buffers, and its workspace is what the budget
-// counts; a scoring out of range is refused before anything is launched.
+// With a scoring of one or two pieces the affine-gap aligner writes the same results / result_lengths buffers, and
+// gwhip_affine_workspace_bytes is what the budget counts for both (the two-piece aligner never needs more); a scoring
+// out of range is refused before anything is launched.
 void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, const ReadSet& q, const ReadSet& t,
-                  int64_t max_device_bytes, const gwm_scoring* scoring, hipStream_t s, float* stage_ms,
+                  int64_t max_device_bytes, const Scoring& scoring, hipStream_t s, float* stage_ms,
                   const std::function<void(const AlignedChunk&)>& consume);
 
 } // namespace gwm
@@ -72,17 +88,20 @@ inline void check_chunk_arguments(const std::string& who, int32_t n_queries, int
         throw std::invalid_argument(who + ": 2^31 overlaps or more");
 }
 
-// a scoring (nullptr: unit costs) outside the ranges of include/gwhip_affine.h; `who` opens the text
-inline void check_scoring(const std::string& who, const gwm_scoring* scoring)
+// a scoring outside the ranges of include/gwhip_affine.h; `who` opens the text
+inline void check_scoring(const std::string& who, const gwm::Scoring& scoring)
 {
-    if (scoring == nullptr)
+    const gwm_scoring2& c = scoring.costs;
+    if (scoring.pieces == 0)
         return;
-    if (scoring->mismatch < 1 || scoring->mismatch > 255 || scoring->gap_open < 0 || scoring->gap_open > 255 ||
-        scoring->gap_extend < 1 || scoring->gap_extend > 255 || scoring->band < 0)
-        throw std::invalid_argument(who + "scoring (mismatch " + std::to_string(scoring->mismatch) + ", gap_open " +
-                                    std::to_string(scoring->gap_open) + ", gap_extend " +
-                                    std::to_string(scoring->gap_extend) + ", band " + std::to_string(scoring->band) +
-                                    ") outside 1..255, 0..255, 1..255, >= 0");
+    if (c.mismatch < 1 || c.mismatch > 255 || c.gap_open < 0 || c.gap_open > 255 || c.gap_extend < 1 || c.gap_extend > 255 ||
+        c.band < 0)
+        throw std::invalid_argument(who + "scoring (mismatch " + std::to_string(c.mismatch) + ", gap_open " +
+                                    std::to_string(c.gap_open) + ", gap_extend " + std::to_string(c.gap_extend) + ", band " +
+                                    std::to_string(c.band) + ") outside 1..255, 0..255, 1..255, >= 0");
+    if (scoring.pieces == 2 && (c.gap_open2 < 0 || c.gap_open2 > 255 || c.gap_extend2 < 1 || c.gap_extend2 > 255))
+        throw std::invalid_argument(who + "scoring (gap_open2 " + std::to_string(c.gap_open2) + ", gap_extend2 " +
+                                    std::to_string(c.gap_extend2) + ") outside 0..255, 1..255");
 }
 
 inline void exclusive_sum(const int64_t* in, int64_t* out, int64_t n, Temp& t, hipStream_t s)

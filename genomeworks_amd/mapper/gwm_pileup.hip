@@ -38,7 +38,7 @@ int gwm_overlap_pileup(const gwm_overlap* overlaps, int64_t n, const char* query
         const ReadSet q = read_set(query_bases, query_offsets, n_queries, first_query_read_id);
         const ReadSet t = read_set(target_bases, target_offsets, n_targets, first_target_read_id);
         if (n > 0)
-            gwm::align_chunks("gwm_overlap_pileup", overlaps, n, q, t, max_device_bytes, nullptr, s, out->stage_ms,
+            gwm::align_chunks("gwm_overlap_pileup", overlaps, n, q, t, max_device_bytes, gwm::Scoring{}, s, out->stage_ms,
                               [&](const AlignedChunk& c) { add_role<false>(c, q, t, n_bases, counts.p, s); });
         GWM_CHECK(hipStreamSynchronize(s));
         out->n_bases = n_bases;
@@ -65,7 +65,7 @@ int gwm_pair_pileup(const gwm_overlap* pairs, int64_t n, const char* bases, cons
         const int64_t n_bases = zeroed_counts(offsets, n_reads, s, counts);
         const ReadSet r = read_set(bases, offsets, n_reads, first_read_id);
         if (n > 0)
-            gwm::align_chunks("gwm_pair_pileup", pairs, n, r, r, max_device_bytes, nullptr, s, out->stage_ms,
+            gwm::align_chunks("gwm_pair_pileup", pairs, n, r, r, max_device_bytes, gwm::Scoring{}, s, out->stage_ms,
                               [&](const AlignedChunk& c) {
                                   add_role<false>(c, r, r, n_bases, counts.p, s);
                                   add_role<true>(c, r, r, n_bases, counts.p, s);

@@ -215,7 +215,7 @@ int gwm_window_segments(const gwm_overlap* overlaps, int64_t n, const char* quer
         Temp temp;
         gwm::align_chunks("gwm_window_segments", overlaps, n,
                           read_set(query_bases, query_offsets, n_queries, first_query_read_id),
-                          read_set(target_bases, target_offsets, n_targets, first_target_read_id), max_device_bytes, nullptr, s,
+                          read_set(target_bases, target_offsets, n_targets, first_target_read_id), max_device_bytes, gwm::Scoring{}, s,
                           out->stage_ms, [&](const AlignedChunk& c) {
                               records.write<false>(c, window_length, edit_distances.p, temp, s);
                           });
@@ -251,7 +251,7 @@ int gwm_pair_segments(const gwm_overlap* pairs, int64_t n, const char* bases, co
         Events ev(3);
         float role_ms[2] = {0.f, 0.f}; // the consumer's time, which align_chunks() sums for both, apart for each role
         const ReadSet r = read_set(bases, offsets, n_reads, first_read_id);
-        gwm::align_chunks("gwm_pair_segments", pairs, n, r, r, max_device_bytes, nullptr, s, target_role->stage_ms,
+        gwm::align_chunks("gwm_pair_segments", pairs, n, r, r, max_device_bytes, gwm::Scoring{}, s, target_role->stage_ms,
                           [&](const AlignedChunk& c) {
                               ev.record(0, s);
                               of_target.write<false>(c, window_length, edit_distances.p, temp, s);

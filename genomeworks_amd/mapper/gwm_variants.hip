@@ -425,6 +425,11 @@ int64_t vote_and_call(dbuf<gwm_insertion_run>& runs, int64_t n_runs, const uint3
     return total;
 }
 
+int overlap_variants(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                     int32_t n_queries, uint32_t first_query_read_id, const char* target_bases, const int64_t* target_offsets,
+                     int32_t n_targets, uint32_t first_target_read_id, int32_t min_count, int32_t min_percent,
+                     const gwm::Scoring& scoring, int64_t max_device_bytes, void* stream, gwm_variants* out);
+
 } // namespace
 
 extern "C" {
@@ -454,6 +459,32 @@ int gwm_overlap_variants_scored(const gwm_overlap* overlaps, int64_t n, const ch
                                 const char* target_bases, const int64_t* target_offsets, int32_t n_targets,
                                 uint32_t first_target_read_id, int32_t min_count, int32_t min_percent,
                                 const gwm_scoring* scoring, int64_t max_device_bytes, void* stream, gwm_variants* out)
+{
+    return overlap_variants(overlaps, n, query_bases, query_offsets, n_queries, first_query_read_id, target_bases,
+                            target_offsets, n_targets, first_target_read_id, min_count, min_percent, gwm::scoring_of(scoring),
+                            max_device_bytes, stream, out);
+}
+
+int gwm_overlap_variants_scored2(const gwm_overlap* overlaps, int64_t n, const char* query_bases,
+                                 const int64_t* query_offsets, int32_t n_queries, uint32_t first_query_read_id,
+                                 const char* target_bases, const int64_t* target_offsets, int32_t n_targets,
+                                 uint32_t first_target_read_id, int32_t min_count, int32_t min_percent,
+                                 const gwm_scoring2* scoring, int64_t max_device_bytes, void* stream, gwm_variants* out)
+{
+    return overlap_variants(overlaps, n, query_bases, query_offsets, n_queries, first_query_read_id, target_bases,
+                            target_offsets, n_targets, first_target_read_id, min_count, min_percent, gwm::scoring_of(scoring),
+                            max_device_bytes, stream, out);
+}
+
+} // extern "C"
+
+namespace
+{
+
+int overlap_variants(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                     int32_t n_queries, uint32_t first_query_read_id, const char* target_bases, const int64_t* target_offsets,
+                     int32_t n_targets, uint32_t first_target_read_id, int32_t min_count, int32_t min_percent,
+                     const gwm::Scoring& scoring, int64_t max_device_bytes, void* stream, gwm_variants* out)
 {
     *out = gwm_variants{};
     try
@@ -521,4 +552,4 @@ int gwm_overlap_variants_scored(const gwm_overlap* overlaps, int64_t n, const ch
     }
 }
 
-} // extern "C"
+} // namespace

@@ -528,6 +528,21 @@ const gwm_scoring* checked_scoring(const char* who, const int32_t* scoring, gwm_
                                     std::to_string(scoring[3]) + ") outside 1..255, 0..255, 1..255, >= 0");
     return storage;
 }
+
+// the same for scoring[0..5] = mismatch, gap_open, gap_extend, gap_open2, gap_extend2, band
+const gwm_scoring2* checked_scoring2(const char* who, const int32_t* scoring, gwm_scoring2* storage)
+{
+    if (scoring == nullptr)
+        return nullptr;
+    gwm_scoring one_piece{};
+    const int32_t first[4] = {scoring[0], scoring[1], scoring[2], scoring[5]};
+    checked_scoring(who, first, &one_piece);
+    *storage = gwm_scoring2{scoring[0], scoring[1], scoring[2], scoring[3], scoring[4], scoring[5]};
+    if (scoring[3] < 0 || scoring[3] > 255 || scoring[4] < 1 || scoring[4] > 255)
+        throw std::invalid_argument(std::string(who) + ": scoring (gap_open2 " + std::to_string(scoring[3]) + ", gap_extend2 " +
+                                    std::to_string(scoring[4]) + ") outside 0..255, 1..255");
+    return storage;
+}
 } // namespace
 
 gw_mapper_cigars* gw_mapper_align_overlaps_scored(const void* overlaps, int64_t n, const char* query_bases,
@@ -547,6 +562,26 @@ gw_mapper_cigars* gw_mapper_align_overlaps_scored(const void* overlaps, int64_t 
         throw_on(gwm_align_overlaps_scored(c.d.p, n, c.q.bases, c.q.offsets, c.reads.queries.n, first_query_read_id,
                                            c.t.bases, c.t.offsets, c.reads.targets.n, first_target_read_id, sc,
                                            max_device_bytes, stream, &h->c));
+        return h.release();
+    }, static_cast<gw_mapper_cigars*>(nullptr));
+}
+
+gw_mapper_cigars* gw_mapper_align_overlaps_scored2(const void* overlaps, int64_t n, const char* query_bases,
+                                                   const int64_t* query_offsets, int32_t n_queries,
+                                                   uint32_t first_query_read_id, const char* target_bases,
+                                                   const int64_t* target_offsets, int32_t n_targets,
+                                                   uint32_t first_target_read_id, const int32_t* scoring,
+                                                   int64_t max_device_bytes, void* stream)
+{
+    return guarded([&] {
+        std::unique_ptr<gw_mapper_cigars> h(new gw_mapper_cigars());
+        gwm_scoring2 storage{};
+        const gwm_scoring2* sc = checked_scoring2("gw_mapper_align_overlaps_scored2", scoring, &storage);
+        device_call c({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets}, overlaps, n,
+                      false);
+        throw_on(gwm_align_overlaps_scored2(c.d.p, n, c.q.bases, c.q.offsets, c.reads.queries.n, first_query_read_id,
+                                            c.t.bases, c.t.offsets, c.reads.targets.n, first_target_read_id, sc,
+                                            max_device_bytes, stream, &h->c));
         return h.release();
     }, static_cast<gw_mapper_cigars*>(nullptr));
 }
@@ -839,6 +874,33 @@ gw_mapper_variants* gw_mapper_overlap_variants_scored(const void* overlaps, int6
         throw_on(gwm_overlap_variants_scored(c.d.p, n, c.q.bases, c.q.offsets, c.reads.queries.n, first_query_read_id,
                                              c.t.bases, c.t.offsets, c.reads.targets.n, first_target_read_id, min_count,
                                              min_percent, sc, max_device_bytes, stream, &h->v));
+        return h.release();
+    }, static_cast<gw_mapper_variants*>(nullptr));
+}
+
+gw_mapper_variants* gw_mapper_overlap_variants_scored2(const void* overlaps, int64_t n, const char* query_bases,
+                                                       const int64_t* query_offsets, int32_t n_queries,
+                                                       uint32_t first_query_read_id, const char* target_bases,
+                                                       const int64_t* target_offsets, int32_t n_targets,
+                                                       uint32_t first_target_read_id, int32_t min_count,
+                                                       int32_t min_percent, const int32_t* scoring,
+                                                       int64_t max_device_bytes, void* stream)
+{
+    return guarded([&] {
+        std::unique_ptr<gw_mapper_variants> h(new gw_mapper_variants());
+        gwm_scoring2 storage{};
+        const gwm_scoring2* sc = checked_scoring2("gw_mapper_overlap_variants_scored2", scoring, &storage);
+        if (n < 0)
+            throw std::invalid_argument("gw_mapper_overlap_variants: negative number of overlaps");
+        if (min_count < 1)
+            throw std::invalid_argument("gw_mapper_overlap_variants: min_count below 1");
+        if (min_percent < 0 || min_percent > 100)
+            throw std::invalid_argument("gw_mapper_overlap_variants: min_percent outside 0..100");
+        device_call c({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets}, overlaps, n,
+                      true);
+        throw_on(gwm_overlap_variants_scored2(c.d.p, n, c.q.bases, c.q.offsets, c.reads.queries.n, first_query_read_id,
+                                              c.t.bases, c.t.offsets, c.reads.targets.n, first_target_read_id, min_count,
+                                              min_percent, sc, max_device_bytes, stream, &h->v));
         return h.release();
     }, static_cast<gw_mapper_variants*>(nullptr));
 }

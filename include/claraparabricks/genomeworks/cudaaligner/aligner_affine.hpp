@@ -38,6 +38,28 @@ std::unique_ptr<Aligner> create_aligner_affine(int32_t max_query_length, int32_t
                                                AffineScoring scoring, int32_t band_width, cudaStream_t stream,
                                                int32_t device_id, int64_t max_device_memory = -1);
 
+/// Two-piece gap costs: a gap run of L columns costs min(gap_open + L * gap_extend, gap_open2 + L * gap_extend2), so a
+/// short gap and a long one are each priced by the piece that suits it. Ranges as AffineScoring's, for both pieces; no
+/// order between the pieces is required. The defaults are minimap2's -A2 -B4 -O4,24 -E2,1 in cost form for a global
+/// alignment (INTEGRATION.md section 3p derives them); the pieces cross at L = 20.
+struct TwoPieceScoring
+{
+    int32_t mismatch    = 6;
+    int32_t gap_open    = 4;
+    int32_t gap_extend  = 3;
+    int32_t gap_open2   = 24;
+    int32_t gap_extend2 = 2;
+};
+
+/// As the two above under two-piece costs; here a pair whose band has more than 1024 diagonals keeps the status
+/// uninitialized. get_alignment_cost, is_optimal and the statuses behave as for the one-piece aligner.
+std::unique_ptr<Aligner> create_aligner_affine(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments,
+                                               TwoPieceScoring scoring, int32_t band_width, DefaultDeviceAllocator allocator,
+                                               cudaStream_t stream, int32_t device_id);
+std::unique_ptr<Aligner> create_aligner_affine(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments,
+                                               TwoPieceScoring scoring, int32_t band_width, cudaStream_t stream,
+                                               int32_t device_id, int64_t max_device_memory = -1);
+
 /// The cost of an alignment made by an affine aligner; -1 for one without a result and for other aligners' alignments.
 int32_t get_alignment_cost(const Alignment& alignment);
 

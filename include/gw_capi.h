@@ -203,6 +203,12 @@ gw_aligner* gw_aligner_create_typed(int32_t alignment_type, int32_t max_query_le
 gw_aligner* gw_aligner_create_affine(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments, int32_t mismatch,
                                      int32_t gap_open, int32_t gap_extend, int32_t band_width, void* stream, int32_t device_id,
                                      int64_t max_device_memory);
+/* The same under two-piece gap costs (TwoPieceScoring): a gap run of L columns costs
+   min(gap_open + L * gap_extend, gap_open2 + L * gap_extend2), both pieces in the ranges above and in any order; the capacity
+   is 1024 diagonals. Every accessor of the affine aligner works on it. NULL on error (parameters out of range). */
+gw_aligner* gw_aligner_create_affine2(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments, int32_t mismatch,
+                                      int32_t gap_open, int32_t gap_extend, int32_t gap_open2, int32_t gap_extend2, int32_t band_width,
+                                      void* stream, int32_t device_id, int64_t max_device_memory);
 void gw_aligner_destroy(gw_aligner* a);
 int gw_aligner_add_alignment(gw_aligner* a, const char* query, int32_t query_length, const char* target,
                              int32_t target_length, int reverse_complement_query, int reverse_complement_target);

@@ -117,6 +117,15 @@ gw_mapper_cigars* gw_mapper_align_overlaps_scored(const void* overlaps, int64_t 
                                                   const int64_t* target_offsets, int32_t n_targets,
                                                   uint32_t first_target_read_id, const int32_t* scoring,
                                                   int64_t max_device_bytes, void* stream);
+/* The same under two-piece gap costs (gwm_align_overlaps_scored2): scoring[0..5] = mismatch, gap_open, gap_extend,
+   gap_open2 (0..255), gap_extend2 (1..255), band; NULL is gw_mapper_align_overlaps itself. Refused out of range before
+   anything reaches the device (NULL). An overlap whose band has more than 1024 diagonals has an empty CIGAR and -1. */
+gw_mapper_cigars* gw_mapper_align_overlaps_scored2(const void* overlaps, int64_t n, const char* query_bases,
+                                                   const int64_t* query_offsets, int32_t n_queries,
+                                                   uint32_t first_query_read_id, const char* target_bases,
+                                                   const int64_t* target_offsets, int32_t n_targets,
+                                                   uint32_t first_target_read_id, const int32_t* scoring,
+                                                   int64_t max_device_bytes, void* stream);
 int64_t gw_mapper_cigars_count(const gw_mapper_cigars* cigars);
 int64_t gw_mapper_cigars_text_bytes(const gw_mapper_cigars* cigars);
 int gw_mapper_cigars_copy(const gw_mapper_cigars* cigars, char* text, int64_t* offsets, int32_t* edit_distances,
@@ -335,6 +344,14 @@ gw_mapper_variants* gw_mapper_overlap_variants_scored(const void* overlaps, int6
                                                       uint32_t first_target_read_id, int32_t min_count,
                                                       int32_t min_percent, const int32_t* scoring,
                                                       int64_t max_device_bytes, void* stream);
+/* The same over the alignments of gw_mapper_align_overlaps_scored2; scoring as there. */
+gw_mapper_variants* gw_mapper_overlap_variants_scored2(const void* overlaps, int64_t n, const char* query_bases,
+                                                       const int64_t* query_offsets, int32_t n_queries,
+                                                       uint32_t first_query_read_id, const char* target_bases,
+                                                       const int64_t* target_offsets, int32_t n_targets,
+                                                       uint32_t first_target_read_id, int32_t min_count,
+                                                       int32_t min_percent, const int32_t* scoring,
+                                                       int64_t max_device_bytes, void* stream);
 /* the number of called records */
 int64_t gw_mapper_variants_count(const gw_mapper_variants* variants);
 /* records[count] (gwm_variant), ascending by cell, within a cell SNV, deletion, insertion -- one copy from the

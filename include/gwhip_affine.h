@@ -64,6 +64,50 @@ int gwhip_affine_align(const gwhip_affine_args* args, void* stream);
    forward pass, between it and the traceback, behind the traceback. Nothing is waited for. */
 int gwhip_affine_align_events(const gwhip_affine_args* args, void* stream, void* const events[3]);
 
+/* ---- two-piece gap costs (genomeworks_amd/affine/gwaffine2_rules.h is their code) --------------
+ * Query, target, match predicate, band, W, the workspace's stride and layout and the states written are those above. A
+ * gap run of L columns costs g(L) = min(o1 + L e1, o2 + L e2); no order between the two pieces is required.
+ *   E1[i][j] = min(E1[i][j-1] + e1, H[i][j-1] + o1 + e1)    E2 likewise with (o2, e2)    (state 2)
+ *   F1[i][j] = min(F1[i-1][j] + e1, H[i-1][j] + o1 + e1)    F2 likewise with (o2, e2)    (state 3)
+ *   H[i][j]  = min(H[i-1][j-1] + sub, E1[i][j], F1[i][j], E2[i][j], F2[i][j])
+ * with ties: extension before opening in each of the four gap matrices; for H the diagonal, E1, F1, E2, F2 in this order,
+ * a later one only when strictly smaller. A cell's byte (this instantiation's alone): bits 0-2 src (0 diagonal, 1 E1,
+ * 2 F1, 3 E2, 4 F2), bit 3 E1ext, bit 4 F1ext, bit 5 E2ext, bit 6 F2ext, bit 7 mismatch. The traceback walks five
+ * matrices: from H a non-zero src switches matrix and emits nothing; a gap matrix emits its state, steps, and returns to
+ * H when its ext bit is clear (E2 and F2 open from H, never from E1 or F1). A pair with
+ * W > GWHIP_AFFINE2_MAX_DIAGONALS or n + m >= 2^21 gets no result: length 0, cost -1, flag 0. */
+#define GWHIP_AFFINE2_MAX_DIAGONALS 1024
+
+typedef struct gwhip_affine2_args
+{
+    int32_t n_alignments;
+    const char* sequences;               /* as gwhip_affine_args, field by field, ... */
+    const int64_t* sequence_starts;
+    const int64_t* sequence_starts_host;
+    int32_t mismatch;                    /* 1 .. 255 */
+    int32_t gap_open;                    /* o1, 0 .. 255 */
+    int32_t gap_extend;                  /* e1, 1 .. 255 */
+    int32_t gap_open2;                   /* ... plus o2, 0 .. 255 */
+    int32_t gap_extend2;                 /* and e2, 1 .. 255 */
+    int32_t band;                        /* B >= 0 */
+    int8_t* results;
+    int32_t* result_lengths;
+    int32_t* costs;
+    uint8_t* optimal;                    /* device, [n]: 1 when cost <= g(B + 1) + g(B + 1 + |m - n|), the cheapest path that
+                                            leaves the band (with one piece: 2 o + e (|m - n| + 2 B + 2)) */
+    void* workspace;                     /* device, gwhip_affine2_workspace_bytes(...) */
+    size_t workspace_bytes;
+} gwhip_affine2_args;
+
+/* gwhip_affine_workspace_bytes' formula; a pair of more than GWHIP_AFFINE2_MAX_DIAGONALS diagonals counts 0. */
+size_t gwhip_affine2_workspace_bytes(int32_t n_alignments, const int64_t* sequence_starts_host, int32_t band);
+
+/* As gwhip_affine_align and gwhip_affine_align_events, under the two-piece costs: the same launches, the same refusals
+   before anything is launched (a value out of range, a missing pointer, a workspace smaller than
+   gwhip_affine2_workspace_bytes()), nothing launched for an empty batch. Errors: gwhip_affine_last_error. */
+int gwhip_affine2_align(const gwhip_affine2_args* args, void* stream);
+int gwhip_affine2_align_events(const gwhip_affine2_args* args, void* stream, void* const events[3]);
+
 const char* gwhip_affine_last_error(void);
 
 #ifdef __cplusplus

@@ -243,6 +243,26 @@ int gwm_align_overlaps_scored(const gwm_overlap* overlaps, int64_t n, const char
 /* gwm_align_bytes_needed for a call with a scoring of this band. Host arithmetic only. */
 int64_t gwm_align_bytes_needed_scored(int32_t query_length, int32_t target_length, int32_t band);
 
+/* Two-piece gap costs (include/gwhip_affine.h, gwhip_affine2_align): a gap run of L columns
+ * costs min(gap_open + L * gap_extend, gap_open2 + L * gap_extend2); both pieces in gwm_scoring's ranges, in any order. */
+typedef struct gwm_scoring2
+{
+    int32_t mismatch;
+    int32_t gap_open;
+    int32_t gap_extend;
+    int32_t gap_open2;
+    int32_t gap_extend2;
+    int32_t band;
+} gwm_scoring2;
+
+/* gwm_align_overlaps_scored under two-piece costs: NULL is gwm_align_overlaps itself. The budget counts what
+ * gwm_align_bytes_needed_scored states; an overlap whose band has more than GWHIP_AFFINE2_MAX_DIAGONALS diagonals is the
+ * aligner's "no result": an empty CIGAR and -1. */
+int gwm_align_overlaps_scored2(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                               int32_t n_queries, uint32_t first_query_read_id, const char* target_bases,
+                               const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
+                               const gwm_scoring2* scoring, int64_t max_device_bytes, void* stream, gwm_cigars* out);
+
 /* ---- polishing: from aligned overlaps to POA windows ----------------------------------------------------------------
  * The target reads are cut into windows of window_length bases: window k of a read is its bases [k W, (k + 1) W). */
 
@@ -421,6 +441,12 @@ int gwm_overlap_variants_scored(const gwm_overlap* overlaps, int64_t n, const ch
                                 const char* target_bases, const int64_t* target_offsets, int32_t n_targets,
                                 uint32_t first_target_read_id, int32_t min_count, int32_t min_percent,
                                 const gwm_scoring* scoring, int64_t max_device_bytes, void* stream, gwm_variants* out);
+/* gwm_overlap_variants over the alignments of gwm_align_overlaps_scored2: NULL is gwm_overlap_variants itself. */
+int gwm_overlap_variants_scored2(const gwm_overlap* overlaps, int64_t n, const char* query_bases,
+                                 const int64_t* query_offsets, int32_t n_queries, uint32_t first_query_read_id,
+                                 const char* target_bases, const int64_t* target_offsets, int32_t n_targets,
+                                 uint32_t first_target_read_id, int32_t min_count, int32_t min_percent,
+                                 const gwm_scoring2* scoring, int64_t max_device_bytes, void* stream, gwm_variants* out);
 void gwm_variants_free(gwm_variants* variants);
 
 /* One sequence of a gather plan (20 B): bases [begin, end) of read `read` (position in its set) of the query set

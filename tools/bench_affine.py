@@ -17,11 +17,18 @@ And once, in the same process, the same two calls without a scoring: the align s
 runs and its records. Medians over the repeats. No threshold: the record says what was measured. Whether affine costs
 improve the calls on real reads is not measured here; the counts say only how much the alignments change.
 
+With --two-piece the arm that is measured is the two-piece aligner under (6, 4, 3, 24, 2),
+and every band also holds the same measurements of the one-piece aligner under its first piece (6, 4, 3), from the same
+process, with the two-piece forward pass over the one-piece forward pass; the gap runs of 20 columns or more are counted
+under unit, one-piece and two-piece costs.
+
     python tools/bench_affine.py [--contig-kbp 200] [--coverage 30] [--repeats 3] [--out profiles/affine_bench.json]
+    python tools/bench_affine.py --two-piece --out profiles/affine2_bench.json
 """
 import argparse
 import json
 import os
+import re
 import statistics
 import sys
 
@@ -36,6 +43,7 @@ import oracle_polish as OPo  # noqa: E402
 from genomeworks_amd import cudaaligner, cudamapper, polisher  # noqa: E402
 
 COSTS = (4, 6, 2)
+TWO_PIECE, ITS_FIRST_PIECE = (6, 4, 3, 24, 2), (6, 4, 3)
 
 
 def med(values):
@@ -44,6 +52,10 @@ def med(values):
 
 def gap_runs(cigars):
     return sum(c.count("I") + c.count("D") for c in cigars)
+
+
+def long_gap_runs(cigars, least=20):
+    return sum(1 for c in cigars for n in re.findall(r"(\d+)[ID]", c) if int(n) >= least)
 
 
 def kinds(records):
@@ -71,15 +83,16 @@ def mapper_side(kept, reads, draft, scoring, repeats):
         records = cudamapper.overlap_variants(kept, reads, [draft], scoring=scoring, timings=t)
         variants_align_ms.append(t["align"])
     return {"align_ms": med(align_ms), "overlap_variants_align_ms": med(variants_align_ms), "gap_runs": gap_runs(cigars),
-            "no_result": int((edits < 0).sum()), "non_match_columns": int(edits[edits >= 0].sum()),
+            "gap_runs_of_20_or_more": long_gap_runs(cigars), "no_result": int((edits < 0).sum()), "non_match_columns": int(edits[edits >= 0].sum()),
             "variants": kinds(records)}
 
 
-def aligner_side(pairs, B, repeats):
-    """the forward pass and the traceback of the affine aligner over `pairs` at band B"""
+def aligner_side(pairs, B, repeats, costs=COSTS):
+    """the forward pass and the traceback of the affine aligner over `pairs` at band B; five costs: the two-piece one"""
     longest = max(max(len(q), len(t)) for q, t in pairs)
-    batch = cudaaligner.CudaAlignerBatch(longest, longest, len(pairs), algorithm="affine", mismatch=COSTS[0], gap_open=COSTS[1],
-                                         gap_extend=COSTS[2], band_width=B, max_device_memory_allocator_caching_size=16 << 30)
+    names = ("mismatch", "gap_open", "gap_extend", "gap_open2", "gap_extend2")
+    batch = cudaaligner.CudaAlignerBatch(longest, longest, len(pairs), algorithm="affine", band_width=B,
+                                         max_device_memory_allocator_caching_size=16 << 30, **dict(zip(names, costs)))
     forward, traceback = [], []
     for k in range(repeats + 1):  # the first is the warm-up
         batch.reset()
@@ -108,6 +121,7 @@ def main():
     ap.add_argument("--draft-error", type=float, default=0.03)
     ap.add_argument("--bands", type=int, nargs="+", default=[64, 128, 256])
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--two-piece", action="store_true")
     ap.add_argument("--out")
     args = ap.parse_args()
     seed, length = 2025, int(args.contig_kbp * 1000)
@@ -123,16 +137,24 @@ def main():
         q = reads[int(x["query_read_id"])][int(x["query_start_position_in_read"]):int(x["query_end_position_in_read"])]
         t = draft[int(x["target_start_position_in_read"]):int(x["target_end_position_in_read"])]
         pairs.append((q, rc(t) if chr(x["relative_strand"]) == "-" else t))
-    rec = {"metric": "affine-gap global alignment of the polishing records next to the unit-cost path", "device": "gpu0",
+    costs = TWO_PIECE if args.two_piece else COSTS
+    rec = {"metric": ("two-piece " if args.two_piece else "") + "affine-gap global alignment of the polishing records next to the unit-cost path", "device": "gpu0",
            "contig_bases": length, "draft_bases": len(draft), "coverage": args.coverage, "reads": len(reads),
            "read_bases": sum(len(r) for r in reads), "mean_read_length": args.read_length, "read_error": args.read_error,
            "draft_error": args.draft_error, "mapping": mapping, "repeats": args.repeats, "records": int(len(kept)),
-           "slice_bases": sum(len(q) + len(t) for q, t in pairs), "costs": dict(zip(("mismatch", "gap_open", "gap_extend"), COSTS)),
+           "slice_bases": sum(len(q) + len(t) for q, t in pairs), "costs": dict(zip(("mismatch", "gap_open", "gap_extend", "gap_open2", "gap_extend2"), costs)),
            "unit_costs": mapper_side(kept, reads, draft, None, args.repeats), "bands": {}}
     for B in args.bands:
-        entry = aligner_side(pairs, B, args.repeats)
-        entry["mapper"] = mapper_side(kept, reads, draft, COSTS + (B,), args.repeats)
+        entry = aligner_side(pairs, B, args.repeats, costs)
+        entry["mapper"] = mapper_side(kept, reads, draft, costs + (B,), args.repeats)
         entry["align_ms_over_unit_costs"] = round(entry["mapper"]["align_ms"] / rec["unit_costs"]["align_ms"], 3)
+        if args.two_piece:
+            one = aligner_side(pairs, B, args.repeats, ITS_FIRST_PIECE)
+            one["costs"] = list(ITS_FIRST_PIECE)
+            one["mapper"] = mapper_side(kept, reads, draft, ITS_FIRST_PIECE + (B,), args.repeats)
+            entry["one_piece"] = one
+            entry["forward_ms_over_one_piece"] = round(entry["forward_ms"] / one["forward_ms"], 3)
+            entry["traceback_ms_over_one_piece"] = round(entry["traceback_ms"] / one["traceback_ms"], 3)
         rec["bands"][str(B)] = entry
     line = json.dumps(rec)
     print(line)
