@@ -198,6 +198,7 @@ def mapper():
         L.gw_mapper_post_process_overlaps.restype = i64
         L.gw_mapper_post_process_overlaps.argtypes = [vp, i64, i32, vp, i64, vp, vp]
         L.gw_mapper_rescue_overlap_ends.argtypes = [vp, i64, vp, vp, i32, vp, vp, i32, u32, u32, i32, f32, vp, vp]
+        L.gw_mapper_extend_overlaps.argtypes = [vp, i64, vp, vp, i32, vp, vp, i32, u32, u32, vp, i32, i64, vp, vp, vp]
         L.gw_mapper_group_reads_into_indices.restype = i64
         L.gw_mapper_group_reads_into_indices.argtypes = [vp, i64, i64, vp, i64]
         L.gw_mapper_map_batched.restype = vp

@@ -18,6 +18,9 @@
 // H, E1, F1, E2, F2, K up to 16, three values across a lane's edge per step instead of two). The policy names the costs,
 // the band's capacity, the cell update, the optimality bound and the traceback step; the wavefront, the base windows,
 // the stores, the tiles and the guards are written once.
+//
+// The affine X-drop extension (gwhip_extend) is the one-piece wavefront in another geometry with a stop rule on top;
+// its kernels are in gwaffine_extend.h, included below, its rules in gwaffine_extend_rules.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,6 +29,7 @@
 #include "gwhip_affine.h"
 
 #include "gwaffine2_rules.h"
+#include "gwaffine_extend_rules.h"
 #include "gwaffine_rules.h"
 
 namespace
@@ -122,16 +126,16 @@ __device__ __forceinline__ Band pair_band(const PairArgs<R>& A, int64_t pair)
 }
 
 // offsets[p] = bytes of the bit matrices of the pairs before p, offsets[n] their total: one block, every thread a run
-// of consecutive pairs
-template <class R>
-__global__ void __launch_bounds__(kScanThreads) offsets_kernel(PairArgs<R> A, int64_t* __restrict__ offsets)
+// of consecutive pairs; bytes_of(p) is pair p's
+template <class BytesOf>
+__device__ __forceinline__ void scan_offsets(int32_t n, BytesOf bytes_of, int64_t* __restrict__ offsets)
 {
     __shared__ int64_t partial[kScanThreads];
-    const int64_t per   = (static_cast<int64_t>(A.n) + kScanThreads - 1) / kScanThreads;
-    const int64_t first = min(static_cast<int64_t>(A.n), threadIdx.x * per), last = min(static_cast<int64_t>(A.n), first + per);
+    const int64_t per   = (static_cast<int64_t>(n) + kScanThreads - 1) / kScanThreads;
+    const int64_t first = min(static_cast<int64_t>(n), threadIdx.x * per), last = min(static_cast<int64_t>(n), first + per);
     int64_t sum = 0;
     for (int64_t p = first; p < last; ++p)
-        sum += bits_bytes(pair_band(A, p));
+        sum += bytes_of(p);
     partial[threadIdx.x] = sum;
     __syncthreads();
     if (threadIdx.x == 0)
@@ -143,15 +147,21 @@ __global__ void __launch_bounds__(kScanThreads) offsets_kernel(PairArgs<R> A, in
             partial[k]      = run;
             run += v;
         }
-        offsets[A.n] = run;
+        offsets[n] = run;
     }
     __syncthreads();
     int64_t run = partial[threadIdx.x];
     for (int64_t p = first; p < last; ++p)
     {
         offsets[p] = run;
-        run += bits_bytes(pair_band(A, p));
+        run += bytes_of(p);
     }
+}
+
+template <class R>
+__global__ void __launch_bounds__(kScanThreads) offsets_kernel(PairArgs<R> A, int64_t* __restrict__ offsets)
+{
+    scan_offsets(A.n, [&](int64_t p) { return bits_bytes(pair_band(A, p)); }, offsets);
 }
 
 // what the wavefront needs of a pair, in 32 bits (n + m < 2^21, W <= 2048)
@@ -162,7 +172,8 @@ struct Pair32
 
 // One anti-diagonal a for the lane's cells of parity PAR (K >= 2): cell t is diagonal index k0 + PAR + 2 t at
 // (i0 - t, j0 + t); qw[t] / tw[t] are its query base and its target base (translated), 0 / 1 where there is none.
-template <class R, int K, int PAR>
+// kStore = false (the extension's score-only mode) writes no row of the bit matrix.
+template <class R, int K, int PAR, bool kStore = true>
 __device__ __forceinline__ void wave_step(int32_t (&H)[K], int32_t (&E)[R::G][K], int32_t (&F)[R::G][K],
                                           const char (&qw)[K / 2], const char (&tw)[K / 2], int32_t a, int32_t k0,
                                           const Pair32& p, const typename R::CostsT& c, uint8_t* __restrict__ row, int lane)
@@ -225,6 +236,8 @@ __device__ __forceinline__ void wave_step(int32_t (&H)[K], int32_t (&E)[R::G][K]
         }
         packed[t / 4] |= r.bits << (8 * (t % 4));
     }
+    if (!kStore)
+        return;
     const int32_t at = lane * C; // (k0 + PAR + 2 t) >> 1 = lane * C + t
     if (C >= 4)
     {
@@ -388,24 +401,15 @@ __global__ void __launch_bounds__(kThreads) forward_kernel(PairArgs<R> A)
 constexpr int kTileRows  = 64;
 constexpr int kTileBytes = 80;
 
+// The walk from (i, j) in H back to (0, 0) through the tiles: the states back to front at out[0 .. cap), their number in
+// len. True: bits that lead out of the band or past the slot, a defect and never an input's property.
 template <class R>
-__global__ void __launch_bounds__(64) traceback_kernel(PairArgs<R> A)
+__device__ __forceinline__ bool walk_tiles(const Band& b, const uint8_t* __restrict__ bits, int8_t* __restrict__ out, int64_t i,
+                                           int64_t j, int64_t cap, int lane, uint32_t* tile, int64_t& len)
 {
-    __shared__ uint32_t tile[kTileRows * kTileBytes / 4];
-    const int64_t pair = blockIdx.x;
-    const int lane     = threadIdx.x;
-    if (A.costs[pair] < 0) // the forward pass gave no result
-    {
-        if (lane == 0)
-            A.result_lengths[pair] = 0;
-        return;
-    }
-    const Band b        = pair_band(A, pair);
-    const uint8_t* bits = A.bits + A.offsets[pair];
-    int8_t* out         = A.results + A.starts[2 * pair];
-    typename R::WalkT w{b.n, b.m, 0};
-    int64_t len = 0;
-    bool lost   = false; // bits that lead out of the band or past the slot: a defect, never an input's property
+    typename R::WalkT w{i, j, 0};
+    len       = 0;
+    bool lost = false;
     while (!lost && (w.i != 0 || w.j != 0 || w.matrix != 0))
     {
         const int64_t a_top = w.i + w.j;
@@ -437,7 +441,7 @@ __global__ void __launch_bounds__(64) traceback_kernel(PairArgs<R> A)
             const int32_t state = R::step(w, cells[r * kTileBytes + cc]);
             if (state >= 0)
             {
-                if (len >= b.n + b.m)
+                if (len >= cap)
                 {
                     lost = true;
                     break;
@@ -448,6 +452,24 @@ __global__ void __launch_bounds__(64) traceback_kernel(PairArgs<R> A)
             }
         }
     }
+    return lost;
+}
+
+template <class R>
+__global__ void __launch_bounds__(64) traceback_kernel(PairArgs<R> A)
+{
+    __shared__ uint32_t tile[kTileRows * kTileBytes / 4];
+    const int64_t pair = blockIdx.x;
+    const int lane     = threadIdx.x;
+    if (A.costs[pair] < 0) // the forward pass gave no result
+    {
+        if (lane == 0)
+            A.result_lengths[pair] = 0;
+        return;
+    }
+    const Band b    = pair_band(A, pair);
+    int64_t len     = 0;
+    const bool lost = walk_tiles<R>(b, A.bits + A.offsets[pair], A.results + A.starts[2 * pair], b.n, b.m, b.n + b.m, lane, tile, len);
     if (lane == 0)
     {
         A.result_lengths[pair] = lost ? 0 : static_cast<int32_t>(len);
@@ -590,6 +612,8 @@ int run_events(const char* name, const Args* args, void* stream, void* const eve
     return run<R>(name, args, static_cast<hipStream_t>(stream), e);
 }
 
+#include "gwaffine_extend.h"
+
 } // namespace
 
 extern "C" {
@@ -622,6 +646,27 @@ int gwhip_affine2_align(const gwhip_affine2_args* args, void* stream)
 int gwhip_affine2_align_events(const gwhip_affine2_args* args, void* stream, void* const events[3])
 {
     return run_events<TwoPiece>("gwhip_affine2_align", args, stream, events);
+}
+
+size_t gwhip_extend_workspace_bytes(int32_t n_alignments, const int64_t* sequence_starts_host, int32_t band, int32_t with_traceback)
+{
+    int64_t bytes = 0;
+    if (!with_traceback)
+        return 0;
+    if (n_alignments <= 0 || sequence_starts_host == nullptr || band < 0 || band > kMaxExtendBand ||
+        !size_extend_batch(n_alignments, sequence_starts_host, band, &bytes))
+        return 256;
+    return static_cast<size_t>(bytes);
+}
+
+int gwhip_extend(const gwhip_extend_args* args, void* stream) { return run_extend(args, static_cast<hipStream_t>(stream), nullptr); }
+
+int gwhip_extend_events(const gwhip_extend_args* args, void* stream, void* const events[3])
+{
+    if (events == nullptr || !events[0] || !events[1] || !events[2])
+        return fail(hipErrorInvalidValue, "gwhip_extend_events: three events are needed");
+    hipEvent_t e[3] = {static_cast<hipEvent_t>(events[0]), static_cast<hipEvent_t>(events[1]), static_cast<hipEvent_t>(events[2])};
+    return run_extend(args, static_cast<hipStream_t>(stream), e);
 }
 
 const char* gwhip_affine_last_error(void) { return g_error.c_str(); }

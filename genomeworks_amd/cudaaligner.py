@@ -5,7 +5,9 @@ banded Myers aligner (create_aligner(global_alignment, max_bandwidth, ...)), whi
 `alignment_type="infix"` / `"prefix"` (not in pygenomeworks) place the whole query on the best slice / the best prefix of
 its target: CudaAlignment.target_begin / .target_end name the slice that the states, the CIGARs and the distance describe.
 `algorithm="affine"` (not in pygenomeworks) aligns globally under gap-open / gap-extend costs inside a diagonal band
-(include/gwhip_affine.h states the rules): its alignments carry `.cost`."""
+(include/gwhip_affine.h states the rules): its alignments carry `.cost`.
+`algorithm="extend"` (not in pygenomeworks) is the affine X-drop extension of the same header: from the first base of both
+sequences to where the similarity stops; its alignments carry `.query_end`, `.target_end`, `.score` and `.dropped`."""
 import ctypes as C
 
 import numpy as np
@@ -51,6 +53,9 @@ def _bind(L):
     L.gw_aligner_create_affine2.restype = vp
     L.gw_aligner_create_affine2.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, C.c_int64]
     L.gw_alignment_cost.argtypes = [vp, i32]
+    L.gw_aligner_create_extension.restype = vp
+    L.gw_aligner_create_extension.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, C.c_int64]
+    L.gw_alignment_extension.argtypes = [vp, i32, C.POINTER(i32 * 4)]
     L.gw_aligner_create_algorithm.restype = vp
     L.gw_aligner_create_algorithm.argtypes = [C.c_char_p, i32, i32, i32, vp, i32, C.c_int64]
     L.gw_aligner_destroy.argtypes = [vp]
@@ -77,7 +82,7 @@ class CudaAlignment:
     """One alignment result (pygenomeworks CudaAlignment): query, target, cigar, status, alignment states."""
 
     def __init__(self, query, target, cigar, cigar_extended, status, is_optimal, edit_distance, states,
-                 target_begin=0, target_end=None, cost=-1):
+                 target_begin=0, target_end=None, cost=-1, extension=None):
         self.query = query
         self.target = target
         self.cigar = cigar
@@ -91,6 +96,11 @@ class CudaAlignment:
         self.target_end = len(target) if target_end is None else target_end
         # algorithm="affine": the alignment's cost under the batch's scoring; -1 for every other aligner
         self.cost = cost
+        # algorithm="extend": query[:query_end] is aligned with target[:target_end] at `score`; dropped: the stop rule ended
+        # the extension. -1, -1 and False for every other aligner, whose target_end is the one above
+        self.query_end, self.score, self.dropped = -1, -1, False
+        if extension is not None:
+            self.query_end, self.target_end, self.score, self.dropped = extension[0], extension[1], extension[2], bool(extension[3])
 
     def format_alignment(self):
         """(query line, pairing line, target line) like Alignment::format_alignment, over target[target_begin:target_end]."""
@@ -111,15 +121,22 @@ class CudaAlignerBatch:
     def __init__(self, max_query_length=None, max_target_length=None, max_alignments=None, alignment_type="global",
                  stream=None, device_id=0, max_device_memory_allocator_caching_size=-1, max_bandwidth=None,
                  algorithm=None, mismatch=None, gap_open=None, gap_extend=None, band_width=None, gap_open2=None,
-                 gap_extend2=None):
+                 gap_extend2=None, match=None, xdrop=None):
         """algorithm (not in pygenomeworks): one of the reference's non-public aligner classes that its C++ tests and
         benchmarks construct directly -- "hirschberg_myers" (the default), "ukkonen", "myers" -- or "affine": global
         alignment under the costs mismatch (4), gap_open (6), gap_extend (2) -- minimised, a gap run of L columns costs
         gap_open + L * gap_extend -- within band_width (128) diagonals on either side of the corners' diagonals. With
         gap_open2 and gap_extend2 (both, or neither) the gap costs are two-piece, min(gap_open + L * gap_extend,
         gap_open2 + L * gap_extend2), and what is left out of (mismatch, gap_open, gap_extend, gap_open2, gap_extend2)
-        is taken from (6, 4, 3, 24, 2)."""
+        is taken from (6, 4, 3, 24, 2). "extend": the affine X-drop extension under the scores match (2), mismatch (4),
+        gap_open (4), gap_extend (2) -- maximised, a gap run of L columns scores -(gap_open + L * gap_extend) -- within
+        band_width (64) diagonals on either side of the start's, stopping xdrop (200; -1: never) below the best score."""
         self._L = _bind(_native.host())
+        extension = dict(match=match, xdrop=xdrop)
+        if algorithm != "extend" and any(v is not None for v in extension.values()):
+            raise RuntimeError("%s: only algorithm=\"extend\" takes these" % ", ".join(k for k, v in extension.items() if v is not None))
+        if algorithm == "extend" and (gap_open2 is not None or gap_extend2 is not None):
+            raise RuntimeError("gap_open2, gap_extend2: the extension has one-piece gap costs")
         scoring = dict(mismatch=mismatch, gap_open=gap_open, gap_extend=gap_extend, band_width=band_width)
         second = dict(gap_open2=gap_open2, gap_extend2=gap_extend2)
         given = [k for k, v in second.items() if v is not None]
@@ -127,7 +144,7 @@ class CudaAlignerBatch:
             raise RuntimeError("%s: only algorithm=\"affine\" takes these" % ", ".join(given))
         if len(given) == 1:
             raise RuntimeError("%s without %s: two-piece gap costs take both" % (given[0], (set(second) - set(given)).pop()))
-        if algorithm != "affine" and any(v is not None for v in scoring.values()):
+        if algorithm not in ("affine", "extend") and any(v is not None for v in scoring.values()):
             raise RuntimeError("%s: only algorithm=\"affine\" takes these" % ", ".join(k for k, v in scoring.items() if v is not None))
         if alignment_type not in _ALIGNMENT_TYPES:
             raise RuntimeError("Unknown alignment_type provided. Must be global, infix or prefix.")
@@ -155,6 +172,12 @@ class CudaAlignerBatch:
             self._h = self._L.gw_aligner_create_affine(int(max_query_length), int(max_target_length), int(max_alignments),
                                                        x, o, e, b, st, device_id,
                                                        int(max_device_memory_allocator_caching_size))
+        elif algorithm == "extend":
+            a, x, o, e, b, X = (d if v is None else int(v) for v, d in
+                                zip((match, mismatch, gap_open, gap_extend, band_width, xdrop), (2, 4, 4, 2, 64, 200)))
+            self._h = self._L.gw_aligner_create_extension(int(max_query_length), int(max_target_length), int(max_alignments),
+                                                          a, x, o, e, b, X, st, device_id,
+                                                          int(max_device_memory_allocator_caching_size))
         elif algorithm is not None:
             self._h = self._L.gw_aligner_create_algorithm(algorithm.encode(), int(max_query_length), int(max_target_length),
                                                           int(max_alignments), st, device_id,
@@ -165,6 +188,7 @@ class CudaAlignerBatch:
         if not self._h:
             raise RuntimeError(self._L.gw_last_error().decode())
         self._pairs = []
+        self._extends = algorithm == "extend"
 
     def __del__(self):
         try:
@@ -287,8 +311,14 @@ class CudaAlignerBatch:
                 rng = self._L.gw_alignment_target_range(self._h, i, C.byref(tb), C.byref(te))
             if ns < 0 or st < 0 or opt < 0 or ed < 0 or rng < 0:  # the C ABI reports a bad index / a thrown accessor as -1 + error string
                 raise RuntimeError("alignment %d: %s" % (i, self._L.gw_last_error().decode()))
+            extension = None
+            if self._extends:
+                four = (C.c_int32 * 4)()
+                if self._L.gw_alignment_extension(self._h, i, C.byref(four)) != 0:
+                    raise RuntimeError("alignment %d: %s" % (i, self._L.gw_last_error().decode()))
+                extension = list(four)
             out.append(CudaAlignment(q, t, cigar, cigar_x, st, bool(opt), ed, [int(x) for x in states[:ns]], tb.value, te.value,
-                                     self._L.gw_alignment_cost(self._h, i)))
+                                     self._L.gw_alignment_cost(self._h, i), extension))
         return out
 
     def reset(self):

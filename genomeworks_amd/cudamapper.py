@@ -359,6 +359,57 @@ def rescue_overlap_ends(overlaps, query_reads, target_reads=None, extension=50, 
     return o
 
 
+_EXTENSION_KEYS = ("match", "mismatch", "gap_open", "gap_extend", "band", "xdrop")
+_EXTENSION_DEFAULTS = (2, 4, 4, 2, 64, 200)
+
+
+def _extension_args(extension):
+    """extension of extend_overlaps as the C API takes it: six int32 (match, mismatch, gap_open, gap_extend, band, xdrop)
+    from None (the defaults 2, 4, 4, 2, 64, 200), a 6-tuple, or a dict with these keys that may leave out any."""
+    if extension is None:
+        values = list(_EXTENSION_DEFAULTS)
+    elif isinstance(extension, dict):
+        unknown = set(extension) - set(_EXTENSION_KEYS)
+        if unknown:
+            raise ValueError("extension: unknown keys %s" % sorted(unknown))
+        values = [extension.get(k, d) for k, d in zip(_EXTENSION_KEYS, _EXTENSION_DEFAULTS)]
+    else:
+        values = list(extension)
+        if len(values) != 6:
+            raise ValueError("extension: a dict or (match, mismatch, gap_open, gap_extend, band, xdrop)")
+    a, x, o, e, b, xd = values = [int(v) for v in values]
+    if not (a >= 1 and x >= 0 and a + x <= 127 and 0 <= o <= 127 and e >= 1 and a + 2 * e <= 255 and 0 <= b <= 511
+            and -1 <= xd <= 2 ** 20):
+        raise ValueError("extension (match %d, mismatch %d, gap_open %d, gap_extend %d, band %d, xdrop %d) outside match >= 1, "
+                         "mismatch >= 0, match + mismatch <= 127, gap_open 0..127, gap_extend >= 1, match + 2 gap_extend <= 255, "
+                         "band 0..511, xdrop -1..2^20" % tuple(values))
+    return np.array(values, np.int32)
+
+
+def extend_overlaps(overlaps, query_reads, target_reads=None, first_query_read_id=0, first_target_read_id=0,
+                    extension=None, max_extension=1024, max_device_bytes=0, stream=None):
+    """The ends of every overlap moved over what the affine X-drop extension aligns beyond
+    them, on the device: behind the tail the up to max_extension (0 .. 2^19) bases of the query and of the target in the
+    target's strand coordinates are extended from the overlap's end, in front of the head the same read back to front.
+    Returns (overlaps, extensions, scores): a copy of the records with the four positions moved and every other field
+    as it was, an int32 array [n][4] of the bases gained (head query, head target, tail query, tail target) and an int32
+    array [n][2] of the two extensions' scores. extension: None, a dict or (match, mismatch, gap_open, gap_extend, band,
+    xdrop); out of range raises ValueError. max_extension 0 returns the input. Reads, read ids, chunking within
+    max_device_bytes and the refusals are align_overlaps'; align_overlaps and every consumer work on the result."""
+    ext = _extension_args(extension)
+    if not 0 <= int(max_extension) <= 2 ** 19:
+        raise ValueError("max_extension %d outside 0..2^19" % int(max_extension))
+    L = _native.mapper()
+    o = np.ascontiguousarray(overlaps, OVERLAP).copy()
+    moved, scores = np.zeros((len(o), 4), np.int32), np.zeros((len(o), 2), np.int32)
+    q, t = _read_set_args(query_reads, target_reads)
+    rc = L.gw_mapper_extend_overlaps(_p(o), len(o), *q, *t, first_query_read_id, first_target_read_id, _p(ext),
+                                     int(max_extension), int(max_device_bytes), _stream(stream), _p(moved), _p(scores))
+    if rc != 0:
+        raise _err(L)
+    return o, moved, scores
+
+
 def _split_cigars(text, offsets):
     t = text.tobytes().decode("ascii")
     return [t[int(a):int(b)] for a, b in zip(offsets[:-1], offsets[1:])]

@@ -69,6 +69,52 @@ private:
     bool timed_                = false;
 };
 
+/// what get_alignment_extension() finds
+class ExtensionAlignment : public AlignmentImpl
+{
+public:
+    using AlignmentImpl::AlignmentImpl;
+    Extension extension{-1, -1, -1, false};
+};
+
+/// The affine X-drop extension (gwhip_extend of include/gwhip_affine.h) behind FixedLimitAligner's limits, statuses and
+/// life cycle; the memory rule of add_alignment() is AlignerGlobalAffine's, with the extension's bit matrix: about
+/// min(n + m, 2 min(n, m) + band_width) * band_width bytes a pair.
+class AlignerExtension : public FixedLimitAligner
+{
+public:
+    /// max_device_memory < 0: the allocator's largest free block
+    AlignerExtension(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments, ExtensionScoring scoring,
+                     int32_t band_width, int32_t xdrop, int64_t max_device_memory, DefaultDeviceAllocator allocator,
+                     cudaStream_t stream, int32_t device_id);
+    ~AlignerExtension() override;
+
+    StatusType add_alignment(const char* query, int32_t query_length, const char* target, int32_t target_length,
+                             bool reverse_complement_query = false, bool reverse_complement_target = false) override;
+    StatusType align_all() override;
+    StatusType sync_alignments() override;
+    void reset() override;
+
+    /// measurement aid: HIP-event times of the last align_all() -- the forward pass and the traceback; false before one
+    bool last_stage_ms(float* forward_ms, float* traceback_ms);
+
+private:
+    void free_device() override;
+    int64_t device_bytes(int64_t pairs, int64_t bases, int64_t bit_bytes) const;
+
+    ExtensionScoring scoring_;
+    int32_t band_width_, xdrop_;
+    int64_t max_device_memory_;
+    int64_t bit_bytes_ = 0; ///< of the queued pairs' bit matrices
+    PinnedVector<int8_t> results_h_;
+    PinnedVector<int32_t> numbers_h_; ///< [4 n]: lengths, scores, query ends, target ends
+    PinnedVector<uint8_t> dropped_h_;
+    char* device_block_        = nullptr;
+    size_t device_block_bytes_ = 0;
+    hipEvent_t events_[3]      = {nullptr, nullptr, nullptr};
+    bool timed_                = false;
+};
+
 } // namespace cudaaligner
 } // namespace genomeworks
 } // namespace claraparabricks

@@ -453,6 +453,19 @@ gw_aligner* gw_aligner_create_affine2(int32_t max_query_length, int32_t max_targ
     GW_CATCH(nullptr)
 }
 
+gw_aligner* gw_aligner_create_extension(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments, int32_t match,
+                                        int32_t mismatch, int32_t gap_open, int32_t gap_extend, int32_t band_width, int32_t xdrop,
+                                        void* stream, int32_t device_id, int64_t max_device_memory)
+{
+    GW_TRY
+    auto h     = std::make_unique<gw_aligner>();
+    h->aligner = aln::create_aligner_extension(max_query_length, max_target_length, max_alignments,
+                                               aln::ExtensionScoring{match, mismatch, gap_open, gap_extend}, band_width, xdrop,
+                                               static_cast<cudaStream_t>(stream), device_id, max_device_memory);
+    return h.release();
+    GW_CATCH(nullptr)
+}
+
 gw_aligner* gw_aligner_create_algorithm(const char* algorithm, int32_t max_query_length, int32_t max_target_length,
                                         int32_t max_alignments, void* stream, int32_t device_id, int64_t max_device_memory)
 {
@@ -555,6 +568,17 @@ int32_t gw_alignment_cost(gw_aligner* a, int32_t i)
     return aln::get_alignment_cost(*a->aligner->get_alignments().at(static_cast<size_t>(i)));
     GW_CATCH(-1)
 }
+int gw_alignment_extension(gw_aligner* a, int32_t i, int32_t out[4])
+{
+    GW_TRY
+    const aln::Extension e = aln::get_alignment_extension(*a->aligner->get_alignments().at(static_cast<size_t>(i)));
+    out[0]                 = e.query_end;
+    out[1]                 = e.target_end;
+    out[2]                 = e.score;
+    out[3]                 = e.dropped ? 1 : 0;
+    return 0;
+    GW_CATCH(-1)
+}
 int gw_aligner_stage_ms(gw_aligner* a, float* ends_ms, float* traceback_ms)
 {
     GW_TRY
@@ -563,6 +587,17 @@ int gw_aligner_stage_ms(gw_aligner* a, float* ends_ms, float* traceback_ms)
     if (auto* affine = dynamic_cast<aln::AlignerGlobalAffine*>(a->aligner.get())) // its forward pass and its traceback
     {
         if (!affine->last_stage_ms(&ends, &traceback))
+        {
+            gwhost::set_last_error("gw_aligner_stage_ms: no align_all() to report");
+            return -1;
+        }
+        if (ends_ms) *ends_ms = ends;
+        if (traceback_ms) *traceback_ms = traceback;
+        return 0;
+    }
+    if (auto* extension = dynamic_cast<aln::AlignerExtension*>(a->aligner.get())) // likewise
+    {
+        if (!extension->last_stage_ms(&ends, &traceback))
         {
             gwhost::set_last_error("gw_aligner_stage_ms: no align_all() to report");
             return -1;

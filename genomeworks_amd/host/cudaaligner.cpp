@@ -669,6 +669,8 @@ std::unique_ptr<Aligner> create_aligner(int32_t max_query_length, int32_t max_ta
                                         AlignmentType type, DefaultDeviceAllocator allocator, cudaStream_t stream,
                                         int32_t device_id)
 {
+    if (type == AlignmentType::extension_alignment)
+        throw std::invalid_argument("extension_alignment takes a scoring, a band and an xdrop: use create_aligner_extension.");
     if (type != AlignmentType::global_alignment && type != AlignmentType::infix_alignment && type != AlignmentType::prefix_alignment)
         throw std::runtime_error("Aligner for specified type not implemented yet.");
     throw_on_negative(max_query_length, "max_query_length must be non-negative.");

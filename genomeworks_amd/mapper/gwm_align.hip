@@ -491,3 +491,248 @@ int align_overlaps(const gwm_overlap* overlaps, int64_t n, const char* query_bas
 }
 
 } // namespace
+
+// ---- extend_overlaps: the ends of overlaps moved by the affine X-drop extension (gwm_extend_overlaps) --------------------
+// Per chunk of consecutive overlaps: four slices an overlap (in front of the head and behind the tail, of the query and of
+// the target in the target's strand coordinates), gathered as two pairs an overlap into the layout gwhip_extend takes,
+// extended in score-only mode, and the ends applied to the records in place. Neither bases nor states exist outside the
+// device; the host reads the records' slice starts to size the chunks.
+namespace
+{
+
+// the lengths of overlap x's four slices: head query, head target, tail query, tail target (strand coordinates)
+__device__ __forceinline__ void extension_lengths(const gwm_overlap& x, const ReadSet& q, const ReadSet& t, int64_t most,
+                                                  int64_t (&len)[4])
+{
+    const uint32_t qi = x.query_read_id - q.first_read_id, ti = x.target_read_id - t.first_read_id;
+    const int64_t ql = q.offsets[qi + 1] - q.offsets[qi], tl = t.offsets[ti + 1] - t.offsets[ti];
+    const int64_t before = x.target_start_position_in_read, behind = tl - x.target_end_position_in_read;
+    const bool minus     = x.relative_strand == '-';
+    len[0] = min(most, static_cast<int64_t>(x.query_start_position_in_read));
+    len[1] = min(most, minus ? behind : before);
+    len[2] = min(most, ql - x.query_end_position_in_read);
+    len[3] = min(most, minus ? before : behind);
+}
+
+// lengths[4 i + s]: bases of slice s of overlap i of the chunk; lengths[4 m] = 0, so that the exclusive scan ends with the total
+__global__ void __launch_bounds__(kThreads) extension_lengths_kernel(const gwm_overlap* __restrict__ o, int64_t m, ReadSet q,
+                                                                     ReadSet t, int64_t most, int64_t* __restrict__ lengths)
+{
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i > m)
+        return;
+    if (i == m)
+    {
+        lengths[4 * m] = 0;
+        return;
+    }
+    int64_t len[4];
+    extension_lengths(o[i], q, t, most, len);
+    for (int s = 0; s < 4; ++s)
+        lengths[4 * i + s] = len[s];
+}
+
+// Block b writes slice b & 3 of overlap b >> 2 to sequences[starts[b] .. starts[b + 1]). Reversal and complement are two
+// switches: a head slice is read back to front, a tail slice front to back, in the strand's coordinates; on '-' the
+// target's strand coordinates run against its bytes, which flips the direction and takes the complement.
+__global__ void __launch_bounds__(kThreads) extension_gather_kernel(const gwm_overlap* __restrict__ o, ReadSet qs, ReadSet ts,
+                                                                    const int64_t* __restrict__ starts,
+                                                                    uint8_t* __restrict__ sequences)
+{
+    const int64_t b     = blockIdx.x;
+    const gwm_overlap x = o[b >> 2];
+    const bool target = (b & 1) != 0, tail = (b & 2) != 0;
+    const bool minus  = target && x.relative_strand == '-';
+    const ReadSet& set  = target ? ts : qs;
+    const uint32_t read = (target ? x.target_read_id : x.query_read_id) - set.first_read_id;
+    const int64_t at = starts[b], len = starts[b + 1] - at;
+    const int64_t start = target ? x.target_start_position_in_read : x.query_start_position_in_read;
+    const int64_t end   = target ? x.target_end_position_in_read : x.query_end_position_in_read;
+    // the slice lies in front of `start` or behind `end` of the bytes; on '-' the head lies behind and the tail in front
+    const bool in_front = tail == minus;
+    const uint8_t* src  = set.bases + set.offsets[read] + (in_front ? start - len : end);
+    const bool reversed = in_front; // read towards the overlap's far side: away from the overlap
+    if (minus)
+        copy_slice(sequences + at, src, len, reversed, Complement{}, Complement{});
+    else
+        copy_slice(sequences + at, src, len, reversed, AsItIs{}, AsItIs{});
+}
+
+// the ends of pairs 2 i (head) and 2 i + 1 (tail) applied to overlap i; a pair without a result moves nothing
+__global__ void __launch_bounds__(kThreads) extension_apply_kernel(gwm_overlap* __restrict__ o, int64_t m,
+                                                                   const int32_t* __restrict__ pair_scores,
+                                                                   const int32_t* __restrict__ query_ends,
+                                                                   const int32_t* __restrict__ target_ends,
+                                                                   int32_t* __restrict__ extensions, int32_t* __restrict__ scores)
+{
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= m)
+        return;
+    gwm_overlap x = o[i];
+    uint32_t moved[4];
+    for (int end = 0; end < 2; ++end)
+    {
+        const bool has = pair_scores[2 * i + end] >= 0;
+        moved[2 * end]     = has ? static_cast<uint32_t>(query_ends[2 * i + end]) : 0u;
+        moved[2 * end + 1] = has ? static_cast<uint32_t>(target_ends[2 * i + end]) : 0u;
+        scores[2 * i + end] = has ? pair_scores[2 * i + end] : 0;
+    }
+    x.query_start_position_in_read -= moved[0];
+    x.query_end_position_in_read += moved[2];
+    if (x.relative_strand == '-')
+    {
+        x.target_end_position_in_read += moved[1];
+        x.target_start_position_in_read -= moved[3];
+    }
+    else
+    {
+        x.target_start_position_in_read -= moved[1];
+        x.target_end_position_in_read += moved[3];
+    }
+    o[i] = x;
+    for (int k = 0; k < 4; ++k)
+        extensions[4 * i + k] = static_cast<int32_t>(moved[k]);
+}
+
+// device bytes of one chunk of m overlaps whose four slices each hold `bases` bases in all: gathered bases, slice lengths
+// and starts, and scores, ends and flags of 2 m pairs
+inline int64_t extension_chunk_bytes(int64_t m, int64_t bases)
+{
+    return bases + kPad + 2 * (4 * m + 1) * 8 + 2 * m * (3 * 4 + 1) + 5 * 256;
+}
+
+void extend_overlaps(gwm_overlap* overlaps, int64_t n, const ReadSet& q, const ReadSet& t, const gwm_extension& e,
+                     int32_t max_extension, int64_t max_device_bytes, hipStream_t s, int32_t* extensions, int32_t* scores)
+{
+    const std::string who = "gwm_extend_overlaps: ";
+    {
+        dbuf<uint32_t> bad(1);
+        GWM_CHECK(hipMemsetAsync(bad.p, 0, sizeof(uint32_t), s));
+        align_validate_kernel<<<grid_for(n), kThreads, 0, s>>>(overlaps, n, q, t, bad.p);
+        GWM_CHECK(hipGetLastError());
+        const uint32_t what = to_host(bad.p, s);
+        if (what & 1u)
+            throw std::invalid_argument(who + "an overlap names a read outside the read set");
+        if (what & 4u)
+            throw std::invalid_argument(who + "an overlap starts behind its end");
+        if (what & 2u)
+            throw std::invalid_argument(who + "an overlap lies beyond the end of its read");
+    }
+    if (max_extension == 0)
+    {
+        GWM_CHECK(hipMemsetAsync(extensions, 0, sizeof(int32_t) * 4 * static_cast<size_t>(n), s));
+        GWM_CHECK(hipMemsetAsync(scores, 0, sizeof(int32_t) * 2 * static_cast<size_t>(n), s));
+        GWM_CHECK(hipStreamSynchronize(s));
+        return;
+    }
+    Temp temp;
+    dbuf<int64_t> lengths(4 * n + 1), starts(4 * n + 1);
+    // the slice starts of the whole call on the host, for sizing only
+    extension_lengths_kernel<<<grid_for(n + 1), kThreads, 0, s>>>(overlaps, n, q, t, max_extension, lengths.p);
+    GWM_CHECK(hipGetLastError());
+    exclusive_sum(lengths.p, starts.p, 4 * n + 1, temp, s);
+    std::vector<int64_t> host_starts(static_cast<size_t>(4 * n + 1));
+    GWM_CHECK(hipMemcpyAsync(host_starts.data(), starts.p, sizeof(int64_t) * host_starts.size(), hipMemcpyDeviceToHost, s));
+    GWM_CHECK(hipStreamSynchronize(s));
+    int64_t budget = max_device_bytes;
+    if (budget == 0)
+    {
+        size_t free_bytes = 0, total_bytes = 0;
+        GWM_CHECK(hipMemGetInfo(&free_bytes, &total_bytes));
+        budget = static_cast<int64_t>(free_bytes / 2);
+    }
+    auto cost = [&](int64_t first, int64_t m) {
+        return extension_chunk_bytes(m, host_starts[4 * (first + m)] - host_starts[4 * first]);
+    };
+    dbuf<uint8_t> sequences, dropped;
+    dbuf<int32_t> numbers;
+    for (int64_t first = 0; first < n;)
+    {
+        if (cost(first, 1) > budget)
+            throw std::invalid_argument(who + "overlap " + std::to_string(first) + " needs " + std::to_string(cost(first, 1)) +
+                                        " device bytes, max_device_bytes allows " + std::to_string(budget));
+        // the longest run of overlaps from `first` within the budget: the cost grows with m, so bisection finds it
+        int64_t m = 1, too_many = std::min(n - first, kMaxChunk / 2) + 1;
+        while (too_many - m > 1)
+        {
+            const int64_t mid = m + (too_many - m) / 2;
+            if (cost(first, mid) <= budget)
+                m = mid;
+            else
+                too_many = mid;
+        }
+        const int64_t* hs   = host_starts.data() + 4 * first;
+        const int64_t bases = hs[4 * m] - hs[0];
+        gwm_overlap* o      = overlaps + first;
+        grow(sequences, bases + kPad);
+        grow(numbers, 3 * 2 * m);
+        grow(dropped, 2 * m);
+        // the chunk's own starts, from 0
+        extension_lengths_kernel<<<grid_for(m + 1), kThreads, 0, s>>>(o, m, q, t, max_extension, lengths.p);
+        GWM_CHECK(hipGetLastError());
+        exclusive_sum(lengths.p, starts.p, 4 * m + 1, temp, s);
+        extension_gather_kernel<<<static_cast<unsigned>(4 * m), kThreads, 0, s>>>(o, q, t, starts.p, sequences.p);
+        GWM_CHECK(hipGetLastError());
+        gwhip_extend_args a{};
+        a.n_alignments         = static_cast<int32_t>(2 * m);
+        a.sequences            = reinterpret_cast<const char*>(sequences.p);
+        a.sequence_starts      = starts.p;
+        a.sequence_starts_host = hs;
+        a.match                = e.match;
+        a.mismatch             = e.mismatch;
+        a.gap_open             = e.gap_open;
+        a.gap_extend           = e.gap_extend;
+        a.band                 = e.band;
+        a.xdrop                = e.xdrop;
+        a.scores               = numbers.p;
+        a.query_ends           = numbers.p + 2 * m;
+        a.target_ends          = numbers.p + 4 * m;
+        a.dropped              = dropped.p;
+        if (gwhip_extend(&a, s) != 0) // score-only mode: no results, no workspace
+            throw std::runtime_error(who + gwhip_affine_last_error());
+        extension_apply_kernel<<<grid_for(m), kThreads, 0, s>>>(o, m, a.scores, a.query_ends, a.target_ends, extensions + 4 * first,
+                                                                scores + 2 * first);
+        GWM_CHECK(hipGetLastError());
+        first += m;
+    }
+    GWM_CHECK(hipStreamSynchronize(s));
+}
+
+} // namespace
+
+extern "C" int gwm_extend_overlaps(gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                                   int32_t n_queries, uint32_t first_query_read_id, const char* target_bases,
+                                   const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
+                                   const gwm_extension* extension, int32_t max_extension, int64_t max_device_bytes, void* stream,
+                                   int32_t* extensions, int32_t* scores)
+{
+    try
+    {
+        check_chunk_arguments("gwm_extend_overlaps", n_queries, n_targets, max_device_bytes, n);
+        if (extension == nullptr)
+            throw std::invalid_argument("gwm_extend_overlaps: no extension parameters");
+        const gwm_extension& e = *extension;
+        if (e.match < 1 || e.mismatch < 0 || int64_t(e.match) + e.mismatch > 127 || e.gap_open < 0 || e.gap_open > 127 ||
+            e.gap_extend < 1 || e.match + 2 * int64_t(e.gap_extend) > 255 || e.band < 0 || e.band > GWHIP_EXTEND_MAX_BAND ||
+            e.xdrop < -1 || e.xdrop > GWHIP_EXTEND_MAX_XDROP)
+            throw std::invalid_argument("gwm_extend_overlaps: extension (match " + std::to_string(e.match) + ", mismatch " +
+                                        std::to_string(e.mismatch) + ", gap_open " + std::to_string(e.gap_open) + ", gap_extend " +
+                                        std::to_string(e.gap_extend) + ", band " + std::to_string(e.band) + ", xdrop " +
+                                        std::to_string(e.xdrop) + ") out of the ranges of gwhip_extend");
+        if (max_extension < 0 || max_extension > (1 << 19))
+            throw std::invalid_argument("gwm_extend_overlaps: max_extension " + std::to_string(max_extension) + " outside 0..2^19");
+        if (n <= 0)
+            return 0;
+        if (overlaps == nullptr || extensions == nullptr || scores == nullptr)
+            throw std::invalid_argument("gwm_extend_overlaps: a null pointer among the arguments");
+        extend_overlaps(overlaps, n, read_set(query_bases, query_offsets, n_queries, first_query_read_id),
+                        read_set(target_bases, target_offsets, n_targets, first_target_read_id), e, max_extension,
+                        max_device_bytes, static_cast<hipStream_t>(stream), extensions, scores);
+        return 0;
+    }
+    catch (const std::exception& e)
+    {
+        gwm_set_error(e.what());
+        return -1;
+    }
+}

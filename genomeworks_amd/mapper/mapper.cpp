@@ -484,6 +484,35 @@ int gw_mapper_rescue_overlap_ends(void* overlaps, int64_t n, const char* query_b
     }, GW_MAPPER_ERROR);
 }
 
+int gw_mapper_extend_overlaps(void* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                              int32_t n_queries, const char* target_bases, const int64_t* target_offsets, int32_t n_targets,
+                              uint32_t first_query_read_id, uint32_t first_target_read_id, const int32_t* extension,
+                              int32_t max_extension, int64_t max_device_bytes, void* stream, int32_t* extensions,
+                              int32_t* scores)
+{
+    return guarded([&] {
+        if (extension == nullptr)
+            throw std::invalid_argument("gw_mapper_extend_overlaps: no extension parameters");
+        const gwm_extension e{extension[0], extension[1], extension[2], extension[3], extension[4], extension[5]};
+        // without overlaps nothing is uploaded, and the argument checks still apply
+        device_call c({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets}, overlaps, n,
+                      false);
+        dbuf<int32_t> moved, score;
+        if (n > 0)
+        {
+            moved.resize(4 * n);
+            score.resize(2 * n);
+        }
+        throw_on(gwm_extend_overlaps(c.d.p, n, c.q.bases, c.q.offsets, c.reads.queries.n, first_query_read_id, c.t.bases,
+                                     c.t.offsets, c.reads.targets.n, first_target_read_id, &e, max_extension, max_device_bytes,
+                                     stream, moved.p, score.p));
+        copy_out(static_cast<gwm_overlap*>(overlaps), c.d.p, n);
+        copy_out(extensions, moved.p, 4 * n);
+        copy_out(scores, score.p, 2 * n);
+        return 0;
+    }, GW_MAPPER_ERROR);
+}
+
 int64_t gw_mapper_group_reads_into_indices(const int64_t* read_lengths, int64_t n_reads, int64_t max_basepairs_per_index,
                                            uint32_t* out, int64_t capacity)
 {

@@ -63,6 +63,44 @@ std::unique_ptr<Aligner> create_aligner_affine(int32_t max_query_length, int32_t
 /// The cost of an alignment made by an affine aligner; -1 for one without a result and for other aligners' alignments.
 int32_t get_alignment_cost(const Alignment& alignment);
 
+/// Scores of the affine X-drop extension, maximised: a match scores +match, a mismatch -mismatch, a gap run of L columns
+/// -(gap_open + L * gap_extend). match >= 1, mismatch >= 0, match + mismatch <= 127, 0 <= gap_open <= 127,
+/// gap_extend >= 1, match + 2 * gap_extend <= 255. The defaults are minimap2's -A2 -B4 -O4 -E2, conventions and not tuned.
+struct ExtensionScoring
+{
+    int32_t match      = 2;
+    int32_t mismatch   = 4;
+    int32_t gap_open   = 4;
+    int32_t gap_extend = 2;
+};
+
+/// An aligner with the limits and statuses of create_aligner(max_query_length, max_target_length, max_alignments, ...)
+/// whose alignments are extension_alignment: from the first base of both sequences a prefix of the query is aligned with
+/// a prefix of the target, within band_width (0 .. 511) diagonals on either side of the start's, and the extension
+/// stops once the best score of two neighbouring anti-diagonals lies more than xdrop (0 .. 2^20; -1: never) below the
+/// best score so far (include/gwhip_affine.h states the rules). An alignment has status success, is_optimal() false
+/// (nothing is proven), the count of its non-match columns as edit distance, and a CIGAR over the aligned prefixes only;
+/// get_alignment_extension names them. Throws std::invalid_argument for a scoring, band_width or xdrop out of range.
+std::unique_ptr<Aligner> create_aligner_extension(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments,
+                                                  ExtensionScoring scoring, int32_t band_width, int32_t xdrop,
+                                                  DefaultDeviceAllocator allocator, cudaStream_t stream, int32_t device_id);
+/// The same with an allocator of max_device_memory bytes (-1: the largest free section of the device).
+std::unique_ptr<Aligner> create_aligner_extension(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments,
+                                                  ExtensionScoring scoring, int32_t band_width, int32_t xdrop, cudaStream_t stream,
+                                                  int32_t device_id, int64_t max_device_memory = -1);
+
+/// Where an extension ended: query[0:query_end] is aligned with target[0:target_end] at `score`; dropped says that the
+/// stop rule ended it before the band's last anti-diagonal.
+struct Extension
+{
+    int32_t query_end, target_end, score;
+    bool dropped;
+};
+
+/// Of an alignment made by an extension aligner; all -1 (dropped false) for one without a result and for other
+/// aligners' alignments.
+Extension get_alignment_extension(const Alignment& alignment);
+
 } // namespace cudaaligner
 } // namespace genomeworks
 } // namespace claraparabricks

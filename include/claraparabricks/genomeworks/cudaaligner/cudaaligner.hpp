@@ -27,7 +27,10 @@ enum AlignmentType
     /// (not in the reference) the whole query against the best-matching slice T[target_begin:target_end] of the target
     infix_alignment,
     /// (not in the reference) the whole query against the best-matching prefix T[0:target_end] of the target
-    prefix_alignment
+    prefix_alignment,
+    /// (not in the reference) a prefix of the query against a prefix of the target, from (0, 0) to where the similarity
+    /// stops: create_aligner_extension (cudaaligner/aligner_affine.hpp) makes these, create_aligner does not
+    extension_alignment
 };
 
 /// One position of an alignment.

@@ -209,6 +209,14 @@ gw_aligner* gw_aligner_create_affine(int32_t max_query_length, int32_t max_targe
 gw_aligner* gw_aligner_create_affine2(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments, int32_t mismatch,
                                       int32_t gap_open, int32_t gap_extend, int32_t gap_open2, int32_t gap_extend2, int32_t band_width,
                                       void* stream, int32_t device_id, int64_t max_device_memory);
+/* create_aligner_extension (cudaaligner/aligner_affine.hpp): the affine X-drop extension. Scores are maximised (match >= 1,
+   mismatch >= 0, match + mismatch <= 127, gap_open 0..127, gap_extend >= 1, match + 2 gap_extend <= 255); band_width 0..511
+   diagonals on either side of the start's; xdrop 0..2^20, or -1 for "never stop"; include/gwhip_affine.h states the rules.
+   Its alignments are extension_alignment (4), never optimal, and cover the prefixes that gw_alignment_extension names. What
+   gw_aligner_create_affine says about device-resident results and gw_aligner_stage_ms holds here. NULL on error. */
+gw_aligner* gw_aligner_create_extension(int32_t max_query_length, int32_t max_target_length, int32_t max_alignments, int32_t match,
+                                        int32_t mismatch, int32_t gap_open, int32_t gap_extend, int32_t band_width, int32_t xdrop,
+                                        void* stream, int32_t device_id, int64_t max_device_memory);
 void gw_aligner_destroy(gw_aligner* a);
 int gw_aligner_add_alignment(gw_aligner* a, const char* query, int32_t query_length, const char* target,
                              int32_t target_length, int reverse_complement_query, int reverse_complement_target);
@@ -223,6 +231,9 @@ int32_t gw_alignment_edit_distance(gw_aligner* a, int32_t i);
 int32_t gw_alignment_type(gw_aligner* a, int32_t i); /* Alignment::get_alignment_type() */
 /* get_alignment_cost(): the cost of an affine aligner's alignment; -1 without a result, for other aligners and on error */
 int32_t gw_alignment_cost(gw_aligner* a, int32_t i);
+/* get_alignment_extension(): out = query_end, target_end, score, dropped of an extension aligner's alignment; -1, -1, -1, 0
+   without a result and for other aligners. 0, or -1 on error. */
+int gw_alignment_extension(gw_aligner* a, int32_t i, int32_t out[4]);
 /* Alignment::get_target_begin() / get_target_end(): 0 and the target's length for a global alignment. 0, or -1 on error. */
 int gw_alignment_target_range(gw_aligner* a, int32_t i, int32_t* begin, int32_t* end);
 /* infix / prefix aligners, measurement aid: HIP-event times (ms) of the last align_all() -- the ends scan, and the gather of

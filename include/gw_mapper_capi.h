@@ -96,6 +96,17 @@ int gw_mapper_rescue_overlap_ends(void* overlaps, int64_t n, const char* query_b
                                   int32_t n_targets, uint32_t first_query_read_id, uint32_t first_target_read_id,
                                   int32_t extension, float required_similarity, void* stream, float* rescue_ms);
 
+/* gwm_extend_overlaps of gwhip_mapper.h over n host overlaps, in place: the ends moved by the affine X-drop extension.
+   Reads and read ids as for gw_mapper_rescue_overlap_ends. extension[0..5] = match, mismatch, gap_open, gap_extend, band,
+   xdrop; 0 <= max_extension <= 2^19. extensions: host, [n][4] = head q, head t, tail q, tail t; scores: host, [n][2]. On an
+   error (GW_MAPPER_ERROR: a value out of range, a read id outside its set, an overlap beyond its read) the overlaps are
+   left as they were. */
+int gw_mapper_extend_overlaps(void* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                              int32_t n_queries, const char* target_bases, const int64_t* target_offsets, int32_t n_targets,
+                              uint32_t first_query_read_id, uint32_t first_target_read_id, const int32_t* extension,
+                              int32_t max_extension, int64_t max_device_bytes, void* stream, int32_t* extensions,
+                              int32_t* scores);
+
 /* CIGARs of n host overlaps over host reads (uploaded for the call; target_bases NULL means the target set is the
    query set): gwm_align_overlaps of gwhip_mapper.h, which states slices, strand, complement, aligner and text format.
    A read id outside its set, start > end or an end beyond its read is an error (NULL). The CIGARs stay on the device

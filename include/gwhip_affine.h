@@ -5,7 +5,9 @@
  * The object-level API on top of it is cudaaligner::create_aligner_affine (C++, cudaaligner/aligner_affine.hpp),
  * gw_aligner_create_affine (gw_capi.h) and CudaAlignerBatch(algorithm="affine") (Python); cudamapper reaches it through
  * gwm_align_overlaps_scored / gwm_overlap_variants_scored (gwhip_mapper.h). This header is kept apart from gwhip.h on
- * purpose, as gwhip_semiglobal.h is: the POA / aligner kernel set and its source digest are not affected by it.
+ * purpose, as gwhip_semiglobal.h is: the POA / aligner kernel set and its source digest are not affected by it. The
+ * affine X-drop extension of the same library (gwhip_extend; create_aligner_extension, gw_aligner_create_extension,
+ * CudaAlignerBatch(algorithm="extend")) is stated at the end of this header.
  *
  * Rules (genomeworks_amd/affine/gwaffine_rules.h is their code). Query Q of n bases,
  * target T of m bases; q matches t when q == "ACTG"[(t >> 1) & 3]. Costs are minimised: match 0, mismatch x, a gap
@@ -107,6 +109,57 @@ size_t gwhip_affine2_workspace_bytes(int32_t n_alignments, const int64_t* sequen
    gwhip_affine2_workspace_bytes()), nothing launched for an empty batch. Errors: gwhip_affine_last_error. */
 int gwhip_affine2_align(const gwhip_affine2_args* args, void* stream);
 int gwhip_affine2_align_events(const gwhip_affine2_args* args, void* stream, void* const events[3]);
+
+/* ---- affine X-drop extension (genomeworks_amd/affine/gwaffine_extend_rules.h is its code) ------
+ * Not a global alignment: it starts at cell (0, 0) of Q and T and stops where the similarity stops. Scores are
+ * maximised: match +a, mismatch -x, a gap run of L columns -(o + L e). It is the DP above under the derived costs
+ * x' = 2 (a + x), o' = 2 o, e' = a + 2 e: the best score of Q[:i] with T[:j] is (a (i + j) - H'[i][j]) / 2, and the cell
+ * update, its ties and the cell's byte are the one-piece ones. The band is d = j - i in [-B, B] whatever n and m are;
+ * the last anti-diagonal with a cell is a_max = min(n + m, 2 min(n, m) + B).
+ * Stop rule, per anti-diagonal A = i + j, in the doubled score D = a (i + j) - H': top(A) is the largest D of A's cells,
+ * best the largest D so far, A included. After A >= 1 with xdrop >= 0: when max(top(A), top(A - 1)) < best - 2 xdrop the
+ * extension stops, dropped = 1, and no later anti-diagonal counts. The end cell is the cell of largest D up to there,
+ * on ties the smallest anti-diagonal, then the smallest d; (0, 0) with score 0 is always a candidate. The states of the
+ * path from the end cell back to (0, 0) are written back to front, as above. A pair with n + m >= 2^21, or one that does
+ * not fit the workspace given, gets score -1, ends -1, length 0. */
+#define GWHIP_EXTEND_MAX_BAND 511
+#define GWHIP_EXTEND_MAX_XDROP (1 << 20)
+
+typedef struct gwhip_extend_args
+{
+    int32_t n_alignments;
+    const char* sequences;               /* as gwhip_affine_args: device, q0 t0 q1 t1 ... */
+    const int64_t* sequence_starts;      /* device, [2n + 1] */
+    const int64_t* sequence_starts_host; /* host, [2n + 1] */
+    int32_t match;                       /* a >= 1 */
+    int32_t mismatch;                    /* x >= 0, a + x <= 127 */
+    int32_t gap_open;                    /* o in 0 .. 127 */
+    int32_t gap_extend;                  /* e >= 1, a + 2 e <= 255 */
+    int32_t band;                        /* B in 0 .. GWHIP_EXTEND_MAX_BAND */
+    int32_t xdrop;                       /* X in 0 .. GWHIP_EXTEND_MAX_XDROP, or -1: never stop */
+    int8_t* results;                     /* device, states BACK TO FRONT in the pair's slot as above; NULL: score-only mode,
+                                            no bit is written, no traceback runs, result_lengths and workspace may be NULL */
+    int32_t* result_lengths;             /* device, [n]: columns of the path from the end cell; 0 = none */
+    int32_t* scores;                     /* device, [n]: the end cell's score; -1 = no result */
+    int32_t* query_ends;                 /* device, [n]: i of the end cell, Q[:i] is aligned; -1 = no result */
+    int32_t* target_ends;                /* device, [n]: j of the end cell; -1 = no result */
+    uint8_t* dropped;                    /* device, [n]: 1 when the stop rule ended the extension before a_max */
+    void* workspace;                     /* device, gwhip_extend_workspace_bytes(..., 1) */
+    size_t workspace_bytes;
+} gwhip_extend_args;
+
+/* with_traceback != 0: 8 (n + 1) bytes of offsets and, per pair with n + m < 2^21, (a_max + 1) * roundup4((2 B + 3) / 2)
+   bytes, each part rounded up to 256. with_traceback == 0: 0, score-only mode needs no workspace. Arguments that no call
+   would be accepted with (n_alignments <= 0, no sequence_starts_host, a band outside 0 .. GWHIP_EXTEND_MAX_BAND, starts that
+   do not ascend) give 256, the size of an empty batch's offsets, as gwhip_affine_workspace_bytes does. */
+size_t gwhip_extend_workspace_bytes(int32_t n_alignments, const int64_t* sequence_starts_host, int32_t band, int32_t with_traceback);
+
+/* Offsets, forward pass and traceback (one wave64 per pair each; the forward pass alone in score-only mode), asynchronous
+   on `stream`. A value out of range, a missing pointer and a workspace smaller than gwhip_extend_workspace_bytes() are
+   refused before anything is launched; an empty batch launches nothing. Returns 0 or a hipError_t as int
+   (gwhip_affine_last_error). gwhip_extend_events records the caller's three HIP events as gwhip_affine_align_events. */
+int gwhip_extend(const gwhip_extend_args* args, void* stream);
+int gwhip_extend_events(const gwhip_extend_args* args, void* stream, void* const events[3]);
 
 const char* gwhip_affine_last_error(void);
 

@@ -243,6 +243,34 @@ int gwm_align_overlaps_scored(const gwm_overlap* overlaps, int64_t n, const char
 /* gwm_align_bytes_needed for a call with a scoring of this band. Host arithmetic only. */
 int64_t gwm_align_bytes_needed_scored(int32_t query_length, int32_t target_length, int32_t band);
 
+/* Scores, band and X-drop of the affine X-drop extension (include/gwhip_affine.h, gwhip_extend; INTEGRATION.md section
+ * 3q), in gwhip_extend_args' ranges. */
+typedef struct gwm_extension
+{
+    int32_t match;
+    int32_t mismatch;
+    int32_t gap_open;
+    int32_t gap_extend;
+    int32_t band;
+    int32_t xdrop;
+} gwm_extension;
+
+/* Moves the ends of device overlaps[0..n) in place over what the affine X-drop extension aligns beyond them. With reads of
+ * Lq and Lt bases and M = max_extension (0 .. 2^19), in the target's strand coordinates (T' = T on '+'; on '-' its reverse
+ * complement by the aligner's table, [ts', te') = [Lt - te, Lt - ts)): the tail extends Q[qe : qe + min(M, Lq - qe)]
+ * against T'[te' : te' + min(M, Lt - te')], then qe += i*, te' += j*; the head extends the slices of the same caps in
+ * front of qs and ts', both read back to front, then qs -= i*, ts' -= j*; on '-' ts', te' are mapped back. Every other
+ * field of a record stays. The 2 n pairs go through gwhip_extend in score-only mode, chunk by chunk within
+ * max_device_bytes (0: half of the free device memory; the result does not depend on it; an overlap that does not fit
+ * alone is an error; a chunk of m overlaps counts its gathered bases + 90 m + 1360 bytes). extensions: device, [n][4] = head i*, head j*, tail i*, tail j*; scores: device, [n][2] = head, tail.
+ * M == 0 changes nothing and gives zeros. A read id outside its set, start > end, an end beyond its read and a value out of
+ * range return -1 with gwm_last_error() set before anything is written. Synchronous on `stream` when it returns. */
+int gwm_extend_overlaps(gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                        int32_t n_queries, uint32_t first_query_read_id, const char* target_bases,
+                        const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
+                        const gwm_extension* extension, int32_t max_extension, int64_t max_device_bytes, void* stream,
+                        int32_t* extensions, int32_t* scores);
+
 /* Two-piece gap costs (include/gwhip_affine.h, gwhip_affine2_align): a gap run of L columns
  * costs min(gap_open + L * gap_extend, gap_open2 + L * gap_extend2); both pieces in gwm_scoring's ranges, in any order. */
 typedef struct gwm_scoring2
