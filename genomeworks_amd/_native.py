@@ -230,6 +230,12 @@ def mapper():
         L.gw_mapper_map_batched_cached.restype = vp
         L.gw_mapper_map_batched_cached.argtypes = L.gw_mapper_map_batched.argtypes[:-1] + [i32, i64, i32, i32, i32, i32, vp]
         L.gw_mapper_overlaps_cache_counts.argtypes = [vp, vp, vp, vp]
+        L.gw_mapper_chain_overlaps.restype = i64
+        L.gw_mapper_chain_overlaps.argtypes = [vp, vp, i32, i64, i64, i64, f32, vp, vp, i64, vp, vp]
+        L.gw_mapper_chain_overlaps_host.restype = i64
+        L.gw_mapper_chain_overlaps_host.argtypes = [vp, i64, vp, i32, i64, i64, i64, f32, vp, vp, i64, vp, vp]
+        L.gw_mapper_map_batched_chained.restype = vp
+        L.gw_mapper_map_batched_chained.argtypes = L.gw_mapper_map_batched_cached.argtypes[:-1] + [i32, i32, i32, i32, vp]
         L.gw_mapper_generate_batches_of_indices.restype = i64
         L.gw_mapper_generate_batches_of_indices.argtypes = [vp, i64, vp, i64, i64, i64, i32, i32, i32, i32, vp, i64]
         L.gw_mapper_index_host_copy_create.restype = vp

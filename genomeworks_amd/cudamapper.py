@@ -5,6 +5,7 @@ gfx950), over the flat C API of include/gw_mapper_capi.h.
     matcher = Matcher(index, index)                                # anchors stay on the device
     overlaps = find_overlaps(matcher, all_to_all=True)             # numpy structured array of OVERLAP records
     overlaps = map_reads(reads)                                    # the same in one call
+    overlaps, scores = chain_overlaps(matcher, return_scores=True)  # chaining DP instead; map_reads(overlapper="chained")
     overlaps = post_process_overlaps(overlaps)                     # fuse neighbouring overlaps (the CLI's -D drops)
     overlaps = rescue_overlap_ends(overlaps, reads, reads)         # extend ends over similar flanks (the CLI's -R)
     overlaps = map_reads_batched(reads, max_basepairs_per_index=30_000_000)   # what the cudamapper tool runs
@@ -311,14 +312,74 @@ def find_overlaps(anchors, all_to_all=True, min_residues=3, min_overlap_len=250,
     return out[:n]
 
 
+CHAINING_DEFAULTS = dict(max_gap=5000, bandwidth=500, min_chain_score=40, max_chains=4)  # minimap2's -g -r -m; not tuned
+
+
+def chain_overlaps(anchors, kmer_size=15, max_gap=5000, bandwidth=500, min_chain_score=40, max_chains=4,
+                   all_to_all=True, min_residues=3, min_overlap_len=250, min_bases_per_residue=1000,
+                   min_overlap_fraction=0.8, return_scores=False, stream=None):
+    """The chaining overlapper on a Matcher (device anchors) or on a sorted ANCHOR array (uploaded first): the anchors
+    of every read pair are chained by dynamic programming, '+' and '-' each on their own, over a look-back of 64
+    anchors; up to max_chains chains of at least min_chain_score per pair and orientation become OVERLAP records, which
+    pass the filter of find_overlaps. Rules C1-C8 are in include/gwhip_mapper.h. Where
+    find_overlaps compares an anchor with its neighbour in sort order only, a stray anchor or a second diagonal between
+    two collinear anchors does not cut a chain here, and the strand is the orientation the chain was found in.
+    The defaults of max_gap, bandwidth and min_chain_score are minimap2's conventions (-g, -r, -m) and are not tuned.
+    Returns an OVERLAP array, or (overlaps, int32 chain scores) with return_scores; a Matcher also records the device
+    time in matcher.stage_ms["chain_dp"]. Parameters out of range raise MapperError."""
+    L = _native.mapper()
+    chaining = np.array([kmer_size, max_gap, bandwidth, min_chain_score, max_chains], np.int32)
+    args = (_p(chaining), int(bool(all_to_all)), int(min_residues), int(min_overlap_len), int(min_bases_per_residue),
+            float(min_overlap_fraction))
+    on_device = isinstance(anchors, Matcher)
+    a = None if on_device else np.ascontiguousarray(anchors, ANCHOR)
+    n_anchors = anchors.n_anchors if on_device else len(a)
+    # a record holds at least max(min_residues, 1) anchors, and the chains of one orientation share none
+    capacity = 2 * (n_anchors // max(int(min_residues), 1)) + 1
+    out, scores, ms = np.zeros(capacity, OVERLAP), np.zeros(capacity, np.int32), C.c_float(0.0)
+    if on_device:
+        n = L.gw_mapper_chain_overlaps(anchors._h, *args, _p(out), _p(scores), capacity, C.byref(ms),
+                                       _stream(stream) or anchors._stream)
+    else:
+        n = L.gw_mapper_chain_overlaps_host(_p(a), len(a), *args, _p(out), _p(scores), capacity, C.byref(ms),
+                                            _stream(stream))
+    if n < 0:
+        raise _err(L)
+    if on_device:
+        anchors.stage_ms["chain_dp"] = ms.value
+    return (out[:n], scores[:n]) if return_scores else out[:n]
+
+
+def _overlapper(overlapper, chaining):
+    """the chaining values of a call that names its overlapper: None for "triggered", which takes none"""
+    if overlapper not in ("triggered", "chained"):
+        raise ValueError('overlapper must be "triggered" or "chained", not %r' % (overlapper,))
+    if overlapper == "triggered":
+        if chaining is not None:
+            raise ValueError('chaining parameters are for overlapper="chained"')
+        return None
+    unknown = set(chaining or ()) - set(CHAINING_DEFAULTS)
+    if unknown:
+        raise ValueError("chaining: unknown keys %s" % sorted(unknown))
+    return dict(CHAINING_DEFAULTS, **(chaining or {}))
+
+
 def map_reads(queries, targets=None, k=15, w=10, filtering_parameter=1e-5, min_residues=3, min_overlap_len=250,
-              min_bases_per_residue=1000, min_overlap_fraction=0.8, stream=None):
+              min_bases_per_residue=1000, min_overlap_fraction=0.8, stream=None, overlapper="triggered",
+              chaining=None):
     """Overlaps of `queries` against `targets`, or all against all (self-mappings dropped) when targets is None, with
     hashed representations as in the reference's cudamapper. One index per read set: batching into several indices
-    (the CLI's -i / -t) is the caller's."""
+    (the CLI's -i / -t) is the caller's. overlapper="chained" finds them with chain_overlaps instead of find_overlaps;
+    `chaining` is then a dict of max_gap, bandwidth, min_chain_score and max_chains (chain_overlaps' defaults for
+    those left out), and the k of the chains is `k`. Any other overlapper is a ValueError."""
+    chaining = _overlapper(overlapper, chaining)
     with Index(queries, k, w, True, filtering_parameter, stream=stream) as q, \
             (q if targets is None else Index(targets, k, w, True, filtering_parameter, stream=stream)) as t, \
             Matcher(q, t, stream) as m:
+        if chaining is not None:
+            return chain_overlaps(m, k, all_to_all=targets is None, min_residues=min_residues,
+                                  min_overlap_len=min_overlap_len, min_bases_per_residue=min_bases_per_residue,
+                                  min_overlap_fraction=min_overlap_fraction, stream=stream, **chaining)
         return find_overlaps(m, targets is None, min_residues, min_overlap_len, min_bases_per_residue,
                              min_overlap_fraction, stream)
 
@@ -1013,7 +1074,8 @@ def map_reads_batched(queries, targets=None, k=15, w=10, filtering_parameter=1e-
                       max_basepairs_per_target_index=None, post_process=True, drop_fused_overlaps=False,
                       rescue_overlap_ends=False, stream=None, timings=None, align=False, max_device_bytes=0,
                       query_indices_in_host_memory=1, query_indices_in_device_memory=1,
-                      target_indices_in_host_memory=None, target_indices_in_device_memory=None):
+                      target_indices_in_host_memory=None, target_indices_in_device_memory=None,
+                      overlapper="triggered", chaining=None):
     """What the cudamapper tool does on one device: queries and targets (None: all against all) grouped into indices
     of at most max_basepairs_per_index / max_basepairs_per_target_index bases (the CLI's -i / -t, given there in
     millions), every index pair mapped, its overlaps post-processed (post_process; drop_fused_overlaps is -D) and
@@ -1034,7 +1096,12 @@ def map_reads_batched(queries, targets=None, k=15, w=10, filtering_parameter=1e-
     with overlaps and reads staying on the device, and returns (overlaps, cigars), one CIGAR per overlap; timings
     also gets gather, align, cigar_text and the int32 array edit_distances. A read shorter than k + w - 1 then raises
     before any device work: the index would skip it and shift the read ids behind it, so the wrong sequences would be
-    aligned. (The reference's -a aligns before fusion appends its records; this aligns the records returned.)"""
+    aligned. (The reference's -a aligns before fusion appends its records; this aligns the records returned.)
+
+    overlapper="chained" (the tool's --chain) runs chain_overlaps in the place of find_overlaps in every index pair,
+    with `chaining` as map_reads takes it; everything behind the overlapper stays as it is, and timings'
+    chain_fuse_filter is then the device time of the chaining. Any other overlapper is a ValueError."""
+    chaining = _overlapper(overlapper, chaining)
     L = _native.mapper()
     q, t = _read_set_args(queries, targets)
     t_limit = max_basepairs_per_index if max_basepairs_per_target_index is None else max_basepairs_per_target_index
@@ -1043,8 +1110,13 @@ def map_reads_batched(queries, targets=None, k=15, w=10, filtering_parameter=1e-
             int(bool(post_process)), int(bool(drop_fused_overlaps)), int(bool(rescue_overlap_ends)))
     C_ = query_indices_in_host_memory if target_indices_in_host_memory is None else target_indices_in_host_memory
     c_ = query_indices_in_device_memory if target_indices_in_device_memory is None else target_indices_in_device_memory
-    h = L.gw_mapper_map_batched_cached(*args, int(bool(align)), int(max_device_bytes), int(query_indices_in_host_memory),
-                                       int(query_indices_in_device_memory), int(C_), int(c_), _stream(stream))
+    args += (int(bool(align)), int(max_device_bytes), int(query_indices_in_host_memory),
+             int(query_indices_in_device_memory), int(C_), int(c_))
+    if chaining is None:
+        h = L.gw_mapper_map_batched_cached(*args, _stream(stream))
+    else:
+        h = L.gw_mapper_map_batched_chained(*args, *(int(chaining[name]) for name in (
+            "max_gap", "bandwidth", "min_chain_score", "max_chains")), _stream(stream))
     if not h:
         raise _err(L)
     try:

@@ -9,6 +9,8 @@
 // cg:Z: column. -Q -q -C -c size the index cache as in the reference, with its checks and its two notes about -C / -c;
 // a run without any of them walks one index pair at a time (1, 1, 1, 1), which keeps the order of the PAF lines that
 // this tool has always printed. The reference's defaults (10, 5) apply to those not given once one of them is.
+// --chain (no letter) finds the overlaps of every index pair with the chaining overlapper instead of the triggered
+// one; --chain-max-gap, --chain-bandwidth, --chain-min-score and --chain-max-chains set its parameters.
 #include "gw_mapper_capi.h"
 
 #include <claraparabricks/genomeworks/cudamapper/overlap_alignment.hpp>
@@ -61,6 +63,12 @@ void help(std::FILE* f)
         "  -R, --rescue-overlap-ends    extend the ends of overlaps over similar flanks\n"
         "  -D, --drop-fused-overlaps    remove overlaps which are joined into larger overlaps\n"
         "      --cigar                  align every printed overlap on the device and add its CIGAR as a cg:Z: column\n"
+        "      --chain                  chain the anchors of every read pair by dynamic programming, both strands,\n"
+        "                               instead of the triggered overlapper\n"
+        "      --chain-max-gap          largest step of a chain in query and in target [5000] (needs --chain)\n"
+        "      --chain-bandwidth        largest difference of the two steps [500] (needs --chain)\n"
+        "      --chain-min-score        smallest score of a chain [40] (needs --chain)\n"
+        "      --chain-max-chains       chains per read pair and strand [4] (1..64, needs --chain)\n"
         "  -Q, --query-indices-in-host-memory    query indices kept as packed copies in host memory [10]\n"
         "  -q, --query-indices-in-device-memory  query indices kept in device memory [5]\n"
         "  -C, --target-indices-in-host-memory   target indices kept in host memory [as -Q]\n"
@@ -113,7 +121,9 @@ int main(int argc, char** argv)
     double index_size = 30, target_index_size = 30, filtering_parameter = 1e-5;
     float min_overlap_fraction = 0.8f;
     bool rescue = false, drop = false, custom_filter = false;
-    int cigar = 0;
+    int cigar = 0, chain = 0;
+    int32_t chain_max_gap = 5000, chain_bandwidth = 500, chain_min_score = 40, chain_max_chains = 4;
+    const char* chain_option_given = nullptr; // the first --chain-* option seen
     int32_t query_host = 10, query_device = 5, target_host = 10, target_device = 5;
     bool query_host_set = false, query_device_set = false, target_host_set = false, target_device_set = false;
     const struct option options[] = {
@@ -132,6 +142,11 @@ int main(int argc, char** argv)
         {"rescue-overlap-ends", no_argument, 0, 'R'},
         {"drop-fused-overlaps", no_argument, 0, 'D'},
         {"cigar", no_argument, &cigar, 1},
+        {"chain", no_argument, &chain, 1},
+        {"chain-max-gap", required_argument, 0, 1001},
+        {"chain-bandwidth", required_argument, 0, 1002},
+        {"chain-min-score", required_argument, 0, 1003},
+        {"chain-max-chains", required_argument, 0, 1004},
         {"query-indices-in-host-memory", required_argument, 0, 'Q'},
         {"query-indices-in-device-memory", required_argument, 0, 'q'},
         {"target-indices-in-host-memory", required_argument, 0, 'C'},
@@ -161,7 +176,23 @@ int main(int argc, char** argv)
             case 'z': min_overlap_fraction = std::stof(optarg); break;
             case 'R': rescue = true; break;
             case 'D': drop = true; break;
-            case 0: break; // --cigar: the flag is set by getopt_long
+            case 0: break; // --cigar, --chain: the flag is set by getopt_long
+            case 1001:
+                chain_max_gap      = std::stoi(optarg);
+                chain_option_given = "--chain-max-gap";
+                break;
+            case 1002:
+                chain_bandwidth    = std::stoi(optarg);
+                chain_option_given = "--chain-bandwidth";
+                break;
+            case 1003:
+                chain_min_score    = std::stoi(optarg);
+                chain_option_given = "--chain-min-score";
+                break;
+            case 1004:
+                chain_max_chains   = std::stoi(optarg);
+                chain_option_given = "--chain-max-chains";
+                break;
             case 'd':
                 if (std::stoi(optarg) != 1)
                     refuse("-d: this tool runs on one device");
@@ -201,6 +232,16 @@ int main(int argc, char** argv)
             refuse("-F / --filtering-parameter must be in range [0.0, 1.0]");
         if (index_size <= 0 || target_index_size <= 0)
             refuse("-i / -t must be positive");
+        if (chain_option_given && !chain)
+            refuse(std::string(chain_option_given) + " needs --chain");
+        if (chain_max_gap < 1)
+            refuse("--chain-max-gap must be at least 1");
+        if (chain_bandwidth < 0)
+            refuse("--chain-bandwidth must not be negative");
+        if (chain_min_score < 0)
+            refuse("--chain-min-score must not be negative");
+        if (chain_max_chains < 1 || chain_max_chains > 64)
+            refuse("--chain-max-chains must be in range [1, 64]");
         if (argc - optind < 2)
         {
             std::cerr << "Invalid inputs. Please refer to the help function." << std::endl;
@@ -267,12 +308,23 @@ int main(int argc, char** argv)
 
         const packed_reads q(queries);
         const packed_reads t(own_targets);
-        gw_mapper_overlaps* result = gw_mapper_map_batched_cached(
-            q.bases.data(), q.offsets.data(), static_cast<int32_t>(queries.size()), all_to_all ? nullptr : t.bases.data(),
-            all_to_all ? nullptr : t.offsets.data(), static_cast<int32_t>(own_targets.size()), k, w, filtering_parameter,
-            min_residues, min_overlap_len, min_bases_per_residue, min_overlap_fraction,
-            static_cast<int64_t>(index_size * 1000000.0), static_cast<int64_t>(target_index_size * 1000000.0), 1,
-            drop ? 1 : 0, rescue ? 1 : 0, cigar, 0, query_host, query_device, target_host, target_device, nullptr);
+        const char* target_bases      = all_to_all ? nullptr : t.bases.data();
+        const int64_t* target_offsets = all_to_all ? nullptr : t.offsets.data();
+        const int64_t query_limit     = static_cast<int64_t>(index_size * 1000000.0);
+        const int64_t target_limit    = static_cast<int64_t>(target_index_size * 1000000.0);
+        gw_mapper_overlaps* result =
+            chain ? gw_mapper_map_batched_chained(
+                        q.bases.data(), q.offsets.data(), static_cast<int32_t>(queries.size()), target_bases,
+                        target_offsets, static_cast<int32_t>(own_targets.size()), k, w, filtering_parameter,
+                        min_residues, min_overlap_len, min_bases_per_residue, min_overlap_fraction, query_limit,
+                        target_limit, 1, drop ? 1 : 0, rescue ? 1 : 0, cigar, 0, query_host, query_device, target_host,
+                        target_device, chain_max_gap, chain_bandwidth, chain_min_score, chain_max_chains, nullptr)
+                  : gw_mapper_map_batched_cached(
+                        q.bases.data(), q.offsets.data(), static_cast<int32_t>(queries.size()), target_bases,
+                        target_offsets, static_cast<int32_t>(own_targets.size()), k, w, filtering_parameter,
+                        min_residues, min_overlap_len, min_bases_per_residue, min_overlap_fraction, query_limit,
+                        target_limit, 1, drop ? 1 : 0, rescue ? 1 : 0, cigar, 0, query_host, query_device, target_host,
+                        target_device, nullptr);
         if (!result)
             refuse(gw_mapper_last_error());
         std::vector<overlap_record> records(static_cast<size_t>(gw_mapper_overlaps_count(result)));

@@ -84,9 +84,14 @@ struct pair_stages
         int64_t count = 0;
         float ms      = 0.f;
         gw_mapper_matcher m(qi, ti, s_);
-        throw_on(gwm_find_overlaps_device(m.a.anchors, m.a.n, reads_.all_to_all ? 1 : 0, opt_.min_residues,
-                                          opt_.min_overlap_len, opt_.min_bases_per_residue, opt_.min_overlap_fraction,
-                                          s_, &found.p, &count, &ms));
+        if (opt_.chained)
+            throw_on(gwm_chain_overlaps_device(m.a.anchors, m.a.n, &opt_.chaining, reads_.all_to_all ? 1 : 0,
+                                               opt_.min_residues, opt_.min_overlap_len, opt_.min_bases_per_residue,
+                                               opt_.min_overlap_fraction, s_, &found.p, nullptr, &count, &ms));
+        else
+            throw_on(gwm_find_overlaps_device(m.a.anchors, m.a.n, reads_.all_to_all ? 1 : 0, opt_.min_residues,
+                                              opt_.min_overlap_len, opt_.min_bases_per_residue,
+                                              opt_.min_overlap_fraction, s_, &found.p, &count, &ms));
         result_.stage_ms[0] += ms;
         return count;
     }

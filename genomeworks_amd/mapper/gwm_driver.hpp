@@ -1,4 +1,4 @@
-// gwm_driver.hpp -- the batched driver of cudamapper: what the three gw_mapper_map_batched* entry points of
+// gwm_driver.hpp -- the batched driver of cudamapper: what the gw_mapper_map_batched* entry points of
 // include/gw_mapper_capi.h run (implementation and its parts in gwm_driver.cpp).
 #ifndef GWM_DRIVER_HPP
 #define GWM_DRIVER_HPP
@@ -21,6 +21,9 @@ struct map_options
     int64_t max_device_bytes;
     int32_t query_indices_in_host_memory, query_indices_in_device_memory;
     int32_t target_indices_in_host_memory, target_indices_in_device_memory;
+    // what gw_mapper_map_batched_chained adds: the chaining overlapper in the place of the triggered one
+    int32_t chained;
+    gwm_chaining chaining;
 };
 
 // Maps queries against targets (targets without bases: all against all) index pair by index pair, walking the pairs

@@ -8,6 +8,7 @@
 #include "gwhip_mapper.h"
 
 #include "gwm_device_utils.hpp"
+#include "gwm_overlap_filter.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -452,17 +453,11 @@ __global__ void __launch_bounds__(kThreads) create_filter_kernel(
         o.target_start_position_in_read = s.target_position_in_read;
         o.target_end_position_in_read   = e.target_position_in_read;
     }
-    out[f] = o;
-    // FilterOverlapOp: unsigned lengths, integer bases per residue, strict > on the float fractions
-    const uint32_t tl     = o.target_end_position_in_read - o.target_start_position_in_read;
-    const uint32_t ql     = o.query_end_position_in_read - o.query_start_position_in_read;
-    const uint32_t len    = tl > ql ? tl : ql;
-    const bool self       = o.query_read_id == o.target_read_id && all_to_all;
-    const bool pass = o.num_residues >= min_residues && (len / o.num_residues) < min_bases_per_residue &&
-                      ql >= min_overlap_len && tl >= min_overlap_len && !self &&
-                      (static_cast<float>(tl) * 1.f / static_cast<float>(len)) > min_overlap_fraction &&
-                      (static_cast<float>(ql) * 1.f / static_cast<float>(len)) > min_overlap_fraction;
-    keep[f] = pass ? 1u : 0u;
+    out[f]  = o;
+    keep[f] = passes_overlap_filter(o, all_to_all, min_residues, min_overlap_len, min_bases_per_residue,
+                                    min_overlap_fraction)
+                  ? 1u
+                  : 0u;
 }
 
 void set_empty(gwm_index* out)

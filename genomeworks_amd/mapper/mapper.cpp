@@ -301,6 +301,14 @@ int64_t copy_selection(const window_selection& s, uint32_t* plan, int64_t plan_c
     return sequences;
 }
 
+// the five integers of gw_mapper_chain_overlaps as the engine takes them
+gwm_chaining chaining_of(const int32_t chaining[5])
+{
+    if (!chaining)
+        throw std::invalid_argument("gw_mapper_chain_overlaps: no chaining parameters");
+    return gwm_chaining{chaining[0], chaining[1], chaining[2], chaining[3], chaining[4]};
+}
+
 } // namespace
 
 extern "C" {
@@ -417,6 +425,39 @@ int64_t gw_mapper_get_overlaps_host(const void* anchors, int64_t n, int32_t all_
         d.upload(static_cast<const gwm_anchor*>(anchors), n);
         throw_on(gwm_find_overlaps(d.p, n, all_to_all, min_residues, min_overlap_len, min_bases_per_residue,
                                    min_overlap_fraction, stream, static_cast<gwm_overlap*>(overlaps), &count, nullptr));
+        return count;
+    }, int64_t(GW_MAPPER_ERROR));
+}
+
+int64_t gw_mapper_chain_overlaps(const gw_mapper_matcher* matcher, const int32_t chaining[5], int32_t all_to_all,
+                                 int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                                 float min_overlap_fraction, void* overlaps, int32_t* scores, int64_t capacity,
+                                 float* chain_ms, void* stream)
+{
+    return guarded([&] {
+        int64_t count        = 0;
+        const gwm_chaining c = chaining_of(chaining);
+        throw_on(gwm_chain_overlaps(matcher->a.anchors, matcher->a.n, &c, all_to_all, min_residues, min_overlap_len,
+                                    min_bases_per_residue, min_overlap_fraction, stream,
+                                    static_cast<gwm_overlap*>(overlaps), scores, capacity, &count, chain_ms));
+        return count;
+    }, int64_t(GW_MAPPER_ERROR));
+}
+
+int64_t gw_mapper_chain_overlaps_host(const void* anchors, int64_t n, const int32_t chaining[5], int32_t all_to_all,
+                                      int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                                      float min_overlap_fraction, void* overlaps, int32_t* scores, int64_t capacity,
+                                      float* chain_ms, void* stream)
+{
+    return guarded([&] {
+        int64_t count        = 0;
+        const gwm_chaining c = chaining_of(chaining);
+        dbuf<gwm_anchor> d;
+        if (n > 0 && n < (int64_t(1) << 32)) // the engine refuses the rest before it reads an anchor
+            d.upload(static_cast<const gwm_anchor*>(anchors), n);
+        throw_on(gwm_chain_overlaps(d.p, n, &c, all_to_all, min_residues, min_overlap_len, min_bases_per_residue,
+                                    min_overlap_fraction, stream, static_cast<gwm_overlap*>(overlaps), scores, capacity,
+                                    &count, chain_ms));
         return count;
     }, int64_t(GW_MAPPER_ERROR));
 }
@@ -1079,7 +1120,30 @@ gw_mapper_overlaps* gw_mapper_map_batched_cached(
                                   max_basepairs_per_target_index, post_process, drop_fused_overlaps, rescue_overlap_ends,
                                   align_overlaps, max_device_bytes, query_indices_in_host_memory,
                                   query_indices_in_device_memory, target_indices_in_host_memory,
-                                  target_indices_in_device_memory};
+                                  target_indices_in_device_memory, 0, gwm_chaining{}};
+        return map_batched({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets}, options,
+                           static_cast<hipStream_t>(stream));
+    }, static_cast<gw_mapper_overlaps*>(nullptr));
+}
+
+gw_mapper_overlaps* gw_mapper_map_batched_chained(
+    const char* query_bases, const int64_t* query_offsets, int32_t n_queries, const char* target_bases,
+    const int64_t* target_offsets, int32_t n_targets, int32_t kmer_size, int32_t window_size, double filtering_parameter,
+    int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue, float min_overlap_fraction,
+    int64_t max_basepairs_per_query_index, int64_t max_basepairs_per_target_index, int32_t post_process,
+    int32_t drop_fused_overlaps, int32_t rescue_overlap_ends, int32_t align_overlaps, int64_t max_device_bytes,
+    int32_t query_indices_in_host_memory, int32_t query_indices_in_device_memory, int32_t target_indices_in_host_memory,
+    int32_t target_indices_in_device_memory, int32_t max_gap, int32_t bandwidth, int32_t min_chain_score,
+    int32_t max_chains, void* stream)
+{
+    return guarded([&] {
+        const map_options options{kmer_size, window_size, filtering_parameter, min_residues, min_overlap_len,
+                                  min_bases_per_residue, min_overlap_fraction, max_basepairs_per_query_index,
+                                  max_basepairs_per_target_index, post_process, drop_fused_overlaps, rescue_overlap_ends,
+                                  align_overlaps, max_device_bytes, query_indices_in_host_memory,
+                                  query_indices_in_device_memory, target_indices_in_host_memory,
+                                  target_indices_in_device_memory, 1,
+                                  gwm_chaining{kmer_size, max_gap, bandwidth, min_chain_score, max_chains}};
         return map_batched({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets}, options,
                            static_cast<hipStream_t>(stream));
     }, static_cast<gw_mapper_overlaps*>(nullptr));

@@ -65,7 +65,9 @@ def polish(reads, targets, overlaps=None, window_length=500, max_depth=30, band_
     off: map_reads_batched's own 1e-5 is meant for indices of many megabases, and in the index of a draft of a few
     hundred kilobases its threshold is 0 occurrences, so nothing would map and the draft would come back as it is;
     pass filtering_parameter for large inputs. Reads shorter than k + w - 1 then raise ValueError: the index
-    would skip them and shift the read ids behind them. devices: the cudapoa workers' devices
+    would skip them and shift the read ids behind them. overlapper="chained" (and chaining=, as map_reads_batched
+    takes them) is one of those mapping parameters: the overlaps then come from the chaining overlapper
+    (INTEGRATION.md section 3r), and nothing else here changes. devices: the cudapoa workers' devices
     (process_windows_multi_device), each with a pool of poa_memory_per_device bytes (-1: cudapoa's share of the free
     memory, which takes seconds to set up on a large device); mapping and windows run on the current device.
     `timings`, if a dict, receives the device times (ms) chain_fuse_filter, fuse, rescue (when mapping), gather, align,
@@ -147,9 +149,10 @@ def correct_reads(reads, overlaps=None, window_length=500, max_depth=30, band_wi
 
     overlaps: OVERLAP records of the reads mapped against themselves, whose read ids are positions in the list, as
     cudamapper returned them -- self overlaps and both directions of a pair may be among them; None maps first, with
-    map_reads_batched(reads, None, **mapping_parameters) over polish()'s defaults, and reads shorter than k + w - 1
-    raise ValueError as there. One record per pair of reads is aligned, once, and both of its reads get layers from
-    it (cudamapper.correction_windows; the rules are in INTEGRATION.md section 3k). All windows of all reads are built
+    map_reads_batched(reads, None, **mapping_parameters) over polish()'s defaults (overlapper="chained" among the
+    parameters maps with the chaining overlapper, as there), and reads shorter than k + w - 1 raise ValueError as
+    there. One record per pair of reads is aligned, once, and both of its reads get layers from it
+    (cudamapper.correction_windows; the rules are in INTEGRATION.md section 3k). All windows of all reads are built
     at once, so the host holds up to (1 + max_depth) sequences of up to 2 * window_length bases per window of every
     read; reads are not corrected in batches. The remaining arguments as for polish(). `timings` receives what
     polish() gives it and pairs, overlaps_in (records aligned, records given) and query_role_segments (device ms).
@@ -253,7 +256,8 @@ def call_variants(reads, targets, overlaps=None, min_count=3, min_percent=30, ti
     "" and its alt the inserted bases. Called deletions of neighbouring bases of one target are joined into one
     variant at the first of them: ref is the deleted bases, alt "", count the smallest of their counts and depth that
     of the first base. scoring, as cudamapper.overlap_variants takes it, aligns under affine gap costs instead of unit
-    costs: one indel event is then one gap run in every read that carries it."""
+    costs: one indel event is then one gap run in every read that carries it.
+    overlapper="chained" among the mapping parameters maps with the chaining overlapper, as in polish()."""
     overlaps = _mapped("call_variants", reads, targets, overlaps, mapping_parameters)
     kept = np.ascontiguousarray(overlaps, cudamapper.OVERLAP)
     kept = kept[one_overlap_per_read(kept)]

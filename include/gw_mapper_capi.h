@@ -70,6 +70,21 @@ int64_t gw_mapper_get_overlaps_host(const void* anchors, int64_t n, int32_t all_
                                     int64_t min_overlap_len, int64_t min_bases_per_residue, float min_overlap_fraction,
                                     void* overlaps, void* stream);
 
+/* The chaining overlapper over the matcher's anchors (gwm_chain_overlaps in gwhip_mapper.h has rules C1-C8).
+   chaining[5] = kmer_size, max_gap, bandwidth, min_chain_score, max_chains. Writes min(capacity, count) records to
+   `overlaps` and as many int32 chain scores to `scores` (either may be NULL) and returns count, or GW_MAPPER_ERROR
+   with nothing written; chain_ms may be NULL. */
+int64_t gw_mapper_chain_overlaps(const gw_mapper_matcher* matcher, const int32_t chaining[5], int32_t all_to_all,
+                                 int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                                 float min_overlap_fraction, void* overlaps, int32_t* scores, int64_t capacity,
+                                 float* chain_ms, void* stream);
+
+/* the same over n sorted host anchors (uploaded first) */
+int64_t gw_mapper_chain_overlaps_host(const void* anchors, int64_t n, const int32_t chaining[5], int32_t all_to_all,
+                                      int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                                      float min_overlap_fraction, void* overlaps, int32_t* scores, int64_t capacity,
+                                      float* chain_ms, void* stream);
+
 /* Whole mapping of one index pair: queries against targets, or all against all when target_bases is NULL
    (all_to_all then drops self-mappings). Writes min(capacity, count) overlaps and returns count. */
 int64_t gw_mapper_map(const char* query_bases, const int64_t* query_offsets, int32_t n_queries,
@@ -470,6 +485,19 @@ gw_mapper_overlaps* gw_mapper_map_batched_cached(
     int32_t drop_fused_overlaps, int32_t rescue_overlap_ends, int32_t align_overlaps, int64_t max_device_bytes,
     int32_t query_indices_in_host_memory, int32_t query_indices_in_device_memory, int32_t target_indices_in_host_memory,
     int32_t target_indices_in_device_memory, void* stream);
+/* gw_mapper_map_batched_cached with the chaining overlapper (gw_mapper_chain_overlaps) in the place of the triggered
+   one in every index pair: max_gap, bandwidth, min_chain_score and max_chains are its parameters, and the k of the
+   chains is kmer_size. Post-processing, end rescue, alignment and the index cache are those of gw_mapper_map_batched_cached;
+   stage_ms[0] of the result is then the device time of the chaining. */
+gw_mapper_overlaps* gw_mapper_map_batched_chained(
+    const char* query_bases, const int64_t* query_offsets, int32_t n_queries, const char* target_bases,
+    const int64_t* target_offsets, int32_t n_targets, int32_t kmer_size, int32_t window_size, double filtering_parameter,
+    int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue, float min_overlap_fraction,
+    int64_t max_basepairs_per_query_index, int64_t max_basepairs_per_target_index, int32_t post_process,
+    int32_t drop_fused_overlaps, int32_t rescue_overlap_ends, int32_t align_overlaps, int64_t max_device_bytes,
+    int32_t query_indices_in_host_memory, int32_t query_indices_in_device_memory, int32_t target_indices_in_host_memory,
+    int32_t target_indices_in_device_memory, int32_t max_gap, int32_t bandwidth, int32_t min_chain_score,
+    int32_t max_chains, void* stream);
 /* indices built from bases, indices restored from a host copy, and pack_unpack_ms[2]: summed device time of packing
    and of restoring (HIP events); any pointer may be NULL */
 int gw_mapper_overlaps_cache_counts(const gw_mapper_overlaps* result, int64_t* index_builds, int64_t* index_restores,

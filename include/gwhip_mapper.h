@@ -144,6 +144,57 @@ int gwm_find_overlaps_device(const gwm_anchor* anchors, int64_t n, int32_t all_t
                              void* stream, gwm_overlap** out, int64_t* count, float* chain_fuse_filter_ms);
 void gwm_device_free(void* device_pointer);
 
+/* The parameters of the chaining overlapper. The defaults the layers above fill in -- max_gap 5000, bandwidth 500,
+ * min_chain_score 40, max_chains 4 -- are minimap2's conventions (its -g, -r and -m); they are not tuned here. */
+typedef struct gwm_chaining
+{
+    int32_t kmer_size;       /* k, 1..32: what one anchor is worth */
+    int32_t max_gap;         /* G >= 1 */
+    int32_t bandwidth;       /* B >= 0 */
+    int32_t min_chain_score; /* S >= 0 */
+    int32_t max_chains;      /* M, 1..64: chains per read pair and orientation */
+} gwm_chaining;
+
+/* Chaining overlapper over sorted device anchors[0..n): a dynamic programme over the anchors of every read pair, in
+ * both orientations, instead of the neighbour test of gwm_find_overlaps. All arithmetic is in integers and exact
+ * (positions are uint32, their differences are taken as signed numbers that never wrap):
+ *   C1  A group is a maximal run of anchors of one (query_read_id, target_read_id); its anchors are 0 .. m - 1 in
+ *       sort order. With all_to_all a group of a read with itself yields nothing, and no group of fewer than
+ *       min_residues anchors does (the filter would drop their records). m >= 2^24 is an error: scores are int32.
+ *   C2  Every group is chained twice, for '+' and for '-', independently; an anchor may be in one chain of each.
+ *       dq = q_i - q_j; dt = t_i - t_j for '+', t_j - t_i for '-'.
+ *   C3  j may precede i iff i - 64 <= j < i, 0 < dq <= G, 0 < dt <= G and |dq - dt| <= B.
+ *   C4  gain = min(dq, dt, k) - cost(|dq - dt|); cost(0) = 0, cost(d) = d * k / 100 + (floor(log2 d) >> 1), integer
+ *       division.
+ *   C5  best = max over the predecessors j of f(j) + gain(j, i). If best > k: f(i) = best and p(i) the largest such j.
+ *       Otherwise f(i) = k and i has no predecessor (a tie with k starts a new chain).
+ *   C6  Per group and orientation, rounds r = 0 .. M - 1: e = the unused anchor of largest f, the smallest index on
+ *       ties; stop when there is none or f(e) < S. Walk e, p(e), p(p(e)), ... until an anchor has no predecessor or
+ *       its predecessor is used; the anchors visited are the chain and become used. score = f(e) - f(u) when the
+ *       walk stopped in front of a used anchor u, else f(e). The chain is a candidate iff score >= S; a round whose
+ *       chain is not one still uses up its anchors and its round.
+ *   C7  One record per candidate: query start / end = q of the chain's first / last anchor; target start / end = t of
+ *       the first / last anchor for '+', of the last / first for '-'; relative_strand the orientation, num_residues
+ *       the number of anchors, overlap_complete 1. Positions are minimizer starts, as in gwm_find_overlaps. Every
+ *       candidate then passes the filter of gwm_find_overlaps, the same arithmetic. scores[i] is the score of kept
+ *       record i.
+ *   C8  Groups in anchor order; within a group the '+' rounds in round order, then the '-' rounds.
+ * min(capacity, *count) records and scores are copied to the host arrays `out` and `scores` (either may be NULL);
+ * *count is the number kept. chain_ms (device time, HIP events) may be NULL. Errors, on which nothing is written:
+ * a parameter outside the ranges above, a negative min_residues, min_overlap_len or min_bases_per_residue,
+ * n >= 2^32, a group of 2^24 anchors or more. */
+int gwm_chain_overlaps(const gwm_anchor* anchors, int64_t n, const gwm_chaining* chaining, int32_t all_to_all,
+                       int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                       float min_overlap_fraction, void* stream, gwm_overlap* out, int32_t* scores, int64_t capacity,
+                       int64_t* count, float* chain_ms);
+
+/* gwm_chain_overlaps with the result left on the device: *out and *scores (scores may be NULL) are device arrays of
+ * *count elements, NULL when there are none, that the caller frees with gwm_device_free. */
+int gwm_chain_overlaps_device(const gwm_anchor* anchors, int64_t n, const gwm_chaining* chaining, int32_t all_to_all,
+                              int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                              float min_overlap_fraction, void* stream, gwm_overlap** out, int32_t** scores,
+                              int64_t* count, float* chain_ms);
+
 /* Overlapper::post_process_overlaps over device overlaps[0..n), in the order get_overlaps gave them. Two neighbours
  * fuse when they share strand ('+' or '-') and read pair and (a) both gaps are below 500, or (b) the float ratio of
  * the smaller gap to the larger exceeds the double 0.8, or (c) both gaps, as float fractions of the summed query /
