@@ -234,6 +234,14 @@ def mapper():
         L.gw_mapper_chain_overlaps.argtypes = [vp, vp, i32, i64, i64, i64, f32, vp, vp, i64, vp, vp]
         L.gw_mapper_chain_overlaps_host.restype = i64
         L.gw_mapper_chain_overlaps_host.argtypes = [vp, i64, vp, i32, i64, i64, i64, f32, vp, vp, i64, vp, vp]
+        L.gw_mapper_chain_overlaps_anchored.restype = i64
+        L.gw_mapper_chain_overlaps_anchored.argtypes = [vp, vp, i32, i64, i64, i64, f32, vp, vp, i64, vp, vp, i64, vp, vp, vp]
+        L.gw_mapper_chain_overlaps_anchored_host.restype = i64
+        L.gw_mapper_chain_overlaps_anchored_host.argtypes = [vp, i64, vp, i32, i64, i64, i64, f32, vp, vp, i64, vp, vp, i64,
+                                                             vp, vp, vp]
+        L.gw_mapper_align_overlaps_anchored.restype = vp
+        L.gw_mapper_align_overlaps_anchored.argtypes = [vp, i64, vp, vp, i32, u32, vp, vp, i32, u32, vp, vp, i64, i32, i32, vp,
+                                                        i32, i64, vp]
         L.gw_mapper_map_batched_chained.restype = vp
         L.gw_mapper_map_batched_chained.argtypes = L.gw_mapper_map_batched_cached.argtypes[:-1] + [i32, i32, i32, i32, vp]
         L.gw_mapper_generate_batches_of_indices.restype = i64
@@ -306,5 +314,7 @@ def mapper():
         L.gwm_align_bytes_needed.argtypes = [i32, i32, i32]
         L.gwm_align_bytes_needed_scored.restype = i64
         L.gwm_align_bytes_needed_scored.argtypes = [i32, i32, i32]
+        L.gwm_align_bytes_needed_anchored.restype = i64
+        L.gwm_align_bytes_needed_anchored.argtypes = [vp, i32, i32, i32, i32]
         _mapper = L
     return _mapper

@@ -43,7 +43,8 @@ POA_HOOKS_KERNEL_SRCS = ["poa_hooks/gwhip_poa_merge_hook.hip"]
 # cudamapper likewise
 MAPPER_KERNEL_SRCS = ["mapper/gwm_mapper.hip", "mapper/gwm_postprocess.hip", "mapper/gwm_align.hip",
                       "mapper/gwm_segments.hip", "mapper/gwm_pileup.hip", "mapper/gwm_variants.hip",
-                      "mapper/gwm_qualities.hip", "mapper/gwm_index_cache.hip", "mapper/gwm_chain.hip"]
+                      "mapper/gwm_qualities.hip", "mapper/gwm_index_cache.hip", "mapper/gwm_chain.hip",
+                      "mapper/gwm_anchored.hip"]
 MAPPER_HOST_SRCS = ["mapper/mapper.cpp", "mapper/gwm_driver.cpp", "mapper/gwm_index_batcher.cpp",
                     "mapper/gwm_windows.cpp"]
 

@@ -317,7 +317,7 @@ CHAINING_DEFAULTS = dict(max_gap=5000, bandwidth=500, min_chain_score=40, max_ch
 
 def chain_overlaps(anchors, kmer_size=15, max_gap=5000, bandwidth=500, min_chain_score=40, max_chains=4,
                    all_to_all=True, min_residues=3, min_overlap_len=250, min_bases_per_residue=1000,
-                   min_overlap_fraction=0.8, return_scores=False, stream=None):
+                   min_overlap_fraction=0.8, return_scores=False, stream=None, return_anchors=False):
     """The chaining overlapper on a Matcher (device anchors) or on a sorted ANCHOR array (uploaded first): the anchors
     of every read pair are chained by dynamic programming, '+' and '-' each on their own, over a look-back of 64
     anchors; up to max_chains chains of at least min_chain_score per pair and orientation become OVERLAP records, which
@@ -326,7 +326,11 @@ def chain_overlaps(anchors, kmer_size=15, max_gap=5000, bandwidth=500, min_chain
     two collinear anchors does not cut a chain here, and the strand is the orientation the chain was found in.
     The defaults of max_gap, bandwidth and min_chain_score are minimap2's conventions (-g, -r, -m) and are not tuned.
     Returns an OVERLAP array, or (overlaps, int32 chain scores) with return_scores; a Matcher also records the device
-    time in matcher.stage_ms["chain_dp"]. Parameters out of range raise MapperError."""
+    time in matcher.stage_ms["chain_dp"]. Parameters out of range raise MapperError.
+    return_anchors adds (anchor_offsets, anchor_positions) behind the overlaps (and the scores): the anchors of every
+    record's chain in chain order, record i's as the uint32 (query_position_in_read, target_position_in_read) rows
+    anchor_positions[anchor_offsets[i]:anchor_offsets[i + 1]], num_residues of them -- what align_overlaps(anchors=)
+    takes. Records and scores are the same with and without it."""
     L = _native.mapper()
     chaining = np.array([kmer_size, max_gap, bandwidth, min_chain_score, max_chains], np.int32)
     args = (_p(chaining), int(bool(all_to_all)), int(min_residues), int(min_overlap_len), int(min_bases_per_residue),
@@ -337,7 +341,18 @@ def chain_overlaps(anchors, kmer_size=15, max_gap=5000, bandwidth=500, min_chain
     # a record holds at least max(min_residues, 1) anchors, and the chains of one orientation share none
     capacity = 2 * (n_anchors // max(int(min_residues), 1)) + 1
     out, scores, ms = np.zeros(capacity, OVERLAP), np.zeros(capacity, np.int32), C.c_float(0.0)
-    if on_device:
+    if return_anchors:
+        # an anchor is in at most one chain of each orientation
+        offsets, positions = np.zeros(capacity + 1, np.int64), np.zeros((2 * n_anchors, 2), np.uint32)
+        members = C.c_int64(0)
+        more = (_p(offsets), _p(positions), len(positions), C.byref(members), C.byref(ms))
+        if on_device:
+            n = L.gw_mapper_chain_overlaps_anchored(anchors._h, *args, _p(out), _p(scores), capacity, *more,
+                                                    _stream(stream) or anchors._stream)
+        else:
+            n = L.gw_mapper_chain_overlaps_anchored_host(_p(a), len(a), *args, _p(out), _p(scores), capacity, *more,
+                                                         _stream(stream))
+    elif on_device:
         n = L.gw_mapper_chain_overlaps(anchors._h, *args, _p(out), _p(scores), capacity, C.byref(ms),
                                        _stream(stream) or anchors._stream)
     else:
@@ -347,7 +362,10 @@ def chain_overlaps(anchors, kmer_size=15, max_gap=5000, bandwidth=500, min_chain
         raise _err(L)
     if on_device:
         anchors.stage_ms["chain_dp"] = ms.value
-    return (out[:n], scores[:n]) if return_scores else out[:n]
+    result = (out[:n], scores[:n]) if return_scores else (out[:n],)
+    if return_anchors:
+        result += (offsets[:n + 1], positions[:members.value].copy())
+    return result if len(result) > 1 else result[0]
 
 
 def _overlapper(overlapper, chaining):
@@ -366,20 +384,25 @@ def _overlapper(overlapper, chaining):
 
 def map_reads(queries, targets=None, k=15, w=10, filtering_parameter=1e-5, min_residues=3, min_overlap_len=250,
               min_bases_per_residue=1000, min_overlap_fraction=0.8, stream=None, overlapper="triggered",
-              chaining=None):
+              chaining=None, return_anchors=False):
     """Overlaps of `queries` against `targets`, or all against all (self-mappings dropped) when targets is None, with
     hashed representations as in the reference's cudamapper. One index per read set: batching into several indices
     (the CLI's -i / -t) is the caller's. overlapper="chained" finds them with chain_overlaps instead of find_overlaps;
     `chaining` is then a dict of max_gap, bandwidth, min_chain_score and max_chains (chain_overlaps' defaults for
-    those left out), and the k of the chains is `k`. Any other overlapper is a ValueError."""
+    those left out), and the k of the chains is `k`. Any other overlapper is a ValueError. return_anchors, with the
+    chained overlapper only (a ValueError otherwise), returns (overlaps, anchor_offsets, anchor_positions) as
+    chain_overlaps(return_anchors=True) does."""
     chaining = _overlapper(overlapper, chaining)
+    if return_anchors and chaining is None:
+        raise ValueError('return_anchors is for overlapper="chained"')
     with Index(queries, k, w, True, filtering_parameter, stream=stream) as q, \
             (q if targets is None else Index(targets, k, w, True, filtering_parameter, stream=stream)) as t, \
             Matcher(q, t, stream) as m:
         if chaining is not None:
             return chain_overlaps(m, k, all_to_all=targets is None, min_residues=min_residues,
                                   min_overlap_len=min_overlap_len, min_bases_per_residue=min_bases_per_residue,
-                                  min_overlap_fraction=min_overlap_fraction, stream=stream, **chaining)
+                                  min_overlap_fraction=min_overlap_fraction, stream=stream,
+                                  return_anchors=bool(return_anchors), **chaining)
         return find_overlaps(m, targets is None, min_residues, min_overlap_len, min_bases_per_residue,
                              min_overlap_fraction, stream)
 
@@ -487,6 +510,18 @@ def align_bytes_needed_scored(query_length, target_length, band):
     return int(_native.mapper().gwm_align_bytes_needed_scored(int(query_length), int(target_length), int(band)))
 
 
+def align_bytes_needed_anchored(piece_lengths, scoring=None, max_query_length=None):
+    """align_bytes_needed for one overlap that align_overlaps(anchors=) cuts into pieces of these (query, target)
+    lengths, under `scoring` as align_overlaps takes it; max_query_length, for scoring None, is the longest query side
+    of a piece of the call (None: of these pieces) (gwm_align_bytes_needed_anchored)."""
+    sc = _scoring_args(scoring)
+    lengths = np.asarray(piece_lengths, np.int64).reshape(-1, 2)
+    starts = np.concatenate([[0], np.cumsum(lengths.reshape(-1))]).astype(np.int64)
+    longest = int(lengths[:, 0].max()) if max_query_length is None else int(max_query_length)
+    return int(_native.mapper().gwm_align_bytes_needed_anchored(_p(starts), len(lengths), 0 if sc is None else len(sc) // 2 - 1,
+                                                                0 if sc is None else int(sc[-1]), longest))
+
+
 def _scoring_args(scoring):
     """scoring of align_overlaps / overlap_variants as the C API takes it: None, or four int32 (mismatch, gap_open,
     gap_extend, band) from a 4-tuple or a dict with these keys (a dict may leave out any: 4, 6, 2, 128), or, for
@@ -521,7 +556,8 @@ def _scoring_args(scoring):
 
 
 def align_overlaps(overlaps, query_reads, target_reads=None, first_query_read_id=0, first_target_read_id=0,
-                   max_device_bytes=0, stream=None, timings=None, scoring=None):
+                   max_device_bytes=0, stream=None, timings=None, scoring=None, anchors=None, anchor_kmer_size=15,
+                   anchor_spacing=256):
     """Global alignment of every overlap over its own slices, on the device from the reads to the CIGAR text: query
     slice [query start, query end) against target slice [target start, target end), on '-' against that target
     slice's reverse complement as cudaaligner takes it ("TGAC"[(c >> 1) & 3] for every byte), with the default aligner
@@ -538,12 +574,36 @@ def align_overlaps(overlaps, query_reads, target_reads=None, first_query_read_id
     an empty CIGAR and -1, and values out of range raise ValueError before anything is launched. A 6-tuple (mismatch,
     gap_open, gap_extend, gap_open2, gap_extend2, band), or a dict with gap_open2 and gap_extend2, asks for two-piece gap
     costs, min(gap_open + L gap_extend, gap_open2 + L gap_extend2) for a run of L columns (INTEGRATION.md section 3p);
-    the capacity is then 1024 diagonals."""
+    the capacity is then 1024 diagonals.
+    anchors: None, or (anchor_offsets, anchor_positions) as chain_overlaps(return_anchors=True) returns them -- every
+    overlap is then cut at anchors of its chain and aligned piece by piece under the same aligner and scoring (rules
+    G1-G6 of include/gwhip_mapper.h): anchors whose k-mer of anchor_kmer_size (1..32) bases
+    does not start strictly inside both slices are dropped, the others must be strictly increasing in query and target
+    (MapperError that names the overlap otherwise), one anchor per anchor_spacing (>= 1; 256 is a convention, not
+    tuned) bases of the query slice becomes a cut, and the band of the scoring applies to every piece. The CIGAR is
+    that of the pieces' alignments one after the other; an overlap with a piece that has no result has none. Every
+    piece is what its aligner returns for that pair alone: the whole is a valid global alignment, not re-priced across
+    cuts, and not claimed to be optimal. Out of range, or offsets that do not start at 0, decrease or do not end at the
+    number of anchors: ValueError before anything is launched."""
     sc = _scoring_args(scoring)
     L = _native.mapper()
     o = np.ascontiguousarray(overlaps, OVERLAP)
     q, t = _read_set_args(query_reads, target_reads)
-    if sc is None:
+    if anchors is not None:
+        offsets, positions = anchors
+        offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        positions = np.ascontiguousarray(positions, np.uint32).reshape(-1, 2)
+        if not (1 <= int(anchor_kmer_size) <= 32 and int(anchor_spacing) >= 1):
+            raise ValueError("anchor_kmer_size %d, anchor_spacing %d outside 1..32, >= 1"
+                             % (int(anchor_kmer_size), int(anchor_spacing)))
+        if len(offsets) != len(o) + 1 or offsets[0] != 0 or (np.diff(offsets) < 0).any() or offsets[-1] != len(positions):
+            raise ValueError("anchors: %d offsets for %d overlaps that must start at 0, never decrease and end at the %d anchors"
+                             % (len(offsets), len(o), len(positions)))
+        h = L.gw_mapper_align_overlaps_anchored(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id,
+                                                _p(offsets), _p(positions), len(positions), int(anchor_kmer_size),
+                                                int(anchor_spacing), None if sc is None else _p(sc),
+                                                0 if sc is None else len(sc), int(max_device_bytes), _stream(stream))
+    elif sc is None:
         h = L.gw_mapper_align_overlaps(_p(o), len(o), *q, first_query_read_id, *t, first_target_read_id,
                                        int(max_device_bytes), _stream(stream))
     else:

@@ -6,12 +6,15 @@
 // into the same buffers), and the CIGAR writer here, the loop's consumer, turns the per-column states into the text
 // of Alignment::convert_to_cigar() and the edit distance. Neither
 // the bases nor the states cross to the host; the overlap records (36 B each) are read there to size the chunks.
+// A call that brings the anchors of its records (gwm_align_overlaps_anchored) gathers and aligns the pieces between
+// them instead and stitches their states into the records' slots (gwm_anchored.hpp), in front of the same consumer.
 //
 // CIGAR text: one wave64 per alignment over
 // tiles of 64 columns (the states as WaveStates of gwm_column_walk.hpp reads them) -- symbol per lane, run heads by
 // comparison with the neighbouring lane, a 64-bit ballot, run lengths from the distance to the next lower set bit, the
 // open run carried between tiles in wave-uniform registers; a counting pass, an exclusive scan of the byte counts, a
 // writing pass (ChunkedOutput of gwm_align_chunks.hpp). No LDS, no scratch.
+#include "gwm_anchored.hpp"
 #include "gwm_column_walk.hpp"
 
 #include "gwhip.h"
@@ -192,6 +195,18 @@ inline int64_t chunk_bytes(int64_t m, int64_t bases, size_t workspace)
     return 2 * (bases + kPad) + 2 * (2 * m + 1) * 8 + m * 4 + 2 * (m + 1) * 8 + static_cast<int64_t>(workspace) + 2 * bases;
 }
 
+// what a chunk of an anchored call holds besides: the pieces' state slots, their slice starts and result lengths
+inline int64_t pieces_bytes(int64_t pieces, int64_t bases) { return bases + kPad + (2 * pieces + 1) * 8 + pieces * 4; }
+
+// the aligner's workspace for `pairs` pairs with slice starts hs[0 .. 2 pairs] (host): the default aligner's at
+// max_query_length `capacity`, or the affine aligner's with the costs and flags that are counted with it
+inline size_t aligner_workspace_bytes(int32_t scoring_pieces, int64_t pairs, const int64_t* hs, int32_t band, int32_t capacity)
+{
+    if (scoring_pieces == 0)
+        return gwhip_hirschberg_myers_workspace_bytes(static_cast<int32_t>(pairs), hs, capacity);
+    return gwhip_affine_workspace_bytes(static_cast<int32_t>(pairs), hs, band) + static_cast<size_t>(pairs) * 5 + 256;
+}
+
 } // namespace
 
 namespace gwm
@@ -199,11 +214,13 @@ namespace gwm
 
 void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, const ReadSet& q, const ReadSet& t,
                   int64_t max_device_bytes, const Scoring& scoring, hipStream_t s, float* stage_ms,
-                  const std::function<void(const AlignedChunk&)>& consume)
+                  const std::function<void(const AlignedChunk&)>& consume, const gwm_anchor_lists* anchors)
 {
     const gwm_scoring2& sc = scoring.costs;
     const std::string who = std::string(name) + ": ";
     check_scoring(who, scoring);
+    if (anchors)
+        check_anchor_lists(who, *anchors, n, s);
     {
         dbuf<uint32_t> bad(1);
         GWM_CHECK(hipMemsetAsync(bad.p, 0, sizeof(uint32_t), s));
@@ -233,6 +250,19 @@ void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, cons
     }
     if (max_query_length > INT32_MAX)
         throw std::invalid_argument(who + "a query slice of 2^31 bases or more");
+    // with anchors: the pieces of the whole call. The aligner then sees the pieces' slice starts in the place of the
+    // records', and the default aligner the longest query side of a piece.
+    AnchorPlan plan;
+    if (anchors)
+    {
+        build_anchor_plan(who, overlaps, n, *anchors, s, plan);
+        max_query_length = plan.longest_query_piece;
+    }
+    const int64_t* piece_first = anchors ? plan.host_piece_first.data() : nullptr;
+    const int64_t* all_starts  = anchors ? plan.host_starts.data() : host_starts.data();
+    // the aligner's pairs of overlaps [first, first + m): the overlaps themselves, or their pieces
+    auto first_pair = [&](int64_t first) { return piece_first ? piece_first[first] : first; };
+    auto pairs_of   = [&](int64_t first, int64_t m) { return first_pair(first + m) - first_pair(first); };
     const int32_t capacity = static_cast<int32_t>(max_query_length);
     int64_t budget         = max_device_bytes;
     if (budget == 0)
@@ -243,24 +273,28 @@ void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, cons
     }
     // the aligner's workspace for overlaps [first, first + m); the affine aligner's costs and flags are counted with it
     auto workspace_bytes = [&](int64_t first, int64_t m) -> size_t {
-        const int64_t* hs = host_starts.data() + 2 * first;
-        if (scoring.pieces == 0)
-            return gwhip_hirschberg_myers_workspace_bytes(static_cast<int32_t>(m), hs, capacity);
-        return gwhip_affine_workspace_bytes(static_cast<int32_t>(m), hs, sc.band) + static_cast<size_t>(m) * 5 + 256;
+        return aligner_workspace_bytes(scoring.pieces, pairs_of(first, m), all_starts + 2 * first_pair(first), sc.band, capacity);
     };
+    // more pairs than one aligner call takes cost more than any budget
     auto cost = [&](int64_t first, int64_t m) {
         const int64_t* hs = host_starts.data() + 2 * first;
-        return chunk_bytes(m, hs[2 * m] - hs[0], workspace_bytes(first, m));
+        const int64_t bases = hs[2 * m] - hs[0];
+        if (pairs_of(first, m) > kMaxChunk)
+            return INT64_MAX;
+        return chunk_bytes(m, bases, workspace_bytes(first, m)) + (anchors ? pieces_bytes(pairs_of(first, m), bases) : 0);
     };
 
     Temp temp;
-    dbuf<uint8_t> sequences, results;
-    dbuf<int64_t> lengths, starts;
-    dbuf<int32_t> result_lengths;
+    dbuf<uint8_t> sequences, results, piece_results;
+    dbuf<int64_t> lengths, starts, piece_starts;
+    dbuf<int32_t> result_lengths, piece_result_lengths;
     dbuf<char> workspace;
     Events ev(4);
     for (int64_t first = 0; first < n;)
     {
+        if (pairs_of(first, 1) > kMaxChunk)
+            throw std::invalid_argument(who + "overlap " + std::to_string(first) + " has " + std::to_string(pairs_of(first, 1)) +
+                                        " pieces, more than the " + std::to_string(kMaxChunk) + " of one aligner call");
         if (cost(first, 1) > budget)
             throw std::invalid_argument(who + "overlap " + std::to_string(first) + " needs " +
                                         std::to_string(cost(first, 1)) + " device bytes, max_device_bytes allows " +
@@ -284,33 +318,54 @@ void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, cons
             else
                 too_many = mid;
         }
-        const int64_t* hs     = host_starts.data() + 2 * first;
-        const int64_t bases   = hs[2 * m] - hs[0];
+        const int64_t pairs   = pairs_of(first, m);
+        const int64_t* hs     = all_starts + 2 * first_pair(first); // of the aligner's pairs
+        const int64_t bases   = hs[2 * pairs] - hs[0];
         const size_t ws_bytes = workspace_bytes(first, m);
         const gwm_overlap* o  = overlaps + first;
         grow(sequences, bases + kPad);
         grow(results, bases + kPad);
-        grow(lengths, 2 * m + 1);
         grow(starts, 2 * m + 1);
         grow(result_lengths, m);
         grow(workspace, static_cast<int64_t>(ws_bytes));
+        if (anchors)
+        {
+            grow(piece_results, bases + kPad);
+            grow(piece_starts, 2 * pairs + 1);
+            grow(piece_result_lengths, pairs);
+        }
+        else
+            grow(lengths, 2 * m + 1);
+        // what the aligner reads and writes: the records' buffers, or the pieces'
+        const int64_t* pair_starts   = anchors ? piece_starts.p : starts.p;
+        uint8_t* pair_results        = anchors ? piece_results.p : results.p;
+        int32_t* pair_result_lengths = anchors ? piece_result_lengths.p : result_lengths.p;
 
         ev.record(0, s);
-        slice_lengths_kernel<<<grid_for(m + 1), kThreads, 0, s>>>(o, m, lengths.p);
-        GWM_CHECK(hipGetLastError());
-        exclusive_sum(lengths.p, starts.p, 2 * m + 1, temp, s);
-        gather_kernel<<<static_cast<unsigned>(2 * m), kThreads, 0, s>>>(o, q, t, starts.p, sequences.p);
-        GWM_CHECK(hipGetLastError());
+        if (anchors)
+        {
+            exclusive_sum(plan.piece_lengths + 2 * first_pair(first), piece_starts.p, 2 * pairs + 1, temp, s);
+            gather_pieces(plan, overlaps, first_pair(first), pairs, q, t, piece_starts.p, sequences.p, s);
+            record_starts(plan, overlaps, first, m, piece_starts.p, starts.p, s);
+        }
+        else
+        {
+            slice_lengths_kernel<<<grid_for(m + 1), kThreads, 0, s>>>(o, m, lengths.p);
+            GWM_CHECK(hipGetLastError());
+            exclusive_sum(lengths.p, starts.p, 2 * m + 1, temp, s);
+            gather_kernel<<<static_cast<unsigned>(2 * m), kThreads, 0, s>>>(o, q, t, starts.p, sequences.p);
+            GWM_CHECK(hipGetLastError());
+        }
         ev.record(1, s);
         if (scoring.pieces == 0)
         {
             gwhip_hirschberg_args a{};
-            a.n_alignments     = static_cast<int32_t>(m);
+            a.n_alignments     = static_cast<int32_t>(pairs);
             a.sequences        = reinterpret_cast<const char*>(sequences.p);
-            a.sequence_starts  = starts.p;
+            a.sequence_starts  = pair_starts;
             a.max_query_length = capacity;
-            a.results          = reinterpret_cast<int8_t*>(results.p);
-            a.result_lengths   = result_lengths.p;
+            a.results          = reinterpret_cast<int8_t*>(pair_results);
+            a.result_lengths   = pair_result_lengths;
             a.workspace        = workspace.p;
             a.workspace_bytes  = ws_bytes;
             if (gwhip_hirschberg_myers(&a, s) != 0)
@@ -323,21 +378,21 @@ void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, cons
         else
         {
             // costs and flags, which no consumer reads, lie behind the aligner's own workspace
-            const size_t own = gwhip_affine_workspace_bytes(static_cast<int32_t>(m), hs, sc.band);
+            const size_t own = gwhip_affine_workspace_bytes(static_cast<int32_t>(pairs), hs, sc.band);
             // both argument structs, field by field
             auto fill = [&](auto& a) {
-                a.n_alignments         = static_cast<int32_t>(m);
+                a.n_alignments         = static_cast<int32_t>(pairs);
                 a.sequences            = reinterpret_cast<const char*>(sequences.p);
-                a.sequence_starts      = starts.p;
+                a.sequence_starts      = pair_starts;
                 a.sequence_starts_host = hs;
                 a.mismatch             = sc.mismatch;
                 a.gap_open             = sc.gap_open;
                 a.gap_extend           = sc.gap_extend;
                 a.band                 = sc.band;
-                a.results              = reinterpret_cast<int8_t*>(results.p);
-                a.result_lengths       = result_lengths.p;
+                a.results              = reinterpret_cast<int8_t*>(pair_results);
+                a.result_lengths       = pair_result_lengths;
                 a.costs                = reinterpret_cast<int32_t*>(workspace.p + ((own + 255) & ~size_t(255)));
-                a.optimal              = reinterpret_cast<uint8_t*>(a.costs + m);
+                a.optimal              = reinterpret_cast<uint8_t*>(a.costs + pairs);
                 a.workspace            = workspace.p;
                 a.workspace_bytes      = own;
             };
@@ -359,6 +414,9 @@ void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, cons
             if (status != 0)
                 throw std::runtime_error(who + gwhip_affine_last_error());
         }
+        if (anchors)
+            stitch_pieces(plan, first, m, piece_results.p, piece_starts.p, piece_result_lengths.p, results.p, starts.p,
+                          result_lengths.p, s);
         ev.record(2, s);
         consume(AlignedChunk{first, m, static_cast<unsigned>((m + kWavesPerBlock - 1) / kWavesPerBlock), o, results.p,
                              starts.p, result_lengths.p});
@@ -377,7 +435,7 @@ namespace
 int align_overlaps(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
                    int32_t n_queries, uint32_t first_query_read_id, const char* target_bases, const int64_t* target_offsets,
                    int32_t n_targets, uint32_t first_target_read_id, const gwm::Scoring& scoring, int64_t max_device_bytes,
-                   void* stream, gwm_cigars* out);
+                   void* stream, gwm_cigars* out, const gwm_anchor_lists* anchors = nullptr);
 
 } // namespace
 
@@ -393,6 +451,33 @@ int64_t gwm_align_bytes_needed_scored(int32_t query_length, int32_t target_lengt
 {
     const int64_t starts[3] = {0, query_length, static_cast<int64_t>(query_length) + target_length};
     return chunk_bytes(1, starts[2], gwhip_affine_workspace_bytes(1, starts, band) + 5 + 256);
+}
+
+int64_t gwm_align_bytes_needed_anchored(const int64_t* piece_starts, int32_t pieces, int32_t scoring_pieces, int32_t band,
+                                        int32_t max_query_length)
+{
+    const int64_t bases = piece_starts[2 * pieces] - piece_starts[0];
+    return chunk_bytes(1, bases, aligner_workspace_bytes(scoring_pieces, pieces, piece_starts, band, max_query_length)) +
+           pieces_bytes(pieces, bases);
+}
+
+int gwm_align_overlaps_anchored(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                                int32_t n_queries, uint32_t first_query_read_id, const char* target_bases,
+                                const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
+                                const gwm_anchor_lists* anchors, int32_t scoring_pieces, const gwm_scoring2* scoring,
+                                int64_t max_device_bytes, void* stream, gwm_cigars* out)
+{
+    gwm::Scoring how{};
+    if (scoring_pieces < 0 || scoring_pieces > 2 || (scoring_pieces > 0 && scoring == nullptr))
+    {
+        gwm_set_error("gwm_align_overlaps_anchored: scoring_pieces outside 0..2, or pieces without a scoring");
+        *out = gwm_cigars{};
+        return -1;
+    }
+    if (scoring_pieces > 0)
+        how = gwm::Scoring{scoring_pieces, *scoring};
+    return align_overlaps(overlaps, n, query_bases, query_offsets, n_queries, first_query_read_id, target_bases, target_offsets,
+                          n_targets, first_target_read_id, how, max_device_bytes, stream, out, anchors);
 }
 
 void gwm_cigars_free(gwm_cigars* cigars)
@@ -440,13 +525,15 @@ namespace
 int align_overlaps(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
                    int32_t n_queries, uint32_t first_query_read_id, const char* target_bases, const int64_t* target_offsets,
                    int32_t n_targets, uint32_t first_target_read_id, const gwm::Scoring& scoring, int64_t max_device_bytes,
-                   void* stream, gwm_cigars* out)
+                   void* stream, gwm_cigars* out, const gwm_anchor_lists* anchors)
 {
     *out = gwm_cigars{};
     try
     {
         check_chunk_arguments("gwm_align_overlaps", n_queries, n_targets, max_device_bytes, n);
         check_scoring("gwm_align_overlaps: ", scoring);
+        if (anchors)
+            gwm::check_anchor_parameters("gwm_align_overlaps: ", *anchors);
         if (n <= 0)
             return 0;
         hipStream_t s = static_cast<hipStream_t>(stream);
@@ -470,7 +557,7 @@ int align_overlaps(const gwm_overlap* overlaps, int64_t n, const char* query_bas
         gwm::align_chunks("gwm_align_overlaps", overlaps, n,
                           read_set(query_bases, query_offsets, n_queries, first_query_read_id),
                           read_set(target_bases, target_offsets, n_targets, first_target_read_id), max_device_bytes,
-                          scoring, s, out->stage_ms, write_cigars);
+                          scoring, s, out->stage_ms, write_cigars, anchors);
         dbuf<int64_t> offsets;
         dbuf<char> text;
         const int64_t total = cigars.finish(n, temp, s, offsets, text);

@@ -63,9 +63,15 @@ inline Scoring scoring_of(const gwm_scoring2* s) { return s == nullptr ? Scoring
 // With a scoring of one or two pieces the affine-gap aligner writes the same results / result_lengths buffers, and
 // gwhip_affine_workspace_bytes is what the budget counts for both (the two-piece aligner never needs more); a scoring
 // out of range is refused before anything is launched.
+// With `anchors` (none: everything above as it stands) every overlap is cut at anchors of its chain and aligned piece
+// by piece, as include/gwhip_mapper.h states it for gwm_align_overlaps_anchored: the plan of the call's pieces is made
+// before the chunk loop (gwm_anchored.hpp), a chunk still holds whole records, its gather and its one aligner call run
+// over its pieces, and a stitch kernel leaves the records' states where the consumer reads them, so that a consumer
+// sees no difference. The chunk's budget then counts the pieces' workspace, their state slots and their starts and
+// result lengths besides; the stitch is timed with the aligner.
 void align_chunks(const char* name, const gwm_overlap* overlaps, int64_t n, const ReadSet& q, const ReadSet& t,
                   int64_t max_device_bytes, const Scoring& scoring, hipStream_t s, float* stage_ms,
-                  const std::function<void(const AlignedChunk&)>& consume);
+                  const std::function<void(const AlignedChunk&)>& consume, const gwm_anchor_lists* anchors = nullptr);
 
 } // namespace gwm
 

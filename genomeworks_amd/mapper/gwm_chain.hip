@@ -128,11 +128,13 @@ __device__ __forceinline__ void settle(int32_t v, uint32_t step, int32_t k, int3
 }
 
 // C6 + C7 for one group and one orientation, by the whole wave. f, dist, used: this orientation's scratch of the
-// group (used starts all zero). Slot r of `records` / `scores` / `keep` is round r.
+// group (used starts all zero). Slot r of `records` / `scores` / `keep` is round r. owner, where the caller asked for
+// the chains: owner[i] = first_slot + r + 1 for every anchor i that round r visits, this orientation's part of the
+// group as `used` is (starts all zero).
 __device__ void extract_chains(const gwm_anchor* __restrict__ a, uint32_t m, const int32_t* f, const uint8_t* dist,
                                uint8_t* used, bool forward, const chain_params& c, uint32_t rounds,
                                gwm_overlap* __restrict__ records, int32_t* __restrict__ scores,
-                               uint32_t* __restrict__ keep)
+                               uint32_t* __restrict__ keep, uint32_t* owner, uint32_t first_slot)
 {
     const uint32_t lane = threadIdx.x & 63u;
     for (uint32_t r = 0; r < rounds; ++r)
@@ -197,7 +199,11 @@ __device__ void extract_chains(const gwm_anchor* __restrict__ a, uint32_t m, con
                     break;
             }
             if ((visited >> lane) & 1u)
+            {
                 used[mine] = 1;
+                if (owner)
+                    owner[mine] = first_slot + r + 1;
+            }
         }
         const int32_t score = end_f - cut_f;
         if (lane == 0 && score >= c.min_score)
@@ -227,13 +233,15 @@ __device__ void extract_chains(const gwm_anchor* __restrict__ a, uint32_t m, con
 
 // anchors: all of them; group w is anchors [first[w], first[w] + length[w]) and owns record slots
 // [slot_end[w] - slots, slot_end[w]). f / dist / used: two arrays of n_anchors each ('+' then '-'), used all zero.
+// owner: null, or laid out as `used` and all zero: the record slot + 1 of every anchor that a chain took.
 __global__ void __launch_bounds__(kThreads) chain_dp_kernel(const gwm_anchor* __restrict__ anchors, int64_t n_anchors,
                                                             const uint32_t* __restrict__ first,
                                                             const uint32_t* __restrict__ length,
                                                             const int64_t* __restrict__ slot_end, uint32_t n_groups,
                                                             chain_params c, int32_t* f, uint8_t* dist, uint8_t* used,
                                                             gwm_overlap* __restrict__ records,
-                                                            int32_t* __restrict__ scores, uint32_t* __restrict__ keep)
+                                                            int32_t* __restrict__ scores, uint32_t* __restrict__ keep,
+                                                            uint32_t* owner)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t w    = __builtin_amdgcn_readfirstlane(blockIdx.x * (kThreads / 64) + threadIdx.x / 64);
@@ -295,9 +303,11 @@ __global__ void __launch_bounds__(kThreads) chain_dp_kernel(const gwm_anchor* __
 
     const uint32_t rounds = m < static_cast<uint32_t>(c.max_chains) ? m : static_cast<uint32_t>(c.max_chains);
     const int64_t slot    = slot_end[w] - 2 * static_cast<int64_t>(rounds);
-    extract_chains(a, m, f_plus, d_plus, used + base, true, c, rounds, records + slot, scores + slot, keep + slot);
+    extract_chains(a, m, f_plus, d_plus, used + base, true, c, rounds, records + slot, scores + slot, keep + slot,
+                   owner ? owner + base : nullptr, static_cast<uint32_t>(slot));
     extract_chains(a, m, f_minus, d_minus, used + n_anchors + base, false, c, rounds, records + slot + rounds,
-                   scores + slot + rounds, keep + slot + rounds);
+                   scores + slot + rounds, keep + slot + rounds, owner ? owner + n_anchors + base : nullptr,
+                   static_cast<uint32_t>(slot + rounds));
 }
 
 template <typename T>
@@ -311,13 +321,99 @@ T* select_kept(const T* in, const uint32_t* keep, int64_t n, uint32_t* d_count, 
     return out.p;
 }
 
+// Entry e of owner (anchor e of '+', then anchor e - n of '-'): flag[e] says that a kept record took the anchor,
+// key[e] is that record's index (kept_through[slot] - 1, the inclusive scan of keep) and value[e] the anchor.
+__global__ void __launch_bounds__(kThreads) chain_members_kernel(const uint32_t* __restrict__ owner, int64_t n,
+                                                                 const uint32_t* __restrict__ keep,
+                                                                 const uint32_t* __restrict__ kept_through,
+                                                                 uint32_t* __restrict__ flag, uint32_t* __restrict__ key,
+                                                                 uint32_t* __restrict__ value)
+{
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (e >= 2 * n)
+        return;
+    const uint32_t own = owner[e];
+    const bool member  = own != 0 && keep[own - 1] != 0;
+    flag[e]            = member ? 1u : 0u;
+    key[e]             = member ? kept_through[own - 1] - 1 : 0u;
+    value[e]           = static_cast<uint32_t>(e < n ? e : e - n);
+}
+
+// positions[2 i], [2 i + 1] = query and target position of anchor member[i]
+__global__ void __launch_bounds__(kThreads) chain_positions_kernel(const gwm_anchor* __restrict__ a,
+                                                                   const uint32_t* __restrict__ member, int64_t count,
+                                                                   uint32_t* __restrict__ positions)
+{
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= count)
+        return;
+    const gwm_anchor x   = a[member[i]];
+    positions[2 * i]     = x.query_position_in_read;
+    positions[2 * i + 1] = x.target_position_in_read;
+}
+
+__global__ void __launch_bounds__(kThreads) chain_residues_kernel(const gwm_overlap* __restrict__ o, int64_t count,
+                                                                  int64_t* __restrict__ residues)
+{
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i < count)
+        residues[i] = o[i].num_residues;
+}
+
+// The anchors of the kept records, in record order and in anchor order within a record, from the slot marks of the
+// extraction: offsets[0 .. n_out] and positions; returns their number. A record's anchors all lie in one half of
+// owner in ascending order, and the radix sort by record index is stable.
+int64_t chain_members(const gwm_anchor* anchors, int64_t n, const uint32_t* owner, const uint32_t* keep, int64_t n_slots,
+                      const gwm_overlap* kept_records, int64_t n_out, Temp& temp, hipStream_t s, dbuf<int64_t>& offsets,
+                      dbuf<uint32_t>& positions)
+{
+    dbuf<uint32_t> kept_through(n_slots), flag(2 * n), key(2 * n), value(2 * n), d_count(1);
+    inclusive_sum(keep, kept_through.p, n_slots, temp, s);
+    chain_members_kernel<<<grid_for(2 * n), kThreads, 0, s>>>(owner, n, keep, kept_through.p, flag.p, key.p, value.p);
+    GWM_CHECK(hipGetLastError());
+    dbuf<uint32_t> keys, values;
+    select_kept(key.p, flag.p, 2 * n, d_count.p, temp, s, keys);
+    select_kept(value.p, flag.p, 2 * n, d_count.p, temp, s, values);
+    const int64_t members = to_host(d_count.p, s);
+    offsets.resize(n_out + 1);
+    GWM_CHECK(hipMemsetAsync(offsets.p, 0, sizeof(int64_t), s));
+    dbuf<int64_t> residues(n_out);
+    chain_residues_kernel<<<grid_for(n_out), kThreads, 0, s>>>(kept_records, n_out, residues.p);
+    GWM_CHECK(hipGetLastError());
+    inclusive_sum(residues.p, offsets.p + 1, n_out, temp, s);
+    if (to_host(offsets.p + n_out, s) != members)
+        throw std::runtime_error("gwm_chain_overlaps: the kept records do not own the anchors their chains took");
+    positions.resize(2 * members);
+    if (members > 0)
+    {
+        dbuf<uint32_t> sorted_keys(members), sorted_values(members);
+        sort_pairs(keys.p, sorted_keys.p, values.p, sorted_values.p, members, bits_for(static_cast<uint64_t>(n_out)), temp, s);
+        chain_positions_kernel<<<grid_for(members), kThreads, 0, s>>>(anchors, sorted_values.p, members, positions.p);
+        GWM_CHECK(hipGetLastError());
+    }
+    return members;
+}
+
+// what a caller that asked for the chains gets: host arrays of given capacity, or device arrays
+struct chain_anchor_output
+{
+    int64_t* offsets_host      = nullptr;
+    uint32_t* positions_host   = nullptr;
+    int64_t capacity           = 0; // pairs of positions_host
+    int64_t** offsets_device   = nullptr;
+    uint32_t** positions_device = nullptr;
+    int64_t* count             = nullptr; // pairs of all kept records
+};
+
 int chain_overlaps(const gwm_anchor* anchors, int64_t n, const gwm_chaining* chaining, int32_t all_to_all,
                    int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
                    float min_overlap_fraction, void* stream, gwm_overlap* out_host, int32_t* scores_host,
                    int64_t capacity, gwm_overlap** out_device, int32_t** scores_device, int64_t* count,
-                   float* chain_ms)
+                   float* chain_ms, const chain_anchor_output* chains = nullptr)
 {
     *count = 0;
+    if (chains && chains->count)
+        *chains->count = 0;
     if (chain_ms)
         *chain_ms = 0.f;
     try
@@ -333,7 +429,11 @@ int chain_overlaps(const gwm_anchor* anchors, int64_t n, const gwm_chaining* cha
             throw std::invalid_argument("gwm_chain_overlaps: min_residues, min_overlap_len and min_bases_per_residue "
                                         "must be >= 0");
         if (n <= 0)
+        {
+            if (chains && chains->offsets_host)
+                chains->offsets_host[0] = 0;
             return 0;
+        }
         if (n >= (int64_t(1) << 32))
             throw std::invalid_argument("gwm_chain_overlaps: 2^32 anchors or more");
         hipStream_t s = static_cast<hipStream_t>(stream);
@@ -355,7 +455,9 @@ int chain_overlaps(const gwm_anchor* anchors, int64_t n, const gwm_chaining* cha
         const uint32_t n_worth = select_indices(worth.p, n_groups, ids.p, d_count.p, temp, s);
         if (to_host(d_longest.p, s) >= kMaxGroup)
             throw std::invalid_argument("gwm_chain_overlaps: 2^24 anchors or more of one read pair");
-        int64_t n_out = 0;
+        int64_t n_out = 0, n_members = 0;
+        dbuf<int64_t> chain_offsets;
+        dbuf<uint32_t> chain_positions;
         dbuf<gwm_overlap> kept_records;
         dbuf<int32_t> kept_scores;
         if (n_worth > 0)
@@ -372,7 +474,14 @@ int chain_overlaps(const gwm_anchor* anchors, int64_t n, const gwm_chaining* cha
             dbuf<int32_t> f(2 * n), slot_scores(n_slots);
             dbuf<uint8_t> dist(2 * n), used(2 * n);
             dbuf<gwm_overlap> slot_records(n_slots);
-            dbuf<uint32_t> keep(n_slots);
+            dbuf<uint32_t> keep(n_slots), owner;
+            if (chains)
+            {
+                if (n_slots >= (int64_t(1) << 32) - 1)
+                    throw std::invalid_argument("gwm_chain_overlaps: 2^32 - 1 record slots or more with the chains asked for");
+                owner.resize(2 * n);
+                GWM_CHECK(hipMemsetAsync(owner.p, 0, sizeof(uint32_t) * static_cast<size_t>(2 * n), s));
+            }
             GWM_CHECK(hipMemsetAsync(used.p, 0, static_cast<size_t>(2 * n), s));
             GWM_CHECK(hipMemsetAsync(keep.p, 0, sizeof(uint32_t) * static_cast<size_t>(n_slots), s));
             const chain_params c{p.kmer_size,
@@ -388,14 +497,29 @@ int chain_overlaps(const gwm_anchor* anchors, int64_t n, const gwm_chaining* cha
             const unsigned waves_per_block = kThreads / 64;
             chain_dp_kernel<<<(n_worth + waves_per_block - 1) / waves_per_block, kThreads, 0, s>>>(
                 anchors, n, first.p, length.p, slot_end.p, n_worth, c, f.p, dist.p, used.p, slot_records.p,
-                slot_scores.p, keep.p);
+                slot_scores.p, keep.p, owner.p);
             GWM_CHECK(hipGetLastError());
             select_kept(slot_records.p, keep.p, n_slots, d_count.p, temp, s, kept_records);
             select_kept(slot_scores.p, keep.p, n_slots, d_count.p, temp, s, kept_scores);
             n_out = to_host(d_count.p, s);
+            if (chains && n_out > 0)
+                n_members = chain_members(anchors, n, owner.p, keep.p, n_slots, kept_records.p, n_out, temp, s, chain_offsets,
+                                          chain_positions);
         }
         ev.record(1, s);
         const int64_t n_copy = n_out < capacity ? n_out : capacity;
+        if (chains && n_copy > 0)
+        {
+            if (chains->offsets_host)
+                GWM_CHECK(hipMemcpyAsync(chains->offsets_host, chain_offsets.p, sizeof(int64_t) * (n_copy + 1), hipMemcpyDeviceToHost, s));
+            // the anchors of the records copied, as far as the room reaches
+            const int64_t theirs = n_copy == n_out ? n_members : to_host(chain_offsets.p + n_copy, s);
+            const int64_t pairs  = theirs < chains->capacity ? theirs : chains->capacity;
+            if (chains->positions_host && pairs > 0)
+                GWM_CHECK(hipMemcpyAsync(chains->positions_host, chain_positions.p, sizeof(uint32_t) * 2 * pairs, hipMemcpyDeviceToHost, s));
+        }
+        else if (chains && chains->offsets_host)
+            chains->offsets_host[0] = 0;
         if (n_copy > 0 && out_host)
             GWM_CHECK(hipMemcpyAsync(out_host, kept_records.p, sizeof(gwm_overlap) * n_copy, hipMemcpyDeviceToHost, s));
         if (n_copy > 0 && scores_host)
@@ -407,6 +531,12 @@ int chain_overlaps(const gwm_anchor* anchors, int64_t n, const gwm_chaining* cha
             *out_device = kept_records.release();
         if (n_out > 0 && scores_device)
             *scores_device = kept_scores.release();
+        if (chains && n_out > 0 && chains->offsets_device)
+            *chains->offsets_device = chain_offsets.release();
+        if (chains && n_out > 0 && chains->positions_device)
+            *chains->positions_device = chain_positions.release();
+        if (chains && chains->count)
+            *chains->count = n_members;
         *count = n_out;
         return 0;
     }
@@ -440,5 +570,41 @@ int gwm_chain_overlaps_device(const gwm_anchor* anchors, int64_t n, const gwm_ch
         *scores = nullptr;
     return chain_overlaps(anchors, n, chaining, all_to_all, min_residues, min_overlap_len, min_bases_per_residue,
                           min_overlap_fraction, stream, nullptr, nullptr, 0, out, scores, count, chain_ms);
+}
+
+int gwm_chain_overlaps_anchored(const gwm_anchor* anchors, int64_t n, const gwm_chaining* chaining, int32_t all_to_all,
+                                int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                                float min_overlap_fraction, void* stream, gwm_overlap* out, int32_t* scores, int64_t capacity,
+                                int64_t* anchor_offsets, uint32_t* anchor_positions, int64_t anchor_capacity, int64_t* count,
+                                int64_t* n_chain_anchors, float* chain_ms)
+{
+    chain_anchor_output chains;
+    chains.offsets_host   = anchor_offsets;
+    chains.positions_host = anchor_positions;
+    chains.capacity       = anchor_capacity;
+    chains.count          = n_chain_anchors;
+    return chain_overlaps(anchors, n, chaining, all_to_all, min_residues, min_overlap_len, min_bases_per_residue,
+                          min_overlap_fraction, stream, out, scores, capacity, nullptr, nullptr, count, chain_ms, &chains);
+}
+
+int gwm_chain_overlaps_anchored_device(const gwm_anchor* anchors, int64_t n, const gwm_chaining* chaining, int32_t all_to_all,
+                                       int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                                       float min_overlap_fraction, void* stream, gwm_overlap** out, int32_t** scores,
+                                       int64_t** anchor_offsets, uint32_t** anchor_positions, int64_t* count,
+                                       int64_t* n_chain_anchors, float* chain_ms)
+{
+    *out = nullptr;
+    if (scores)
+        *scores = nullptr;
+    if (anchor_offsets)
+        *anchor_offsets = nullptr;
+    if (anchor_positions)
+        *anchor_positions = nullptr;
+    chain_anchor_output chains;
+    chains.offsets_device   = anchor_offsets;
+    chains.positions_device = anchor_positions;
+    chains.count            = n_chain_anchors;
+    return chain_overlaps(anchors, n, chaining, all_to_all, min_residues, min_overlap_len, min_bases_per_residue,
+                          min_overlap_fraction, stream, nullptr, nullptr, 0, out, scores, count, chain_ms, &chains);
 }
 }

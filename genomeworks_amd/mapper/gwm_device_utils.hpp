@@ -95,6 +95,24 @@ __device__ __forceinline__ void copy_slice(Out* dst, const uint8_t* src, Length 
     }
 }
 
+// copy_slice by one wave64, for slices of a few hundred bytes: lane L of a pass takes output byte L
+template <typename Out, typename Length, typename Forward, typename Backward>
+__device__ __forceinline__ void copy_slice_wave(Out* dst, const uint8_t* src, Length len, bool reversed, Forward forward,
+                                                Backward backward)
+{
+    const Length lane = threadIdx.x & 63u;
+    if (reversed)
+    {
+        for (Length j = lane; j < len; j += 64)
+            dst[j] = static_cast<Out>(backward(src[len - 1 - j]));
+    }
+    else
+    {
+        for (Length j = lane; j < len; j += 64)
+            dst[j] = static_cast<Out>(forward(src[j]));
+    }
+}
+
 template <typename In, typename Out>
 void inclusive_sum(In in, Out out, int64_t n, Temp& t, hipStream_t s)
 {

@@ -2,6 +2,7 @@
 // Index / Matcher / host copy / result objects of gwm_handles.hpp, the index batcher (gwm_index_batcher.hpp) and the
 // batched driver (gwm_driver.hpp).
 #include "gw_mapper_capi.h"
+#include "gwm_anchor_plan.hpp"
 #include "gwm_driver.hpp"
 #include "gwm_index_batcher.hpp"
 
@@ -462,6 +463,44 @@ int64_t gw_mapper_chain_overlaps_host(const void* anchors, int64_t n, const int3
     }, int64_t(GW_MAPPER_ERROR));
 }
 
+int64_t gw_mapper_chain_overlaps_anchored(const gw_mapper_matcher* matcher, const int32_t chaining[5], int32_t all_to_all,
+                                          int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                                          float min_overlap_fraction, void* overlaps, int32_t* scores, int64_t capacity,
+                                          int64_t* anchor_offsets, uint32_t* anchor_positions, int64_t anchor_capacity,
+                                          int64_t* n_chain_anchors, float* chain_ms, void* stream)
+{
+    return guarded([&] {
+        int64_t count        = 0;
+        const gwm_chaining c = chaining_of(chaining);
+        throw_on(gwm_chain_overlaps_anchored(matcher->a.anchors, matcher->a.n, &c, all_to_all, min_residues, min_overlap_len,
+                                             min_bases_per_residue, min_overlap_fraction, stream,
+                                             static_cast<gwm_overlap*>(overlaps), scores, capacity, anchor_offsets,
+                                             anchor_positions, anchor_capacity, &count, n_chain_anchors, chain_ms));
+        return count;
+    }, int64_t(GW_MAPPER_ERROR));
+}
+
+int64_t gw_mapper_chain_overlaps_anchored_host(const void* anchors, int64_t n, const int32_t chaining[5],
+                                               int32_t all_to_all, int64_t min_residues, int64_t min_overlap_len,
+                                               int64_t min_bases_per_residue, float min_overlap_fraction, void* overlaps,
+                                               int32_t* scores, int64_t capacity, int64_t* anchor_offsets,
+                                               uint32_t* anchor_positions, int64_t anchor_capacity,
+                                               int64_t* n_chain_anchors, float* chain_ms, void* stream)
+{
+    return guarded([&] {
+        int64_t count        = 0;
+        const gwm_chaining c = chaining_of(chaining);
+        dbuf<gwm_anchor> d;
+        if (n > 0 && n < (int64_t(1) << 32)) // the engine refuses the rest before it reads an anchor
+            d.upload(static_cast<const gwm_anchor*>(anchors), n);
+        throw_on(gwm_chain_overlaps_anchored(d.p, n, &c, all_to_all, min_residues, min_overlap_len, min_bases_per_residue,
+                                             min_overlap_fraction, stream, static_cast<gwm_overlap*>(overlaps), scores,
+                                             capacity, anchor_offsets, anchor_positions, anchor_capacity, &count,
+                                             n_chain_anchors, chain_ms));
+        return count;
+    }, int64_t(GW_MAPPER_ERROR));
+}
+
 int64_t gw_mapper_map(const char* query_bases, const int64_t* query_offsets, int32_t n_queries,
                       const char* target_bases, const int64_t* target_offsets, int32_t n_targets, int32_t kmer_size,
                       int32_t window_size, double filtering_parameter, int64_t min_residues, int64_t min_overlap_len,
@@ -652,6 +691,63 @@ gw_mapper_cigars* gw_mapper_align_overlaps_scored2(const void* overlaps, int64_t
         throw_on(gwm_align_overlaps_scored2(c.d.p, n, c.q.bases, c.q.offsets, c.reads.queries.n, first_query_read_id,
                                             c.t.bases, c.t.offsets, c.reads.targets.n, first_target_read_id, sc,
                                             max_device_bytes, stream, &h->c));
+        return h.release();
+    }, static_cast<gw_mapper_cigars*>(nullptr));
+}
+
+gw_mapper_cigars* gw_mapper_align_overlaps_anchored(const void* overlaps, int64_t n, const char* query_bases,
+                                                    const int64_t* query_offsets, int32_t n_queries,
+                                                    uint32_t first_query_read_id, const char* target_bases,
+                                                    const int64_t* target_offsets, int32_t n_targets,
+                                                    uint32_t first_target_read_id, const int64_t* anchor_offsets,
+                                                    const uint32_t* anchor_positions, int64_t n_anchors,
+                                                    int32_t anchor_kmer_size, int32_t anchor_spacing,
+                                                    const int32_t* scoring, int32_t scoring_values,
+                                                    int64_t max_device_bytes, void* stream)
+{
+    return guarded([&] {
+        const std::string who = "gw_mapper_align_overlaps_anchored";
+        std::unique_ptr<gw_mapper_cigars> h(new gw_mapper_cigars());
+        if ((scoring_values != 0 && scoring_values != 4 && scoring_values != 6) || (scoring_values != 0 && scoring == nullptr))
+            throw std::invalid_argument(who + ": scoring_values must be 0, 4 or 6, with a scoring unless it is 0");
+        gwm_scoring one{};
+        gwm_scoring2 costs{};
+        if (scoring_values == 4)
+        {
+            checked_scoring(who.c_str(), scoring, &one);
+            costs = gwm_scoring2{one.mismatch, one.gap_open, one.gap_extend, 0, 0, one.band};
+        }
+        else if (scoring_values == 6)
+            checked_scoring2(who.c_str(), scoring, &costs);
+        // the lists, before anything is uploaded
+        if (!gwm_plan::parameters_in_range(anchor_kmer_size, anchor_spacing))
+            throw std::invalid_argument(who + ": anchor_kmer_size " + std::to_string(anchor_kmer_size) + ", anchor_spacing " +
+                                        std::to_string(anchor_spacing) + " outside 1..32, >= 1");
+        if (n_anchors < 0 || n_anchors >= (int64_t(1) << 32) || (n > 0 && anchor_offsets == nullptr) ||
+            (n_anchors > 0 && anchor_positions == nullptr))
+            throw std::invalid_argument(who + ": anchors without offsets or positions, or their number outside 0..2^32 - 1");
+        if (n > 0)
+        {
+            const int64_t bad = gwm_plan::first_bad_offset(anchor_offsets, n, n_anchors);
+            if (bad >= 0)
+                throw std::invalid_argument(who + ": anchor offsets must start at 0, never decrease and end at the number of "
+                                            "anchors (" + std::to_string(n_anchors) + "): entry " + std::to_string(bad) + " is " +
+                                            std::to_string(anchor_offsets[bad]));
+        }
+        device_call c({query_bases, query_offsets, n_queries}, {target_bases, target_offsets, n_targets}, overlaps, n,
+                      false);
+        dbuf<int64_t> offsets;
+        dbuf<uint32_t> positions;
+        if (n > 0)
+        {
+            offsets.upload(anchor_offsets, n + 1);
+            positions.upload(anchor_positions, 2 * n_anchors);
+        }
+        const gwm_anchor_lists lists{offsets.p, positions.p, n_anchors, anchor_kmer_size, anchor_spacing};
+        throw_on(gwm_align_overlaps_anchored(c.d.p, n, c.q.bases, c.q.offsets, c.reads.queries.n, first_query_read_id,
+                                             c.t.bases, c.t.offsets, c.reads.targets.n, first_target_read_id, &lists,
+                                             scoring_values == 0 ? 0 : scoring_values == 4 ? 1 : 2, &costs, max_device_bytes,
+                                             stream, &h->c));
         return h.release();
     }, static_cast<gw_mapper_cigars*>(nullptr));
 }

@@ -85,6 +85,24 @@ int64_t gw_mapper_chain_overlaps_host(const void* anchors, int64_t n, const int3
                                       float min_overlap_fraction, void* overlaps, int32_t* scores, int64_t capacity,
                                       float* chain_ms, void* stream);
 
+/* gw_mapper_chain_overlaps that also hands out the chains (gwm_chain_overlaps_anchored): for the records written,
+   anchor_offsets[min(capacity, count) + 1] (int64) and, as far as anchor_capacity pairs reach, their anchors in chain
+   order as (query_position_in_read, target_position_in_read) pairs of uint32 in anchor_positions; twice the anchor
+   count always suffices. *n_chain_anchors is the number of pairs of all kept records. Any output may be NULL. */
+int64_t gw_mapper_chain_overlaps_anchored(const gw_mapper_matcher* matcher, const int32_t chaining[5], int32_t all_to_all,
+                                          int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                                          float min_overlap_fraction, void* overlaps, int32_t* scores, int64_t capacity,
+                                          int64_t* anchor_offsets, uint32_t* anchor_positions, int64_t anchor_capacity,
+                                          int64_t* n_chain_anchors, float* chain_ms, void* stream);
+
+/* the same over n sorted host anchors (uploaded first) */
+int64_t gw_mapper_chain_overlaps_anchored_host(const void* anchors, int64_t n, const int32_t chaining[5],
+                                               int32_t all_to_all, int64_t min_residues, int64_t min_overlap_len,
+                                               int64_t min_bases_per_residue, float min_overlap_fraction, void* overlaps,
+                                               int32_t* scores, int64_t capacity, int64_t* anchor_offsets,
+                                               uint32_t* anchor_positions, int64_t anchor_capacity,
+                                               int64_t* n_chain_anchors, float* chain_ms, void* stream);
+
 /* Whole mapping of one index pair: queries against targets, or all against all when target_bases is NULL
    (all_to_all then drops self-mappings). Writes min(capacity, count) overlaps and returns count. */
 int64_t gw_mapper_map(const char* query_bases, const int64_t* query_offsets, int32_t n_queries,
@@ -152,6 +170,23 @@ gw_mapper_cigars* gw_mapper_align_overlaps_scored2(const void* overlaps, int64_t
                                                    const int64_t* target_offsets, int32_t n_targets,
                                                    uint32_t first_target_read_id, const int32_t* scoring,
                                                    int64_t max_device_bytes, void* stream);
+/* The same with every overlap cut at anchors of its chain and aligned piece by piece (gwm_align_overlaps_anchored of
+   gwhip_mapper.h has rules G1-G6). Overlap i has the host anchors anchor_positions[anchor_offsets[i] ..
+   anchor_offsets[i + 1]) as (query, target) pairs of uint32, what gw_mapper_chain_overlaps_anchored returns;
+   anchor_kmer_size 1..32, anchor_spacing >= 1. scoring_values 0: the default aligner; 4: scoring[0..3] as for
+   gw_mapper_align_overlaps_scored; 6: scoring[0..5] as for gw_mapper_align_overlaps_scored2. Refused before anything
+   reaches the device (NULL): a scoring, k or S out of range, another scoring_values, offsets that do not start at 0,
+   decrease, or do not end at n_anchors. Valid anchors of a record that are not strictly increasing are an error that
+   names the record. */
+gw_mapper_cigars* gw_mapper_align_overlaps_anchored(const void* overlaps, int64_t n, const char* query_bases,
+                                                    const int64_t* query_offsets, int32_t n_queries,
+                                                    uint32_t first_query_read_id, const char* target_bases,
+                                                    const int64_t* target_offsets, int32_t n_targets,
+                                                    uint32_t first_target_read_id, const int64_t* anchor_offsets,
+                                                    const uint32_t* anchor_positions, int64_t n_anchors,
+                                                    int32_t anchor_kmer_size, int32_t anchor_spacing,
+                                                    const int32_t* scoring, int32_t scoring_values,
+                                                    int64_t max_device_bytes, void* stream);
 int64_t gw_mapper_cigars_count(const gw_mapper_cigars* cigars);
 int64_t gw_mapper_cigars_text_bytes(const gw_mapper_cigars* cigars);
 int gw_mapper_cigars_copy(const gw_mapper_cigars* cigars, char* text, int64_t* offsets, int32_t* edit_distances,

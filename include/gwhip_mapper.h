@@ -342,6 +342,84 @@ int gwm_align_overlaps_scored2(const gwm_overlap* overlaps, int64_t n, const cha
                                const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
                                const gwm_scoring2* scoring, int64_t max_device_bytes, void* stream, gwm_cigars* out);
 
+/* The chains of gwm_chain_overlaps with their anchors: everything gwm_chain_overlaps does and returns, and for kept
+ * record i the anchors of its chain in chain order (ascending anchor index), anchor_positions[anchor_offsets[i] ..
+ * anchor_offsets[i + 1]) as (query_position_in_read, target_position_in_read) pairs; record i owns num_residues of
+ * them. Records, scores and their order are those of gwm_chain_overlaps. min(capacity, *count) records, scores and
+ * that many + 1 offsets are copied to the host arrays, and the anchors of those records as far as anchor_capacity pairs
+ * reach (2 n always suffices: an anchor is in at most one chain of each orientation); *n_chain_anchors is the number of
+ * pairs of all kept records. Any output array may be NULL. Membership is found on the device: the extraction marks
+ * every anchor it visits with its record slot, a scan of the kept slots turns slots into record indices, and a stable
+ * radix sort by record index brings the marked anchors into record order. */
+int gwm_chain_overlaps_anchored(const gwm_anchor* anchors, int64_t n, const gwm_chaining* chaining, int32_t all_to_all,
+                                int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                                float min_overlap_fraction, void* stream, gwm_overlap* out, int32_t* scores, int64_t capacity,
+                                int64_t* anchor_offsets, uint32_t* anchor_positions, int64_t anchor_capacity, int64_t* count,
+                                int64_t* n_chain_anchors, float* chain_ms);
+
+/* gwm_chain_overlaps_anchored with the result left on the device: *out, *scores (may be NULL), *anchor_offsets
+ * (*count + 1 entries) and *anchor_positions (*n_chain_anchors pairs) are device arrays, NULL when *count is 0, that the
+ * caller frees with gwm_device_free. */
+int gwm_chain_overlaps_anchored_device(const gwm_anchor* anchors, int64_t n, const gwm_chaining* chaining, int32_t all_to_all,
+                                       int64_t min_residues, int64_t min_overlap_len, int64_t min_bases_per_residue,
+                                       float min_overlap_fraction, void* stream, gwm_overlap** out, int32_t** scores,
+                                       int64_t** anchor_offsets, uint32_t** anchor_positions, int64_t* count,
+                                       int64_t* n_chain_anchors, float* chain_ms);
+
+/* The anchors of the records of one gwm_align_overlaps_anchored call: record i has anchors positions[offsets[i] ..
+ * offsets[i + 1]) as (query_position_in_read, target_position_in_read) pairs in forward read coordinates, minimizer
+ * starts as gwm_anchor has them -- what gwm_chain_overlaps_anchored_device returns. */
+typedef struct gwm_anchor_lists
+{
+    const int64_t* offsets;    /* device [n + 1] */
+    const uint32_t* positions; /* device [n_anchors][2] */
+    int64_t n_anchors;
+    int32_t kmer_size; /* k, 1..32: the anchors' k-mers */
+    int32_t spacing;   /* S >= 1; the layers above fill in 256, a convention that is not tuned */
+} gwm_anchor_lists;
+
+/* gwm_align_overlaps with every overlap cut at anchors of its chain and aligned piece by piece (INTEGRATION.md section
+ * 3s). scoring_pieces 0: the default aligner, `scoring` is not read; 1 / 2: gwhip_affine_align / gwhip_affine2_align
+ * under `scoring` (with one piece gap_open2 and gap_extend2 are not read). anchors NULL is the call without anchors.
+ *   G1  n, m are the slice lengths. An anchor (q, t) lies at u = q - query_start and, on '+', v = t - target_start; on
+ *       '-', v = target_end - t - k, the start of the k-mer in the reverse-complemented target slice that the gather
+ *       produces. Signed 64-bit arithmetic; nothing wraps.
+ *   G2  An anchor is valid iff 0 < u < n and 0 < v < m. The others are dropped silently: a chained record starts and
+ *       ends on an anchor, so its first and last anchor normally are; after gwm_extend_overlaps has moved the ends
+ *       they normally are not.
+ *   G3  The valid anchors of a record must be strictly increasing in both u and v, in list order; otherwise the call
+ *       returns -1 with an error that names the first such record, before any alignment is launched. The chains of
+ *       gwm_chain_overlaps always are (C3).
+ *   G4  A valid anchor is a cut iff it is the first valid anchor of its record, or floor(u / S) differs from that of
+ *       the valid anchor before it.
+ *   G5  With cuts c_1 .. c_p, c_0 = (0, 0) and c_(p+1) = (n, m), piece j is Q[u_j, u_(j+1)) against
+ *       T'[v_j, v_(j+1)), a global alignment by the call's aligner; the band of the scoring applies to every piece, and
+ *       the default aligner's max_query_length is the longest query side of a piece of the call. A record without
+ *       valid anchors is one piece: the alignment of gwm_align_overlaps, byte for byte.
+ *   G6  The states of a record are its pieces' states concatenated, so CIGARs and edit distances read as before. If
+ *       a piece has no result the record has none (an empty CIGAR and -1). Every piece is what its aligner returns for
+ *       that pair alone; the whole is a valid global alignment of the slices. It is not re-priced across cuts -- a gap
+ *       run that a cut divides stays two runs in the pieces' costs -- and no global optimality is claimed for it.
+ * Pieces are gathered piece-major from the resident reads, aligned in one aligner call per chunk, and a wave64 per
+ * record stitches the pieces' states into the record's slot. The chunks still hold whole records; a chunk's budget
+ * counts gwm_align_bytes_needed_anchored over its pieces. What the plan of the whole call keeps on the device besides
+ * the chunks -- 28 B per piece and 8 B per record, and while it is built 56 B per anchor -- lies outside
+ * max_device_bytes.
+ * Refused before anything is launched: k or S out of range, offsets that do not start at 0, decrease, or do not end at
+ * n_anchors; then what gwm_align_overlaps refuses, then G3. */
+int gwm_align_overlaps_anchored(const gwm_overlap* overlaps, int64_t n, const char* query_bases, const int64_t* query_offsets,
+                                int32_t n_queries, uint32_t first_query_read_id, const char* target_bases,
+                                const int64_t* target_offsets, int32_t n_targets, uint32_t first_target_read_id,
+                                const gwm_anchor_lists* anchors, int32_t scoring_pieces, const gwm_scoring2* scoring,
+                                int64_t max_device_bytes, void* stream, gwm_cigars* out);
+
+/* Device bytes gwm_align_overlaps_anchored counts for a chunk that holds one overlap of these pieces: piece_starts[0 ..
+ * 2 pieces] are the exclusive sums of query and target length of piece 0, of piece 1, ... (host). scoring_pieces and
+ * band as above; max_query_length, read with scoring_pieces 0 only, is the longest query side of a piece of the call.
+ * Host arithmetic only. */
+int64_t gwm_align_bytes_needed_anchored(const int64_t* piece_starts, int32_t pieces, int32_t scoring_pieces, int32_t band,
+                                        int32_t max_query_length);
+
 /* ---- polishing: from aligned overlaps to POA windows ----------------------------------------------------------------
  * The target reads are cut into windows of window_length bases: window k of a read is its bases [k W, (k + 1) W). */
 
